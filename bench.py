@@ -2,16 +2,24 @@
 """Benchmark of the MI355X ADMM hot path: ADMM iterations/second on the Group Graphical Lasso
 workload BASELINE.json quotes the metric on, (K=32, p=500), fp64.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one full ADMM iteration (Omega-step: W formation + matrix-function products; Theta-step:
 group prox over the (K,p,p) stack; dual update; the five stopping-test norms; rho rule on the host)
 driven by the same host loop ``ADMM_MGL`` uses (gglasso_amd/solver.py::_run_admm) with tol=rtol=1e-20
 so that it cannot exit early.  S, Omega, Theta, X are resident in HBM before the timed region starts.
 
-The timed region is EXACTLY ``steps`` iterations between barrier + synchronize on both sides; it is run
-``--regions`` times back to back (default 7; 20 iterations are only ~20 ms of wall clock) and ``value`` /
-``ms_per_step`` are those of the MEDIAN region, with the fastest and slowest one reported next to it.
+The timed region is EXACTLY ``steps`` iterations between barrier + synchronize on both sides, after ``warmup`` untimed
+ones.  A plain run times one region and reports the headline line only: ``value`` / ``ms_per_step`` are those of that
+region.  ``--full`` runs it ``--regions`` times back to back (default 7 there; 20 iterations are only ~20 ms of wall
+clock), reports the MEDIAN region with the fastest and slowest one next to it, and adds everything below.
+
+``--dump-outputs DIR`` writes what the last timed step computed, the arrays a caller of ADMM_MGL (ADMM_SGL for the
+lambda grid) receives, as DIR/<name>.npy in float64: ``Omega``, ``Theta``, ``L`` (MGL; SGL only when latent) and ``X``.
+An array of more than 2**20 entries is written as the fixed sample ``a.ravel()[dump_index(a.size)]`` (a seeded choice
+of 2**20 flat indices, ascending), so that the whole dump stays under 64 MB.  The inputs are drawn from the workload's
+fixed seed: two builds run with the same arguments can be compared output for output.  With N > 1 ranks, rank 0
+writes its K-slab.
 
 N > 1, one rank per GPU: the K=32 stack is sharded into K/N slabs (strong scaling); per iteration one (p,p) fp64
 all-reduce of the group sums of squares and one 5-scalar all-reduce of the residual norms go over RCCL.  Started either
@@ -20,9 +28,10 @@ environment) or bare (``python bench.py --gpus N``): the bare process then start
 ``torch.distributed.run`` on 127.0.0.1 before anything in it has touched the GPU (it never does), relays rank 0's JSON
 line and exits with the child's code.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  Extra objects with ``--full``:
   roofline     -- the phase that dominates the iteration, timed live with HIP events on the ctx stream
   cpu_baseline -- the CPU oracle (NumPy/LAPACK + C prox) on this box's host cores, bounded sample
+  (and value_exact, parity, phases_ms, newton_schulz, iteration_hbm_roofline: see main())
 """
 import argparse
 import contextlib
@@ -123,6 +132,27 @@ def committed_profile(kernel_key):
     return out
 
 
+SETTLE_ITERS = 30
+DUMP_MAX_ENTRIES = 1 << 20      # per array: 8 MB in float64, four arrays at most
+DUMP_SEED = 20240917
+
+
+def dump_index(size):
+    """The flat indices --dump-outputs keeps of an array of `size` entries: all of them up to DUMP_MAX_ENTRIES, else a
+    fixed seeded sample of DUMP_MAX_ENTRIES, ascending."""
+    if size <= DUMP_MAX_ENTRIES:
+        return np.arange(size)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(size, DUMP_MAX_ENTRIES, replace=False))
+
+
+def dump_outputs(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        flat = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        np.save(os.path.join(directory, name + ".npy"), flat[dump_index(flat.size)] if flat.size > DUMP_MAX_ENTRIES
+                else np.asarray(a, dtype=np.float64))
+
+
 def quiet(fn, *a, **k):
     with contextlib.redirect_stdout(io.StringIO()):
         return fn(*a, **k)
@@ -218,7 +248,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--regions", type=int, default=7, help="how often the timed region of `steps` iterations is run")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="how often the timed region of `steps` iterations is run (default 1; 7 with --full)")
     ap.add_argument("--workload", default="ggl_K32_p500", choices=sorted(WORKLOADS))
     ap.add_argument("--cpu-iters", type=int, default=24)
     ap.add_argument("--cpu-threads", type=int, default=16)
@@ -230,7 +261,14 @@ def main():
                     help="ctx option (gglasso_amd._lib.OPTIONS), e.g. --opt pipeline=0; repeatable")
     ap.add_argument("--no-exact-region", action="store_true",
                     help="skip the one extra timed region at ns_tol=0 (value_exact)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the median of several regions, per-phase / roofline figures, the ns_tol=0 region and the CPU "
+                         "baseline with its parity check")
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 7 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare start on a multi-GPU node: become the launcher (before any GPU call; never re-exec)
@@ -338,9 +376,18 @@ def main():
                 if np.any(fac != 1.0):
                     eng.scale_X_batch(fac)
             return rhos
-        info, rho = quiet(solver._run_admm, eng, reg, K, p, l1, l2, latent, mu_loc, nk, rho, 1e-20, 1e-20, 'boyd',
-                          True, iters, False, False, "Multiple", comm=comm)
-        return rho
+        # exactly `iters` iterations: the solve reaches the fixed point of fp64 (every residual 0, "optimal" even at
+        # tol = 1e-20) after ~150 iterations and stops; the remaining ones start it again from the saved start point
+        # (measure=True only to learn how many iterations ran)
+        done = 0
+        while True:
+            info, rho = quiet(solver._run_admm, eng, reg, K, p, l1, l2, latent, mu_loc, nk, rho, 1e-20, 1e-20, 'boyd',
+                              True, iters - done, False, True, "Multiple", comm=comm)
+            done += len(info['runtime'])
+            if done >= iters:
+                return rho
+            eng.restore_state()
+            rho = 1.0
 
     def fence():
         if distributed:
@@ -356,6 +403,9 @@ def main():
     # tools/iter_profile.py: iterations 5..24 take 0.863 ms each after an upload and 0.811 ms after a device-side restore,
     # 0.800 ms in the steady state.  A solve (or a grid of them) keeps the GPU busy; so do the regions now.
     eng.save_state()
+    # one untimed settling pass first: after the upload the chip needs ~15 busy iterations to reach its loaded clock
+    # state, and no timed region may start from an idle GPU (with one region, nothing before it would keep it busy)
+    run(SETTLE_ITERS, 1.0)
 
     def one_region():
         """-> (seconds of the timed `steps` iterations, max over ranks; ns_stats before; ns_stats after; rho)"""
@@ -364,16 +414,17 @@ def main():
         rho = 1.0
         if args.warmup > 0:
             rho = run(args.warmup, rho)
-        # live HIP-event timing of the dominant (eigen / matrix-function) phases only during the timed regions:
+        # --full: live HIP-event timing of the dominant (eigen / matrix-function) phases only during the timed regions:
         # every extra event pair costs a few microseconds of host time per iteration
-        eng.profile(2)
-        na = eng.ns_stats()
+        if args.full:
+            eng.profile(2)
+        na = eng.ns_stats() if args.full else None
         fence()
         t0 = time.perf_counter()
         rho = run(args.steps, rho)
         fence()
         dt = time.perf_counter() - t0
-        nb = eng.ns_stats()
+        nb = eng.ns_stats() if args.full else None
         if distributed:
             t = torch.tensor([dt], dtype=torch.float64, device=f"cuda:{local_rank}")
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -387,136 +438,68 @@ def main():
     rho = 1.0
     for _ in range(max(1, args.regions)):
         dt, na, nb, rho = one_region()
-        if ns0 is None:
-            ns0 = na
-        ns1 = nb if ns1 is None else {k: (ns1[k] + nb[k] - na[k]) if k not in ("last_parts", "last_variant") else nb[k]
-                                      for k in nb}
+        if args.full:
+            if ns0 is None:
+                ns0 = na
+            ns1 = nb if ns1 is None else {k: (ns1[k] + nb[k] - na[k]) if k not in ("last_parts", "last_variant") else nb[k]
+                                          for k in nb}
         region_s.append(dt)
     dt = statistics.median(region_s)
     timed_iters = args.steps * len(region_s)
-    prof = eng.profile_read(reset=True)
-    pipe_totals = eng.pipeline_stats() if hasattr(eng, "pipeline_stats") else None
-    # untimed extra pass with every phase instrumented, for the per-phase breakdown
-    eng.profile(1)
-    extra_iters = min(10, args.steps)
-    run(extra_iters, rho)
-    prof_all = eng.profile_read(reset=True)
-    for ph, v in prof_all.items():
-        if ph not in ("eig_omega", "eig_omega2", "eig_L"):
-            prof[ph] = v
-    # one more region with the Omega-step iterated to fp64 resolution (GGL_OPT_NS_TOL = 0): the same record then carries
-    # the rate at the accuracy of an eigendecomposition next to the rate at the default stopping tolerance
-    exact = None
-    omega_is_ns = (args.eig == _lib.EIG_NEWTON_SCHULZ) or (args.eig == _lib.EIG_AUTO and p > _lib.NS_MIN_P)
-    if omega_is_ns and not args.no_exact_region and effective_options["ns_tol"] > 5e-16:
-        eng.set_option("ns_tol", 0.0)
-        dte, na, nb, _ = one_region()
-        eng.profile(0)
-        eng.profile_read(reset=True)
-        exact = {"value": args.steps / dte, "ms_per_step": dte / args.steps * 1e3, "ns_tol": 0.0, "regions": 1,
-                 "products_per_step": (nb["units"] - na["units"]) / max(1, nb["calls"] - na["calls"])}
-        eng.set_option("ns_tol", effective_options["ns_tol"])
-    # CPU oracle on this box's host cores (bounded sample) -- and, from the SAME oracle run, the parity of this engine
-    # after the same number of iterations of the same problem (outside every timed region)
-    cpu = parity = None
-    if rank == 0 and not distributed and not args.no_cpu_baseline and is_grid:
-        cpu, parity = grid_cpu_baseline(S1[0], lam_grid, args.cpu_threads, eng, run)
-    elif rank == 0 and not distributed and not args.no_cpu_baseline:
-        cpu, ref = cpu_baseline(S, reg, l1, l2, latent, mu1, args.cpu_iters, args.cpu_threads)
-        eng.profile(0)
-        eng.set_state(Om0, Om0, np.zeros_like(S_loc))
-        run(args.cpu_iters, 1.0)
-        got = eng.state()
-        names = ("Omega", "Theta", "X") + (("L",) if latent else ())
-        parity = {"iters": args.cpu_iters, "against": "oracle/ggl_oracle.py (the cpu_baseline run), identity start, rho rule on",
-                  "max_abs_vs_oracle": max(float(np.abs(got[nm] - ref[nm]).max()) for nm in names),
-                  "theta_fro_vs_oracle": float(np.linalg.norm(got["Theta"] - ref["Theta"])),
-                  "theta_fro": float(np.linalg.norm(ref["Theta"])), "ns_tol": effective_options["ns_tol"],
-                  "tolerance": "north_star: Theta within 1e-8 Frobenius of the reference"}
+    if args.dump_outputs and rank == 0:
+        # every region starts from the same point: the state now is what the last timed step computed
+        st = eng.state()
+        names = ("Omega", "Theta", "X") + (("L",) if latent else ()) if is_grid else ("Omega", "Theta", "L", "X")
+        dump_outputs(args.dump_outputs, {nm: st[nm] for nm in names})
+    prof = pipe_totals = exact = cpu = parity = rank_totals = group_totals = None
+    if args.full:
+        prof = eng.profile_read(reset=True)
+        pipe_totals = eng.pipeline_stats() if hasattr(eng, "pipeline_stats") else None
+        # untimed extra pass with every phase instrumented, for the per-phase breakdown
+        eng.profile(1)
+        extra_iters = min(10, args.steps)
+        run(extra_iters, rho)
+        prof_all = eng.profile_read(reset=True)
+        for ph, v in prof_all.items():
+            if ph not in ("eig_omega", "eig_omega2", "eig_L"):
+                prof[ph] = v
+        # one more region with the Omega-step iterated to fp64 resolution (GGL_OPT_NS_TOL = 0): the same record then carries
+        # the rate at the accuracy of an eigendecomposition next to the rate at the default stopping tolerance
+        omega_is_ns = (args.eig == _lib.EIG_NEWTON_SCHULZ) or (args.eig == _lib.EIG_AUTO and p > _lib.NS_MIN_P)
+        if omega_is_ns and not args.no_exact_region and effective_options["ns_tol"] > 5e-16:
+            eng.set_option("ns_tol", 0.0)
+            dte, na, nb, _ = one_region()
+            eng.profile(0)
+            eng.profile_read(reset=True)
+            exact = {"value": args.steps / dte, "ms_per_step": dte / args.steps * 1e3, "ns_tol": 0.0, "regions": 1,
+                     "products_per_step": (nb["units"] - na["units"]) / max(1, nb["calls"] - na["calls"])}
+            eng.set_option("ns_tol", effective_options["ns_tol"])
+        # CPU oracle on this box's host cores (bounded sample) -- and, from the SAME oracle run, the parity of this engine
+        # after the same number of iterations of the same problem (outside every timed region)
+        if rank == 0 and not distributed and not args.no_cpu_baseline and is_grid:
+            cpu, parity = grid_cpu_baseline(S1[0], lam_grid, args.cpu_threads, eng, run)
+        elif rank == 0 and not distributed and not args.no_cpu_baseline:
+            cpu, ref = cpu_baseline(S, reg, l1, l2, latent, mu1, args.cpu_iters, args.cpu_threads)
+            eng.profile(0)
+            eng.set_state(Om0, Om0, np.zeros_like(S_loc))
+            run(args.cpu_iters, 1.0)
+            got = eng.state()
+            names = ("Omega", "Theta", "X") + (("L",) if latent else ())
+            parity = {"iters": args.cpu_iters, "against": "oracle/ggl_oracle.py (the cpu_baseline run), identity start, rho rule on",
+                      "max_abs_vs_oracle": max(float(np.abs(got[nm] - ref[nm]).max()) for nm in names),
+                      "theta_fro_vs_oracle": float(np.linalg.norm(got["Theta"] - ref["Theta"])),
+                      "theta_fro": float(np.linalg.norm(ref["Theta"])), "ns_tol": effective_options["ns_tol"],
+                      "tolerance": "north_star: Theta within 1e-8 Frobenius of the reference"}
     n_ranks_seen = eng.comm_count() if (distributed and args.comm == "capi") else (world if distributed else 1)
-    rank_totals = eng.rank_stats() if latent else None
-    group_totals = eng.group_stats() if hasattr(eng, "group_stats") else None
+    if args.full:
+        rank_totals = eng.rank_stats() if latent else None
+        group_totals = eng.group_stats() if hasattr(eng, "group_stats") else None
     eng.close()
 
     if rank == 0:
         eig_jacobi = (args.eig == _lib.EIG_JACOBI) or (args.eig == _lib.EIG_AUTO and p <= _lib.NS_MIN_P)
-        phases = {ph: {"ms_per_launch": ms / cnt, "launches": cnt} for ph, (ms, cnt) in prof.items() if cnt}
-        if "eig_omega" in phases and ns1["launches"] > ns0["launches"]:
-            # the Newton-Schulz Omega-step is timed in one event pair (speculative step: no host sync inside) or two
-            # (before / after the spectral-bound sync); either way: total elapsed time / product launches
-            tot = sum(phases[q]["ms_per_launch"] * phases[q]["launches"] for q in ("eig_omega", "eig_omega2")
-                      if q in phases)
-            nl = max(1, ns1["launches"] - ns0["launches"])
-            phases["eig_omega"] = {"ms_per_launch": tot / nl, "launches": nl}
-            phases.pop("eig_omega2", None)
-        hot = ("eig_omega", "eig_L")
-
-        def per_iter(ph):   # hot phases were timed over the timed regions, the others over the extra pass
-            return phases[ph]["ms_per_launch"] * phases[ph]["launches"] / (timed_iters if ph in hot else extra_iters)
-
-        dom = max(phases, key=per_iter)
         omega_ns = (args.eig == _lib.EIG_NEWTON_SCHULZ) or (args.eig == _lib.EIG_AUTO and not eig_jacobi)
-        bound, amount, unit = phase_model(dom, reg, Kl, p, latent, eig_jacobi, omega_ns)
-        # what the library dispatched in its last matrix-function step (ggl_ns_stats), not a copy of its rules
-        parts, variant = ns1["last_parts"], ns1["last_variant"]
-        ns_kernel = VARIANT_NAMES.get(variant, f"product-kernel variant {variant}")
-        kernel_name = {"eig_omega": ns_kernel + (" -- W, bound, schedule and all Newton-Schulz products" if variant == 41 else
-                                                 " -- Newton-Schulz product") if omega_ns else
-                       ("k_jacobi" if eig_jacobi else "rocsolver_dsyevd (library, many kernels)"),
-                       "theta": "k_theta_ggl" if reg == "GGL" else ("k_theta_fgl" if reg == "FGL" else "k_theta_sgl"),
-                       "allreduce_groupsq": "ncclAllReduce p(p+1)/2+1 fp64 (packed upper triangle + flag)", "allreduce_norms": "ncclAllReduce 5 fp64",
-                       "recon_omega": "k_recon", "recon_L": "k_recon", "form_W": "k_form_W",
-                       "dual": "k_dual_update", "eig_L": "k_jacobi" if eig_jacobi else "rocsolver_dsyevd"}.get(dom, dom)
-        sec = phases[dom]["ms_per_launch"] * 1e-3
-        step_amount = None
-        if dom == "eig_L" and omega_ns and ns1["rank_launches"] > ns0["rank_launches"]:
-            # L-step by sign Newton-Schulz: the phase is (2n+1) symmetric products of K p^3 flop each
-            launches = ns1["rank_launches"] - ns0["rank_launches"]
-            kernel_name = ns_kernel + " -- sign Newton-Schulz product, L-step"
-            bound, unit = "mfma", "TFLOP/s"
-            amount = 1.0 * Kl * p ** 3
-            sec = phases[dom]["ms_per_launch"] * phases[dom]["launches"] * 1e-3 / launches
-            phases[dom] = {"ms_per_launch": sec * 1e3, "launches": launches}
-            step_amount = amount * launches / timed_iters
-        if dom == "eig_omega" and omega_ns:
-            # the Omega-step's launches differ in size (a pair launch carries two products): average over
-            # the step = algorithmic flop of all its launches / their total duration (HIP events)
-            units = ns1["units"] - ns0["units"]
-            launches = ns1["launches"] - ns0["launches"]
-            amount = units * 1.0 * Kl * p ** 3 / launches
-            step_amount = units * 1.0 * Kl * p ** 3 / timed_iters
-        if bound == "hbm":
-            achieved, peak, scale = amount / sec / 1e9, HBM_PEAK_GBS, 1e9
-        else:
-            achieved, peak, scale = amount / sec / 1e12, FP64_MFMA_PEAK_TF, 1e12
-        if step_amount is None:
-            step_amount = amount * phases[dom]["launches"] / (timed_iters if dom in hot else extra_iters)
         its = args.steps / dt
-        iter_bytes = (120.0 if latent else 72.0) * Kl * p * p          # SURVEY.md 8(d), per GPU
-        default_cfg = (args.workload == "ggl_K32_p500" and args.eig == 0 and not args.opt)
-        roof = {"kernel": kernel_name, "phase": dom, "launches_per_step": phases[dom]["launches"] / timed_iters,
-                "bound": bound, "achieved": achieved, "peak": peak, "unit": unit, "frac": achieved / peak,
-                # the same algorithmic amount against the WHOLE iteration's wall time (everything that is not this
-                # phase counts as zero work): the figure a reader can check against ms_per_step alone
-                "frac_of_step": step_amount / (dt / args.steps) / scale / peak,
-                "traffic": None,      # HBM counters need separate rocprofv3 --pmc passes: see profiled_* below
-                "ms_per_launch": phases[dom]["ms_per_launch"],
-                "concurrent_launch_sequences": parts if dom in hot else 1,
-                "note": "achieved = algorithmic amount of the phase / its elapsed time (HIP events on the ctx stream, "
-                        "all timed regions); ms_per_launch = that time / the phase's kernel launches"
-                        + ("; the parts of the batch run their launch sequences concurrently, so one kernel's own "
-                           "duration in a rocprofv3 trace is about concurrent_launch_sequences x ms_per_launch"
-                           if (dom in hot and parts > 1) else "")}
-        if default_cfg:
-            # labelled as what they are: numbers of the committed rocprofv3 runs of this command, not of this run
-            roof.update(committed_profile(ns_kernel.split("<")[0]))
-            if "profiled_traffic_bytes" in roof:
-                # HBM bytes per launch of the dominant kernel from the separate --pmc passes of the same command (FETCH_SIZE with
-                # the guide's gfx950 correction for 16-byte-per-lane loads + WRITE_SIZE, tools/summarize_pmc.py): counters cannot
-                # be collected inside this run, so the committed passes' figure stands here with its source beside it
-                roof["traffic"] = roof["profiled_traffic_bytes"]
-                roof["traffic_source"] = roof.get("profiled_traffic_source")
-                roof["traffic_algorithmic_bytes"] = 3 * 8.0 * (Kl / max(parts, 1)) * p * p
         out = {
             "metric": "ADMM iters/sec on (K=32,p=500) GGL at 1/2/4/8 GPUs; eigh HBM GB/s vs peak", "value": its, "unit": "ADMM iters/s",
             "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -540,37 +523,115 @@ def main():
                                              "between regions), then `warmup` untimed iterations",
                               "ms_per_step_min": min(region_s) / args.steps * 1e3,
                               "ms_per_step_max": max(region_s) / args.steps * 1e3},
-            "roofline": roof,
-            "iteration_hbm_roofline": {"algorithmic_bytes": iter_bytes, "achieved_GBs": its * iter_bytes / 1e9,
-                                       "frac": its * iter_bytes / 1e9 / HBM_PEAK_GBS},
-            "phases_ms": {ph: round(v["ms_per_launch"], 4) for ph, v in phases.items()},
-            "phases_ms_per_step": {ph: round(per_iter(ph), 4) for ph in phases},
-            "newton_schulz": {"steps_per_omega_step": (ns1["steps"] - ns0["steps"]) / max(1, ns1["calls"] - ns0["calls"]),
-                              "stable_schedule_calls": ns1["stable_calls"] - ns0["stable_calls"],
-                              "lstep_calls": ns1["rank_calls"] - ns0["rank_calls"],
-                              "lstep_retries": ns1["rank_retries"] - ns0["rank_retries"],
-                              "lstep_eigh_fallbacks": ns1["rank_fallbacks"] - ns0["rank_fallbacks"],
-                              # two-tier L-step, totals since ctx creation (all regions, warm-up included): calls, calls whose
-                              # coarse first pass was continued on a compact sub-batch, instances continued
-                              "lstep_two_tier_totals": rank_totals,
-                              "lstep_products_per_call": (ns1["rank_launches"] - ns0["rank_launches"])
-                              / max(1, ns1["rank_calls"] - ns0["rank_calls"]) if latent else None,
-                              "speculative_omega_steps": ns1["spec_calls"] - ns0["spec_calls"],
-                              "speculation_misses": ns1["spec_misses"] - ns0["spec_misses"],
-                              "prelaunched_chains_dropped": ns1["pre_dropped"] - ns0["pre_dropped"],
-                              # totals since ctx creation: whole chains launched ahead / forgotten, early first parts / continued
-                              "pipeline_totals": pipe_totals,
-                              "end_of_iteration_poll_timeouts": ns1["spin_timeouts"] - ns0["spin_timeouts"],
-                              # GGL_OPT_GROUP_SCHED (totals since ctx creation): Omega-steps that ran as contiguous groups with
-                              # their own schedules, the split and the product units (A', B' included) of the last such step,
-                              # mean units per group slot over the grouped steps
-                              "group_schedules": (lambda g: {"grouped_steps": g["steps"], "last_groups": g["len"],
-                                                             "last_products_per_group": g["units"],
-                                                             "mean_products_per_group": [round(u / max(1, g["steps"]), 3)
-                                                                                         for u in g["units_sum"][:max(len(g["len"]), 1)]]})
-                              (group_totals) if group_totals else None}
-            if omega_ns else None,
         }
+        if args.full:
+            phases = {ph: {"ms_per_launch": ms / cnt, "launches": cnt} for ph, (ms, cnt) in prof.items() if cnt}
+            if "eig_omega" in phases and ns1["launches"] > ns0["launches"]:
+                # the Newton-Schulz Omega-step is timed in one event pair (speculative step: no host sync inside) or two
+                # (before / after the spectral-bound sync); either way: total elapsed time / product launches
+                tot = sum(phases[q]["ms_per_launch"] * phases[q]["launches"] for q in ("eig_omega", "eig_omega2")
+                          if q in phases)
+                nl = max(1, ns1["launches"] - ns0["launches"])
+                phases["eig_omega"] = {"ms_per_launch": tot / nl, "launches": nl}
+                phases.pop("eig_omega2", None)
+            hot = ("eig_omega", "eig_L")
+
+            def per_iter(ph):   # hot phases were timed over the timed regions, the others over the extra pass
+                return phases[ph]["ms_per_launch"] * phases[ph]["launches"] / (timed_iters if ph in hot else extra_iters)
+
+            dom = max(phases, key=per_iter)
+            bound, amount, unit = phase_model(dom, reg, Kl, p, latent, eig_jacobi, omega_ns)
+            # what the library dispatched in its last matrix-function step (ggl_ns_stats), not a copy of its rules
+            parts, variant = ns1["last_parts"], ns1["last_variant"]
+            ns_kernel = VARIANT_NAMES.get(variant, f"product-kernel variant {variant}")
+            kernel_name = {"eig_omega": ns_kernel + (" -- W, bound, schedule and all Newton-Schulz products" if variant == 41 else
+                                                     " -- Newton-Schulz product") if omega_ns else
+                           ("k_jacobi" if eig_jacobi else "rocsolver_dsyevd (library, many kernels)"),
+                           "theta": "k_theta_ggl" if reg == "GGL" else ("k_theta_fgl" if reg == "FGL" else "k_theta_sgl"),
+                           "allreduce_groupsq": "ncclAllReduce p(p+1)/2+1 fp64 (packed upper triangle + flag)", "allreduce_norms": "ncclAllReduce 5 fp64",
+                           "recon_omega": "k_recon", "recon_L": "k_recon", "form_W": "k_form_W",
+                           "dual": "k_dual_update", "eig_L": "k_jacobi" if eig_jacobi else "rocsolver_dsyevd"}.get(dom, dom)
+            sec = phases[dom]["ms_per_launch"] * 1e-3
+            step_amount = None
+            if dom == "eig_L" and omega_ns and ns1["rank_launches"] > ns0["rank_launches"]:
+                # L-step by sign Newton-Schulz: the phase is (2n+1) symmetric products of K p^3 flop each
+                launches = ns1["rank_launches"] - ns0["rank_launches"]
+                kernel_name = ns_kernel + " -- sign Newton-Schulz product, L-step"
+                bound, unit = "mfma", "TFLOP/s"
+                amount = 1.0 * Kl * p ** 3
+                sec = phases[dom]["ms_per_launch"] * phases[dom]["launches"] * 1e-3 / launches
+                phases[dom] = {"ms_per_launch": sec * 1e3, "launches": launches}
+                step_amount = amount * launches / timed_iters
+            if dom == "eig_omega" and omega_ns:
+                # the Omega-step's launches differ in size (a pair launch carries two products): average over
+                # the step = algorithmic flop of all its launches / their total duration (HIP events)
+                units = ns1["units"] - ns0["units"]
+                launches = ns1["launches"] - ns0["launches"]
+                amount = units * 1.0 * Kl * p ** 3 / launches
+                step_amount = units * 1.0 * Kl * p ** 3 / timed_iters
+            if bound == "hbm":
+                achieved, peak, scale = amount / sec / 1e9, HBM_PEAK_GBS, 1e9
+            else:
+                achieved, peak, scale = amount / sec / 1e12, FP64_MFMA_PEAK_TF, 1e12
+            if step_amount is None:
+                step_amount = amount * phases[dom]["launches"] / (timed_iters if dom in hot else extra_iters)
+            iter_bytes = (120.0 if latent else 72.0) * Kl * p * p          # SURVEY.md 8(d), per GPU
+            default_cfg = (args.workload == "ggl_K32_p500" and args.eig == 0 and not args.opt)
+            roof = {"kernel": kernel_name, "phase": dom, "launches_per_step": phases[dom]["launches"] / timed_iters,
+                    "bound": bound, "achieved": achieved, "peak": peak, "unit": unit, "frac": achieved / peak,
+                    # the same algorithmic amount against the WHOLE iteration's wall time (everything that is not this
+                    # phase counts as zero work): the figure a reader can check against ms_per_step alone
+                    "frac_of_step": step_amount / (dt / args.steps) / scale / peak,
+                    "traffic": None,      # HBM counters need separate rocprofv3 --pmc passes: see profiled_* below
+                    "ms_per_launch": phases[dom]["ms_per_launch"],
+                    "concurrent_launch_sequences": parts if dom in hot else 1,
+                    "note": "achieved = algorithmic amount of the phase / its elapsed time (HIP events on the ctx stream, "
+                            "all timed regions); ms_per_launch = that time / the phase's kernel launches"
+                            + ("; the parts of the batch run their launch sequences concurrently, so one kernel's own "
+                               "duration in a rocprofv3 trace is about concurrent_launch_sequences x ms_per_launch"
+                               if (dom in hot and parts > 1) else "")}
+            if default_cfg:
+                # labelled as what they are: numbers of the committed rocprofv3 runs of this command, not of this run
+                roof.update(committed_profile(ns_kernel.split("<")[0]))
+                if "profiled_traffic_bytes" in roof:
+                    # HBM bytes per launch of the dominant kernel from the separate --pmc passes of the same command (FETCH_SIZE with
+                    # the guide's gfx950 correction for 16-byte-per-lane loads + WRITE_SIZE, tools/summarize_pmc.py): counters cannot
+                    # be collected inside this run, so the committed passes' figure stands here with its source beside it
+                    roof["traffic"] = roof["profiled_traffic_bytes"]
+                    roof["traffic_source"] = roof.get("profiled_traffic_source")
+                    roof["traffic_algorithmic_bytes"] = 3 * 8.0 * (Kl / max(parts, 1)) * p * p
+            out.update({
+                "roofline": roof,
+                "iteration_hbm_roofline": {"algorithmic_bytes": iter_bytes, "achieved_GBs": its * iter_bytes / 1e9,
+                                           "frac": its * iter_bytes / 1e9 / HBM_PEAK_GBS},
+                "phases_ms": {ph: round(v["ms_per_launch"], 4) for ph, v in phases.items()},
+                "phases_ms_per_step": {ph: round(per_iter(ph), 4) for ph in phases},
+                "newton_schulz": {"steps_per_omega_step": (ns1["steps"] - ns0["steps"]) / max(1, ns1["calls"] - ns0["calls"]),
+                                  "stable_schedule_calls": ns1["stable_calls"] - ns0["stable_calls"],
+                                  "lstep_calls": ns1["rank_calls"] - ns0["rank_calls"],
+                                  "lstep_retries": ns1["rank_retries"] - ns0["rank_retries"],
+                                  "lstep_eigh_fallbacks": ns1["rank_fallbacks"] - ns0["rank_fallbacks"],
+                                  # two-tier L-step, totals since ctx creation (all regions, warm-up included): calls, calls whose
+                                  # coarse first pass was continued on a compact sub-batch, instances continued
+                                  "lstep_two_tier_totals": rank_totals,
+                                  "lstep_products_per_call": (ns1["rank_launches"] - ns0["rank_launches"])
+                                  / max(1, ns1["rank_calls"] - ns0["rank_calls"]) if latent else None,
+                                  "speculative_omega_steps": ns1["spec_calls"] - ns0["spec_calls"],
+                                  "speculation_misses": ns1["spec_misses"] - ns0["spec_misses"],
+                                  "prelaunched_chains_dropped": ns1["pre_dropped"] - ns0["pre_dropped"],
+                                  # totals since ctx creation: whole chains launched ahead / forgotten, early first parts / continued
+                                  "pipeline_totals": pipe_totals,
+                                  "end_of_iteration_poll_timeouts": ns1["spin_timeouts"] - ns0["spin_timeouts"],
+                                  # GGL_OPT_GROUP_SCHED (totals since ctx creation): Omega-steps that ran as contiguous groups with
+                                  # their own schedules, the split and the product units (A', B' included) of the last such step,
+                                  # mean units per group slot over the grouped steps
+                                  "group_schedules": (lambda g: {"grouped_steps": g["steps"], "last_groups": g["len"],
+                                                                 "last_products_per_group": g["units"],
+                                                                 "mean_products_per_group": [round(u / max(1, g["steps"]), 3)
+                                                                                             for u in g["units_sum"][:max(len(g["len"]), 1)]]})
+                                  (group_totals) if group_totals else None}
+                if omega_ns else None,
+            })
         if exact is not None:
             out["value_exact"] = exact
         if distributed:

@@ -80,7 +80,7 @@ def test_bench_bare_start_on_two_gpus():
     """``python bench.py --gpus 2`` with no launcher and no WORLD_SIZE: starts its own two ranks."""
     if _n_gpus() < 2:
         pytest.skip("needs two GPUs")
-    line = _bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--regions", "2"])
+    line = _bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--regions", "2", "--full"])
     assert line["n_gpus"] == 2 and line["n_ranks_seen"] == 2 and line["scaling"] == "strong", line
     assert line["roofline"]["frac"] > 0 and "K-slabs of 16" in line["config"]["sharding"], line
 

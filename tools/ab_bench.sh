@@ -10,7 +10,7 @@ cd $R
 for r in $(seq 1 $ROUNDS); do
   i=0
   for cfg in "$@"; do
-    python bench.py --no-cpu-baseline --steps 60 --warmup 10 $cfg 2>/dev/null | grep "^{" >> $O/cfg$i.jsonl
+    python bench.py --full --no-cpu-baseline --steps 60 --warmup 10 $cfg 2>/dev/null | grep "^{" >> $O/cfg$i.jsonl
     i=$((i+1))
   done
 done

@@ -18,7 +18,7 @@ for r in $(seq 1 $ROUNDS); do
     if [ $side = A ]; then cp $LA gglasso_amd/lib/libggl_hip.so; else cp $LB gglasso_amd/lib/libggl_hip.so; fi
     i=0
     for cfg in "$@"; do
-      python bench.py --no-cpu-baseline --steps 60 --warmup 10 $cfg 2>/dev/null | grep "^{" >> $O/$side$i.jsonl
+      python bench.py --full --no-cpu-baseline --steps 60 --warmup 10 $cfg 2>/dev/null | grep "^{" >> $O/$side$i.jsonl
       i=$((i+1))
     done
   done

@@ -8,5 +8,5 @@ mkdir -p $O
 cd $R
 ( time python -m pytest tests -m gpu -q -x --durations=15 "$@" ) > $O/pytest_gpu.txt 2>&1
 tail -30 $O/pytest_gpu.txt
-python bench.py --no-cpu-baseline > $O/bench.log 2>&1
+python bench.py --full --no-cpu-baseline > $O/bench.log 2>&1
 grep "^{" $O/bench.log | head -c 1500
