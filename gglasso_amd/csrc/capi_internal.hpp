@@ -209,6 +209,10 @@ struct ggl_ctx {
         double* fused[4] = {nullptr, nullptr, nullptr, nullptr};
         double* beta = nullptr;                       // (K) beta the part was built for
         int nh = 0, Kh[4] = {}, k0h[4] = {};          // the split the part was launched with (the rest must use the same)
+        // ... and how it was launched: groups with their own schedules, and the product-kernel variant of the parts, which
+        // also fixes the tile layout of the bound partials the part's B' launch left behind
+        bool grouped = false;
+        int var_parts = -1;
     } early;
     bool early_part = true;                           // GGL_OPT_EARLY_PART
     GGL_DEV_OPT(int, part_priority);                  // GGL_OPT_PART_PRIORITY

@@ -388,6 +388,7 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool 
         int gunits[ggl_ctx::MAX_PARTS] = {};
         if (resume) {
             nh = c->early.nh;
+            grouped = c->early.grouped;
             for (int h = 0; h < nh; ++h) { Kh[h] = c->early.Kh[h]; k0h[h] = c->early.k0h[h]; }
         } else {
             for (int h = 0, k0 = 0; h < nh; ++h) {
@@ -412,7 +413,12 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool 
         // (the instance the WHOLE batch would take -- the groups share the chip -- with three DMA stages where that is the
         // 64x64 kernel, as for any concurrent parts)
         const int var_grouped = c->symm_variant >= 0 ? c->symm_variant : (symm_auto_variant(K, c->p) == 16 ? 17 : symm_auto_variant(K, c->p));
-        const int var_parts = grouped ? var_grouped
+        // (resume: the variant of the early part -- its B' launch laid out the bound partials the rest reads, by that tile size.
+        // Everything else the rest derives again below is fixed by the restored split and by options, which cannot change
+        // between the two halves: both are launched inside one ggl_admm_step call, with only the validation of the previous
+        // iteration in between, which advances the Collatz-Wielandt vector the rest is meant to read.)
+        const int var_parts = resume ? c->early.var_parts
+                            : grouped ? var_grouped
                                       : ((c->symm_variant < 0 && nh > 1 && K >= 16) ? 17 : c->symm_variant);
         c->last_parts = nh;
         c->last_variant = symm_effective_variant(var_parts >= 0 ? var_parts : symm_auto_variant(Kh[0], c->p), c->p);
@@ -799,6 +805,8 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool 
         if (want_A) {
             for (int h = 0; h < nh; ++h) { c->early.plans[h] = plans[h]; c->early.fused[h] = fused[h]; c->early.Kh[h] = Kh[h]; c->early.k0h[h] = k0h[h]; }
             c->early.nh = nh;
+            c->early.grouped = grouped;
+            c->early.var_parts = var_parts;
             memcpy(c->early.beta, c->par_h, K * sizeof(double));
             c->early.valid = true;
             c->early_launched += 1;

@@ -87,26 +87,37 @@ def test_grouping_leaves_uniform_batches_and_small_launches_alone():
 def test_grouped_mgl_step_with_early_part_is_consistent():
     """ggl_admm_step with heterogeneous instances (an FGL-less GGL problem whose instances are scaled differently): the early
     first part of the next chain and the rest that follows it use the SAME split, and the iterates agree with the ungrouped
-    run to the Omega-step's tolerance and with the oracle to 1e-9."""
+    run to the Omega-step's tolerance and with the oracle to 1e-9.  With the reference's rho rule (admm_solver.py:227-233):
+    the residual ratio settles, so that early parts are launched and continued (with rho fixed at 1 for 12 iterations, only
+    one early part was continued)."""
     from gglasso_amd import solver
     from oracle import ggl_oracle as orc
-    K, p, iters = 6, 256, 12
+    K, p, iters = 6, 256, 40
     S = _problem(K, p, 47) * np.array([0.2, 0.4, 0.7, 1.0, 1.6, 2.5])[:, None, None]
     eye = np.repeat(np.eye(p)[None], K, axis=0)
     out = {}
     for name, opt in (("grouped", 13.0), ("whole", 0.0)):
         eng = solver.HipEngine(S, eye, eye, np.zeros_like(S), options={"group_sched": opt})
         try:
+            rho, rhos = 1.0, []
             for _ in range(iters):
-                eng.step(1.0, 0.05, 0.02, "GGL", False, None, np.ones(K))
-            out[name] = (eng.state(), eng.group_stats(), eng.pipeline_stats())
+                rhos.append(rho)
+                sq = eng.step(rho, 0.05, 0.02, "GGL", False, None, np.ones(K)).copy()
+                r_t, s_t, _, _ = solver.residuals_from_norms(sq, rho, 1e-20, 1e-20, 1.0)
+                new = solver.next_rho(rho, r_t, s_t)
+                if new != rho:
+                    eng.scale_X(rho / new)
+                rho = new
+            out[name] = (eng.state(), eng.group_stats(), eng.pipeline_stats(), rhos)
         finally:
             eng.close()
+    assert out["grouped"][3] == out["whole"][3]
     assert out["grouped"][1]['steps'] >= 3, out["grouped"][1]
+    assert out["grouped"][2]['early_used'] >= 3, out["grouped"][2]          # (the early part ran, and was continued)
     assert out["whole"][1]['steps'] == 0
     for nm in ("Omega", "Theta", "X"):
         assert np.abs(out["grouped"][0][nm] - out["whole"][0][nm]).max() <= 1e-10, nm
-    ref, _ = orc.ADMM_MGL(S, 0.05, 0.02, "GGL", eye, max_iter=iters, tol=1e-20, rtol=1e-20, update_rho=False)
+    ref, _ = orc.ADMM_MGL(S, 0.05, 0.02, "GGL", eye, max_iter=iters, tol=1e-20, rtol=1e-20)
     for nm in ("Omega", "Theta", "X"):
         assert np.abs(out["grouped"][0][nm] - ref[nm]).max() <= 1e-9, nm
 
