@@ -397,6 +397,10 @@ static int set_option(ggl_ctx* c, int opt, double v)
                 return fail(GGL_E_ARG, "bad argument: GGL_OPT_GROUP_SCHED is 0, 1, 2, 3, 12 or 13");
             c->group_sched = (int)v;
             break;
+        case GGL_OPT_OMEGA_POLY:
+            if (v != 0.0 && v != 1.0) return fail(GGL_E_ARG, "bad argument: GGL_OPT_OMEGA_POLY is 0 or 1");
+            c->omega_poly = (int)v;
+            break;
 #ifdef GGL_DEV
         case GGL_OPT_PARTS_BIAS: c->parts_bias = (int)v; break;
         case GGL_OPT_PARTS_ORDER: c->parts_order = (int)v; break;
@@ -488,6 +492,7 @@ extern "C" int ggl_ctx_get_option(ggl_ctx* c, int opt, double* value)
         case GGL_OPT_FUSED_START: *value = c->fused_start; break;
         case GGL_OPT_PARTS_SMALL: *value = c->parts_small; break;
         case GGL_OPT_GROUP_SCHED: *value = c->group_sched; break;
+        case GGL_OPT_OMEGA_POLY: *value = c->omega_poly; break;
         case GGL_OPT_PARTS_BIAS: *value = c->parts_bias; break;
         case GGL_OPT_PARTS_ORDER: *value = c->parts_order; break;
         case GGL_OPT_DOWNLOAD_THREADS: *value = c->download_threads; break;

@@ -164,6 +164,11 @@ struct ggl_ctx {
     long long group_changes = 0;               // ... whose split differed from the previous grouped step's
     int last_groups = 1, last_group_len[MAX_PARTS] = {}, last_group_units[MAX_PARTS] = {};
     double group_units_sum[MAX_PARTS] = {};    // per group slot: product units summed over the grouped steps
+    // GGL_OPT_OMEGA_POLY: a launch sequence of the Omega-step whose interval and tolerance make one direct polynomial in A'
+    // strictly cheaper than the Newton-Schulz schedule runs that polynomial (ns_plan); 0 = Newton-Schulz everywhere
+    int omega_poly = 1;
+    long long poly_seqs = 0, poly_seqs_total = 0;   // launch sequences that ran the direct family / all of them
+    int poly_last_deg = 0;                     // degree of the last direct polynomial
     int parts_small = 8;                       // smallest K (< 16, p >= 384) that is split into two concurrent parts; 0 = never
                                                // (measured at p = 500: K = 8 +7.6 % iterations/s as 4 + 4, K = 4 -2.4 % as 2 + 2)
     bool fused_start = true;                   // speculative step: first step's start matrix as 2nd output of the B' launch

@@ -266,6 +266,13 @@ void trace_host(ggl_ctx* c, int tag)
 }
 void trace_symm_hook(hipStream_t st, int kind, void* arg) { trace_mark((ggl_ctx*)arg, st, 10 + kind); }
 
+// GGL_OPT_OMEGA_POLY: which family a launch sequence of the Omega-step ran (ggl_omega_poly_stats)
+static void note_family(ggl_ctx* c, const NsPlan& pl)
+{
+    c->poly_seqs_total += 1;
+    if (pl.direct) { c->poly_seqs += 1; c->poly_last_deg = pl.direct; }
+}
+
 // GGL_OPT_GROUP_SCHED: contiguous groups of a batch whose instances need different product counts (ns_group_partition).
 // cb[k] >= lambda_max(A'_k), beta_k = nk/rho.  Returns the number of groups (1: the batch stays whole, Kh / k0h untouched).
 static int omega_groups(const ggl_ctx* c, const double* cb, const double* beta_h, int K, int* Kh, int* k0h, int* gunits)
@@ -356,8 +363,8 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool 
         for (int k = 0; !resume && k < K; ++k) {
             double* o0 = pre + (size_t)k * NS_NCOEF;
             double* o1 = pre + NS_SLOT(K) + (size_t)k * NS_NCOEF;
-            o0[0] = 4.0 * c->par_h[k]; o0[1] = 1.0; o0[2] = o0[3] = o0[4] = o0[5] = 0.0;
-            o1[0] = 0.0; o1[1] = 1.0; o1[2] = o1[3] = o1[4] = o1[5] = 0.0;
+            o0[0] = 4.0 * c->par_h[k]; o0[1] = 1.0; o0[2] = o0[3] = o0[4] = o0[5] = o0[6] = o0[7] = 0.0;
+            o1[0] = 0.0; o1[1] = 1.0; o1[2] = o1[3] = o1[4] = o1[5] = o1[6] = o1[7] = 0.0;
         }
         double* pre_d = c->coef + (size_t)(NS_MAX_LAUNCHES - 2) * NS_SLOT(K);
         // Parts of the batch on concurrent streams: while one part's product drains its output and the next
@@ -532,12 +539,12 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool 
             SymmOp ops[CHAIN_MAX_OPS];
             int nops = 0;
             const int bT = (c->p + 63) / 64;
-            if (ns_plan(c->cuse_h, c->par_h, K, c->coef_h, start_base_h, &pl, c->ns_force, c->ns_degrees, c->ns_tol) == 0 &&
+            if (ns_plan(c->cuse_h, c->par_h, K, c->coef_h, start_base_h, &pl, c->ns_force, c->ns_degrees, c->ns_tol, c->omega_poly) == 0 &&
                 !pl.stable) {
                 double* f0 = nullptr;
                 for (int k = 0; k < K; ++k)
                     f0 = ns_fused_start(pl, start_base_h + 5 * (size_t)k, c->nsYP[1], c->nsT, (size_t)K * pp,
-                                        pre + NS_SLOT(K) + (size_t)k * NS_NCOEF + 3);
+                                        pre + NS_SLOT(K) + (size_t)k * NS_NCOEF);
                 if (f0)
                     nops = ns_chain_ops(pl, pre_d, pre_d + NS_SLOT(K), c->coef, c->W, c->nsYP[0], c->nsYP[1], c->nsNX, c->nsT,
                                         c->Om[nxt], K, c->p, 0, f0, c->rowpart, c->fropart, ops, CHAIN_MAX_OPS);
@@ -579,6 +586,7 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool 
                 c->last_variant = 40;
                 c->chain_calls += 1;
                 c->ns_launches_total += pl.products;
+                note_family(c, pl);
                 c->ns_units_frac += pl.units;
                 c->ns_steps_frac += pl.steps;
                 c->ns_units_total = (long long)(c->ns_units_frac + 0.5);
@@ -603,12 +611,12 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool 
             for (int h = 0; spec && h < nh; ++h) {
                 const int k0 = k0h[h];
                 const int prc = ns_plan(c->cuse_h + k0, c->par_h + k0, Kh[h], c->coef_h + h * region,
-                                        start_base_h + 5 * k0, &plans[h], c->ns_force, c->ns_degrees, c->ns_tol);
+                                        start_base_h + 5 * k0, &plans[h], c->ns_force, c->ns_degrees, c->ns_tol, c->omega_poly);
                 spec = (prc == 0) && !plans[h].stable;
                 for (int k = k0; spec && c->fused_start && k < k0 + Kh[h]; ++k) {
                     // the bound is assumed known, so the start is a fixed combination of A' and B': {dI, dC, dE} of B' launch
                     fused[h] = ns_fused_start(plans[h], start_base_h + 5 * (size_t)k, c->nsYP[1] + k0 * pp, c->nsT + k0 * pp,
-                                              nh > 1 ? c->n : (size_t)K * pp, pre + NS_SLOT(K) + (size_t)k * NS_NCOEF + 3);
+                                              nh > 1 ? c->n : (size_t)K * pp, pre + NS_SLOT(K) + (size_t)k * NS_NCOEF);
                 }
             }
         }
@@ -712,7 +720,7 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool 
             // the direct-to-LDS kernel, its epilogue leaves the row sums and Frobenius shares of B' behind (no norm pass
             // over B'), and the Collatz-Wielandt pass finishes the bound itself.
             ns_prepare(sh, pre_d + NS_NCOEF * (size_t)k0, pre_d + NS_SLOT(K) + NS_NCOEF * (size_t)k0, c->W + k0 * pp, Ap, Bp, Kh[h], c->p,
-                       var_parts, spec ? fused[h] : nullptr, rowp, frop);
+                       var_parts, spec ? fused[h] : nullptr, rowp, frop, plans[h].direct != 0);
             symm_flush_rider(sh);
             if (early_ev) {
                 (void)hipEventRecord(c->ev_early[c->ev_early_par][1], c->stream);
@@ -795,6 +803,7 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool 
                        var_parts, nh > 1 ? c->n : 0, fused[h] != nullptr, bfree);
                 symm_flush_rider(sh);                     // (a chain without a direct-to-LDS product launch: its own launch)
                 c->ns_launches_total += plans[h].products;
+                note_family(c, plans[h]);
                 const double frac = (double)Kh[h] / K;
                 c->ns_units_frac += frac * plans[h].units;
                 c->ns_steps_frac += frac * plans[h].steps;
@@ -866,7 +875,7 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool 
         for (int h = 0; h < nh; ++h) {
             const int k0 = k0h[h];
             const int prc = ns_plan(c->bounds_h + k0, c->par_h + k0, Kh[h], c->coef_h + h * region_b, start_base_h + 5 * k0,
-                                    &plans[h], c->ns_force, c->ns_degrees, c->ns_tol);
+                                    &plans[h], c->ns_force, c->ns_degrees, c->ns_tol, c->omega_poly);
             if (prc == -1) return fail(GGL_E_SOLVER, "Newton-Schulz Omega-step: non-finite W (diverged iterate?)");
             if (prc == -2) {
                 // pathological scaling (|W|^2 rho / nk > 1e12): eigendecomposition of the (still intact) W
@@ -881,7 +890,8 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool 
         }
         if (nh > 1 && any_stable) {
             // the stable schedule multiplies a contiguous [Y|P] pair: run the whole batch as one sequence
-            const int prc = ns_plan(c->bounds_h, c->par_h, K, c->coef_h, start_base_h, &plans[0], c->ns_force, c->ns_degrees, c->ns_tol);
+            const int prc = ns_plan(c->bounds_h, c->par_h, K, c->coef_h, start_base_h, &plans[0], c->ns_force, c->ns_degrees, c->ns_tol,
+                                    c->omega_poly);
             if (prc != 0) return fail(GGL_E_SOLVER, "Newton-Schulz Omega-step: plan failed (%d)", prc);
         }
         const int nrun = (nh > 1 && !any_stable) ? nh : 1;
@@ -909,6 +919,7 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool 
                    nrun > 1 ? var_b : c->symm_variant, nrun > 1 ? c->n : 0);
             c->ns_stable_calls += plans[h].stable ? 1 : 0;
             c->ns_launches_total += plans[h].products;
+            note_family(c, plans[h]);
             // algorithmic work in units of (whole-stack) K p^3 flop
             const double frac = (double)Kr / K;
             c->ns_units_frac += frac * plans[h].units;

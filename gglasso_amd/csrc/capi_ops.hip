@@ -784,6 +784,16 @@ extern "C" int ggl_dev_group_partition(const int* units, int K, int p, int max_g
     return ns_group_partition(units, K, p, max_groups, len_out);
 }
 extern "C" int ggl_dev_ns_units(double l, int degrees, double tol) { return ns_units_query(l, degrees, tol); }
+// host only: the direct family of the Omega-step for the spectral interval [a, 1] of A'/c (GGL_OPT_OMEGA_POLY): out[0..15]
+// the monomial coefficients of p in X = (A'/c - m I)/h, m = (1+a)/2, h = (1-a)/2, for the QUANTISED a (out[16]), out[17] its
+// certified relative deviation; *deg its degree (0: none up to 15 meets tol), *units its products (A', B' included, -1: none).
+// Returns 1 where an Omega-step launch sequence with this interval takes the direct family (strictly fewer products than
+// the Newton-Schulz schedule of degrees / tol), 0 where it keeps Newton-Schulz, < 0 for a bad argument.
+extern "C" int ggl_dev_omega_poly_plan(double a, double tol, int degrees, int* deg, double* out, int* units)
+{
+    ARGCHK(deg && out && units && a > 0.0 && a < 1.0, "deg, out, units, 0 < a < 1");
+    return ns_poly_query(std::sqrt(a), degrees, tol, deg, out, units, out + 16, out + 17);
+}
 
 extern "C" int ggl_dev_ns_schedule_tol(double l, int degrees, double tol, int max_steps, int* deg_out, double* coef_out,
                                        int* units_out)

@@ -49,6 +49,17 @@ extern "C" int ggl_ns_stats(ggl_ctx* c, long long out[16])
     return GGL_OK;
 }
 
+// GGL_OPT_OMEGA_POLY: { launch sequences of the Omega-step that ran the direct family, launch sequences in all, degree of the
+// last direct polynomial }
+extern "C" int ggl_omega_poly_stats(ggl_ctx* c, long long out[3])
+{
+    ARGCHK(c && out, "ctx, out");
+    out[0] = c->poly_seqs;
+    out[1] = c->poly_seqs_total;
+    out[2] = c->poly_last_deg;
+    return GGL_OK;
+}
+
 // The LDS-resident Omega-step: { launches, launches an instance fell outside the kernel's range (step repeated on the launch
 // chain), products summed over all instances of all launches, Newton-Schulz steps likewise }.  Waits for the stream.
 // GGL_OPT_GROUP_SCHED: out = { Omega-steps that ran as groups with their own schedules, groups of the last step (1: whole),

@@ -27,6 +27,12 @@ typedef double v4d __attribute__((ext_vector_type(4)));
 // second output of a product launch, C2 = dI I + dC C + dE E: one fixed evaluation order at every store site (upper
 // triangle, diagonal-tile mirror, LDS-transposed mirror), so that the output is bitwise symmetric
 __device__ __forceinline__ double c2val(double dC, double v, double dE, double e) { return __builtin_fma(dE, e, dC * v); }
+// ... with the second affine operand E2 (present: has2) added last: C2 = dI I + dC C + dE E + dE2 E2
+__device__ __forceinline__ double c2val2(double dC, double v, double dE, double e, bool has2, double dE2, double f)
+{
+    const double w = c2val(dC, v, dE, e);
+    return has2 ? __builtin_fma(dE2, f, w) : w;
+}
 
 template <int BM, int BK, int WM, int WN, bool LM>
 struct SymCfg {
@@ -105,7 +111,8 @@ template <int BM, int BK, int WM, int WN, bool LM, int ABL = 0>
 __global__ __launch_bounds__(sym_nt(BM, WM, WN)) void k_symm_tn(
     const double* __restrict__ A, const double* __restrict__ B, double* __restrict__ C, double* __restrict__ C2,
     const double* __restrict__ E, const double* __restrict__ coef, int K, int p, const double* __restrict__ A1,
-    const double* __restrict__ B1, double* __restrict__ C1, int K1, double* __restrict__ maxdev)
+    const double* __restrict__ B1, double* __restrict__ C1, int K1, double* __restrict__ maxdev,
+    const double* __restrict__ E2)
 {
     // maxdev != null: maxdev[k] = max over the instance of |C - I| (atomic max on the bit pattern of a
     // non-negative double: order independent, hence deterministic).
@@ -231,6 +238,8 @@ __global__ __launch_bounds__(sym_nt(BM, WM, WN)) void k_symm_tn(
     double* Ck = (second ? C1 : C) + (size_t)kk * pp;
     double* C2k = (C2 && !second) ? C2 + (size_t)kk * pp : nullptr;
     const double* Ek = (E && !second) ? E + (size_t)kk * pp : nullptr;
+    const double* E2k = (E2 && !second) ? E2 + (size_t)kk * pp : nullptr;     // second affine operand, added last
+    const double cE2 = E2k ? coef[k * NS_NCOEF + 6] : 0.0, dE2 = E2k ? coef[k * NS_NCOEF + 7] : 0.0;
 #pragma unroll
     for (int ti = 0; ti < Cfg::TI; ++ti)
 #pragma unroll
@@ -246,14 +255,16 @@ __global__ __launch_bounds__(sym_nt(BM, WM, WN)) void k_symm_tn(
                     if (gi == gj) v += cI;
                     const double e0 = Ek ? Ek[(size_t)gi * p + gj] : 0.0;
                     v += cE * e0;
+                    const double f0 = E2k ? E2k[(size_t)gi * p + gj] : 0.0;
+                    if (E2k) v += cE2 * f0;
                     Ck[(size_t)gi * p + gj] = v;
-                    if (C2k) C2k[(size_t)gi * p + gj] = c2val(dC, v, dE, e0) + (gi == gj ? dI : 0.0);
+                    if (C2k) C2k[(size_t)gi * p + gj] = c2val2(dC, v, dE, e0, E2k != nullptr, dE2, f0) + (gi == gj ? dI : 0.0);
                     // mirrored store.  Diagonal tiles: only the upper triangle is kept, so the result is
                     // bitwise symmetric even though A != B.  Off-diagonal tiles without the LDS transpose:
                     // the four r-values of a lane quad complete a 128-B line.
                     if ((I == J && gi != gj) || (!LM && I != J)) {
                         Ck[(size_t)gj * p + gi] = v;
-                        if (C2k) C2k[(size_t)gj * p + gi] = c2val(dC, v, dE, e0);
+                        if (C2k) C2k[(size_t)gj * p + gi] = c2val2(dC, v, dE, e0, E2k != nullptr, dE2, f0);
                     }
                 }
                 if (LM && I != J) smem[row * Cfg::CLD + col] = v;
@@ -271,6 +282,7 @@ __global__ __launch_bounds__(sym_nt(BM, WM, WN)) void k_symm_tn(
                     if (gi < p && gj < p && (I != J || gi <= gj)) {
                         double v = cAcc * acc[ti][tj][r] + (gi == gj ? cI - 1.0 : 0.0);
                         if (Ek) v += cE * Ek[(size_t)gi * p + gj];      // the deviation of the OUTPUT, E term included
+                        if (E2k) v += cE2 * E2k[(size_t)gi * p + gj];
                         dev = fmax(dev, fabs(v));
                     }
                 }
@@ -288,7 +300,8 @@ __global__ __launch_bounds__(sym_nt(BM, WM, WN)) void k_symm_tn(
                 if (C2k) {
                     // E is bitwise symmetric (an output of this kernel family): its mirrored entry IS the upper one
                     const double e0 = (dE != 0.0 && Ek) ? Ek[(size_t)(J0 + a) * p + I0 + c] : 0.0;
-                    C2k[(size_t)(J0 + a) * p + I0 + c] = c2val(dC, v, dE, e0);
+                    const double f0 = E2k ? E2k[(size_t)(J0 + a) * p + I0 + c] : 0.0;
+                    C2k[(size_t)(J0 + a) * p + I0 + c] = c2val2(dC, v, dE, e0, E2k != nullptr, dE2, f0);
                 }
             }
         }
@@ -308,12 +321,12 @@ __global__ __launch_bounds__(sym_nt(BM, WM, WN)) void k_symm_tn(
 template <int BM, int BK, int WM, int WN, bool LM>
 static void launch_cfg(hipStream_t st, const double* A, const double* B, double* C, double* C2, const double* E,
                        const double* coef, int K, int p, const double* A1 = nullptr, const double* B1 = nullptr,
-                       double* C1 = nullptr, int K1 = 0, double* maxdev = nullptr)
+                       double* C1 = nullptr, int K1 = 0, double* maxdev = nullptr, const double* E2 = nullptr)
 {
     using Cfg = SymCfg<BM, BK, WM, WN, LM>;
     const int T = (p + BM - 1) / BM;
     hipLaunchKernelGGL((k_symm_tn<BM, BK, WM, WN, LM>), dim3(xcd_grid(T * (T + 1) / 2, K + K1)), dim3(Cfg::NT), 0, st, A,
-                       B, C, C2, E, coef, K, p, A1, B1, C1, K1, maxdev);
+                       B, C, C2, E, coef, K, p, A1, B1, C1, K1, maxdev, E2);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -363,7 +376,8 @@ template <int AUX> __device__ __forceinline__ double ld_pol(const double* p)
 template <int BK, int NSTG, int ABL, int BM, int NW, int AUX = 0>
 __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const double* __restrict__ B,
                                              double* __restrict__ C, double* __restrict__ C2,
-                                             const double* __restrict__ E, const double* __restrict__ coef, int K,
+                                             const double* __restrict__ E, const double* __restrict__ E2,
+                                             const double* __restrict__ coef, int K,
                                              int p, const double* __restrict__ A1, const double* __restrict__ B1,
                                              double* __restrict__ C1, int K1, double* __restrict__ maxdev,
                                              double* __restrict__ rowpart, double* __restrict__ fropart, int k, int b,
@@ -589,6 +603,9 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
     double* Ck = (second ? C1 : C) + (size_t)kk * pp;
     double* C2k = (C2 && !second) ? C2 + (size_t)kk * pp : nullptr;
     const double* Ek = (E && !second) ? E + (size_t)kk * pp : nullptr;
+    // second affine operand (E2, coefficients cE2 / dE2): added after the E term, so a launch without it keeps its bits
+    const double* E2k = (E2 && !second) ? E2 + (size_t)kk * pp : nullptr;
+    const double cE2 = E2k ? coef[k * NS_NCOEF + 6] : 0.0, dE2 = E2k ? coef[k * NS_NCOEF + 7] : 0.0;
     double dev = 0.0;
     // Off-diagonal tiles: the accumulators go to the (XOR-swizzled) LDS tile first and BOTH copies -- the tile and its
     // mirror -- are written from there with 16-byte accesses, two consecutive columns per lane (p is even, tile columns start
@@ -620,17 +637,20 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
             double2 t = ld2(smem + row * BM + ((c2 ^ row) & ~1));
             if (row & 1) { const double h = t.x; t.x = t.y; t.y = h; }
             if (gi < p && gj + 1 < p) {
-                double2 e = {0.0, 0.0};
+                double2 e = {0.0, 0.0}, f = {0.0, 0.0};
                 if (Ek) e = lde2(Ek + (size_t)gi * p + gj);
+                if (E2k) f = lde2(E2k + (size_t)gi * p + gj);
                 double2 v;
                 v.x = t.x + cE * e.x;
                 v.y = t.y + cE * e.y;
+                if (E2k) { v.x += cE2 * f.x; v.y += cE2 * f.y; }
                 dev = fmax(dev, fmax(fabs(v.x), fabs(v.y)));
                 *reinterpret_cast<double2*>(Ck + (size_t)gi * p + gj) = v;
                 if (C2k) {
                     double2 w;
                     w.x = c2val(dC, v.x, dE, e.x);
                     w.y = c2val(dC, v.y, dE, e.y);
+                    if (E2k) { w.x = __builtin_fma(dE2, f.x, w.x); w.y = __builtin_fma(dE2, f.y, w.y); }
                     *reinterpret_cast<double2*>(C2k + (size_t)gi * p + gj) = w;
                 }
                 if (rowpart) {          // the bound partials (and then the mirror) read the FINAL values from the tile
@@ -640,10 +660,12 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
             } else if (gi < p && gj < p) {
                 // odd p: the last column is the first half of a pair whose second half lies outside the matrix
                 const double e0 = Ek ? ld_pol<AUX>(Ek + (size_t)gi * p + gj) : 0.0;
-                const double v0 = t.x + cE * e0;
+                const double f0 = E2k ? ld_pol<AUX>(E2k + (size_t)gi * p + gj) : 0.0;
+                double v0 = t.x + cE * e0;
+                if (E2k) v0 += cE2 * f0;
                 dev = fmax(dev, fabs(v0));
                 Ck[(size_t)gi * p + gj] = v0;
-                if (C2k) C2k[(size_t)gi * p + gj] = c2val(dC, v0, dE, e0);
+                if (C2k) C2k[(size_t)gi * p + gj] = c2val2(dC, v0, dE, e0, E2k != nullptr, dE2, f0);
                 if (rowpart) {
                     double2 v = {v0, 0.0};
                     if (row & 1) { v.x = 0.0; v.y = v0; }
@@ -678,12 +700,14 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
                     if (gi == gj) v += cI;
                     const double e0 = Ek ? ld_pol<AUX>(Ek + (size_t)gi * p + gj) : 0.0;
                     v += cE * e0;
+                    const double f0 = E2k ? ld_pol<AUX>(E2k + (size_t)gi * p + gj) : 0.0;
+                    if (E2k) v += cE2 * f0;
                     dev = fmax(dev, fabs(v - (gi == gj ? 1.0 : 0.0)));
                     Ck[(size_t)gi * p + gj] = v;
-                    if (C2k) C2k[(size_t)gi * p + gj] = c2val(dC, v, dE, e0) + (gi == gj ? dI : 0.0);
+                    if (C2k) C2k[(size_t)gi * p + gj] = c2val2(dC, v, dE, e0, E2k != nullptr, dE2, f0) + (gi == gj ? dI : 0.0);
                     if (I == J && gi != gj) {
                         Ck[(size_t)gj * p + gi] = v;
-                        if (C2k) C2k[(size_t)gj * p + gi] = c2val(dC, v, dE, e0);
+                        if (C2k) C2k[(size_t)gj * p + gi] = c2val2(dC, v, dE, e0, E2k != nullptr, dE2, f0);
                     }
                 }
                 // XOR-swizzled BM x BM tile in LDS: the mirror pass of an off-diagonal tile reads it transposed; with
@@ -750,15 +774,21 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
                 double2 v;
                 v.x = smem[c2 * BM + (a ^ c2)];
                 v.y = smem[(c2 + 1) * BM + (a ^ (c2 + 1))];
-                double2 e = {0.0, 0.0};
+                double2 e = {0.0, 0.0}, f = {0.0, 0.0};
                 const bool need_e = Ek && (!rowpart || (C2k && dE != 0.0));
                 if (need_e) e = lde2(Ek + (size_t)(J0 + a) * p + I0 + c2);
-                if (!rowpart) { v.x += cE * e.x; v.y += cE * e.y; }
+                const bool need_f = E2k && (!rowpart || (C2k && dE2 != 0.0));
+                if (need_f) f = lde2(E2k + (size_t)(J0 + a) * p + I0 + c2);
+                if (!rowpart) {
+                    v.x += cE * e.x; v.y += cE * e.y;
+                    if (E2k) { v.x += cE2 * f.x; v.y += cE2 * f.y; }
+                }
                 *reinterpret_cast<double2*>(Ck + (size_t)(J0 + a) * p + I0 + c2) = v;
                 if (C2k) {
                     double2 w;
                     w.x = c2val(dC, v.x, dE, e.x);
                     w.y = c2val(dC, v.y, dE, e.y);
+                    if (E2k) { w.x = __builtin_fma(dE2, f.x, w.x); w.y = __builtin_fma(dE2, f.y, w.y); }
                     *reinterpret_cast<double2*>(C2k + (size_t)(J0 + a) * p + I0 + c2) = w;
                 }
             } else if (J0 + a < p && I0 + c2 < p) {
@@ -767,9 +797,11 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
                 double v0 = smem[c2 * BM + (a ^ c2)];
                 const bool need_e = Ek && (!rowpart || (C2k && dE != 0.0));
                 const double e0 = need_e ? ld_pol<AUX>(Ek + (size_t)(J0 + a) * p + I0 + c2) : 0.0;
-                if (!rowpart) v0 += cE * e0;
+                const bool need_f = E2k && (!rowpart || (C2k && dE2 != 0.0));
+                const double f0 = need_f ? ld_pol<AUX>(E2k + (size_t)(J0 + a) * p + I0 + c2) : 0.0;
+                if (!rowpart) { v0 += cE * e0; if (E2k) v0 += cE2 * f0; }
                 Ck[(size_t)(J0 + a) * p + I0 + c2] = v0;
-                if (C2k) C2k[(size_t)(J0 + a) * p + I0 + c2] = c2val(dC, v0, dE, e0);
+                if (C2k) C2k[(size_t)(J0 + a) * p + I0 + c2] = c2val2(dC, v0, dE, e0, E2k != nullptr, dE2, f0);
             }
         }
     }
@@ -932,7 +964,8 @@ __global__ __launch_bounds__(256) void k_cw_rider(const CwRider rider)
 template <int BK, int NSTG, int ABL = 0, int BM = 64, int NW = 4>
 __global__ __launch_bounds__(NW * 64) void k_symm_dl(const double* __restrict__ A, const double* __restrict__ B,
                                                  double* __restrict__ C, double* __restrict__ C2,
-                                                 const double* __restrict__ E, const double* __restrict__ coef, int K,
+                                                 const double* __restrict__ E, const double* __restrict__ E2,
+                                                 const double* __restrict__ coef, int K,
                                                  int p, const double* __restrict__ A1, const double* __restrict__ B1,
                                                  double* __restrict__ C1, int K1, double* __restrict__ maxdev,
                                                  double* __restrict__ rowpart, double* __restrict__ fropart, const CwRider rider,
@@ -983,7 +1016,7 @@ __global__ __launch_bounds__(NW * 64) void k_symm_dl(const double* __restrict__ 
     }
     int k, b;
     if (!decode_block_xcd(T * (T + 1) / 2, K + K1, k, b, bid)) return;
-    symm_dl_tile<BK, NSTG, ABL, BM, NW>(A, B, C, C2, E, coef, K, p, A1, B1, C1, K1, maxdev, rowpart, fropart, k, b, smem);
+    symm_dl_tile<BK, NSTG, ABL, BM, NW>(A, B, C, C2, E, E2, coef, K, p, A1, B1, C1, K1, maxdev, rowpart, fropart, k, b, smem);
 }
 
 #ifdef GGL_DEV
@@ -1408,7 +1441,7 @@ __global__ __launch_bounds__(256) void k_omega_chain(const ChainProg P, unsigned
         const SymmOp& o = P.op[js];
         int kk = jk;
         if (o.pair && jb >= P.ntiles) { kk = P.K + jk; jb -= P.ntiles; }
-        symm_dl_tile<BK, NSTG, 0, BM, 4, AUX>(o.A, o.B, o.C, o.C2, o.E, o.coef, P.K, P.p, o.A1, o.B1, o.C1, o.pair ? P.K : 0,
+        symm_dl_tile<BK, NSTG, 0, BM, 4, AUX>(o.A, o.B, o.C, o.C2, o.E, o.E2, o.coef, P.K, P.p, o.A1, o.B1, o.C1, o.pair ? P.K : 0,
                                                nullptr, o.rowpart, o.fropart, kk, jb, smem);
         // this tile's stores are in the XCD's L2 before the arrival is counted; the barrier also frees the LDS image
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1528,7 +1561,7 @@ __global__ __launch_bounds__(256) void k_symm_chain_probe(double* X0, double* X1
         for (int L = blockIdx.x; L < total; L += gridDim.x) {       // gridDim.x is a multiple of 8: L % 8 = this XCD
             int k, b;
             if (decode_block_xcd(ntiles, K, k, b, L))
-                symm_dl_tile<BK, NSTG, 0, BM, 4>(src, src, dst, nullptr, nullptr, coef, K, p, nullptr, nullptr, nullptr, 0,
+                symm_dl_tile<BK, NSTG, 0, BM, 4>(src, src, dst, nullptr, nullptr, nullptr, coef, K, p, nullptr, nullptr, nullptr, 0,
                                                  nullptr, nullptr, nullptr, k, b, smem);
             __syncthreads();                                         // the slab storage is reused by the next tile
         }
@@ -1590,7 +1623,8 @@ void symm_flush_rider(hipStream_t st)
 
 static void launch_dl(hipStream_t st, const double* A, const double* B, double* C, double* C2, const double* E,
                       const double* coef, int K, int p, const double* A1, const double* B1, double* C1, int K1,
-                      double* maxdev, int dl_cfg = 0, double* rowpart = nullptr, double* fropart = nullptr)
+                      double* maxdev, int dl_cfg = 0, double* rowpart = nullptr, double* fropart = nullptr,
+                      const double* E2 = nullptr)
 {
     // (the eight-wave development variants do not carry riders: the rider stays pending)
     const bool eight = dl_cfg == 6 || dl_cfg == 7;
@@ -1603,7 +1637,7 @@ static void launch_dl(hipStream_t st, const double* A, const double* B, double* 
     int ncopy = red.nblk > 0 ? NXCD : 0;          // (in front of the tiles, see k_symm_dl)
     for (int i = 0; i < cps.n; ++i) ncopy += (int)((cps.words[i] + 1023u) / 1024u);
     const int nride = rider.K * rider.nbx + ncopy;
-#define GGL_DL(...) hipLaunchKernelGGL((k_symm_dl<__VA_ARGS__>), grid, dim3(256), 0, st, A, B, C, C2, E, coef, K, p, A1, B1, C1, K1, maxdev, rowpart, fropart, rider, cps, red)
+#define GGL_DL(...) hipLaunchKernelGGL((k_symm_dl<__VA_ARGS__>), grid, dim3(256), 0, st, A, B, C, C2, E, E2, coef, K, p, A1, B1, C1, K1, maxdev, rowpart, fropart, rider, cps, red)
     if (dl_cfg == 4 || (dl_cfg >= 8 && dl_cfg <= 13) || (dl_cfg >= 18 && dl_cfg <= 21)) {
         const int T32 = (p + 31) / 32;
         const dim3 grid(xcd_grid(T32 * (T32 + 1) / 2, K + K1) + nride);
@@ -1634,7 +1668,7 @@ static void launch_dl(hipStream_t st, const double* A, const double* B, double* 
         // eight waves per workgroup (two per SIMD) for batches that leave one workgroup per CU.  Measured (MI355X, p = 500):
         // K = 4: 27.0 / 26.3 us vs 26.6 us for the 32x32 kernel; K = 8: 43.9 / 49.3 vs 40.4; K = 16: 68.6 / 74.9 vs 63.9 --
         // no gain anywhere, so the shipped library does not carry them
-#define GGL_DL8(...) hipLaunchKernelGGL((k_symm_dl<__VA_ARGS__>), grid, dim3(512), 0, st, A, B, C, C2, E, coef, K, p, A1, B1, C1, K1, maxdev, rowpart, fropart, rider, cps, red)
+#define GGL_DL8(...) hipLaunchKernelGGL((k_symm_dl<__VA_ARGS__>), grid, dim3(512), 0, st, A, B, C, C2, E, E2, coef, K, p, A1, B1, C1, K1, maxdev, rowpart, fropart, rider, cps, red)
         if (dl_cfg == 6) GGL_DL8(16, 4, 0, 64, 8);
         else GGL_DL8(32, 3, 0, 64, 8);
 #undef GGL_DL8
@@ -2038,13 +2072,15 @@ int symm_bounds_tile(int K, int p, int variant)
 }
 
 void launch_symm(hipStream_t st, const double* A, const double* B, double* C, double* C2, const double* E,
-                 const double* coef, int K, int p, int variant, double* maxdev, double* rowpart, double* fropart)
+                 const double* coef, int K, int p, int variant, double* maxdev, double* rowpart, double* fropart,
+                 const double* E2)
 {
     SymmHookAtExit hook{st, 0};
     if (variant < 0) variant = symm_auto_variant(K, p);
 #define GGL_TN(BM, BK, WM, WN, LM) \
-    launch_cfg<BM, BK, WM, WN, LM>(st, A, B, C, C2, E, coef, K, p, nullptr, nullptr, nullptr, 0, maxdev)
+    launch_cfg<BM, BK, WM, WN, LM>(st, A, B, C, C2, E, coef, K, p, nullptr, nullptr, nullptr, 0, maxdev, E2)
 #ifdef GGL_DEV
+    if (E2 && variant >= 41 && variant <= 50) variant = 20;    // k_symm_sk carries one affine operand only
     if (variant >= 41 && variant <= 50) {
         if ((p & 1) == 0 && p >= 2) { launch_sk(st, A, B, C, C2, E, coef, K, p, maxdev, rowpart, fropart, variant); return; }
         variant = 9;                                     // odd p: the register-staged 32x32 kernel
@@ -2053,7 +2089,7 @@ void launch_symm(hipStream_t st, const double* A, const double* B, double* C, do
     switch (variant) {
         case 16: case 17: case 18: case 19: case 20: case 21: case 22: case 23: case 24: case 25: case 26: case 27: case 28: case 29: case 30: case 31: case 32: case 33: case 34: case 35: case 36: case 37: case 38: case 39:
             if (symm_dl_serves(p)) {
-                launch_dl(st, A, B, C, C2, E, coef, K, p, nullptr, nullptr, nullptr, 0, maxdev, variant - 16, rowpart, fropart);
+                launch_dl(st, A, B, C, C2, E, coef, K, p, nullptr, nullptr, nullptr, 0, maxdev, variant - 16, rowpart, fropart, E2);
                 break;
             }
             if (variant == 20 || variant >= 24) GGL_TN(32, 32, 16, 16, true);
@@ -2076,7 +2112,7 @@ void launch_symm(hipStream_t st, const double* A, const double* B, double* C, do
             const int T = (p + 63) / 64;
             const dim3 grid(xcd_grid(T * (T + 1) / 2, K));
             double* md = (variant == 10) ? maxdev : nullptr;
-#define GGL_ABL(N) hipLaunchKernelGGL((k_symm_tn<64, 16, 32, 32, true, N>), grid, dim3(256), 0, st, A, B, C, C2, E, coef, K, p, nullptr, nullptr, nullptr, 0, md)
+#define GGL_ABL(N) hipLaunchKernelGGL((k_symm_tn<64, 16, 32, 32, true, N>), grid, dim3(256), 0, st, A, B, C, C2, E, coef, K, p, nullptr, nullptr, nullptr, 0, md, E2)
             if (variant == 6) GGL_ABL(1); else if (variant == 7) GGL_ABL(2); else if (variant == 10) GGL_ABL(3);
             else if (variant == 14) GGL_ABL(4); else GGL_ABL(5);
 #undef GGL_ABL

@@ -268,9 +268,11 @@ void launch_recon(hipStream_t st, double* out, const double* R, const double* D,
                   int map, int K, int p, double* scale_work);
 
 // ---- gemm_sym.hip -----------------------------------------------------------------------
-// C[k] = cI*I + cAcc*(A[k]*B[k]) + cE*E[k]  and optionally  C2[k] = dI*I + dC*C[k] + dE*E[k]  for commuting
-// symmetric A, B (so that A*B = A^T*B is symmetric).  coef: device [K][NS_NCOEF] = {cI,cAcc,cE,dI,dC,dE}.
-static constexpr int NS_NCOEF = 6;
+// C[k] = cI*I + cAcc*(A[k]*B[k]) + cE*E[k] [+ cE2*E2[k]]  and optionally  C2[k] = dI*I + dC*C[k] + dE*E[k] [+ dE2*E2[k]]
+// for commuting symmetric A, B (so that A*B = A^T*B is symmetric).  coef: device [K][NS_NCOEF] =
+// {cI,cAcc,cE,dI,dC,dE,cE2,dE2}; the E2 terms (read only where E2 is given) are added last, so a launch without E2 computes
+// what it did before the second operand existed.
+static constexpr int NS_NCOEF = 8;
 // variant < 0: pick by problem size.  FP64 MFMA.
 int symm_variants();
 bool symm_variant_built(int v);          // the shipped library holds the dispatched instances only (gemm_sym.hip)
@@ -283,7 +285,7 @@ int symm_auto_variant(int nprod, int p); // what variant < 0 resolves to for npr
 // [K][T][p] with T = ceil(p / tile), and the tiles' shares of |C|_F^2, [K][T(T+1)/2] -- what launch_bound_rows sums up
 void launch_symm(hipStream_t st, const double* A, const double* B, double* C, double* C2, const double* E,
                  const double* coef, int K, int p, int variant, double* maxdev = nullptr, double* rowpart = nullptr,
-                 double* fropart = nullptr);
+                 double* fropart = nullptr, const double* E2 = nullptr);
 int symm_bounds_tile(int K, int p, int variant);
 // frees the split-K scratch (k_symm_sk with a tile's k-range over several workgroups) that launches on this stream allocated
 void symm_release_workspace(hipStream_t st);
@@ -292,7 +294,7 @@ void symm_release_workspace(hipStream_t st);
 // one product of the chain: C = coef-affine(A B) [+ C2] for all K instances (stack base pointers; instance k at + k p^2);
 // pair: a second, independent product C1 = A1 B1 with the coefficient rows K + k rides in the same step
 struct SymmOp {
-    const double *A, *B, *E, *A1, *B1;
+    const double *A, *B, *E, *A1, *B1, *E2;
     double *C, *C2, *C1;
     const double* coef;
     double *rowpart, *fropart;
@@ -396,8 +398,9 @@ static constexpr double NS_SYM_KAPPA_MAX = 300.0;
 static constexpr double NS_KAPPA_LIMIT = 1e12;
 // steps: polynomial steps; products: kernel launches of products (incl. A', B'); units: symmetric products
 // of the whole stack (K p^3 flop each); deg[it]: degree (3, 5 or 9) of step it in x = sqrt(eig(Z Y))
+// direct: 0 = Newton-Schulz schedule; d = the direct family, one polynomial of degree d in A' (ns_plan, GGL_OPT_OMEGA_POLY)
 struct NsPlan {
-    int steps = 0; int products = 0; bool stable = false; double kappa = 0.0; int units = 0;
+    int steps = 0; int products = 0; bool stable = false; double kappa = 0.0; int units = 0; int direct = 0;
     double check = 5e-5;      // L-step: largest max|T_last - I| that still means "every eigenvalue resolved"
     unsigned char deg[NS_RANK_MAX_STEPS] = {};
 };
@@ -412,8 +415,12 @@ void launch_form_W_sym(hipStream_t st, double* W, const double* Theta, const dou
 // ns_plan returns 0, -1 (non-finite input) or -2 (condition number above NS_KAPPA_LIMIT: use the
 // eigendecomposition); fills coef_h[launch slots] and start_h[K][5].
 // degrees: highest step degree of the fast schedule: 3 = cubic only, 5 = cubic/quintic mix, 9 = + degree nine.
+// poly != 0: a launch sequence whose (quantised) interval and tolerance make the direct family strictly cheaper runs it
 int ns_plan(const double* cbound_h, const double* beta_h, int K, double* coef_h, double* start_h, NsPlan* plan,
-            int force_mode, int degrees = 9, double tol = NS_TOL_EXACT);
+            int force_mode, int degrees = 9, double tol = NS_TOL_EXACT, int poly = 0);
+// the direct family for [l, 1] (host): deg, monomial coefficients coef[16] in X = (A'/c - m I)/h, units (A', B' included; -1:
+// no degree up to 15 meets tol), the quantised a = l^2 and the certified relative deviation; returns 1 where ns_plan takes it
+int ns_poly_query(double l, int degrees, double tol, int* deg, double* coef, int* units, double* a_out, double* err_out);
 // the schedule alone (host): returns steps, fills deg[max_steps], coef[max_steps*6] = {t0..t4,l_after}
 int ns_schedule_query(double l, int degrees, int max_steps, int* deg, double* coef, int* units, double tol = NS_TOL_EXACT);
 // products of the all-symmetric schedule for [l, 1] (A', B' included), -1 where it does not apply; contiguous groups of a
@@ -421,7 +428,8 @@ int ns_schedule_query(double l, int degrees, int max_steps, int* deg, double* co
 int ns_units_query(double l, int degrees, double tol);
 int ns_group_partition(const int* units, int K, int p, int max_groups, int* len_out);
 void ns_prepare(hipStream_t st, const double* pre0_d, const double* pre1_d, const double* W, double* Ap, double* Bp,
-                int K, int p, int variant, double* start2 = nullptr, double* rowpart = nullptr, double* fropart = nullptr);
+                int K, int p, int variant, double* start2 = nullptr, double* rowpart = nullptr, double* fropart = nullptr,
+                bool start_w = false);
 void ns_run(hipStream_t st, const NsPlan& plan, const double* coef_d, const double* start_d, const double* W,
             double* AB, double* YP, double* Tb, double* out, int K, int p, int variant, size_t pstride = 0,
             bool fused_start = false, hipEvent_t bprime_free = nullptr);
@@ -429,9 +437,10 @@ void ns_run(hipStream_t st, const NsPlan& plan, const double* coef_d, const doub
 int ns_chain_ops(const NsPlan& plan, const double* pre0_d, const double* pre1_d, const double* coef_d, const double* W,
                  double* AB, double* YP, double* NX, double* Tb, double* out, int K, int p, size_t pstride, double* start2,
                  double* rowpart, double* fropart, SymmOp* ops, int max_ops);
-// speculative step (bound known before B' exists): target buffer and {dI, dC, dE} of the start the B' launch can emit
-// as its second output; null if the schedule's first step has none.  start_hk: row k of ns_plan's start table.
-double* ns_fused_start(const NsPlan& plan, const double* start_hk, double* YP, double* Tb, size_t n1, double out3[3]);
+// speculative step (bound known before B' exists): target buffer and {dI, dC, dE} (row[3..5]) and dE2 (row[7]) of the
+// start the B' launch can emit as its second output, row = the B' launch's coefficient row; null if the schedule's first
+// step has none.  start_hk: row k of ns_plan's start table.
+double* ns_fused_start(const NsPlan& plan, const double* start_hk, double* YP, double* Tb, size_t n1, double* row);
 
 // L-step (C - mu I)_+ by a sign-function Newton-Schulz iteration (newton_schulz.hip)
 int norm_bounds_blocks(int p);

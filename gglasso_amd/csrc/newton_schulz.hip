@@ -401,6 +401,173 @@ static const NsSeq& ns_sign_schedule(double l, int degrees, double tol = NS_TOL_
     return pl.plan(l);
 }
 
+// ---- direct family: Omega = W/2 + (sqrt(c)/2) p(X) with ONE polynomial p of degree d = 3J -------------------------------
+// On s = eig(A')/c in [a, 1], a = l^2, work in X = (A'/c - m I)/h, m = (1+a)/2, h = (1-a)/2 (spectrum in [-1, 1]; the monomial
+// coefficients of sqrt(m + h x) decay like (h/m)^k, so they are well conditioned).  p is the minimax polynomial of the RELATIVE
+// error |p(x) - sqrt(s)| / sqrt(s) (Remez exchange in the Chebyshev basis on a Chebyshev-spaced grid): a relative deviation
+// e gives |Omega - phiplus(W)|_2 <= e |(W^2 + 4 beta I)^(1/2)|_2 / 2, the meaning the Newton-Schulz planner gives ns_tol.
+// Paterson-Stockmeyer with block size 3, Y = X^3 (one product A' B' with the A', B' and I terms in its epilogue):
+//   p = P0 + Y (P1 + Y (P2 + ... + Y (P_{J-1} + c_{3J} Y))),  P_j = c_{3j} + c_{3j+1} X + c_{3j+2} X^2 = alpha I + beta A' + gamma B'
+// so every Horner step is one product with the digit in the epilogue (operands B', A'): A', B', Y, J - 2 Horner products and
+// the last one, J + 2 products in all -- degree 6 / 9 / 12 / 15 for 4 / 5 / 6 / 7.
+// allowance for the fp64 evaluation of the chain (relative, ~90 ulp): an estimate, not a rounding-error proof.  The largest
+// cancellation is in Y = (A'/c - m I)^3 / h^3 (terms up to ~(m/h)^3 times Y); its error reaches p only through the digits
+// multiplying Y, whose size falls like (h/m)^3, so it stays at the level of the products' own rounding
+static constexpr double NS_POLY_EVAL = 2e-14;
+static constexpr int NS_POLY_MAXDEG = 15;
+
+static double ns_poly_fit(double a, int d, double* mono)
+{
+    constexpr int G = 1024, NM = NS_POLY_MAXDEG + 2;
+    const double m = 0.5 * (1.0 + a), h = 0.5 * (1.0 - a);
+    static thread_local double gx[G + 1], gf[G + 1], gt[G + 1][NS_POLY_MAXDEG + 1], err[G + 1];
+    for (int i = 0; i <= G; ++i) {
+        const double x = -std::cos(M_PI * i / G);
+        gx[i] = x;
+        gf[i] = std::sqrt(m + h * x);
+        gt[i][0] = 1.0;
+        gt[i][1] = x;
+        for (int j = 2; j <= d; ++j) gt[i][j] = 2.0 * x * gt[i][j - 1] - gt[i][j - 2];
+    }
+    const int n = d + 2;                                 // unknowns: d + 1 Chebyshev coefficients and the level E
+    int ref[NM];
+    for (int r = 0; r < n; ++r) ref[r] = (int)std::lround((double)G * r / (n - 1));     // Chebyshev extrema (the grid is)
+    double co[NM] = {}, best[NM] = {}, ebest = 1e300;
+    for (int iter = 0; iter < 24; ++iter) {
+        double A[NM][NM + 1];
+        for (int r = 0; r < n; ++r) {
+            const int i = ref[r];
+            for (int j = 0; j <= d; ++j) A[r][j] = gt[i][j];
+            A[r][d + 1] = ((r & 1) ? -1.0 : 1.0) * gf[i];  // p(x_r) = f_r (1 + (-1)^r E)
+            A[r][n] = gf[i];
+        }
+        for (int i = 0; i < n; ++i) {                     // Gauss-Jordan with partial pivoting
+            int pv = i;
+            for (int r = i + 1; r < n; ++r) if (std::fabs(A[r][i]) > std::fabs(A[pv][i])) pv = r;
+            for (int cc = 0; cc <= n; ++cc) std::swap(A[i][cc], A[pv][cc]);
+            for (int r = 0; r < n; ++r) {
+                if (r == i) continue;
+                const double f = A[r][i] / A[i][i];
+                for (int cc = i; cc <= n; ++cc) A[r][cc] -= f * A[i][cc];
+            }
+        }
+        for (int i = 0; i < n; ++i) co[i] = A[i][n] / A[i][i];
+        double emax = 0.0;
+        for (int i = 0; i <= G; ++i) {
+            double v = 0.0;
+            for (int j = 0; j <= d; ++j) v += co[j] * gt[i][j];
+            err[i] = (v - gf[i]) / gf[i];
+            emax = std::fmax(emax, std::fabs(err[i]));
+        }
+        // near the rounding floor the error curve is noise and the exchange can wander off: keep the best iterate
+        const bool settled = emax > 0.999 * ebest;     // (levelled to 0.1 %: what is left does not change the choice)
+        if (emax < ebest) { ebest = emax; for (int j = 0; j <= d; ++j) best[j] = co[j]; }
+        if (settled) break;
+        int alt[G + 2], na = 0;                           // alternating extrema, as in ns_nonic_step
+        for (int i = 0; i <= G; ++i) {
+            const bool ext = (i == 0 || i == G) || ((err[i] - err[i - 1]) * (err[i + 1] - err[i]) <= 0.0);
+            if (!ext) continue;
+            if (na > 0 && (err[i] > 0.0) == (err[alt[na - 1]] > 0.0)) {
+                if (std::fabs(err[i]) > std::fabs(err[alt[na - 1]])) alt[na - 1] = i;
+            } else {
+                alt[na++] = i;
+            }
+        }
+        int lo = 0;
+        while (na - lo > n) {
+            if (std::fabs(err[alt[lo]]) < std::fabs(err[alt[na - 1]])) ++lo; else --na;
+        }
+        if (na - lo < n) break;
+        bool same = true;
+        for (int r = 0; r < n; ++r) { same = same && (ref[r] == alt[lo + r]); ref[r] = alt[lo + r]; }
+        if (same) break;
+    }
+    for (int j = 0; j <= d; ++j) co[j] = best[j];
+    // Chebyshev -> monomial coefficients in x (T_{j+1} = 2x T_j - T_{j-1})
+    double tp[NM] = {}, tc[NM] = {}, tn[NM];
+    for (int j = 0; j <= d; ++j) mono[j] = 0.0;
+    tp[0] = 1.0;                                          // T_0
+    tc[1] = 1.0;                                          // T_1
+    mono[0] += co[0];
+    if (d >= 1) mono[1] += co[1];
+    for (int j = 2; j <= d; ++j) {
+        for (int i = 0; i <= j; ++i) tn[i] = (i > 0 ? 2.0 * tc[i - 1] : 0.0) - tp[i];
+        for (int i = 0; i <= j; ++i) { mono[i] += co[j] * tn[i]; tp[i] = tc[i]; tc[i] = tn[i]; }
+    }
+    // deviation: the monomial form (what the chain evaluates) on the grid in long double, inflated for what lies between grid
+    // points (<= 17 alternations over 1025 Chebyshev-spaced points: the curve rises < 1e-3 of its amplitude there).  This is a
+    // sampled bound of the polynomial's own deviation; the fp64 evaluation of the chain is covered by NS_POLY_EVAL, an
+    // ESTIMATE (not a proof) checked by emulation and on the device against eigh, as the Newton-Schulz planner's tol is
+    double E = 0.0;
+    for (int i = 0; i <= G; ++i) {
+        long double v = 0.0L;
+        for (int j = d; j >= 0; --j) v = v * (long double)gx[i] + (long double)mono[j];
+        const long double f = std::sqrt((long double)(m + h * gx[i]));
+        E = std::fmax(E, (double)std::fabs((v - f) / f));
+    }
+    return E * (1.0 + 1e-2);
+}
+
+struct NsPoly { int deg = 0; int units = 1 << 30; double a = 0.0; double err = 0.0; double co[NS_POLY_MAXDEG + 1] = {}; };
+
+// the cheapest direct polynomial of degree <= dmax for the quantised interval of l (ns_quantise: a only widens) at this
+// tolerance; deg = 0 if none meets it.  The fits are pure functions of (quantised l, degree), memoised across tolerances (the
+// exchange is host work on the Omega-step's critical path: a few hundred microseconds per new interval and degree).
+static NsPoly ns_poly_plan(double l, double tol, int dmax = NS_POLY_MAXDEG)
+{
+    struct Fit { double err; double co[NS_POLY_MAXDEG + 1]; };
+    static thread_local std::unordered_map<long long, Fit> memo;
+    const double t = std::fmin(std::fmax(tol, NS_TOL_EXACT), 1e-6);
+    const NsKey q = ns_quantise(l);
+    NsPoly r;
+    r.a = q.l * q.l;
+    if (!(r.a > 0.0 && r.a < 1.0) || t <= 2.0 * NS_POLY_EVAL) return r;     // below the evaluation floor: no fit at all
+    if (memo.size() > 4096) memo.clear();
+    for (int d = 6; d <= std::min(dmax, NS_POLY_MAXDEG); d += 3) {
+        const long long id = (long long)q.key * 32 + d;
+        auto it = memo.find(id);
+        if (it == memo.end()) {
+            Fit f;
+            f.err = ns_poly_fit(r.a, d, f.co);
+            it = memo.emplace(id, f).first;
+        }
+        if (it->second.err + NS_POLY_EVAL <= t) {
+            r.deg = d;
+            r.units = 2 + d / 3;
+            r.err = it->second.err;
+            for (int j = 0; j <= d; ++j) r.co[j] = it->second.co[j];
+            break;
+        }
+    }
+    return r;
+}
+
+// the family an Omega-step launch sequence takes: the direct polynomial only where it needs STRICTLY fewer products than the
+// Newton-Schulz schedule for the same (l, tol); 0 = Newton-Schulz
+static int ns_poly_choice(double l, int degrees, double tol)
+{
+    if (!(l > 0.0) || !(l < 1.0) || 1.0 / (l * l) > NS_SYM_KAPPA_MAX) return 0;
+    const NsSeq& sq = ns_mixed_schedule(l, degrees, tol);
+    const int ns_units = (sq.n < 1 || sq.cost >= (1 << 29)) ? (1 << 30) : 2 + sq.cost;
+    // only degrees that would be strictly cheaper are fitted: d / 3 + 2 < ns_units (no schedule: every degree)
+    const int dmax = ns_units > NS_POLY_MAXDEG / 3 + 2 ? NS_POLY_MAXDEG : 3 * (ns_units - 3);
+    const NsPoly pp = ns_poly_plan(l, tol, dmax);
+    return (pp.deg && pp.units < ns_units) ? pp.deg : 0;
+}
+
+int ns_poly_query(double l, int degrees, double tol, int* deg, double* coef, int* units, double* a_out, double* err_out)
+{
+    if (!(l > 0.0) || !(l <= 1.0)) return -1;
+    const NsPoly pp = ns_poly_plan(l, tol);
+    const int chosen = ns_poly_choice(l, degrees, tol);
+    *deg = pp.deg;
+    for (int j = 0; j <= NS_POLY_MAXDEG; ++j) coef[j] = j <= pp.deg ? pp.co[j] : 0.0;
+    *units = pp.deg ? pp.units : -1;
+    if (a_out) *a_out = pp.a;
+    if (err_out) *err_out = pp.err;
+    return chosen ? 1 : 0;
+}
+
 int ns_schedule_query(double l, int degrees, int max_steps, int* deg, double* coef, int* units, double tol)
 {
     if (!(l > 0.0) || !(l <= 1.0)) return -1;
@@ -509,6 +676,10 @@ __global__ __launch_bounds__(256) void k_ns_start(double* __restrict__ Y1, doubl
                 Y1[base + i] = __builtin_fma(y1a, a, y1b * b2) + (r == c ? z1i : 0.0);     // same order as c2val()
                 continue;
             }
+            if (mode == 4) {            // direct family: G = W/2 + (sqrt(c)/2) P0, same order as the fused start (c2val2)
+                Y1[base + i] = __builtin_fma(0.5, W[base + i], __builtin_fma(y1a, a, y1b * b2)) + (r == c ? z1i : 0.0);
+                continue;
+            }
             const double y = y1a * a + y1b * b2;
             if (mode == 1) {
                 Y1[base + i] = 0.5 * W[base + i] + h * y;          // Y1 is Omega here
@@ -532,7 +703,7 @@ static void launch_ns_start(hipStream_t st, double* Y1, double* Z1, const double
 // One schedule for the whole batch, built for the smallest l_k = sqrt(4 beta_k / c_k) (every spectrum lies in
 // [l_k, 1] after scaling by c_k, so the polynomials of the widest interval converge for all of them).
 int ns_plan(const double* cbound_h, const double* beta_h, int K, double* coef_h, double* start_h, NsPlan* plan,
-            int force_mode, int degrees, double tol)
+            int force_mode, int degrees, double tol, int poly)
 {
     std::vector<double> c(K);
     double kappa = 1.0;
@@ -549,10 +720,51 @@ int ns_plan(const double* cbound_h, const double* beta_h, int K, double* coef_h,
     const double lmin = 1.0 / std::sqrt(kappa);
     plan->stable = stable;
     plan->kappa = kappa;
-    auto put = [&](int g, int k, double cI, double cAcc, double cE, double dI = 0.0, double dC = 0.0, double dE = 0.0) {
+    plan->direct = 0;
+    auto put = [&](int g, int k, double cI, double cAcc, double cE, double dI = 0.0, double dC = 0.0, double dE = 0.0,
+                   double cE2 = 0.0, double dE2 = 0.0) {
         double* o = coef_h + (size_t)g * NS_SLOT(K) + (size_t)k * NS_NCOEF;
-        o[0] = cI; o[1] = cAcc; o[2] = cE; o[3] = dI; o[4] = dC; o[5] = dE;
+        o[0] = cI; o[1] = cAcc; o[2] = cE; o[3] = dI; o[4] = dC; o[5] = dE; o[6] = cE2; o[7] = dE2;
     };
+    const int pd = (!stable && poly) ? ns_poly_choice(lmin, degrees, tol) : 0;
+    if (pd) {
+        // direct family (ns_poly_plan): launches after B' -- Y = X^3 with H_{J-1} = c_{3J} Y + P_{J-1} as its second output,
+        // H_j = H_{j+1} Y + P_j (j = J-2 .. 1), Omega = (sqrt(c)/2) H_1 Y + G; the start table holds G = W/2 + (sqrt(c)/2) P0
+        // as {A', B', I} coefficients (the W term is 1/2).  Epilogue operands: E = B', E2 = A' (digits), E = G (last launch).
+        const NsPoly pp = ns_poly_plan(lmin, tol, pd);
+        const int J = pd / 3;
+        const double a = pp.a, m = 0.5 * (1.0 + a), h = 0.5 * (1.0 - a), u = 1.0 / (h * h * h);
+        plan->direct = pd;
+        plan->steps = 1;
+        plan->deg[0] = 0;
+        plan->units = pp.units;
+        plan->products = J + 2;
+        for (int k = 0; k < K; ++k) {
+            const double ck = c[k], hc = 0.5 * std::sqrt(ck);
+            // digit j as {alpha (I), beta (A'), gamma (B')}: X = A'/(c h) - m/h, X^2 = B'/(c h)^2 - 2 m A'/(c h^2) + (m/h)^2
+            auto digit = [&](int j, double* o3) {
+                const double a0 = pp.co[3 * j], a1 = pp.co[3 * j + 1], a2 = pp.co[3 * j + 2];
+                o3[0] = a0 - a1 * (m / h) + a2 * (m / h) * (m / h);
+                o3[1] = a1 / (ck * h) - 2.0 * a2 * m / (ck * h * h);
+                o3[2] = a2 / (ck * ck * h * h);
+            };
+            double dg[3];
+            digit(0, dg);
+            double* s = start_h + (size_t)k * 5;
+            s[0] = hc * dg[1]; s[1] = hc * dg[2]; s[2] = hc * dg[0]; s[3] = 0.0; s[4] = 0.0;
+            int g = 0;
+            digit(J - 1, dg);
+            // Y = (A' B'/c^3 - 3 m B'/c^2 + 3 m^2 A'/c - m^3 I) / h^3 (E = B', E2 = A');  H_{J-1} = c_{3J} Y + P_{J-1}
+            put(g++, k, -m * m * m * u, u / (ck * ck * ck), -3.0 * m * u / (ck * ck), dg[0], pp.co[3 * J], dg[2],
+                3.0 * m * m * u / ck, dg[1]);
+            for (int j = J - 2; j >= 1; --j) {
+                digit(j, dg);
+                put(g++, k, dg[0], 1.0, dg[2], 0.0, 0.0, 0.0, dg[1]);     // H_j = H_{j+1} Y + P_j
+            }
+            put(g++, k, 0.0, hc, 1.0);                                     // Omega = (sqrt(c)/2) H_1 Y + G
+        }
+        return 0;
+    }
     if (!stable) {
         const NsSeq& sq = ns_mixed_schedule(lmin, degrees, tol);
         if (sq.n < 1 || sq.n > NS_MAX_STEPS || sq.cost >= (1 << 29)) return -2;
@@ -644,19 +856,28 @@ int ns_plan(const double* cbound_h, const double* beta_h, int K, double* coef_h,
 // Phase A (before the bound is known): A' = W^2 + 4 beta I -> Ap, B' = A'^2 -> Bp.
 // pre0_d / pre1_d: the coefficient rows {4 beta, 1, 0, 0, 0} and {0, 1, 0, 0, 0} of the K instances.
 void ns_prepare(hipStream_t st, const double* pre0_d, const double* pre1_d, const double* W, double* Ap, double* Bp, int K,
-                int p, int variant, double* start2, double* rowpart, double* fropart)
+                int p, int variant, double* start2, double* rowpart, double* fropart, bool start_w)
 {
     // start2 != null (the bound is already known): the B' launch also writes start2 = dI I + dC B' + dE A' -- the
     // first step's U (degree nine) or Z1 (quintic) -- with {dI, dC, dE} in pre1_d
     launch_symm(st, W, W, Ap, nullptr, nullptr, pre0_d, K, p, variant);
     symm_flush_rider(st);         // (tables riding in the A' launch: a launch of another kernel family did not take them)
-    launch_symm(st, Ap, Ap, Bp, start2, start2 ? Ap : nullptr, pre1_d, K, p, variant, nullptr, rowpart, fropart);
+    // start_w (direct family): the start is G, which also takes W (E2, coefficient dE2 of pre1_d)
+    launch_symm(st, Ap, Ap, Bp, start2, start2 ? Ap : nullptr, pre1_d, K, p, variant, nullptr, rowpart, fropart,
+                start2 && start_w ? W : nullptr);
 }
 
 // where the first step's elementwise start goes (ns_run's layout) and its coefficients {dI, dC, dE} from the start
 // table of ns_plan; null when the first step has no single-matrix start (cubic first step, stable schedule)
-double* ns_fused_start(const NsPlan& plan, const double* start_hk, double* YP, double* Tb, size_t n1, double out3[3])
+double* ns_fused_start(const NsPlan& plan, const double* start_hk, double* YP, double* Tb, size_t n1, double* row)
 {
+    double* out3 = row + 3;
+    row[7] = 0.0;
+    if (plan.direct) {
+        // G = W/2 + (sqrt(c)/2) P0 = dI I + dC B' + dE A' + dE2 W into Tb (ns_prepare passes E2 = W)
+        out3[0] = start_hk[2]; out3[1] = start_hk[1]; out3[2] = start_hk[0]; row[7] = 0.5;
+        return Tb;
+    }
     if (plan.stable || plan.deg[0] < 5) return nullptr;
     if (plan.deg[0] == 5) { out3[0] = start_hk[2]; out3[1] = start_hk[1]; out3[2] = start_hk[3]; return YP + n1; }   // Z1
     out3[0] = start_hk[2]; out3[1] = start_hk[1]; out3[2] = start_hk[0];                                              // U
@@ -691,6 +912,19 @@ void ns_run(hipStream_t st, const NsPlan& plan, const double* coef_d, const doub
     const size_t cs = NS_SLOT(K), n1 = pstride ? pstride : (size_t)K * p * p;
     const int n = plan.steps;
     int g = 0;
+    if (plan.direct) {
+        // direct family: G -> Tb, Y = X^3 -> YP, the Horner iterates alternate between YP + n1 and out (H_1 in YP + n1);
+        // A' and B' (the digits' operands) are never overwritten
+        if (!fused_start) launch_ns_start(st, Tb, nullptr, AB, AB + n1, W, start_d, K, p, 4);
+        const int J = plan.direct / 3;
+        auto hbuf = [&](int j) { return (j & 1) ? YP + n1 : out; };
+        launch_symm(st, AB, AB + n1, YP, hbuf(J - 1), AB + n1, coef_d + cs * g++, K, p, variant, nullptr, nullptr, nullptr, AB);
+        for (int j = J - 2; j >= 1; --j)
+            launch_symm(st, hbuf(j + 1), YP, hbuf(j), nullptr, AB + n1, coef_d + cs * g++, K, p, variant, nullptr, nullptr,
+                        nullptr, AB);
+        launch_symm(st, hbuf(1), YP, out, nullptr, Tb, coef_d + cs * g++, K, p, variant);
+        return;
+    }
     double *cur = YP, *nxt = AB;      // cur = [Y | Z]
     if (plan.deg[0] >= 5 && !plan.stable) {
         if (plan.deg[0] == 5) {
@@ -756,7 +990,7 @@ int ns_chain_ops(const NsPlan& plan, const double* pre0_d, const double* pre1_d,
                  double* AB, double* YP, double* NX, double* Tb, double* out, int K, int p, size_t pstride, double* start2,
                  double* rowpart, double* fropart, SymmOp* ops, int max_ops)
 {
-    if (plan.stable || plan.deg[0] < 5 || !start2) return 0;
+    if (plan.stable || (plan.deg[0] < 5 && !plan.direct) || !start2) return 0;
     const size_t cs = NS_SLOT(K), n1 = pstride ? pstride : (size_t)K * p * p;
     const int n = plan.steps;
     int no = 0, g = 0;
@@ -771,6 +1005,23 @@ int ns_chain_ops(const NsPlan& plan, const double* pre0_d, const double* pre1_d,
     };
     double* Ap = AB;
     double* Bp = AB + n1;
+    if (plan.direct) {
+        // the launches of ns_run's direct branch (start G fused into the B' launch)
+        const int J = plan.direct / 3;
+        auto hbuf = [&](int j) { return (j & 1) ? YP + n1 : out; };
+        add(W, W, Ap, nullptr, nullptr, pre0_d);
+        SymmOp* o = add(Ap, Ap, Bp, start2, Ap, pre1_d, rowpart, fropart);
+        if (o) o->E2 = W;
+        o = add(Ap, Bp, YP, hbuf(J - 1), Bp, coef_d + cs * g++);
+        if (o) o->E2 = Ap;
+        for (int j = J - 2; j >= 1; --j) {
+            o = add(hbuf(j + 1), YP, hbuf(j), nullptr, Bp, coef_d + cs * g++);
+            if (o) o->E2 = Ap;
+        }
+        add(hbuf(1), YP, out, nullptr, start2, coef_d + cs * g++);
+        (void)NX;
+        return ok ? no : 0;
+    }
     add(W, W, Ap, nullptr, nullptr, pre0_d);
     add(Ap, Ap, Bp, start2, Ap, pre1_d, rowpart, fropart);
     double *cur = YP, *nxt = NX;

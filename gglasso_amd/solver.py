@@ -504,6 +504,14 @@ class HipEngine:
                          "rank_fallbacks", "rank_launches", "spec_calls", "spec_misses", "spin_timeouts", "last_parts",
                          "last_variant", "eigh_fallbacks", "pre_dropped"), (int(v) for v in out)))
 
+    def poly_stats(self):
+        """GGL_OPT_OMEGA_POLY: {'seqs': Omega-step launch sequences that ran the direct polynomial, 'seqs_total': all of them,
+        'last_deg': degree of the last direct polynomial}."""
+        import ctypes
+        out = (ctypes.c_longlong * 3)()
+        check(self.lib.ggl_omega_poly_stats(self.h, out))
+        return dict(zip(("seqs", "seqs_total", "last_deg"), (int(v) for v in out)))
+
     def rank_stats(self):
         import ctypes
         out = (ctypes.c_longlong * 4)()

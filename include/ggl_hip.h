@@ -183,6 +183,10 @@ void *ggl_device_ptr(ggl_ctx *ctx, int which);
                                       parts of the engine -- where the size rule would run it as one launch sequence on the worst
                                       instance's schedule; taken when a deterministic time model gains >= 6 %.  0 off, 2 / 3 = at most
                                       that many groups; 12 / 13 (tests) = at most 2 / 3 groups wherever the product counts differ */
+#define GGL_OPT_OMEGA_POLY 38      /* [1] a launch sequence of the Omega-step (part or group) whose spectral interval and ns_tol let ONE
+                                      polynomial in A' (degree 6 / 9 / 12 / 15, Paterson-Stockmeyer evaluation: 4 / 5 / 6 / 7 products,
+                                      A' and B' included) meet the tolerance with strictly fewer products than the Newton-Schulz
+                                      schedule runs that polynomial instead; 0 = Newton-Schulz everywhere */
 #define GGL_OPT_PART_PRIORITY 25   /* DEV [0] streams of the concurrent parts of an Omega-step: 0 = created like any stream, 1 = with the highest,
                                       2 = with the lowest stream priority (streams of another priority never share a hardware queue with
                                       the ctx's main stream) */
@@ -515,6 +519,9 @@ int ggl_lds_stats(ggl_ctx *ctx, long long out[4]);
  * lengths of its groups [4], product units (A', B' included) of their schedules [4], grouped steps whose split differed from
  * the previous grouped step's }; units_sum (4 doubles, may be NULL): the units of every group slot summed over the grouped steps. */
 int ggl_group_stats(ggl_ctx *ctx, long long out[11], double *units_sum);
+/* GGL_OPT_OMEGA_POLY: out = { launch sequences of the Omega-step that ran the direct family, launch sequences in all (concurrent
+ * parts and groups count one each), degree of the last direct polynomial }. */
+int ggl_omega_poly_stats(ggl_ctx *ctx, long long out[3]);
 /* c_k >= lambda_max(W_k^2 + 4 beta_k I) and beta_k (K doubles each) of the last validated matrix-function Omega-step; returns 1,
  * or 0 when there is none yet. */
 int ggl_spectral_bounds(ggl_ctx *ctx, double *c_out, double *beta_out);
@@ -590,6 +597,12 @@ int ggl_dev_ns_schedule_tol(double l, int degrees, double tol, int max_steps, in
  * schedule for a spectrum in [l, 1] at the stopping tolerance tol (-1: condition number above 300, the stable schedule's range) */
 int ggl_dev_group_partition(const int *units, int K, int p, int max_groups, int *len_out);
 int ggl_dev_ns_units(double l, int degrees, double tol);
+/* host only: the direct family of the Omega-step (GGL_OPT_OMEGA_POLY) for the spectral interval [a, 1] of A'/c: out[18] = the
+ * monomial coefficients [16] of p in X = (A'/c - m I)/h, m = (1+a)/2, h = (1-a)/2, for the quantised a (out[16]; rounded down),
+ * and p's certified relative deviation from sqrt(m + h X) (out[17]); *deg = its degree (6, 9, 12, 15; 0 = none meets tol),
+ * *units = its products, A' and B' included (-1: none).  Returns 1 where an Omega-step launch sequence with this interval takes
+ * the direct family -- strictly fewer products than the Newton-Schulz schedule of (degrees, tol) -- and 0 where it does not. */
+int ggl_dev_omega_poly_plan(double a, double tol, int degrees, int *deg, double *out, int *units);
 #ifdef GGL_DEV
 /* C = A B on the INT8 matrix cores from S signed-digit slices per operand (error-free split; gemm_i8.hip), slice pairs
  * t + u <= dmax; |A| <= scaleA, |B| <= scaleB entrywise.  ms_out = {slicing both operands, one product launch, overflow flag}. */
