@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libggl_hip.so")
 DEV_LIB_PATH = os.path.join(_HERE, "lib", "libggl_hip_dev.so")     # python -m gglasso_amd.build --dev (tools/ only)
 
 # mirrors include/ggl_hip.h
-REG_SGL, REG_GGL, REG_FGL = 0, 1, 2
+REG_SGL, REG_GGL, REG_FGL, REG_FSGL = 0, 1, 2, 3
 EIG_AUTO, EIG_JACOBI, EIG_ROCSOLVER, EIG_NEWTON_SCHULZ = 0, 1, 2, 3
 CTX_STREAM_GIVEN = 1 << 16
 # ggl_ctx_set_option ids (GGL_OPT_*)
@@ -56,6 +56,10 @@ _SIGNATURES = {
     "ggl_set_lambda1_mask": ([_vp, _dp], _i),
     "ggl_set_lambda1_mask_k": ([_vp, _dp], _i),
     "ggl_set_instance_dims": ([_vp, ctypes.POINTER(_i)], _i),
+    "ggl_set_block_size": ([_vp, _i], _i),
+    "ggl_fsgl_stats": ([_vp, ctypes.POINTER(ctypes.c_longlong)], _i),
+    "ggl_prox_sum_frob": ([_i, _i, _dp, _d, _dp], _i),
+    "ggl_frob_norm_per_block": ([_i, _i, _dp, _i, _dp], _i),
     "ggl_admm_step": ([_vp, _d, _d, _d, _i, _i, _dp, _dp, _dp], _i),
     "ggl_hint_last_step": ([_vp], _i),
     "ggl_step_omega": ([_vp, _d, _i, _dp], _i),

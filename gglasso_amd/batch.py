@@ -43,6 +43,14 @@ def ADMM_SGL_batch(S, lambda1, Omega_0=None, Theta_0=None, X_0=None, rho=1., max
     then be (K,p,p): one mask per instance (with one lambda1 per instance).
     A point whose data are not finite (a NaN in its S) ends with ``info['status'] == 'solver error'`` and costs that point
     only; ``compact``: once a quarter of the live slots hold finished points, the rest go on in a smaller stack."""
+    return _sgl_batch_impl(S, lambda1, Omega_0, Theta_0, X_0, rho, max_iter, tol, rtol, update_rho, verbose, latent, mu1,
+                           lambda1_mask, selection_stats, dims, tau_range, compact, fetch, select, None)
+
+
+def _sgl_batch_impl(S, lambda1, Omega_0, Theta_0, X_0, rho, max_iter, tol, rtol, update_rho, verbose, latent, mu1, lambda1_mask,
+                    selection_stats, dims, tau_range, compact, fetch, select, _block_size):
+    """Body of ``ADMM_SGL_batch`` and ``ADMM_FSGL_batch``; ``_block_size``: every point is a Functional SGL problem with
+    blocks of this size (the block penalty in the Theta-step), None: element-wise penalty."""
     S = as_c(S)
     assert S.ndim in (2, 3) and S.shape[-1] == S.shape[-2]
     p = S.shape[-1]
@@ -90,6 +98,10 @@ def ADMM_SGL_batch(S, lambda1, Omega_0=None, Theta_0=None, X_0=None, rho=1., max
     eng = _solver.ENGINE(np.broadcast_to(S, (K, p, p)), Om0, Th0, X0)
     engines = [eng]                  # eng: the original ctx (snapshots, statistics); cur: where the live points iterate
     try:
+        if _block_size:
+            # (a compacted ctx takes the block size over from the one it is cut out of)
+            assert lambda1_mask is None and dims is None, "the block penalty takes neither a mask nor per-instance dimensions"
+            eng.set_block_size(int(_block_size))
         if lam_pp is not None and lam_pp.ndim == 3:
             eng.set_lambda1_mask_k(lam[:, None, None] * lam_pp)        # single_admm_solver.py:114, per instance
         elif lam_pp is not None:
@@ -209,11 +221,23 @@ def ADMM_SGL_batch(S, lambda1, Omega_0=None, Theta_0=None, X_0=None, rho=1., max
                     for nm in ('Omega', 'X'):
                         if nm in own:
                             target.setdefault(nm, own[nm])
-        _warn_failures(results)
+        _warn_failures(results, stacklevel=4)       # (the caller of the public function, one frame further up)
     finally:
         for e in engines:
             e.close()
     return results
+
+
+def ADMM_FSGL_batch(S, lambda1, M, Omega_0=None, Theta_0=None, X_0=None, rho=1., max_iter=1000, tol=1e-7, rtol=1e-4,
+                    update_rho=True, verbose=False, latent=False, mu1=None, compact=True):
+    """Solve ``ADMM_FSGL(S, lambda1[k], M, ...)`` (solver/functional_sgl_admm.py:12-238) for every k of the 1-D array
+    ``lambda1`` at once: a lambda path of Functional SGL problems as one batch, over the machinery of ``ADMM_SGL_batch``
+    (the loop in C, compaction, per-point failure isolation, ``latent`` with one ``mu1`` per point) with the block penalty
+    in the Theta-step.  S: (pM,pM) shared or (K,pM,pM); returns a list of K ``(sol, info)`` as ``ADMM_SGL_batch`` does."""
+    pM = np.shape(S)[-1]
+    assert int(M) >= 1 and pM % int(M) == 0
+    return _sgl_batch_impl(S, lambda1, Omega_0, Theta_0, X_0, rho, max_iter, tol, rtol, update_rho, verbose, latent, mu1,
+                           None, False, None, None, compact, None, None, int(M))
 
 
 def _leftover_status(row):
@@ -291,14 +315,14 @@ def _why(ctx, first, group):
     return "its residual sums are not finite (NaN / Inf in its data or a diverged iterate)"
 
 
-def _warn_failures(results):
+def _warn_failures(results, stacklevel=3):
     """One warning per point that ends as 'solver error' (the reference warns about numerical trouble and goes on,
     solver/admm_solver.py:284-301): the point's index and what went wrong."""
     import warnings
     for g, res in enumerate(results):
         if res is not None and res[1].get('status') == 'solver error':
             warnings.warn(f"batch point {g}: solver error -- {res[1].get('error', 'marked by the library')}; "
-                          f"the other points are not affected", RuntimeWarning, stacklevel=3)
+                          f"the other points are not affected", RuntimeWarning, stacklevel=stacklevel)
 
 
 def _mark_inconsistent(results, points):

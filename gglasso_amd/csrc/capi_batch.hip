@@ -117,12 +117,21 @@ int sgl_batch_step_impl(ggl_ctx* c, const double* rho, const double* lambda1, in
     CopySegs sg;
     sg.add(c->par, h, 5 * (size_t)K * sizeof(double));
     ARGCHK(!(c->has_dims && latent), "padded instances of different dimension: not with latent variables");
+    // a block size makes every instance a Functional SGL problem (functional_sgl_admm.py:136-191): the block penalty instead of
+    // the element-wise one
+    const bool fsgl = c->block_M > 0;
+    if (fsgl) {
+        for (int k = 0; k < K; ++k) ARGCHK(lambda1[k] > 0, "lambda1 must be positive (functional_sgl_admm.py:94)");
+        const int rcf = fsgl_check(c, GGL_REG_FSGL, 1.0);
+        if (rcf) return rcf;
+    }
     int rc = GGL_OK;
     for (int attempt = 0; attempt < 2; ++attempt) {
         // (first attempt: the LDS-resident Omega-step may run unvalidated; when an instance falls outside its range the
         // Theta-step has left the iterate alone and the step is repeated on the launch chain)
         LdsSgl req;
-        if (attempt == 0 && !latent) {
+        if (attempt == 0 && !latent && !fsgl) {
+            // (the fused kernel applies the element-wise shrink: never with a block size)
             // p <= 64: ask for the fused form -- Omega-step, Theta-step, dual update and sums in ONE launch (omega_lds.hip)
             req.l1K = c->par + K;
             req.mask = c->has_maskK ? c->maskK : (c->has_mask ? c->mask : nullptr);
@@ -138,10 +147,13 @@ int sgl_batch_step_impl(ggl_ctx* c, const double* rho, const double* lambda1, in
         double* Om = c->Om[c->cur];
         double* OmPrev = c->Om[c->cur ^ 1];
         PB(c, GGL_PH_THETA);
-        launch_theta_sgl(c->stream, c->Theta, c->X, c->W, Om, OmPrev, latent ? c->L : nullptr, c->par + K,
-                         c->has_maskK ? c->maskK : (c->has_mask ? c->mask : nullptr), c->par + 4 * (size_t)K, latent, c->partials,
-                         K, c->p, c->spec_pending ? c->spec_flag : nullptr, c->has_dims ? c->inst_pk : nullptr,
-                         c->has_maskK ? (size_t)c->p * c->p : 0);
+        if (fsgl)
+            (void)fsgl_theta(c, latent);
+        else
+            launch_theta_sgl(c->stream, c->Theta, c->X, c->W, Om, OmPrev, latent ? c->L : nullptr, c->par + K,
+                             c->has_maskK ? c->maskK : (c->has_mask ? c->mask : nullptr), c->par + 4 * (size_t)K, latent, c->partials,
+                             K, c->p, c->spec_pending ? c->spec_flag : nullptr, c->has_dims ? c->inst_pk : nullptr,
+                             c->has_maskK ? (size_t)c->p * c->p : 0);
         PE(c, GGL_PH_THETA);
         HIPCHK(hipGetLastError());
         if (latent) {
@@ -155,8 +167,9 @@ int sgl_batch_step_impl(ggl_ctx* c, const double* rho, const double* lambda1, in
         // the K rows of sums go to pinned memory, the last workgroup publishes a sequence number: the host polls that word
         // instead of synchronising the stream (~10 us of a 70-us batch iteration at p <= 64)
         if (c->seq_h && c->spin_wait) c->seq_wait = ++c->seq_next;
-        launch_reduce_partials(c->stream, c->partials, K, elementwise_blocks(c->p), GGL_NNORM, c->norms_h,
-                               c->seq_wait ? c->seq_h : nullptr, c->seq_wait, c->arrive);
+        launch_reduce_partials(c->stream, c->partials, K,
+                               (fsgl && !latent) ? fsgl_partial_blocks(c->p, c->block_M) : elementwise_blocks(c->p), GGL_NNORM,
+                               c->norms_h, c->seq_wait ? c->seq_h : nullptr, c->seq_wait, c->arrive);
         PE(c, GGL_PH_REDUCE);
         HIPCHK(hipGetLastError());
         c->norms_host = true;
@@ -623,6 +636,10 @@ extern "C" int ggl_ctx_create_subset(ggl_ctx* src, const int* idx, int m, ggl_ct
     if (e == hipSuccess) e = hipStreamSynchronize(src->stream);
     (void)hipFree(didx);
     if (e != hipSuccess) { ggl_ctx_destroy(c); return fail(GGL_E_HIP, "subset: %s", hipGetErrorString(e)); }
+    if (src->block_M > 0) {
+        rc = ggl_set_block_size(c, src->block_M);
+        if (rc) { ggl_ctx_destroy(c); return rc; }
+    }
     *out = c;
     return GGL_OK;
 }

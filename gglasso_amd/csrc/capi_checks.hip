@@ -181,7 +181,8 @@ extern "C" int ggl_selection_stats(ggl_ctx* c, double* out)
 extern "C" int ggl_objective(ggl_ctx* c, double lambda1, double lambda2, int reg, double out[3])
 {
     ARGCHK(c && out, "ctx, out");
-    ARGCHK(reg == GGL_REG_GGL || reg == GGL_REG_FGL, "reg");
+    ARGCHK(reg == GGL_REG_GGL || reg == GGL_REG_FGL || reg == GGL_REG_FSGL, "reg");
+    { const int rcf = fsgl_check(c, reg, lambda1); if (rcf) return rcf; }
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);
     // -log det Omega_k = -sum_m log phip(d_m): eigenvalues of the last Omega-step (ggl_helper.py:266-270);
@@ -224,6 +225,22 @@ extern "C" int ggl_objective(ggl_ctx* c, double lambda1, double lambda2, int reg
         }
     }
     out[0] = ld;
+    if (reg == GGL_REG_FSGL) {
+        // lambda1 sum_{I != J} |Theta_IJ|_F (functional_sgl_admm.py:36): the table of block norms, added up in row-major order
+        const int nB = c->p / c->block_M;
+        const size_t nt = (size_t)c->K * nB * nB;
+        DevBuf dT;
+        HIPCHK(dT.alloc(nt));
+        launch_fsgl_block_table(c->stream, dT.p, c->Theta, nullptr, nullptr, c->K, c->p, c->block_M, 2, nullptr);
+        HIPCHK(hipGetLastError());
+        std::vector<double> tab(nt);
+        HIPCHK(hipMemcpyAsync(tab.data(), dT.p, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        double s = 0.0;
+        for (size_t i = 0; i < nt; ++i) s += tab[i];
+        out[2] = lambda1 * s;
+        return GGL_OK;
+    }
     const int nb = pval_blocks(c->p);
     launch_pval(c->stream, reg, c->Theta, lambda1, lambda2, c->K, c->p, c->partials);
     launch_reduce_partials(c->stream, c->partials, 1, nb, 1, c->norms);
@@ -244,6 +261,10 @@ extern "C" int ggl_kkt_residual(ggl_ctx* c, double rho, double lambda1, double l
 {
     ARGCHK(c && out, "ctx, out");
     ARGCHK(!latent || mu1, "latent needs mu1");
+    if (reg == GGL_REG_FSGL)
+        return fail(GGL_E_ARG, "bad argument: the KKT stopping criterion is not part of the Functional SGL "
+                    "(solver/functional_sgl_admm.py has none)");
+    ARGCHK(reg == GGL_REG_SGL || reg == GGL_REG_GGL || reg == GGL_REG_FGL, "reg");
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);
     double* Om = c->Om[c->cur];

@@ -594,7 +594,7 @@ extern "C" int ggl_ctx_destroy(ggl_ctx* c)
     // (the rocBLAS handle is the process-wide one of blas_handle(): never destroyed here)
     // lazily allocated buffers, each its own allocation
     double* lazy[] = {c->partials_own, c->nsNX, c->lds_tab, c->snapT, c->snapL, c->Lam[0], c->Lam[1], c->X1, c->Ckeep_alloc, c->snapC, c->snapOm, c->snapX, c->cwvecL[0], c->cwvecL[1], c->defl_G,
-                      c->defl_work, c->defl_meta, c->maskK};
+                      c->defl_work, c->defl_meta, c->maskK, c->fsgl_sq};
     for (double* b : lazy)
         if (b) (void)hipFree(b);
     if (c->defl_meta_h) (void)hipHostFree(c->defl_meta_h);
@@ -883,6 +883,26 @@ extern "C" int ggl_set_lambda1_mask_k(ggl_ctx* c, const double* lam)
         HIPCHK(hipMemcpyAsync(c->maskK, lam, c->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
+    return GGL_OK;
+}
+
+extern "C" int ggl_set_block_size(ggl_ctx* c, int M)
+{
+    ARGCHK(c, "ctx");
+    ARGCHK(M >= 0, "block size M >= 0 (0 clears it)");
+    if (M > 0 && c->p % M != 0)
+        return fail(GGL_E_ARG, "bad argument: the block size M = %d does not divide the dimension %d (functional_sgl_admm.py:102)", M, c->p);
+    HIPCHK(hipSetDevice(c->device));
+    DROP_PRE(c);
+    if (M > 0) {
+        int rc = ensure_partials(c, (size_t)c->K * fsgl_partial_blocks(c->p, M) * GGL_NNORM);
+        if (rc) return rc;
+        if (M > 32 && !c->fsgl_sq) {
+            const size_t nB = (size_t)c->p / 33 + 1;      // (p / M <= p / 33 block rows for every M > 32)
+            HIPCHK(malloc_filled(&c->fsgl_sq, (size_t)c->K * nB * nB * sizeof(double), c->stream));
+        }
+    }
+    c->block_M = M;
     return GGL_OK;
 }
 

@@ -70,6 +70,10 @@ struct ggl_ctx {
     bool has_maskK = false;
     int* inst_pk = nullptr;                       // (K) instance dimensions of a padded batch of single problems, lazy
     bool has_dims = false;
+    // Functional SGL (ggl_set_block_size): the Theta-step shrinks M x M blocks by their Frobenius norm (theta_fsgl.hip)
+    int block_M = 0;                              // 0: none
+    double* fsgl_sq = nullptr;                    // (K, p/M, p/M) table of block sums of squares, M > 32 only, lazy
+    long long fsgl_pair_calls = 0, fsgl_table_calls = 0;   // FSGL Theta-steps: one launch / behind the table launch
     double* sqwork = nullptr;                     // (ggl_chunks, p, p) per-chunk sums of squares
     bool has_mask = false;
     double* partials = nullptr;
@@ -369,6 +373,10 @@ int eig_recon(ggl_ctx* c, double* A, double* out, double* Dv, int map, const dou
                      int ph_recon = -1);
 int eigvals_only(ggl_ctx* c, double* A, double* Dv);
 int ensure_partials(ggl_ctx* c, size_t need);
+// FSGL Theta-step on the ctx state (ggl_step_finish_impl, sgl_batch_step_impl): l1K = par slot 1; non-latent also the dual
+// update and the partial sums [K][fsgl_partial_blocks(p, block_M)][5]
+int fsgl_theta(ggl_ctx* c, int latent);
+int fsgl_check(ggl_ctx* c, int reg, double lambda1);
 int finish_norms(ggl_ctx* c, int rows, double* out_norms, int group = 0);
 int ggl_step_finish_impl(ggl_ctx* c, double rho, double lambda1, double lambda2, int reg, int latent,
                                 const double* mu1, int groupsq_ready, double out_norms[5]);

@@ -1087,12 +1087,37 @@ extern "C" int ggl_step_finish(ggl_ctx* c, double rho, double lambda1, double la
     return ggl_step_finish_impl(c, rho, lambda1, lambda2, reg, latent, mu1, groupsq_ready, out_norms);
 }
 
+// GGL_REG_FSGL: what the step cannot serve is refused before anything is launched
+int fsgl_check(ggl_ctx* c, int reg, double lambda1)
+{
+    if (reg != GGL_REG_FSGL) return GGL_OK;
+    if (c->block_M <= 0)
+        return fail(GGL_E_ARG, "bad argument: GGL_REG_FSGL needs a block size (ggl_set_block_size; M of functional_sgl_admm.py:14)");
+    if (c->has_mask || c->has_maskK)
+        return fail(GGL_E_ARG, "bad argument: a block size and lambda1_mask together (the block penalty has one lambda1)");
+    if (c->has_dims)
+        return fail(GGL_E_ARG, "bad argument: a block size and per-instance dimensions together");
+    ARGCHK(lambda1 > 0, "lambda1 must be positive (functional_sgl_admm.py:94)");
+    return GGL_OK;
+}
+
+// Theta-step of the Functional SGL on the ctx state (theta_fsgl.hip); thresholds lambda1_k / rho_k in parameter slot 1
+int fsgl_theta(ggl_ctx* c, int latent)
+{
+    const int n = launch_theta_fsgl(c->stream, c->Theta, c->X, c->W, c->Om[c->cur], c->Om[c->cur ^ 1], latent ? c->L : nullptr,
+                                    c->par + c->K, latent ? 1 : 0, c->fsgl_sq, c->partials, c->K, c->p, c->block_M,
+                                    c->spec_pending ? c->spec_flag : nullptr);
+    if (n == 2) c->fsgl_table_calls += 1; else c->fsgl_pair_calls += 1;
+    return GGL_OK;
+}
+
 int ggl_step_finish_impl(ggl_ctx* c, double rho, double lambda1, double lambda2, int reg, int latent,
                                 const double* mu1, int groupsq_ready, double out_norms[5])
 {
     ARGCHK(c && out_norms, "ctx, out_norms");
     ARGCHK(rho > 0, "rho must be positive");
-    ARGCHK(reg == GGL_REG_SGL || reg == GGL_REG_GGL || reg == GGL_REG_FGL, "reg");
+    ARGCHK(reg == GGL_REG_SGL || reg == GGL_REG_GGL || reg == GGL_REG_FGL || reg == GGL_REG_FSGL, "reg");
+    { const int rcf = fsgl_check(c, reg, lambda1); if (rcf) return rcf; }
     ARGCHK(!latent || mu1, "latent needs mu1");
     HIPCHK(hipSetDevice(c->device));
     const bool defer_norms = (groupsq_ready & 2) != 0;
@@ -1105,20 +1130,25 @@ int ggl_step_finish_impl(ggl_ctx* c, double rho, double lambda1, double lambda2,
     double* Om = c->Om[c->cur];
     double* OmPrev = c->Om[c->cur ^ 1];
     int rows = 1;
-    if (reg == GGL_REG_SGL) {
+    if (reg == GGL_REG_SGL || reg == GGL_REG_FSGL) {
         int rc = upload_par(c, 1, nullptr, l1, 1.0);
         if (rc) return rc;
         rc = upload_par(c, 4, nullptr, inv_rho, 1.0);
         if (rc) return rc;
         PB(c, GGL_PH_THETA);
-        launch_theta_sgl(c->stream, c->Theta, c->X, c->W, Om, OmPrev, latent ? c->L : nullptr, c->par + c->K,
-                         c->has_mask ? c->mask : nullptr, c->par + 4 * (size_t)c->K, latent, c->partials, c->K, c->p,
-                         c->spec_pending ? c->spec_flag : nullptr);
+        if (reg == GGL_REG_FSGL)
+            (void)fsgl_theta(c, latent);          // prox_sum_Frob, functional_sgl_admm.py:147
+        else
+            launch_theta_sgl(c->stream, c->Theta, c->X, c->W, Om, OmPrev, latent ? c->L : nullptr, c->par + c->K,
+                             c->has_mask ? c->mask : nullptr, c->par + 4 * (size_t)c->K, latent, c->partials, c->K, c->p,
+                             c->spec_pending ? c->spec_flag : nullptr);
         PE(c, GGL_PH_THETA);
         HIPCHK(hipGetLastError());
         if (!latent) {
             PB(c, GGL_PH_REDUCE);
-            launch_reduce_partials(c->stream, c->partials, c->K, elementwise_blocks(c->p), GGL_NNORM, norms_dst);
+            launch_reduce_partials(c->stream, c->partials, c->K,
+                                   reg == GGL_REG_FSGL ? fsgl_partial_blocks(c->p, c->block_M) : elementwise_blocks(c->p),
+                                   GGL_NNORM, norms_dst);
             PE(c, GGL_PH_REDUCE);
             rows = c->K;
         }
@@ -1312,6 +1342,7 @@ extern "C" int ggl_admm_step(ggl_ctx* c, double rho, double lambda1, double lamb
 {
     ARGCHK(c, "ctx");
     ARGCHK(rho > 0, "rho must be positive");
+    { const int rcf = fsgl_check(c, reg, lambda1); if (rcf) return rcf; }
     HIPCHK(hipSetDevice(c->device));
     trace_host(c, 100);
     CopySegs sg;

@@ -1007,6 +1007,44 @@ extern "C" int ggl_prox_od_1norm(int p, const double* A, double lam, const doubl
     return GGL_OK;
 }
 
+extern "C" int ggl_prox_sum_frob(int p, int M, const double* X, double l, double* out)
+{
+    ARGCHK(p >= 1 && X && out, "arguments");
+    ARGCHK(M >= 1 && p % M == 0, "the block size M has to divide the dimension (ggl_helper.py:52)");
+    const size_t n = (size_t)p * p;
+    const size_t nB = (size_t)p / M;
+    DevBuf dX, dO, dl, dT;
+    HIPCHK(dX.alloc(n));
+    HIPCHK(dO.alloc(n));
+    HIPCHK(dl.alloc(1));
+    if (M > 32) HIPCHK(dT.alloc(nB * nB));
+    UP(dX.p, X, n);
+    UP(dl.p, &l, 1);
+    (void)launch_theta_fsgl(nullptr, dO.p, nullptr, nullptr, dX.p, nullptr, nullptr, dl.p, 2, M > 32 ? dT.p : nullptr, nullptr,
+                            1, p, M, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    DOWN(out, dO.p, n);
+    return GGL_OK;
+}
+
+extern "C" int ggl_frob_norm_per_block(int p, int M, const double* S, int off_diag, double* out)
+{
+    ARGCHK(p >= 1 && S && out, "arguments");
+    ARGCHK(M >= 1 && p % M == 0, "the block size M has to divide the dimension (helper/utils.py:71)");
+    const size_t n = (size_t)p * p;
+    const size_t nB = (size_t)p / M;
+    DevBuf dS, dT;
+    HIPCHK(dS.alloc(n));
+    HIPCHK(dT.alloc(nB * nB));
+    UP(dS.p, S, n);
+    launch_fsgl_block_table(nullptr, dT.p, dS.p, nullptr, nullptr, 1, p, M, off_diag ? 2 : 1, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    DOWN(out, dT.p, nB * nB);
+    return GGL_OK;
+}
+
 extern "C" int ggl_prox_p(int K, int p, const double* X, double l1, double l2, int reg, double* out)
 {
     ARGCHK(K >= 1 && p >= 1 && X && out, "arguments");

@@ -191,6 +191,16 @@ extern "C" int ggl_eig_info(ggl_ctx* c, int* out)
 
 // What ran last: { concurrent parts, product-kernel variant of the last matrix-function step, code of the Theta kernel the
 // process's last Theta-step launched (theta_pair.hip: theta_last_kernel), eigendecompositions ggl_finalize_L ran on this ctx }
+extern "C" int ggl_fsgl_stats(ggl_ctx* c, long long out[4])
+{
+    ARGCHK(c && out, "ctx, out");
+    out[0] = c->block_M;
+    out[1] = c->fsgl_pair_calls;
+    out[2] = c->fsgl_table_calls;
+    out[3] = c->sgl_fused_calls;
+    return GGL_OK;
+}
+
 extern "C" int ggl_last_dispatch(ggl_ctx* c, long long out[4])
 {
     ARGCHK(c && out, "ctx, out");

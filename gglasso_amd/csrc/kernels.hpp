@@ -89,6 +89,26 @@ void launch_sqdiff(hipStream_t st, const double* A, const double* B, int K, int 
 // plain elementwise prox_od_1norm for the operator entry point
 void launch_prox_od(hipStream_t st, double* out, const double* A, double lam, const double* lam_pp, int p);
 
+// ---- theta_fsgl.hip ---------------------------------------------------------------------
+// Functional SGL Theta-step: Theta = prox_sum_Frob((Omega + L) + X, M, l1K[k]) (solver/ggl_helper.py:45-66;
+// functional_sgl_admm.py:147) over tile pairs of edge fsgl_tile(M) = M floor(32 / M) (32 for M > 32); M divides p.
+//   mode 0 (non-latent): also X <- (X + Omega) - Theta (:156) and the five sums, partials [K][fsgl_partial_blocks(p,M)][5]
+//   mode 1 (latent):     also C = (Theta - X) - Omega for the L-step
+//   mode 2:              the operator alone, V = Omega (X, OmegaPrev, L, C, partials unused)
+// sqtab [K][p/M][p/M] (M > 32 only): table of block sums of squares a first launch fills.  Returns the launches (1 or 2).
+int fsgl_tile(int M);
+int fsgl_partial_blocks(int p, int M);
+int launch_theta_fsgl(hipStream_t st, double* Theta, double* X, double* C, const double* Omega, const double* OmegaPrev,
+                      const double* L, const double* l1K, int mode, double* sqtab, double* partials, int K, int p, int M,
+                      const int* skip);
+// out [K][p/M][p/M] over the blocks of (Omega + L) + X (X, L may be null), upper blocks deciding: what 0 sums of squares
+// (upper blocks only), 1 Frobenius norms, 2 Frobenius norms with a zero diagonal (frob_norm_per_block, helper/utils.py:69-87)
+void launch_fsgl_block_table(hipStream_t st, double* out, const double* Omega, const double* X, const double* L, int K,
+                             int p, int M, int what, const int* skip);
+// theta_pair.hip: the code ggl_last_dispatch reports for the process's last Theta-step, set by a launcher outside that file
+// (4000 + tile edge: FSGL tile pairs; 5000 + tile edge: FSGL tile pairs behind the table of block sums, M > 32)
+void theta_note_kernel(int code);
+
 // ---- theta_pair.hip ---------------------------------------------------------------------
 int pair_blocks(int p, int reg, int K);
 // flat != 0 and K <= GGL_FLAT_MAX_K (GGL only): one thread per element with its K-column in registers; valid for an

@@ -1360,6 +1360,7 @@ static void launch_flat4(hipStream_t st, double* Theta, double* X, double* C, co
 // (10216: K <= 128, 10416: K <= 256); 2000 + tile edge: FGL Condat tiles.
 static int g_theta_kernel = -1;
 int theta_last_kernel() { return g_theta_kernel; }
+void theta_note_kernel(int code) { g_theta_kernel = code; }     // (theta_fsgl.hip: 4000 / 5000 + tile edge)
 
 static void launch_flat4_any(hipStream_t st, double* Theta, double* X, double* C, const double* Omega,
                              const double* OmegaPrev, const double* L, double l1, double l2, int fuse_dual,

@@ -102,6 +102,17 @@ def prox_od_1norm(A, l):
     return out
 
 
+def prox_sum_Frob(X, M, l):
+    """solver/ggl_helper.py:45-66: prox of l * sum_{j != l} |X^M_jl|_F for a (pM,pM) matrix; the upper blocks decide."""
+    X = as_c(X)
+    assert X.ndim == 2 and X.shape[0] == X.shape[1]
+    pM = X.shape[0]
+    assert pM % M == 0
+    out = np.empty((pM, pM))
+    check(_lib_gpu().ggl_prox_sum_frob(pM, int(M), ptr(X), float(l), ptr(out)))
+    return out
+
+
 def prox_p(X, l1, l2, reg):
     """solver/ggl_helper.py:190-207 (same asserts: symmetric input to 1e-5, positive lambdas)."""
     X = as_c(X)

@@ -1,6 +1,6 @@
-"""Drop-in ADMM solvers: ``ADMM_MGL`` and ``ADMM_SGL`` with the reference's keyword signatures and
-return contracts (solver/admm_solver.py:13-313, solver/single_admm_solver.py:15-275 of
-fabian-sp/GGLasso), usable as the ``solver`` callable of ``grid_search`` (helper/model_selection.py:55,222).
+"""Drop-in ADMM solvers: ``ADMM_MGL``, ``ADMM_SGL`` and ``ADMM_FSGL`` with the reference's keyword signatures and
+return contracts (solver/admm_solver.py:13-313, solver/single_admm_solver.py:15-275, solver/functional_sgl_admm.py:12-238
+of fabian-sp/GGLasso), usable as the ``solver`` callable of ``grid_search`` (helper/model_selection.py:55,222).
 
 What stays on the host (as in the reference): iteration count, the rho rule, the stopping decision,
 status strings, verbose printing, exit warnings.  What moves to the MI355X: every array operation of
@@ -18,7 +18,7 @@ import numpy as np
 from . import _lib
 from ._lib import as_c, check, ptr
 
-_REG = {"SGL": _lib.REG_SGL, "GGL": _lib.REG_GGL, "FGL": _lib.REG_FGL}
+_REG = {"SGL": _lib.REG_SGL, "GGL": _lib.REG_GGL, "FGL": _lib.REG_FGL, "FSGL": _lib.REG_FSGL}
 
 
 # ctx options (include/ggl_hip.h GGL_OPT_*, names in _lib.OPTIONS) every engine is created with.  Empty in normal
@@ -146,6 +146,19 @@ class HipEngine:
         pk = np.ascontiguousarray(pk, dtype=np.int32)
         assert pk.shape == (self.K,)
         check(self.lib.ggl_set_instance_dims(self.h, pk.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+
+    def set_block_size(self, M):
+        """Functional SGL (functional_sgl_admm.py:14): the Theta-step of ``step(..., 'FSGL', ...)`` and of the batched
+        single problems shrinks M x M blocks by their Frobenius norm (prox_sum_Frob, ggl_helper.py:45-66); 0 / None clears."""
+        check(self.lib.ggl_set_block_size(self.h, int(M or 0)))
+
+    def fsgl_stats(self):
+        """{'M': block size, 'pair_steps': FSGL Theta-steps as one launch over tile pairs (M <= 32), 'table_steps': behind the
+        table of block sums (M > 32), 'fused_sgl_steps': fused one-launch SGL iterations (p <= 64) this ctx ran}."""
+        import ctypes
+        out = (ctypes.c_longlong * 4)()
+        check(self.lib.ggl_fsgl_stats(self.h, out))
+        return dict(zip(("M", "pair_steps", "table_steps", "fused_sgl_steps"), (int(v) for v in out)))
 
     def _cptr(self, a):
         """ctypes pointer of a parameter vector, cached per array object (this sits on the per-iteration path)."""
@@ -610,9 +623,10 @@ def next_rho(rho, r_t, s_t):
 
 
 def _run_admm(eng, reg, K_total, p, lambda1, lambda2, latent, mu1, nk, rho, tol, rtol, stopping_criterion,
-              update_rho, max_iter, verbose, measure, title, comm=None, want_objective=False):
-    """Host control flow shared by ADMM_MGL / ADMM_SGL / the K-sharded driver.
-    comm: None or an object with ``allreduce_groupsq(engine)`` and ``allreduce_norms(np.ndarray)``."""
+              update_rho, max_iter, verbose, measure, title, comm=None, want_objective=False, show_rho=False):
+    """Host control flow shared by ADMM_MGL / ADMM_SGL / ADMM_FSGL / the K-sharded driver.
+    comm: None or an object with ``allreduce_groupsq(engine)`` and ``allreduce_norms(np.ndarray)``.
+    show_rho: the verbose table carries a rho column (functional_sgl_admm.py:129-131, :188)."""
     runtime = np.zeros(max_iter)
     residual = np.zeros(max_iter)
     objective = np.zeros(max_iter)
@@ -628,7 +642,9 @@ def _run_admm(eng, reg, K_total, p, lambda1, lambda2, latent, mu1, nk, rho, tol,
 
     if verbose:
         print(f"------------ADMM Algorithm for {title} Graphical Lasso----------------")
-        if stopping_criterion == 'boyd':
+        if stopping_criterion == 'boyd' and show_rho:
+            print("%4s\t%10s\t%10s\t%10s\t%10s\t%10s" % ("iter", "r_t", "s_t", "eps_pri", "eps_dual", "rho"))
+        elif stopping_criterion == 'boyd':
             print("%4s\t%10s\t%10s\t%10s\t%10s" % ("iter", "r_t", "s_t", "eps_pri", "eps_dual"))
         else:
             print("%4s\t%10s" % ("iter", "kkt residual"))
@@ -686,7 +702,9 @@ def _run_admm(eng, reg, K_total, p, lambda1, lambda2, latent, mu1, nk, rho, tol,
                     eng.scale_X(rho / rho_new)       # solver/admm_solver.py:236
                 rho = rho_new
             residual[iter_t] = max(r_t, s_t)
-            if verbose:
+            if verbose and show_rho:
+                print("%4d\t%10.4g\t%10.4g\t%10.4g\t%10.4g\t%10.4g" % (iter_t, r_t, s_t, e_pri, e_dual, rho))
+            elif verbose:
                 print("%4d\t%10.4g\t%10.4g\t%10.4g\t%10.4g" % (iter_t, r_t, s_t, e_pri, e_dual))
             if (r_t <= e_pri) and (s_t <= e_dual):
                 status = 'optimal'
@@ -836,6 +854,67 @@ def ADMM_SGL(S, lambda1, Omega_0, Theta_0=np.array([]), X_0=np.array([]), rho=1.
         if latent:
             eng.finalize_L()
         _exit_report(eng, latent, 1e-8, True)
+        st = eng.state()
+    finally:
+        eng.close()
+    sol = {'Omega': st['Omega'][0], 'Theta': st['Theta'][0], 'X': st['X'][0]}
+    if latent:
+        sol['L'] = st['L'][0]
+    return sol, info
+
+
+def ADMM_FSGL(S, lambda1, M, Omega_0, Theta_0=np.array([]), X_0=np.array([]), rho=1., max_iter=1000, tol=1e-7,
+              rtol=1e-4, update_rho=True, verbose=False, measure=False, latent=False, mu1=None):
+    """(Latent variable) Functional Single Graphical Lasso by ADMM on the MI355X -- the reference's ``ADMM_FSGL``
+    (solver/functional_sgl_admm.py:12-238): each of the p variables has an M-dimensional functional representation, S is
+    (p*M,p*M), and the penalty is lambda1 * sum_{j != l} |Theta^M_jl|_F.  Same arguments, defaults, asserts, prints, exit
+    warnings and return contract: ``sol = {'Omega','Theta','X'}`` (+ 'L' when ``latent``), ``info = {'status'}``
+    (+ ``runtime``, ``residual`` with ``measure``).  The Omega-step is the SGL Omega-step at dimension p*M, the Theta-step
+    prox_sum_Frob (solver/ggl_helper.py:45-66) as one HIP kernel with the dual update and the stopping-test sums."""
+    assert Omega_0.shape == S.shape
+    assert S.shape[0] == S.shape[1]
+    assert lambda1 > 0
+    if latent:
+        assert mu1 is not None
+        assert mu1 > 0
+    (pM, pM) = S.shape
+    assert pM % M == 0
+    p = int(pM / M)
+    if verbose:
+        print(f"Derived a Functional SGL problem of dimensionality p={p}.")
+    assert rho > 0, "ADMM penalization parameter must be positive."
+
+    if len(Theta_0) == 0:
+        Theta_0 = Omega_0
+    if len(X_0) == 0:
+        X_0 = np.zeros((pM, pM))
+
+    eng = ENGINE(np.asarray(S)[None], np.asarray(Omega_0)[None], np.asarray(Theta_0)[None], np.asarray(X_0)[None])
+    try:
+        eng.set_block_size(int(M))
+        mu = as_c(np.array([mu1])) if latent else None
+        # (dim = (pM^2 + pM) / 2, functional_sgl_admm.py:248: the single-problem test at dimension pM)
+        info, _ = _run_admm(eng, 'FSGL', 1, pM, float(lambda1), 0.0, bool(latent), mu, np.ones(1), float(rho), tol,
+                            rtol, 'boyd', update_rho, max_iter, verbose, measure, "Functional Single", show_rho=True)
+        if latent:
+            eng.finalize_L()
+        # functional_sgl_admm.py:207-226: warnings, not prints, with the eigenvalue in the message
+        definite = False
+        if hasattr(eng, "exit_checks_fast"):
+            # the decisions by two Cholesky factorisations; the eigenvalues only for the text of a warning (as _exit_report)
+            f = eng.exit_checks_fast(latent, 1e-8)
+            a_om, a_th, a_l = f[:, 0].max(), f[:, 1].max(), f[:, 2].max()
+            definite = f[:, 3].min() > 0 and f[:, 4].min() > 0
+            min_tl, min_l = 1.0, 0.0
+        if not definite:
+            a_om, a_th, a_l, min_tl, min_l = eng.exit_checks(latent)
+        for name, dev in (("Omega", a_om), ("Theta", a_th), ("L", a_l)):
+            if dev > 1e-5:
+                warnings.warn(f"{name} variable is not symmetric, largest deviation is {dev}.")
+        if min_tl <= 0:
+            warnings.warn(f"Theta (Theta - L resp.) is not positive definite. Solve to higher accuracy! (min EV is {min_tl})")
+        if latent and min_l < -1e-8:
+            warnings.warn(f"L is not positive semidefinite. Solve to higher accuracy! (min EV is {min_l})")
         st = eng.state()
     finally:
         eng.close()

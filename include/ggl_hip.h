@@ -24,7 +24,9 @@ extern "C" {
 /* ABI version: major * 100 + minor.  Bumped whenever an entry point changes its argument layout or an existing buffer its
  * format -- 300 (round 6): ggl_pipeline_stats writes out[10] (was out[5]), GGL_BUF_GROUPSQ is the packed upper triangle with
  * the flag at p (p + 1) / 2 (was (p,p) + 1), the int8 entry points live in the development library only, ggl_debug_poison
- * takes a byte pattern.  A binding built against another major version must refuse to load (gglasso_amd/_lib.py does). */
+ * takes a byte pattern.  A binding built against another major version must refuse to load (gglasso_amd/_lib.py does).
+ * Entry points and selector values that are only ADDED (GGL_REG_FSGL, ggl_set_block_size, ggl_prox_sum_frob,
+ * ggl_frob_norm_per_block, ggl_fsgl_stats) leave every existing layout alone and the number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -39,6 +41,8 @@ extern "C" {
 #define GGL_REG_SGL 0       /* K independent single problems: prox_od_1norm (ggl_helper.py:16-27) */
 #define GGL_REG_GGL 1       /* prox_phi_ggl (ggl_helper.py:68-71) */
 #define GGL_REG_FGL 2       /* prox_phi_fgl (ggl_helper.py:131-134) */
+#define GGL_REG_FSGL 3      /* K independent Functional SGL problems, ADMM_FSGL (solver/functional_sgl_admm.py:12-238): prox_sum_Frob
+                             * (ggl_helper.py:45-66) over the M x M blocks of ggl_set_block_size */
 
 /* eigensolver selector (ctx flags, low byte) */
 #define GGL_EIG_AUTO 0      /* p <= GGL_NS_MIN_P: LDS Jacobi for everything.  Larger p: Newton-Schulz matrix functions for the
@@ -314,6 +318,20 @@ int ggl_sgl_batch_step(ggl_ctx *ctx, const double *rho, const double *lambda1, i
  * ggl_set_lambda1_mask_k: one (p,p) threshold array lambda1 * lambda1_mask PER INSTANCE, (K,p,p) (block_SGL hands every
  * component its own slice of the mask, :447); NULL clears it (the shared mask of ggl_set_lambda1_mask applies again). */
 int ggl_set_instance_dims(ggl_ctx *ctx, const int *pk);
+/* Functional SGL (solver/functional_sgl_admm.py:12-238; argument M, :14): every (p,p) instance of the ctx is a (p/M) x (p/M)
+ * grid of M x M blocks and the Theta-step is prox_sum_Frob (solver/ggl_helper.py:45-66, called at functional_sgl_admm.py:147):
+ * off-diagonal blocks shrunk by their Frobenius norm (prox_2norm, ggl_helper.py:38-43; the upper block decides, the lower
+ * one is its transpose), diagonal blocks passed through.  M has to divide p (:102, GGL_E_ARG otherwise); M = 0 clears it.
+ *   ggl_admm_step / ggl_step_finish / ggl_objective with GGL_REG_FSGL: one problem per instance with the same lambda1;
+ *     the penalty of ggl_objective is lambda1 sum_{I != J} |Theta_IJ|_F (:36).  GGL_E_ARG without a block size.
+ *   ggl_sgl_batch_step / ggl_sgl_batch_run with a block size set: the block penalty instead of the element-wise one, one
+ *     lambda1 per instance -- a lambda path of ADMM_FSGL problems as one batch.  The fused one-launch iteration of p <= 64
+ *     (element-wise shrink) is not requested then; the LDS-resident Omega-step alone still runs.
+ *   GGL_E_ARG, before anything is launched: a block size together with ggl_set_lambda1_mask / ggl_set_lambda1_mask_k, or with
+ *     ggl_set_instance_dims.  The reference's ADMM_FSGL has no KKT stopping criterion: ggl_kkt_residual refuses GGL_REG_FSGL.
+ * M <= 32: one launch over tile pairs of edge M floor(32/M); M > 32: a table of block sums first, then the same kernel
+ * (csrc/theta_fsgl.hip).  Deterministic: fixed reduction order, no floating-point atomics. */
+int ggl_set_block_size(ggl_ctx *ctx, int M);
 int ggl_set_lambda1_mask_k(ggl_ctx *ctx, const double *lam_Kpp_host);
 int ggl_scale_X_batch(ggl_ctx *ctx, const double *factor);
 int ggl_get_state_k(ggl_ctx *ctx, int k, double *Omega, double *Theta, double *L, double *X);
@@ -549,6 +567,10 @@ int ggl_finalize_stats(ggl_ctx *ctx, long long out[2]);
  * in one thread; 100*KQ+NW per-element kernel with the K-column over NW waves: 404, 408, 808, 816, 1616; 2000+tile FGL
  * Condat tiles), eigendecompositions ggl_finalize_L ran on this ctx }.  The parity tests assert the dispatch with it. */
 int ggl_last_dispatch(ggl_ctx *ctx, long long out[4]);
+/* Functional SGL (ggl_set_block_size): out = { block size M (0 = none), Theta-steps that ran as ONE launch over tile pairs
+ * (M <= 32; ggl_last_dispatch reports 4000 + tile edge), Theta-steps behind the table of block sums (M > 32; 5000 + tile edge),
+ * fused one-launch SGL iterations (p <= 64, element-wise shrink) this ctx ran -- 0 for as long as a block size was set }. */
+int ggl_fsgl_stats(ggl_ctx *ctx, long long out[4]);
 /* Event timeline of ggl_admm_step's iterations without a profiler (round 5; tools/event_timeline.py): after ggl_trace_start every
  * launch of the iteration is followed by an event on its stream and the host notes its own marks; ggl_trace_read stops the
  * recording and returns rows {kind 0 device / 1 host, lane (0 main stream, 1.. part streams; -1 host), tag, microseconds since the
@@ -669,6 +691,12 @@ int ggl_rank_matrix_deflate(int K, int p, const double *beta, const double *C, d
                             long long stats[8]);
 /* prox_od_1norm(A,l), ggl_helper.py:16-27; lam_pp NULL => scalar lam. */
 int ggl_prox_od_1norm(int p, const double *A, double lam, const double *lam_pp, double *out);
+/* prox_sum_Frob(X,M,l), ggl_helper.py:45-66: X, out (p,p), M divides p.  The upper blocks decide; the lower triangle of X
+ * is read on the diagonal blocks only. */
+int ggl_prox_sum_frob(int p, int M, const double *X, double l, double *out);
+/* frob_norm_per_block(S,M,off_diag), helper/utils.py:69-87: out (p/M,p/M), Frobenius norm of every M x M block (upper blocks
+ * mirrored), diagonal 0 when off_diag; lambda_max_fsgl (helper/utils.py:89-107) is the maximum of that table. */
+int ggl_frob_norm_per_block(int p, int M, const double *S, int off_diag, double *out);
 /* prox_p(X,l1,l2,reg), ggl_helper.py:190-207 (reg = GGL_REG_GGL | GGL_REG_FGL). */
 int ggl_prox_p(int K, int p, const double *X, double l1, double l2, int reg, double *out);
 /* n independent K-vectors, Y (n,K) row-major: prox_tv = condat_method (fgl_helper.py:11-68),

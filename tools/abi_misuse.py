@@ -139,6 +139,31 @@ expect_error("ggl_trace_start(max_events=-5)", lib.ggl_trace_start(h, -5))
 expect_error("ggl_comm_init(nranks=0)", lib.ggl_comm_init(h, 0, 0, ctypes.create_string_buffer(128)))
 expect_error("ggl_comm_init(rank >= nranks)", lib.ggl_comm_init(h, 3, 2, ctypes.create_string_buffer(128)))
 expect_error("ggl_allreduce_norms without a communicator", lib.ggl_allreduce_norms(h))
+# Functional SGL (ggl_set_block_size / GGL_REG_FSGL): what a step cannot serve is refused before anything is launched
+n5 = np.zeros(8)
+fstep = lambda: lib.ggl_admm_step(h, ctypes.c_double(1.0), ctypes.c_double(0.1), ctypes.c_double(0.0), 3, 0, None, None, ptr(n5))
+expect_error("ggl_admm_step(GGL_REG_FSGL without a block size)", fstep())
+expect_error("ggl_set_block_size(M=3 of p=8)", lib.ggl_set_block_size(h, 3))
+expect_error("ggl_set_block_size(M=-2)", lib.ggl_set_block_size(h, -2))
+assert lib.ggl_set_block_size(h, 4) == 0, last()
+expect_error("ggl_kkt_residual(GGL_REG_FSGL)", lib.ggl_kkt_residual(h, ctypes.c_double(1.0), ctypes.c_double(0.1), ctypes.c_double(0.0), 3, 0,
+                                                                    None, ptr(r4), ptr(np.zeros(1))))
+expect_error("ggl_admm_step(GGL_REG_FSGL, lambda1=0)", lib.ggl_admm_step(h, ctypes.c_double(1.0), ctypes.c_double(0.0), ctypes.c_double(0.0), 3, 0,
+                                                                         None, None, ptr(n5)))
+assert lib.ggl_set_lambda1_mask(h, ptr(np.ones((8, 8)))) == 0, last()
+expect_error("ggl_admm_step(GGL_REG_FSGL with lambda1_mask)", fstep())
+expect_error("ggl_sgl_batch_step(block size with lambda1_mask)", lib.ggl_sgl_batch_step(h, ptr(r4), ptr(l4), 0, None, ptr(o20)))
+assert lib.ggl_set_lambda1_mask(h, None) == 0, last()
+assert lib.ggl_set_instance_dims(h, (ctypes.c_int * 4)(8, 8, 4, 8)) == 0, last()
+expect_error("ggl_sgl_batch_step(block size with per-instance dims)", lib.ggl_sgl_batch_step(h, ptr(r4), ptr(l4), 0, None, ptr(o20)))
+assert lib.ggl_set_instance_dims(h, None) == 0, last()
+expect_error("ggl_prox_sum_frob(M=4 of p=6)", lib.ggl_prox_sum_frob(6, 4, ptr(A), ctypes.c_double(0.1), ptr(out6)))
+expect_error("ggl_prox_sum_frob(X=NULL)", lib.ggl_prox_sum_frob(6, 3, None, ctypes.c_double(0.1), ptr(out6)))
+expect_error("ggl_frob_norm_per_block(M=0)", lib.ggl_frob_norm_per_block(6, 0, ptr(A), 0, ptr(out6)))
+rc = fstep()
+print("valid ggl_admm_step(GGL_REG_FSGL, M=4) after the probes: rc", rc, last() if rc else "", "sums finite", bool(np.all(np.isfinite(n5[:5]))))
+bad += 0 if rc == 0 and np.all(np.isfinite(n5[:5])) else 1
+assert lib.ggl_set_block_size(h, 0) == 0, last()
 rc = lib.ggl_sgl_batch_step(h, ptr(r4), ptr(l4), 0, None, ptr(o20))
 print("valid ggl_sgl_batch_step after the probes: rc", rc, last() if rc else "", "sums finite", bool(np.all(np.isfinite(o20))))
 bad += 0 if rc == 0 and np.all(np.isfinite(o20)) else 1
