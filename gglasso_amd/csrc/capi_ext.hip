@@ -220,6 +220,8 @@ extern "C" int ggl_ext_kkt_residual(ggl_ctx* c, double rho, const double* lambda
     // solver/ext_admm_solver.py:347-392; the duals there are rho * X0, rho * X1
     ARGCHK(c && lambda1K && out, "ctx, lambda1, out");
     ARGCHK(c->ext_L >= 0, "ggl_ext_setup first");
+    // the group table of a batch ctx covers K / nprob instances: the group shrink below would read past its end
+    ARGCHK(c->ext_nprob == 1, "a ctx set up with ggl_ext_setup (one problem), not ggl_ext_setup_batch");
     ARGCHK(!latent || mu1, "latent needs mu1");
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);

@@ -116,9 +116,15 @@ __global__ __launch_bounds__(256) void k_ext_group(double* __restrict__ Lam, con
         const double v = Lam[(size_t)k * pp + (size_t)i * p + gj[(size_t)k * L]];
         ss += v * v;
     }
-    const double lam = l2 * sqrt((double)gsize[l]);
-    const double a = fmax(sqrt(ss), lam);
-    const double amul = a - lam;
+    // no contraction here: with lam = l2 * sqrt(n) fused into a - lam, the difference of a group at or under its threshold
+    // (a == lam) came out as the product's rounding error instead of 0, and the group as ~1e-18 (either sign) instead of zero
+    double a, amul;
+    {
+#pragma clang fp contract(off)
+        const double lam = l2 * sqrt((double)gsize[l]);
+        a = fmax(sqrt(ss), lam);
+        amul = a - lam;
+    }
     for (int k = 0; k < K; ++k) {
         const int i = gi[(size_t)k * L];
         if (i < 0) continue;

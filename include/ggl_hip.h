@@ -410,7 +410,8 @@ int ggl_exit_checks_fast_k(ggl_ctx *ctx, int latent, double shift_tl, double shi
  *   ggl_ext_admm_step  one iteration; lambda1 (K) per instance (:133-134), out_norms = the five sums of :325-345:
  *                      |Omega|^2+|Lambda|^2, |Theta-L|^2+|Theta|^2, |X0|^2+|X1|^2, |Omega-Theta+L|^2+|Lambda-Theta|^2,
  *                      |Omega-Omega_prev|^2+|Lambda-Lambda_prev|^2 over all instances (this solver has no rho update).
- *   ggl_ext_kkt_residual  the opt-in stopping_criterion='kkt' of the same solver. */
+ *   ggl_ext_kkt_residual  the opt-in stopping_criterion='kkt' of the same solver.  The ctx must hold ONE problem (ggl_ext_setup):
+ *                      on a ctx set up with ggl_ext_setup_batch it returns GGL_E_ARG before anything is launched. */
 int ggl_ext_setup(ggl_ctx *ctx, const int *pk, const int *G, int L);
 int ggl_ext_set_state(ggl_ctx *ctx, const double *Lambda, const double *X1);
 int ggl_ext_get_state(ggl_ctx *ctx, double *Lambda, double *X1);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """C-ABI misuse probe (include/ggl_hip.h): arguments a careless binding could pass -- K or p of 0 or negative, a device that does not
 exist, NULL handles and buffers, instance indices out of range, unknown options / penalties, non-positive rho / lambda, steps on a
-ctx that was never given S -- must come back as an error CODE with a message in ggl_last_error, never as a crash, a hang or a
+ctx that was never given S, ext_ADMM_MGL calls before their setup or on a ctx set up for the other form (one problem / a batch) -- must come back as an error CODE with a message in ggl_last_error, never as a crash, a hang or a
 silent success.  Every call runs in the same process; the script ends with a normal solve on a fresh ctx to show the library is
 still in order.        python tools/abi_misuse.py        -> one line per probe, 'ok' at the end"""
 import ctypes
@@ -167,6 +167,50 @@ assert lib.ggl_set_block_size(h, 0) == 0, last()
 rc = lib.ggl_sgl_batch_step(h, ptr(r4), ptr(l4), 0, None, ptr(o20))
 print("valid ggl_sgl_batch_step after the probes: rc", rc, last() if rc else "", "sums finite", bool(np.all(np.isfinite(o20))))
 bad += 0 if rc == 0 and np.all(np.isfinite(o20)) else 1
+lib.ggl_ctx_destroy(h)
+
+# ---- ext_ADMM_MGL (ggl_ext_*): every probe below is refused on the host, before anything is launched ----
+rc, h = ctx(4, 8)
+assert rc == 0, last()
+assert lib.ggl_set_S(h, ptr(S4)) == 0 and lib.ggl_set_state(h, ptr(S4), ptr(S4), None, ptr(np.zeros_like(S4))) == 0, last()
+d = ctypes.c_double
+ints = lambda a: np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+l1x, mu4, o5, kkt = np.full(4, 0.1), np.full(4, 0.2), np.zeros(5), np.zeros(1)
+xstep = lambda l2=0.05, latent=0, mu=None: lib.ggl_ext_admm_step(h, d(1.0), ptr(l1x), d(l2), latent, mu, ptr(o5))
+xkkt = lambda latent=0, mu=None: lib.ggl_ext_kkt_residual(h, d(1.0), ptr(l1x), d(0.05), latent, mu, ptr(kkt))
+expect_error("ggl_ext_admm_step before ggl_ext_setup", xstep())
+expect_error("ggl_ext_kkt_residual before ggl_ext_setup", xkkt())
+G4 = -np.ones((2, 2, 4), dtype=np.int32)              # (2,L,K): group 0 = entry (0,1) of instances 0 and 1, group 1 = (1,2) of 2 and 3
+G4[:, 0, 0] = G4[:, 0, 1] = (0, 1)
+G4[:, 1, 2] = G4[:, 1, 3] = (1, 2)
+pk4 = [8, 5, 8, 3]
+expect_error("ggl_ext_setup(p_k > p)", lib.ggl_ext_setup(h, ints([8, 9, 8, 3]), ints(G4), 2))
+Gdup = np.concatenate([G4, G4[:, :1]], axis=1)
+expect_error("ggl_ext_setup(an entry listed in two groups)", lib.ggl_ext_setup(h, ints(pk4), ints(Gdup), 3))
+expect_error("ggl_ext_setup_batch(nprob=3 of K=4)", lib.ggl_ext_setup_batch(h, 3, ints(pk4), ints(G4), 2))
+# a batch ctx: 2 problems of 2 instances; its group table covers ONE problem's instances
+G2 = np.ascontiguousarray(G4[:, :1, :2])
+assert lib.ggl_ext_setup_batch(h, 2, ints([8, 5]), ints(G2), 1) == 0, last()
+assert lib.ggl_ext_set_state(h, ptr(S4), None) == 0, last()
+expect_error("ggl_ext_kkt_residual on a batch ctx", xkkt())
+expect_error("ggl_ext_admm_step on a batch ctx", xstep())
+o10 = np.full(10, np.nan)
+rc = lib.ggl_ext_batch_step(h, d(1.0), ptr(l1x), ptr(np.array([0.05, 0.02])), 0, None, ptr(o10))
+print("valid ggl_ext_batch_step after the probes: rc", rc, last() if rc else "", "sums finite", bool(np.all(np.isfinite(o10))))
+bad += 0 if rc == 0 and np.all(np.isfinite(o10)) else 1
+# one problem of 4 instances
+assert lib.ggl_ext_setup(h, ints(pk4), ints(G4), 2) == 0, last()
+assert lib.ggl_set_state(h, ptr(S4), ptr(S4), None, ptr(np.zeros_like(S4))) == 0 and lib.ggl_ext_set_state(h, ptr(S4), None) == 0, last()
+expect_error("ggl_ext_admm_step(lambda2=0)", xstep(l2=0.0))
+expect_error("ggl_ext_admm_step(lambda2=-1)", xstep(l2=-1.0))
+expect_error("ggl_ext_admm_step(latent without mu1)", xstep(latent=1))
+expect_error("ggl_ext_kkt_residual(latent without mu1)", xkkt(latent=1))
+o5[:] = np.nan
+rc = xstep()
+rck = xkkt()
+print("valid ggl_ext_admm_step / ggl_ext_kkt_residual after the probes: rc", rc, rck, last() if rc or rck else "", "sums finite",
+      bool(np.all(np.isfinite(o5))), "kkt finite", bool(np.isfinite(kkt[0])))
+bad += 0 if rc == 0 and rck == 0 and np.all(np.isfinite(o5)) and np.isfinite(kkt[0]) else 1
 lib.ggl_ctx_destroy(h)
 print("ok" if bad == 0 else f"{bad} probes misbehaved")
 sys.exit(0 if bad == 0 else 1)
