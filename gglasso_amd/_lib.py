@@ -26,6 +26,7 @@ JACOBI_MAX_P = 128
 NS_MIN_P = 8          # GGL_EIG_AUTO: matrix-function Omega- / L-step for p above this (include/ggl_hip.h GGL_NS_MIN_P)
 BUF_S, BUF_OMEGA, BUF_THETA, BUF_L, BUF_X, BUF_GROUPSQ, BUF_NORMS, BUF_OMEGA_PREV = range(8)
 E_ARG, E_HIP, E_SOLVER, E_ALLOC, E_COMM = -1, -2, -3, -4, -5
+COV_CENTER, COV_SCALE, COV_TILE32, COV_TILE64 = 1, 2, 4, 8      # flags of ggl_covariance / ggl_set_S_from_data
 PHASES = ("form_W", "eig_omega", "recon_omega", "theta", "eig_L", "recon_L", "dual", "reduce", "eig_omega2", "bound",
           "allreduce_groupsq", "allreduce_norms")
 
@@ -147,6 +148,10 @@ _SIGNATURES = {
     "ggl_prox_tv": ([_i, _i, _dp, _d, _dp], _i),
     "ggl_prox_2norm": ([_i, _i, _dp, _d, _dp], _i),
     "ggl_prox_phi": ([_i, _i, _dp, _d, _d, _i, _dp], _i),
+    "ggl_covariance": ([_i, _i, _i, _ip, ctypes.POINTER(_dp), _i, _dp, _dp], _i),
+    "ggl_scale_by_diagonal": ([_i, _i, _i, _dp, _dp, _dp, _dp], _i),
+    "ggl_set_S_from_data": ([_vp, ctypes.POINTER(_dp), _ip, _i], _i),
+    "ggl_get_S": ([_vp, _dp, _dp], _i),
 }
 
 # libggl_hip_dev.so only (-DGGL_DEV)

@@ -717,6 +717,7 @@ static int upload_stack(ggl_ctx* c, double* dst, const double* src, int period)
 extern "C" int ggl_set_S_ex(ggl_ctx* c, const double* S, int period)
 {
     ARGCHK(c && S, "ctx, S");
+    c->cov_scale.clear();
     c->spec_have = false;
     c->cw_have = false;
     c->cwL_have = false;

@@ -1,0 +1,176 @@
+// C ABI: the input side -- sample covariance from observations and scaling by a diagonal (kernels: covariance.hip), as
+// stateless operators (host buffers in, host buffers out) and straight into the S of a ctx.
+#include "capi_internal.hpp"
+
+namespace {
+template <class T> struct DevArr {
+    T* p = nullptr;
+    ~DevArr() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T) + STACK_SLACK); }
+};
+
+constexpr int COV_FLAGS = GGL_COV_CENTER | GGL_COV_SCALE | GGL_COV_TILE32 | GGL_COV_TILE64;
+
+int check_data_args(int K, int p, const int* N, const double* const* X_host, int flags)
+{
+    ARGCHK(K >= 1 && p >= 1, "K >= 1, p >= 1");
+    ARGCHK(N && X_host, "N, X");
+    ARGCHK((flags & ~COV_FLAGS) == 0, "flags: unknown bits (GGL_COV_CENTER | GGL_COV_SCALE | GGL_COV_TILE32 | GGL_COV_TILE64)");
+    ARGCHK(!((flags & GGL_COV_TILE32) && (flags & GGL_COV_TILE64)), "flags: GGL_COV_TILE32 and GGL_COV_TILE64 exclude each other");
+    ARGCHK((size_t)K * p < (size_t)GGL_DIAG_OK, "K * p too large");
+    for (int k = 0; k < K; ++k) {
+        if (!X_host[k]) return fail(GGL_E_ARG, "bad argument: X[%d] is NULL", k);
+        if (N[k] < 1) return fail(GGL_E_ARG, "bad argument: N[%d] = %d, every instance needs at least one sample", k, N[k]);
+    }
+    return GGL_OK;
+}
+
+// the error word of launch_scale_by_diag -> GGL_E_ARG naming instance and variable.  dvals: the (K,p) diagonal on the device
+// as far as it was written (null: d_host holds the caller's), Xdiag: the stack the diagonal was taken from
+int diag_error(hipStream_t st, const int* err_d, int p, const double* d_host, const double* Xdiag, const char* what)
+{
+    int err = GGL_DIAG_OK;
+    HIPCHK(hipMemcpyAsync(&err, err_d, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (err == GGL_DIAG_OK) return GGL_OK;
+    const int k = err / p, i = err % p;
+    double v = 0.0;
+    if (d_host) v = d_host[err];
+    else HIPCHK(hipMemcpy(&v, Xdiag + (size_t)k * p * p + (size_t)i * p + i, sizeof(double), hipMemcpyDeviceToHost));
+    return fail(GGL_E_ARG, "bad argument: %s of instance %d, variable %d is %g; scaling by the diagonal needs positive finite values",
+                what, k, i, v);
+}
+
+// S_dev (K,p,p) from the host data on stream st; with GGL_COV_SCALE the correlations, and the variances in var_dev (K,p)
+int covariance_to_device(hipStream_t st, int K, int p, const int* N, const double* const* X_host, int flags, double* S_dev,
+                         double* var_dev)
+{
+    std::vector<long long> off(K);
+    size_t total = 0;
+    for (int k = 0; k < K; ++k) { off[k] = (long long)total; total += (size_t)p * N[k]; }
+    // the data go up once, into one arena of sum_k p N_k doubles (instance k packed at off[k], row length N_k)
+    DevArr<double> dX, dMean, dSd;
+    DevArr<long long> dOff;
+    DevArr<int> dN, dErr;
+    HIPCHK(dX.alloc(total));
+    HIPCHK(dOff.alloc(K));
+    HIPCHK(dN.alloc(K));
+    HIPCHK(hipMemcpyAsync(dOff.p, off.data(), K * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dN.p, N, K * sizeof(int), hipMemcpyHostToDevice, st));
+    for (int k = 0; k < K; ++k)
+        HIPCHK(hipMemcpyAsync(dX.p + off[k], X_host[k], (size_t)p * N[k] * sizeof(double), hipMemcpyHostToDevice, st));
+    const bool center = (flags & GGL_COV_CENTER) != 0;
+    if (center) {
+        HIPCHK(dMean.alloc((size_t)K * p));
+        launch_row_means(st, dX.p, dOff.p, dN.p, 0, dMean.p, K, p);
+        HIPCHK(hipGetLastError());
+    }
+    const int tile = (flags & GGL_COV_TILE64) ? 64 : ((flags & GGL_COV_TILE32) ? 32 : 0);
+    launch_gram_nt(st, dX.p, dOff.p, dN.p, 0, center ? dMean.p : nullptr, S_dev, K, p, tile);
+    HIPCHK(hipGetLastError());
+    if (flags & GGL_COV_SCALE) {
+        HIPCHK(dSd.alloc((size_t)K * p));
+        HIPCHK(dErr.alloc(1));
+        HIPCHK(hipMemsetAsync(dErr.p, 0x7f, sizeof(int), st));
+        launch_scale_by_diag(st, S_dev, nullptr, S_dev, var_dev, dSd.p, dErr.p, K, p);
+        HIPCHK(hipGetLastError());
+        int rc = diag_error(st, dErr.p, p, nullptr, S_dev, "the variance");
+        if (rc) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(st));      // the arena is freed on return
+    return GGL_OK;
+}
+}  // namespace
+
+extern "C" int ggl_covariance(int device, int K, int p, const int* N, const double* const* X_host, int flags, double* S_out,
+                              double* scale_out)
+{
+    int rc = check_data_args(K, p, N, X_host, flags);
+    if (rc) return rc;
+    ARGCHK(S_out, "S_out");
+    ARGCHK(!(flags & GGL_COV_SCALE) || scale_out, "GGL_COV_SCALE needs scale_out");
+    HIPCHK(hipSetDevice(device));
+    const size_t n = (size_t)K * p * p;
+    DevBuf dS, dVar;
+    HIPCHK(dS.alloc(n));
+    HIPCHK(dVar.alloc((size_t)K * p));
+    rc = covariance_to_device(nullptr, K, p, N, X_host, flags, dS.p, dVar.p);
+    if (rc) return rc;
+    DOWN(S_out, dS.p, n);
+    if (flags & GGL_COV_SCALE) DOWN(scale_out, dVar.p, (size_t)K * p);
+    return GGL_OK;
+}
+
+extern "C" int ggl_scale_by_diagonal(int device, int K, int p, const double* X_host, const double* d_in, double* Y_out,
+                                     double* d_out)
+{
+    ARGCHK(K >= 1 && p >= 1, "K >= 1, p >= 1");
+    ARGCHK(X_host && Y_out, "X, Y_out");
+    ARGCHK((size_t)K * p < (size_t)GGL_DIAG_OK, "K * p too large");
+    HIPCHK(hipSetDevice(device));
+    const size_t n = (size_t)K * p * p, kp = (size_t)K * p;
+    DevBuf dX, dY, dD, dDo, dSd;
+    DevArr<int> dErr;
+    HIPCHK(dX.alloc(n));
+    HIPCHK(dY.alloc(n));
+    HIPCHK(dDo.alloc(kp));
+    HIPCHK(dSd.alloc(kp));
+    HIPCHK(dErr.alloc(1));
+    UP(dX.p, X_host, n);
+    if (d_in) { HIPCHK(dD.alloc(kp)); UP(dD.p, d_in, kp); }
+    HIPCHK(hipMemset(dErr.p, 0x7f, sizeof(int)));
+    launch_scale_by_diag(nullptr, dX.p, d_in ? dD.p : nullptr, dY.p, dDo.p, dSd.p, dErr.p, K, p);
+    HIPCHK(hipGetLastError());
+    int rc = diag_error(nullptr, dErr.p, p, d_in, dX.p, d_in ? "d" : "the diagonal");
+    if (rc) return rc;
+    DOWN(Y_out, dY.p, n);
+    if (d_out) DOWN(d_out, dDo.p, kp);
+    return GGL_OK;
+}
+
+extern "C" int ggl_set_S_from_data(ggl_ctx* c, const double* const* X_host, const int* N, int flags)
+{
+    ARGCHK(c, "ctx");
+    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) takes its S from ggl_set_S");
+    int rc = check_data_args(c->K, c->p, N, X_host, flags);
+    if (rc) return rc;
+    c->spec_have = false;
+    c->cw_have = false;
+    c->cwL_have = false;
+    // S is overwritten from here on, also where a later step fails: nothing built for the old S may survive
+    c->wf_ready = false;
+    c->S_symmetric = false;
+    c->cov_scale.clear();
+    HIPCHK(hipSetDevice(c->device));
+    DROP_PRE(c);
+    const size_t kp = (size_t)c->K * c->p;
+    DevBuf dVar;
+    HIPCHK(dVar.alloc(kp));
+    rc = covariance_to_device(c->stream, c->K, c->p, N, X_host, flags, c->S, dVar.p);
+    if (rc) return rc;
+    if (flags & GGL_COV_SCALE) {
+        c->cov_scale.resize(kp);
+        HIPCHK(hipMemcpyAsync(c->cov_scale.data(), dVar.p, kp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    // as ggl_set_S: exact symmetry of S decides whether a Theta kernel may form the next W per element
+    launch_asym_max(c->stream, c->S, c->K, c->p, c->norms);
+    HIPCHK(hipGetLastError());
+    double asym = 1.0;
+    rc = host_reduce(c, c->K, 1, &asym, true);
+    if (rc) return rc;
+    c->S_symmetric = (asym == 0.0);
+    return GGL_OK;
+}
+
+extern "C" int ggl_get_S(ggl_ctx* c, double* S_out, double* scale_out)
+{
+    ARGCHK(c && S_out, "ctx, S_out");
+    ARGCHK(!scale_out || !c->cov_scale.empty(), "scale_out: the S of this ctx was not computed from data with GGL_COV_SCALE");
+    HIPCHK(hipSetDevice(c->device));
+    DROP_PRE(c);
+    int rc = download_stacks(c, {{S_out, c->S, c->n * sizeof(double)}});
+    if (rc) return rc;
+    if (scale_out) std::memcpy(scale_out, c->cov_scale.data(), c->cov_scale.size() * sizeof(double));
+    return GGL_OK;
+}

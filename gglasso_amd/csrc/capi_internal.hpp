@@ -11,6 +11,7 @@
 //   capi_comm.hip       RCCL behind the C ABI (K-sharded step)
 //   capi_ext.hip        ext_ADMM_MGL (instances of different dimension)
 //   capi_ops.hip        stateless operator entry points, development probes
+//   capi_data.hip       sample covariance from data, scaling by a diagonal (stateless and into a ctx's S)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
@@ -191,6 +192,7 @@ struct ggl_ctx {
     int theta_flat = 2;                        // GGL Theta-step for symmetric states: 0 tile pairs, 1 per-element kernel, 2 per-element with the K-column over four waves
     bool state_symmetric = true;               // X and L exactly symmetric (checked when the state is set)
     bool S_symmetric = false;                  // S exactly symmetric (checked by ggl_set_S)
+    std::vector<double> cov_scale;             // host (K,p): variances, while S holds correlations computed from data (capi_data.hip)
     // W of the next Omega-step written by this iteration's Theta kernel (GGL_OPT_FUSED_W, launch_theta_pair's WNext): valid for
     // the early first part that follows in the same ggl_admm_step, built for wf_beta
     bool fused_w = true, wf_ready = false;

@@ -72,11 +72,12 @@ def aic(S, Theta, N):
 
 
 def ebic(S, Theta, N, gamma=0.5):
-    """(p,p) or (K,p,p) stacks (model_selection.py:824-866)."""
-    if S.ndim == 2:
+    """(p,p), (K,p,p) stacks, or dicts (keys 0..K-1) of instances of different dimension (model_selection.py:824-882)."""
+    if not isinstance(S, dict) and S.ndim == 2:
         return ebic_single(S, Theta, N, gamma)
-    Nk = np.ones(S.shape[0]) * N if isinstance(N, _NUMBER) else N
-    return sum(ebic_single(S[k], Theta[k], Nk[k], gamma) for k in range(S.shape[0]))
+    K = len(S)
+    Nk = np.ones(K) * N if isinstance(N, _NUMBER) else N
+    return sum(ebic_single(S[k], Theta[k], Nk[k], gamma) for k in range(K))
 
 
 def _solve_grid(S, lam, mu, latent, tol, rtol, max_iter, tau_range=None, fetch=None, select=None):

@@ -157,3 +157,25 @@ def prox_phi_ggl(v, l1, l2):
 def prox_phi_fgl(v, l1, l2):
     """solver/ggl_helper.py:131-134."""
     return _vec(_lib_gpu().ggl_prox_phi, v, float(l1), float(l2), _lib.REG_FGL)
+
+
+def scale_array_by_diagonal(X, d=None):
+    """helper/basic_linalg.py:46-65: X_ij / (sqrt(d_i) sqrt(d_j)) for a (p,p) matrix or a (K,p,p) stack; ``d`` (p,) resp.
+    (K,p), default the diagonal of X.  Unlike the reference, a non-positive or non-finite d is an AssertionError that
+    names the instance and the variable."""
+    return _scale_by_diagonal(X, d)[0]
+
+
+def _scale_by_diagonal(X, d=None, device=0):
+    """(scaled X, the diagonal that was used)."""
+    X = as_c(X)
+    assert len(X.shape) in (2, 3)
+    assert X.shape[-1] == X.shape[-2]
+    single = X.ndim == 2
+    K, p = (1 if single else X.shape[0]), X.shape[-1]
+    if d is not None:
+        d = as_c(d)
+        assert d.shape == ((p,) if single else (K, p)), f"d has shape {d.shape}, X {X.shape}"
+    Y, d_out = np.empty_like(X), np.empty((p,) if single else (K, p))
+    check(_lib_gpu().ggl_scale_by_diagonal(int(device), K, p, ptr(X), ptr(d), ptr(Y), ptr(d_out)))
+    return Y, d_out

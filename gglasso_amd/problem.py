@@ -1,0 +1,334 @@
+"""``glasso_problem`` and ``GGLassoEstimator``: the front end a GGLasso user types (problem.py of fabian-sp/GGLasso), on
+this package's solvers and batched model-selection drivers -- no reference package, no numba.
+
+Public names, signatures, defaults, assertion messages and warnings are the reference class's; the
+implementation is this package's own:
+
+* ``solve()`` runs ``ADMM_SGL`` / ``block_SGL`` / ``ADMM_MGL`` / ``ext_ADMM_MGL`` of this package (the MI355X).
+* ``model_selection()`` calls this package's ``single_grid_search`` / ``K_single_grid`` / ``grid_search``, so a grid is
+  solved as batches (``ADMM_SGL_batch`` / ``ADMM_MGL_batch`` / ``ext_ADMM_MGL_batch``) instead of a sequential walk.
+* ``do_scaling`` (covariances -> correlations, and Theta, L back) goes through the device kernel (``ggl_scale_by_diagonal``).
+* ``glasso_problem.from_data(X, ...)`` starts from observations: S comes from ``utils.sample_covariance``.
+"""
+import numbers
+import warnings
+from collections import namedtuple
+
+import numpy as np
+
+from . import ops, utils
+from . import model_selection as _ms
+from . import solver as _solver
+from . import ext_solver as _ext
+
+assert_tol = 1e-5
+
+# What the input says about the problem.  kind: 'single' (one (p,p) matrix), 'stack' ((K,p,p), one dimension) or 'dict'
+# (instances of different dimension, keys 0..K-1); p is an int, or the K dimensions for 'dict'.
+_Formulation = namedtuple("_Formulation", "kind K p S N")
+
+# messages of the shape / symmetry checks per kind of checked array
+_INPUT_MESSAGES = {
+    'single': ("Dimensions are not correct, 1st and 2nd dimension have to match but shape is {shape}. "
+               "Specify covariance data in format(p,p)!", "Covariance data is not symmetric."),
+    'stack': ("Dimensions are not correct, 2nd and 3rd dimension have to match but shape is {shape}. "
+              "Specify covariance data in format(K,p,p)!", "Covariance data is not symmetric."),
+    'dict': ("Dimensions are not correct, 1st and 2nd dimension have to match but do not match for instance {k}.",
+             "Covariance data for instance {k} is not symmetric."),
+}
+
+# kind (and, for a single problem, latent) -> (module, solver, entries of reg_params it takes, attributes it takes)
+_SOLVE_ROUTES = {
+    ('single', False): (_solver, 'block_SGL', ('lambda1_mask',), ()),
+    ('single', True): (_solver, 'ADMM_SGL', ('lambda1_mask', 'mu1'), ('latent',)),
+    'stack': (_solver, 'ADMM_MGL', ('lambda2', 'mu1'), ('reg', 'latent')),
+    'dict': (_ext, 'ext_ADMM_MGL', ('lambda2', 'mu1'), ('reg', 'latent', 'G')),
+}
+
+_SCALING_WARNINGS = (
+    "NOTE: Input data S is rescaled to correlations, this has impact on the scale of the regularization parameters!",
+    "The output/solution is rescaled to covariances. All model selection output, in particular the optimal regularization "
+    "parameters in self.reg_params are corresponding to the correlations.",
+)
+
+
+def _is_number(x):
+    return isinstance(x, numbers.Real)
+
+
+def _per_instance(A, fn):
+    """fn over the instances of a dict, or on the array itself."""
+    return {k: fn(A[k]) for k in A} if isinstance(A, dict) else fn(A)
+
+
+def _square_and_symmetric(A, kind, **where):
+    not_square, not_symmetric = _INPUT_MESSAGES[kind]
+    assert A.shape[-2] == A.shape[-1], not_square.format(shape=A.shape, **where)
+    assert np.abs(A - np.swapaxes(A, -1, -2)).max() <= assert_tol, not_symmetric.format(**where)
+
+
+def _formulate(S, N, G):
+    """The ``_Formulation`` of the input (a copy of S, N per instance for multiple problems), or the reference's complaint."""
+    if isinstance(S, np.ndarray):
+        assert S.ndim in (2, 3), f"The specified covariance data has shape {S.shape}, GGLasso can only handle 2 or 3dim-input"
+        kind = 'single' if S.ndim == 2 else 'stack'
+        _square_and_symmetric(S, kind)
+        K, p, S = (1 if kind == 'single' else S.shape[0]), S.shape[-1], S.copy()
+        if kind == 'single':
+            assert _is_number(N), "For SGL problems, N needs to be a single number, float or int."
+    elif isinstance(S, (list, dict)):
+        assert len(S) > 1, \
+            "Covariance data is a list/dict with only one entry. This is a Single Graphical Lasso problem. Specify S as 2d-array."
+        assert G is not None, \
+            "For non-conforming dimensions, the input G has to be specified for bookeeping the overlapping variables."
+        kind, K = 'dict', len(S)
+        for k in range(K):
+            _square_and_symmetric(S[k], kind, k=k)
+        S = {k: np.array(S[k]) for k in range(K)}
+        p = np.array([S[k].shape[0] for k in range(K)], dtype=int)
+        _ext.check_G(G, p)
+    else:
+        raise TypeError(f"Incorrect input type of S. You input {type(S)}, but np.ndarray or list/dict is expected.")
+    if kind != 'single' and _is_number(N):
+        N = N * np.ones(K)
+    assert np.all(np.asarray(N) > 0), "N must be positive."
+    return _Formulation(kind, K, p, S, N)
+
+
+def adjacency_matrix(S, t=1e-10):
+    """|S| >= t off the diagonal as an int array, for a matrix or a stack (helper/basic_linalg.py:35)."""
+    A = (np.abs(S) >= t).astype(int)
+    i = np.arange(A.shape[-1])
+    A[..., i, i] = 0
+    return A
+
+
+class glasso_problem:
+    """A Graphical Lasso problem; the formulation is derived from the input (print the object to see it):
+
+    * ``S`` a (p,p) array: Single Graphical Lasso (``multiple = False``).
+    * ``S`` a (K,p,p) array: Group (``reg='GGL'``) or Fused (``reg='FGL'``) Graphical Lasso, ``conforming = True``.
+    * ``S`` a list / dict of (p_k,p_k) arrays with the bookkeeping array ``G``: Group Graphical Lasso over instances of
+      different dimension (``conforming = False``); S becomes a dict with keys 0..K-1.
+
+    ``N``: the number of samples, one number or an array of length K.  ``reg_params``: dict with ``lambda1``, ``lambda2``,
+    ``mu1`` (``latent=True``), ``lambda1_mask`` (single problems).  ``latent``: model Theta - L (sparse minus low rank).
+    After ``solve()`` or ``model_selection()`` the estimates are in ``self.solution`` (a ``GGLassoEstimator``).
+
+    ``do_scaling``: S is scaled to correlations before solving.  For a single matrix and for a list / dict the variances are
+    kept in ``_scale`` and the solution is scaled back to the covariances' scale.  For a (K,p,p) stack the reference's
+    ``_scale`` is all ones (it holds views of the stack it then scales in place), so its solution stays on the CORRELATIONS'
+    scale whatever its second warning says; that observable behaviour is kept here, and the variances are in ``_variances``."""
+
+    def __init__(self, S, N, reg="GGL", reg_params=None, latent=False, G=None, do_scaling=False):
+        form = _formulate(S, N, G)
+        self._kind = form.kind
+        self.S, self.N, self.K, self.p = form.S, form.N, form.K, form.p
+        self.multiple, self.conforming = form.kind != 'single', form.kind != 'dict'
+        self.latent, self.G, self.do_scaling = latent, G, do_scaling
+        self.reg = None
+        if self.multiple:
+            assert reg in ["GGL", "FGL"], \
+                "Specify 'GGL' for Group Graphical Lasso or 'FGL' for Fused Graphical Lasso (or None for Single Graphical Lasso)"
+            self.reg = reg
+        self.reg_params = self._default_reg_params()
+        self.set_reg_params(reg_params)
+        self.modelselect_params = self._default_modelselect_params()
+        # the estimator keeps the input on its own scale
+        self.solution = GGLassoEstimator(S=self.S, N=self.N, p=self.p, K=self.K, multiple=self.multiple, latent=self.latent,
+                                         conforming=self.conforming)
+        if do_scaling:
+            for text in _SCALING_WARNINGS:
+                warnings.warn(text)
+            self._to_correlations()
+
+    @classmethod
+    def from_data(cls, X, *, reg="GGL", reg_params=None, latent=False, G=None, do_scaling=False, center=True):
+        """The problem of observations ``X``: (p,N), (K,p,N) or a list / dict of (p_k,N_k) arrays, variables in rows.
+        ``N`` is read off the data and S is computed on the device (``utils.sample_covariance``)."""
+        _, Xs = utils._data_list(X)
+        N = np.array([x.shape[1] for x in Xs])
+        S = utils.sample_covariance(X, center=center)
+        if isinstance(S, dict) and G is None and len({s.shape[0] for s in S.values()}) == 1:
+            S = np.stack([S[k] for k in range(len(S))])       # a list of instances of ONE dimension is a conforming stack
+        if isinstance(S, np.ndarray) and S.ndim == 2:
+            N = int(N[0])
+        return cls(S, N, reg=reg, reg_params=reg_params, latent=latent, G=G, do_scaling=do_scaling)
+
+    def __repr__(self):
+        name = {None: "SINGLE", "GGL": "GROUP", "FGL": "FUSED"}[self.reg]
+        tail = "WITH LATENT VARIABLES" if self.latent else ""
+        return f" \n{name} GRAPHICAL LASSO PROBLEM {tail}\nRegularization parameters:\n{self.reg_params}"
+
+    # -- scaling (device kernel) -----------------------------------------------------------------------------------------
+    def _to_correlations(self):
+        if self._kind == 'dict':
+            scaled = [ops._scale_by_diagonal(self.S[k]) for k in range(self.K)]
+            self.S = {k: c for k, (c, _) in enumerate(scaled)}
+            self._scale = [d for _, d in scaled]
+            return
+        self.S, d = ops._scale_by_diagonal(self.S)
+        if self._kind == 'single':
+            self._scale = d
+        else:                                                   # see the class docstring
+            self._variances = list(d)
+            self._scale = [np.ones(self.p) for _ in range(self.K)]
+
+    def _from_correlations(self, X):
+        """An estimate of an inverse covariance goes back to the covariances' scale by the same division, X_ij /
+        sqrt(scale_i scale_j); nothing to do where the scale is one."""
+        if self._kind == 'stack':
+            return X
+        if self._kind == 'single':
+            return ops.scale_array_by_diagonal(X, d=self._scale)
+        return {k: ops.scale_array_by_diagonal(X[k], d=self._scale[k]) for k in range(self.K)}
+
+    # -- defaults ----------------------------------------------------------------------------------------------------------
+    def _default_reg_params(self):
+        return dict.fromkeys(('lambda1', 'lambda2', 'mu1') if self.multiple else ('lambda1', 'mu1'))
+
+    def _default_start_point(self):
+        if self._kind == 'dict':
+            return {k: np.eye(self.p[k]) for k in range(self.K)}
+        return np.eye(self.p) if self._kind == 'single' else np.tile(np.eye(self.p), (self.K, 1, 1))
+
+    def _default_solver_params(self):
+        params = dict(verbose=False, measure=False, rho=1., max_iter=1000, update_rho=True)
+        if self._kind == 'dict':
+            del params['update_rho']                          # ext_ADMM_MGL has no such argument
+        return params
+
+    def _default_modelselect_params(self):
+        grid = [('lambda1_range', np.logspace(0, -3, 10))]
+        if self.multiple:
+            grid.append(('lambda2_range', np.logspace(-1, -4, 5)))
+        grid.append(('mu1_range', np.logspace(2, -1, 10) if self.latent else None))
+        if not self.multiple:
+            grid.append(('lambda1_mask', None))
+        return dict(grid)
+
+    def set_reg_params(self, reg_params=None):
+        """Set or update (a subset of) ``lambda1``, ``lambda2``, ``mu1``, ``lambda1_mask``; other entries are kept."""
+        assert reg_params is None or type(reg_params) == dict
+        self.reg_params.update(reg_params or {})
+
+    def set_start_point(self, Omega_0=None):
+        """Start point of the solver, of the same kind as S; default the identity."""
+        self.Omega_0 = self._default_start_point() if Omega_0 is None else Omega_0.copy()
+
+    def set_modelselect_params(self, modelselect_params=None):
+        """Set or update (a subset of) ``lambda1_range``, ``lambda2_range``, ``mu1_range``, ``lambda1_mask``."""
+        if modelselect_params is None:
+            warnings.warn("No grid for model selection is specified and thus default (or previous) values are used. A grid can be specified with the argument modelselect_params.")
+            return
+        assert isinstance(modelselect_params, dict)
+        self.modelselect_params.update(modelselect_params)
+
+    # -- solving -----------------------------------------------------------------------------------------------------------
+    def solve(self, Omega_0=None, solver_params=dict(), tol=1e-8, rtol=1e-7, solver='admm', verbose=False):
+        """Solve at ``self.reg_params``; the estimates go to ``self.solution``, the solver's info to ``self.solver_info``."""
+        assert solver in ["admm"], "Currently only the ADMM solver is supported as it is implemented for all cases."
+        assert self.reg_params.get('lambda1') is not None, \
+            "Regularization parameters need to be set first (at least lambda1), see function glasso_problem.set_reg_params()"
+        self.set_start_point(Omega_0)
+        self.tol, self.rtol = tol, rtol
+        self.solver_params = {**self._default_solver_params(), **solver_params, 'verbose': verbose}
+
+        module, name, from_reg, from_self = _SOLVE_ROUTES[(self._kind, bool(self.latent)) if self._kind == 'single' else self._kind]
+        kw = dict(S=self.S, lambda1=self.reg_params['lambda1'], Omega_0=self.Omega_0, tol=self.tol, rtol=self.rtol)
+        kw.update({key: self.reg_params.get(key) for key in from_reg})
+        kw.update({key: getattr(self, key) for key in from_self})
+        if name == 'block_SGL':
+            kw['rtol'] = self.tol       # the reference hands block_SGL its absolute tolerance as the relative one (problem.py:447)
+        out = getattr(module, name)(**kw, **self.solver_params)
+        sol, info = out if isinstance(out, tuple) else (out, {})        # block_SGL returns no info
+        self._keep(sol)
+        self.solver_info = dict(info)
+
+    def _keep(self, sol):
+        """A solver's result, on the input's scale, into ``self.solution``."""
+        Theta, L = sol['Theta'], (sol['L'] if self.latent else None)
+        if self.do_scaling:
+            Theta, L = self._from_correlations(Theta), (None if L is None else self._from_correlations(L))
+        self.solution._set_solution(Theta=Theta, L=L)
+
+    # -- model selection ---------------------------------------------------------------------------------------------------
+    def model_selection(self, modelselect_params=None, method='eBIC', gamma=0.1, tol=1e-7, rtol=1e-7, store_all=False):
+        """Pick the regularization parameters on a grid by eBIC or AIC; every grid is solved as batches on the device.
+
+        * single problem: the ``lambda1`` path, or the ``(lambda1, mu1)`` grid if ``latent``;
+        * multiple, not latent: the ``(lambda1, lambda2)`` grid;
+        * multiple, latent: first the ``(lambda1, mu1)`` grid of every instance on its own, then the ``(lambda1, lambda2)``
+          grid with, per ``lambda1`` and instance, the ``mu1`` that stage one preferred.
+
+        ``self.reg_params`` is set to the best point, the tables are in ``self.modelselect_stats``."""
+        assert (gamma >= 0) and (gamma <= 1), "gamma needs to be chosen as a parameter in [0,1]."
+        assert method in ['eBIC', 'AIC'], "Supported evaluation methods are eBIC and AIC."
+        self.set_modelselect_params(modelselect_params)
+        lambda1_range = self.modelselect_params['lambda1_range']
+        if np.any(np.diff(lambda1_range) > 0):
+            warnings.warn("Ideally the lambda1 range is sorted in descending order, so the grid search is performed from sparse to dense.")
+        if store_all:
+            warnings.warn("Setting store_all=True might cause memory issues as the solution is stored at all grid points.")
+        if self.do_scaling and np.max(lambda1_range) > 1:
+            warnings.warn("Using do_scaling=True, you can restrict the range for lambda1 to 1. Larger lambdas will result in the zero solution.")
+        criterion = dict(method=method, gamma=gamma, tol=tol, rtol=rtol)
+        select = self._select_multiple if self.multiple else self._select_single
+        sol, stats = select(criterion, store_all)
+        self._keep(sol)
+        self.modelselect_stats = dict(stats)
+
+    def _select_single(self, criterion, store_all):
+        grid = self.modelselect_params
+        sol, Thetas, Ls, stats = _ms.single_grid_search(
+            S=self.S, lambda_range=grid['lambda1_range'], N=self.N, latent=self.latent, mu_range=grid['mu1_range'],
+            use_block=True, store_all=store_all, lambda1_mask=grid['lambda1_mask'], **criterion)
+        self._grid_estimates = {'Theta': Thetas, 'L': Ls}       # every grid point's, with store_all
+        self.set_reg_params(stats['BEST'])
+        return sol, stats
+
+    def _select_multiple(self, criterion, store_all):
+        grid = self.modelselect_params
+        mu_choice = None
+        if self.latent:
+            # stage one: every instance alone over (lambda1, mu1); its ix_mu (K, len(lambda1_range)) is the mu1 each instance
+            # prefers at each lambda1
+            uniform, individual, stage1 = _ms.K_single_grid(
+                S=self.S, lambda_range=grid['lambda1_range'], N=self.N, latent=True, mu_range=grid['mu1_range'],
+                use_block=True, store_all=store_all, **criterion)
+            self._stage1 = {'uniform': uniform, 'individual': individual, 'stats': stage1}
+            mu_choice = stage1['ix_mu']
+        stats, best, sol = _ms.grid_search(
+            _solver.ADMM_MGL if self.conforming else _ext.ext_ADMM_MGL, S=self.S, N=self.N, p=self.p, reg=self.reg,
+            l1=grid['lambda1_range'], l2=grid['lambda2_range'], w2=None, G=self.G, latent=self.latent,
+            mu_range=grid['mu1_range'], ix_mu=mu_choice, verbose=False, **criterion)
+        self.set_reg_params(stats['BEST'])
+        if self.latent:
+            # best is (lambda2 index, lambda1 index): the lambda1 column picks every instance's mu1
+            self.set_reg_params({'mu1': grid['mu1_range'][mu_choice[:, best[1]]]})
+        return sol, stats
+
+
+class GGLassoEstimator:
+    """The estimates of a ``glasso_problem``, scikit-learn style: ``precision_`` (the sparse component Theta),
+    ``lowrank_`` (L, with ``latent=True``), ``sample_covariance_`` (the input S), ``adjacency_``, ``n_samples``,
+    ``n_features``.  For instances of different dimension every attribute is a dict with keys 0..K-1."""
+
+    def __init__(self, S, N, p, K, multiple=True, latent=False, conforming=True):
+        self.multiple, self.latent, self.conforming, self.K = multiple, latent, conforming, K
+        self.n_samples, self.n_features = N, p
+        self.sample_covariance_ = _per_instance(S, np.array)
+        self.precision_ = self.lowrank_ = self.adjacency_ = self.ebic_ = None
+
+    def _set_solution(self, Theta, L=None):
+        self.precision_ = _per_instance(Theta, np.array)
+        self.lowrank_ = None if L is None else _per_instance(L, np.array)
+        self.calc_adjacency()
+
+    def calc_ebic(self, gamma=0.5):
+        """The eBIC of the estimate against the input S (which differs from the tables of a scaled model selection)."""
+        self.ebic_ = _ms.ebic(self.sample_covariance_, self.precision_, self.n_samples, gamma=gamma)
+        return self.ebic_
+
+    def calc_adjacency(self, t=1e-8):
+        self.adjacency_ = _per_instance(self.precision_, lambda Theta: adjacency_matrix(Theta, t=t))

@@ -71,6 +71,7 @@ def _host_period(A, K=None, p=None):
 
 class HipEngine:
     """Device-resident ADMM state behind the C ABI (one ggl_ctx)."""
+    _S_scaled = False       # True while the ctx holds variances beside its S: after set_data(scale=True), until S is set anew
 
     def __init__(self, S, Omega_0, Theta_0, X_0, L_0=None, eig=_lib.EIG_AUTO, device=0, stream=None, options=None):
         """stream: None (the ctx creates a private stream) or an int HIP stream handle -- 0 is the legacy default
@@ -104,6 +105,30 @@ class HipEngine:
         self._norms = np.zeros(5)
         self._norms_p = ptr(self._norms)
         self._ptr_cache = {}
+
+    def set_data(self, X, N=None, center=True, scale=False):
+        """The ctx's S computed on the device from observations and left there (``ggl_set_S_from_data``): X a (K,p,N)
+        array or a list of K (p,N_k) arrays, variables in rows; N (optional) the K sample counts, checked against the
+        data.  ``scale``: S becomes the correlations, ``get_S`` then also returns the variances."""
+        import ctypes
+        Xs = [as_c(x) for x in (X if isinstance(X, (list, tuple)) else np.asarray(X))]
+        assert len(Xs) == self.K and all(x.ndim == 2 and x.shape[0] == self.p for x in Xs), \
+            f"data must be {self.K} arrays of shape ({self.p}, N_k)"
+        Nk = [x.shape[1] for x in Xs]
+        if N is not None:
+            assert list(np.broadcast_to(np.asarray(N, dtype=int), (self.K,))) == Nk, f"N = {N} does not match the data ({Nk})"
+        flags = (_lib.COV_CENTER if center else 0) | (_lib.COV_SCALE if scale else 0)
+        self._S_scaled = False              # the call drops the ctx's variances first, also where it fails
+        check(self.lib.ggl_set_S_from_data(self.h, (_lib._dp * self.K)(*[ptr(x) for x in Xs]), (ctypes.c_int * self.K)(*Nk),
+                                           flags))
+        self._S_scaled = bool(scale)
+
+    def get_S(self):
+        """S (K,p,p) as it lies on the device; after ``set_data(..., scale=True)`` the pair (S, variances (K,p))."""
+        S = np.empty((self.K, self.p, self.p))
+        var = np.empty((self.K, self.p)) if self._S_scaled else None
+        check(self.lib.ggl_get_S(self.h, ptr(S), ptr(var)))
+        return S if var is None else (S, var)
 
     def set_state(self, Omega, Theta, X, L=None):
         """Overwrite the iterate (admm_solver.py:142-150 semantics: L None zeroes it)."""

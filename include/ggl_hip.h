@@ -26,7 +26,7 @@ extern "C" {
  * the flag at p (p + 1) / 2 (was (p,p) + 1), the int8 entry points live in the development library only, ggl_debug_poison
  * takes a byte pattern.  A binding built against another major version must refuse to load (gglasso_amd/_lib.py does).
  * Entry points and selector values that are only ADDED (GGL_REG_FSGL, ggl_set_block_size, ggl_prox_sum_frob,
- * ggl_frob_norm_per_block, ggl_fsgl_stats) leave every existing layout alone and the number where it is. */
+ * ggl_frob_norm_per_block, ggl_fsgl_stats, ggl_covariance, ggl_scale_by_diagonal, ggl_set_S_from_data, ggl_get_S) leave every existing layout alone and the number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -705,6 +705,28 @@ int ggl_prox_p(int K, int p, const double *X, double l1, double l2, int reg, dou
 int ggl_prox_tv(int n, int K, const double *Y, double lam, double *out);
 int ggl_prox_2norm(int n, int K, const double *Y, double lam, double *out);
 int ggl_prox_phi(int n, int K, const double *Y, double l1, double l2, int reg, double *out);
+
+/* ---- sample covariance from data, scaling by a diagonal (covariance.hip) ----------------------------------------------
+ * flags of ggl_covariance / ggl_set_S_from_data */
+#define GGL_COV_CENTER 1    /* subtract the row means (off: the raw second moment) */
+#define GGL_COV_SCALE 2     /* also scale to correlations; scale_out gets the variances */
+#define GGL_COV_TILE32 4    /* tile choice of the Gram kernel forced to 32 x 32 / 64 x 64 (tests, measurements); */
+#define GGL_COV_TILE64 8    /* default: 64 x 64 where K T (T + 1) / 2 tile pairs fill the chip, else 32 x 32 */
+/* numpy.cov(X_k, bias=True) per instance (helper/data_generation.py:221,234): X_host[k] is the row-major (p, N[k]) array of
+ * instance k, variables in rows; S_out (K,p,p), exactly symmetric; scale_out (K,p) or NULL (needed with GGL_COV_SCALE).
+ * Fixed reduction orders: two calls give bitwise equal results, instance k's result does not depend on the others.
+ * GGL_COV_SCALE with a variable of zero (or non-finite) variance is GGL_E_ARG, naming instance and variable. */
+int ggl_covariance(int device, int K, int p, const int *N, const double *const *X_host, int flags, double *S_out,
+                   double *scale_out);
+/* scale_array_by_diagonal (helper/basic_linalg.py:46-65): Y[k,i,j] = X[k,i,j] / (sqrt(d[k,i]) sqrt(d[k,j])), X, Y (K,p,p);
+ * d_in (K,p), or NULL = diag(X), which d_out (K,p, may be NULL) then returns.  A d <= 0 or non-finite is GGL_E_ARG (the
+ * reference returns NaN / inf silently), naming instance and variable; nothing is written then. */
+int ggl_scale_by_diagonal(int device, int K, int p, const double *X_host, const double *d_in, double *Y_out, double *d_out);
+/* The S of a ctx computed on the device from data and left there (no upload of S, no round trip); ctxs without instance
+ * dimensions (ggl_set_instance_dims).  Like ggl_set_S it forgets what earlier iterations carried. */
+int ggl_set_S_from_data(ggl_ctx *ctx, const double *const *X_host, const int *N, int flags);
+/* S_out (K,p,p); scale_out (K,p): the variances, NULL unless the ctx's S came from data with GGL_COV_SCALE */
+int ggl_get_S(ggl_ctx *ctx, double *S_out, double *scale_out);
 
 #ifdef __cplusplus
 }
