@@ -61,8 +61,7 @@ static int sgl_fused_finish(ggl_ctx* c, const double* rho, const double* lambda1
     // ---- some instances fell outside the kernel's range ----
     lds_missed(c);
     c->spec_have = false;
-    HIPCHK(hipMemsetAsync(c->spec_flag, 0, ggl_ctx::MAX_PARTS * sizeof(int), c->stream));
-    for (int h = 0; h < ggl_ctx::MAX_PARTS; ++h) c->spec_flag_h[h] = 0;
+    if (const int rcf = clear_spec_flags(c)) return rcf;
     std::vector<int> idx;
     for (int k = 0; k < K; ++k) if (c->sgl_fail_h[k]) idx.push_back(k);
     const int m = (int)idx.size();

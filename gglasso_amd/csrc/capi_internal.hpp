@@ -3,6 +3,9 @@
 // lines) by subject:
 //   capi_ctx.hip        ctx, arenas / stream pool, options, state upload / download
 //   capi_omega.hip      the Omega-step pipeline (speculation, parts, groups, riders), Theta-step, ggl_admm_step
+//                       omega_step is the dispatcher: omega_split fills an OmegaChainPlan (host only), then one function per
+//                       route -- omega_eig_route, omega_lds_route, omega_dev_chain (development library), omega_plan_spec,
+//                       per part omega_phase_a / omega_bound_pass, omega_finish_spec / omega_finish_validated
 //   capi_lstep.hip      the L-step (sign iteration, deflation, continuation) and ggl_finalize_L
 //   capi_batch.hip      batches of independent problems: steps, the loop in C, isolation, compaction
 //   capi_snapshots.hip  per-instance snapshots of finished points
@@ -214,16 +217,22 @@ struct ggl_ctx {
     // device has ~0.2 ms of work queued across the host's round trip.  The rest of the chain (bound kernels, products,
     // Omega) follows from the SAME plan once the iteration is validated and the rho rule leaves rho alone; otherwise the
     // early part is forgotten (it wrote W and the A'/B' scratch pair only).
-    struct EarlyA {
-        bool valid = false;
-        NsPlan plans[4];
-        double* fused[4] = {nullptr, nullptr, nullptr, nullptr};
-        double* beta = nullptr;                       // (K) beta the part was built for
-        int nh = 0, Kh[4] = {}, k0h[4] = {};          // the split the part was launched with (the rest must use the same)
-        // ... and how it was launched: groups with their own schedules, and the product-kernel variant of the parts, which
-        // also fixes the tile layout of the bound partials the part's B' launch left behind
+    // What a launch chain of the Omega-step is launched with (omega_split / omega_plan_spec, capi_omega.hip): the split of
+    // the batch into parts, how the parts are launched -- groups with their own schedules, and the product-kernel variant of
+    // the parts, which also fixes the tile layout of the bound partials a part's B' launch leaves behind -- and per part the
+    // schedule and the first step's start (2nd output of the B' launch).  Everything else a chain needs (the coefficient
+    // region of a part, its bound tile) is derived from this: plan_region, plan_bound_tile.
+    struct OmegaChainPlan {
+        int nh = 0, Kh[MAX_PARTS] = {}, k0h[MAX_PARTS] = {};
         bool grouped = false;
         int var_parts = -1;
+        NsPlan plans[MAX_PARTS];
+        double* fused[MAX_PARTS] = {};
+    };
+    struct EarlyA {
+        bool valid = false;
+        double* beta = nullptr;                       // (K) beta the part was built for
+        OmegaChainPlan plan;                          // what the part was launched with: the rest is launched from the same
     } early;
     bool early_part = true;                           // GGL_OPT_EARLY_PART
     GGL_DEV_OPT(int, part_priority);                  // GGL_OPT_PART_PRIORITY
@@ -368,6 +377,7 @@ int blas_handle(ggl_ctx* c, rocblas_handle* out);
 bool use_jacobi(const ggl_ctx* c);
 bool use_ns(int eig, int p);
 int check_info(ggl_ctx* c, const char* what);
+int clear_spec_flags(ggl_ctx* c);   // every validation flag slot, device (on the ctx stream) and host mirror
 int download_stacks(ggl_ctx* c, const std::vector<Xfer>& xs);
 int drop_prelaunch(ggl_ctx* c);
 bool early_wanted(const ggl_ctx* c);

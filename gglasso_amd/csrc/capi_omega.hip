@@ -324,49 +324,153 @@ static void note_groups(ggl_ctx* c, int G, const int* Kh, const NsPlan* plans)
     }
 }
 
-// Omega-step with beta_k in parameter slot 0 (already on the device, or part of the pending transfer)
-int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool only_spec)
+int clear_spec_flags(ggl_ctx* c)
 {
-    // only_spec: launch the chain only if it can run speculatively (no host synchronisation inside); else do nothing
-    int rc;
-    const double* beta = c->par;
-    const int nxt = c->cur ^ 1;
-    c->step_latent = latent;
-    if (latent && !c->pre0_beta.empty()) std::fill(c->pre0_beta.begin(), c->pre0_beta.end(), std::nan(""));   // (the L-step's tables share the buffer)
-    CopySegs first;
-    if (pending) first = *pending;
-    // a step whose kernels read their parameters from the pinned mirror never uploaded them: whoever reads the DEVICE copy
-    // next (every other route below does, through `first`) gets it now
-    else if (c->par0_stale) first.add(c->par, c->par_h, 8 * (size_t)c->K * sizeof(double));      // (all eight slots: a few KB)
-    c->par0_stale = false;
-    if (c->omega_ns) {
-        const int K = c->K;
-        // early phase A (ggl_ctx::EarlyA): `want_A` launches the first part of a speculative chain only; `resume` finds that
-        // part in the stream, built for this beta, and adds the rest from the same plan
-        const bool want_A = c->early_request;
-        c->early_request = false;
-        // W already in place?  (written by the Theta kernel that precedes this early first part in the stream, for this beta)
-        bool w_ready = c->wf_ready && want_A && !latent;
-        for (int k = 0; w_ready && k < K; ++k) w_ready = (c->par_h[k] == c->wf_beta[k]);
-        c->wf_ready = false;
-        bool resume = c->early.valid && allow_spec && !latent && !want_A && c->spec_enable;
-        for (int k = 0; resume && k < K; ++k) resume = (c->par_h[k] == c->early.beta[k]);
-        c->early.valid = false;
-        if (!resume) {
-            // a new plan goes into the OTHER copy of the pinned tables (a forgotten early part's copy kernel may not have run yet)
-            c->plan_par ^= 1;
-            c->coef_h = c->coef_hh[c->plan_par];
-            c->cuse_h = c->cuse_hh[c->plan_par];
-        }
-        // phase A: A' = W^2 + 4 beta I, B' = A'^2 (both needed anyway), then the bound from B'
-        double* pre = c->coef_h + (size_t)(NS_MAX_LAUNCHES - 2) * NS_SLOT(K);
-        for (int k = 0; !resume && k < K; ++k) {
-            double* o0 = pre + (size_t)k * NS_NCOEF;
-            double* o1 = pre + NS_SLOT(K) + (size_t)k * NS_NCOEF;
-            o0[0] = 4.0 * c->par_h[k]; o0[1] = 1.0; o0[2] = o0[3] = o0[4] = o0[5] = o0[6] = o0[7] = 0.0;
-            o1[0] = 0.0; o1[1] = 1.0; o1[2] = o1[3] = o1[4] = o1[5] = o1[6] = o1[7] = 0.0;
-        }
-        double* pre_d = c->coef + (size_t)(NS_MAX_LAUNCHES - 2) * NS_SLOT(K);
+    HIPCHK(hipMemsetAsync(c->spec_flag, 0, ggl_ctx::MAX_PARTS * sizeof(int), c->stream));
+    for (int h = 0; h < ggl_ctx::MAX_PARTS; ++h) c->spec_flag_h[h] = 0;
+    return GGL_OK;
+}
+
+// ---- what the routes of omega_step share ------------------------------------------------------------------------------------
+typedef ggl_ctx::OmegaChainPlan OmegaChainPlan;
+
+// the locals of one omega_step call that more than one route reads
+struct OmegaStep {
+    int latent = 0, nxt = 0;
+    const double* beta = nullptr;      // beta_k: parameter slot 0 on the device (the pinned mirror where the LDS kernel took it from there)
+    CopySegs first;                    // parameter transfers that go in front of the step's first kernel
+    double *pre = nullptr, *pre_d = nullptr;                      // coefficient rows of A' and B' (pinned / device)
+    double *start_base_h = nullptr, *start_base_d = nullptr;      // the first step's start coefficients, 5 per instance
+    size_t pp = 0;
+    // early phase A (ggl_ctx::EarlyA): `want_A` launches the first part of a speculative chain only; `resume` finds that
+    // part in the stream, built for this beta, and adds the rest from the same plan
+    bool want_A = false, resume = false;
+    bool w_ready = false;              // W already in place (written by the Theta kernel that precedes this early first part)
+    bool spec = false;                 // the chain runs speculatively, on the previous iteration's bounds
+    bool cw_written = false;           // this step's bound pass left a Collatz-Wielandt vector behind
+};
+
+static void note_sequence(ggl_ctx* c, const NsPlan& pl, int Kr)
+{
+    c->ns_launches_total += pl.products;
+    note_family(c, pl);
+    // algorithmic work in units of (whole-stack) K p^3 flop
+    const double frac = (double)Kr / c->K;
+    c->ns_units_frac += frac * pl.units;
+    c->ns_steps_frac += frac * pl.steps;
+}
+
+// a matrix-function step is in the stream: Omega[nxt] becomes the current iterate (no eigenvalues behind it)
+static void step_advance(ggl_ctx* c, int nxt)
+{
+    c->dvo_valid = false;
+    c->cur = nxt;
+}
+
+static void step_epilogue(ggl_ctx* c, int nxt)
+{
+    c->ns_units_total = (long long)(c->ns_units_frac + 0.5);
+    c->ns_steps_total = (long long)(c->ns_steps_frac + 0.5);
+    c->ns_calls += 1;
+    if (c->info_dirty) { memset(c->info_h, 0, c->K * sizeof(int)); c->info_dirty = false; }
+    step_advance(c, nxt);
+}
+
+// the carried Collatz-Wielandt vector of a part that starts at instance k0: the accepted one / the one the pass in flight writes
+static const double* cw_prev(const ggl_ctx* c, int k0)
+{
+    return (c->cw_warm && c->cw_have) ? c->cwvec[c->cw_cur] + (size_t)k0 * c->p : nullptr;
+}
+static double* cw_next(const ggl_ctx* c, int k0)
+{
+    return c->cw_warm ? c->cwvec[c->cw_cur ^ 1] + (size_t)k0 * c->p : nullptr;
+}
+
+// coefficient slots per part
+static size_t plan_region(const OmegaChainPlan& pl, int K) { return (size_t)(NS_MAX_LAUNCHES - 4) / pl.nh * NS_SLOT(K); }
+
+// the bound partials part h's B' launch leaves behind (bT = 0: none, the three-kernel norm bound)
+struct BoundTile { int bT; double *rowp, *frop; };
+static BoundTile plan_bound_tile(const ggl_ctx* c, const OmegaChainPlan& pl, int h)
+{
+    const int k0 = pl.k0h[h];
+    const int btile = c->fused_bounds ? symm_bounds_tile(pl.Kh[h], c->p, pl.var_parts) : 0;
+    const int bT = btile ? (c->p + btile - 1) / btile : 0;
+    return {bT, btile ? c->rowpart + (size_t)k0 * bT * c->p : nullptr, btile ? c->fropart + (size_t)k0 * (bT * (bT + 1) / 2) : nullptr};
+}
+
+// which halves of a chain this call launches, and whether the chain can run speculatively
+static void omega_step_flags(ggl_ctx* c, OmegaStep& S, bool allow_spec, bool only_spec)
+{
+    const int K = c->K, latent = S.latent;
+    S.want_A = c->early_request;
+    c->early_request = false;
+    // W already in place?  (written by the Theta kernel that precedes this early first part in the stream, for this beta)
+    S.w_ready = c->wf_ready && S.want_A && !latent;
+    for (int k = 0; S.w_ready && k < K; ++k) S.w_ready = (c->par_h[k] == c->wf_beta[k]);
+    c->wf_ready = false;
+    S.resume = c->early.valid && allow_spec && !latent && !S.want_A && c->spec_enable;
+    for (int k = 0; S.resume && k < K; ++k) S.resume = (c->par_h[k] == c->early.beta[k]);
+    c->early.valid = false;
+    // Speculation: same beta as the last validated step => its bounds, inflated by 2 %, are very likely still
+    // bounds (W moves little between ADMM iterations and the spectrum usually shrinks); the schedule is built
+    // from them NOW and the products follow the bound kernels without the host round trip.
+    S.spec = allow_spec && c->spec_enable && c->spec_have && !latent && c->spec_cool == 0;
+    if (allow_spec && !only_spec && c->spec_cool > 0) c->spec_cool -= 1;      // one tick per iteration, not per attempt
+    for (int k = 0; S.spec && k < K; ++k) S.spec = (c->par_h[k] == c->spec_beta[k]);
+    if (S.resume) S.spec = true;
+}
+
+// the pinned plan tables this step writes, and the coefficient rows of A' and B' in them
+static void omega_step_tables(ggl_ctx* c, OmegaStep& S)
+{
+    const int K = c->K;
+    if (!S.resume) {
+        // a new plan goes into the OTHER copy of the pinned tables (a forgotten early part's copy kernel may not have run yet)
+        c->plan_par ^= 1;
+        c->coef_h = c->coef_hh[c->plan_par];
+        c->cuse_h = c->cuse_hh[c->plan_par];
+    }
+    // phase A: A' = W^2 + 4 beta I, B' = A'^2 (both needed anyway), then the bound from B'
+    S.pre = c->coef_h + (size_t)(NS_MAX_LAUNCHES - 2) * NS_SLOT(K);
+    for (int k = 0; !S.resume && k < K; ++k) {
+        double* o0 = S.pre + (size_t)k * NS_NCOEF;
+        double* o1 = S.pre + NS_SLOT(K) + (size_t)k * NS_NCOEF;
+        o0[0] = 4.0 * c->par_h[k]; o0[1] = 1.0; o0[2] = o0[3] = o0[4] = o0[5] = o0[6] = o0[7] = 0.0;
+        o1[0] = 0.0; o1[1] = 1.0; o1[2] = o1[3] = o1[4] = o1[5] = o1[6] = o1[7] = 0.0;
+    }
+    S.pre_d = c->coef + (size_t)(NS_MAX_LAUNCHES - 2) * NS_SLOT(K);
+    S.start_base_h = c->coef_h + (size_t)(NS_MAX_LAUNCHES - 3) * NS_SLOT(K);
+    S.start_base_d = c->coef + (size_t)(NS_MAX_LAUNCHES - 3) * NS_SLOT(K);
+}
+
+// ---- the split (host only) --------------------------------------------------------------------------------------------------
+// instances that need different product counts: contiguous groups with their own schedules (cb: the bounds to group by)
+static bool plan_regroup(const ggl_ctx* c, const double* cb, OmegaChainPlan& pl)
+{
+    int gunits[ggl_ctx::MAX_PARTS] = {};
+    const int G = omega_groups(c, cb, c->par_h, c->K, pl.Kh, pl.k0h, gunits);
+    if (G <= 1) return false;
+    pl.nh = G;
+    pl.grouped = true;
+    // (groups of different sizes: ONE kernel instance for all of them -- the bound partials of the parts are laid out
+    // by the tile size, and the size rule could pick 32x32 tiles for a small group next to 64x64 for a large one)
+    // (the instance the WHOLE batch would take -- the groups share the chip -- with three DMA stages where that is the
+    // 64x64 kernel, as for any concurrent parts)
+    pl.var_parts = c->symm_variant >= 0 ? c->symm_variant : (symm_auto_variant(c->K, c->p) == 16 ? 17 : symm_auto_variant(c->K, c->p));
+    return true;
+}
+
+static void omega_split(ggl_ctx* c, const OmegaStep& S, OmegaChainPlan& pl)
+{
+    const int K = c->K;
+    if (S.resume) {
+        // the split, the variant and the schedules of the early part: its B' launch laid out the bound partials the rest reads,
+        // by that variant's tile size.  What the rest derives from the plan (plan_region, plan_bound_tile) depends on options
+        // besides, which cannot change between the two halves: both are launched inside one ggl_admm_step call, with only the
+        // validation of the previous iteration in between, which advances the Collatz-Wielandt vector the rest is meant to read.
+        pl = c->early.plan;
+    } else {
         // Parts of the batch on concurrent streams: while one part's product drains its output and the next
         // launch ramps up, the other part keeps the matrix cores busy (a single launch sequence leaves them idle
         // for ~20 % of every product at p = 500).  Each part gets its own schedule.
@@ -383,573 +487,583 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool 
         // (K = 8, p = 500: +2 %; K = 16 on the 32x32 kernel: -13 %, K = 4: -16 % -- so only the narrow band below 16)
         if (nh == 1 && c->parts_small && K >= c->parts_small && K < 16 && c->p >= 384 && c->ns_parts >= 2) nh = 2;
         nh = std::max(nh, 1);
-        // Speculation: same beta as the last validated step => its bounds, inflated by 2 %, are very likely still
-        // bounds (W moves little between ADMM iterations and the spectrum usually shrinks); the schedule is built
-        // from them NOW and the products follow the bound kernels without the host round trip.
-        bool spec = allow_spec && c->spec_enable && c->spec_have && !latent && c->spec_cool == 0;
-        if (allow_spec && !only_spec && c->spec_cool > 0) c->spec_cool -= 1;      // one tick per iteration, not per attempt
-        for (int k = 0; spec && k < K; ++k) spec = (c->par_h[k] == c->spec_beta[k]);
-        if (resume) spec = true;
-        int Kh[ggl_ctx::MAX_PARTS], k0h[ggl_ctx::MAX_PARTS];
-        bool grouped = false;
-        int gunits[ggl_ctx::MAX_PARTS] = {};
-        if (resume) {
-            nh = c->early.nh;
-            grouped = c->early.grouped;
-            for (int h = 0; h < nh; ++h) { Kh[h] = c->early.Kh[h]; k0h[h] = c->early.k0h[h]; }
-        } else {
-            for (int h = 0, k0 = 0; h < nh; ++h) {
-                Kh[h] = K / nh + (h < K % nh ? 1 : 0);
-                if (nh == 2 && c->parts_bias && std::abs(c->parts_bias) < K / 2) Kh[h] += h == 0 ? c->parts_bias : -c->parts_bias;
-                k0h[h] = k0;
-                k0 += Kh[h];
-            }
-            if (spec && nh == 1) {
-                // instances that need different product counts: contiguous groups with their own schedules
-                std::vector<double> cb(K);
-                for (int k = 0; k < K; ++k) cb[k] = c->spec_c[k] * c->spec_factor;
-                const int G = omega_groups(c, cb.data(), c->par_h, K, Kh, k0h, gunits);
-                if (G > 1) { nh = G; grouped = true; }
-            }
+        pl.nh = nh;
+        for (int h = 0, k0 = 0; h < nh; ++h) {
+            pl.Kh[h] = K / nh + (h < K % nh ? 1 : 0);
+            if (nh == 2 && c->parts_bias && std::abs(c->parts_bias) < K / 2) pl.Kh[h] += h == 0 ? c->parts_bias : -c->parts_bias;
+            pl.k0h[h] = k0;
+            k0 += pl.Kh[h];
         }
-        const size_t pp = (size_t)c->p * c->p;
-        const int nbb = norm_bounds_blocks(c->p);
         // concurrent parts of a large batch: the 3-stage 64x64 DMA kernel; parts of a small batch: the size rule
-        // (groups of different sizes: ONE kernel instance for all of them -- the bound partials of the parts are laid out
-        // by the tile size, and the size rule could pick 32x32 tiles for a small group next to 64x64 for a large one)
-        // (the instance the WHOLE batch would take -- the groups share the chip -- with three DMA stages where that is the
-        // 64x64 kernel, as for any concurrent parts)
-        const int var_grouped = c->symm_variant >= 0 ? c->symm_variant : (symm_auto_variant(K, c->p) == 16 ? 17 : symm_auto_variant(K, c->p));
-        // (resume: the variant of the early part -- its B' launch laid out the bound partials the rest reads, by that tile size.
-        // Everything else the rest derives again below is fixed by the restored split and by options, which cannot change
-        // between the two halves: both are launched inside one ggl_admm_step call, with only the validation of the previous
-        // iteration in between, which advances the Collatz-Wielandt vector the rest is meant to read.)
-        const int var_parts = resume ? c->early.var_parts
-                            : grouped ? var_grouped
-                                      : ((c->symm_variant < 0 && nh > 1 && K >= 16) ? 17 : c->symm_variant);
-        c->last_parts = nh;
-        c->last_variant = symm_effective_variant(var_parts >= 0 ? var_parts : symm_auto_variant(Kh[0], c->p), c->p);
-        const size_t region = (size_t)(NS_MAX_LAUNCHES - 4) / nh * NS_SLOT(K);      // coefficient slots per part
-        NsPlan plans[ggl_ctx::MAX_PARTS];
-        double* start_base_h = c->coef_h + (size_t)(NS_MAX_LAUNCHES - 3) * NS_SLOT(K);
-        double* start_base_d = c->coef + (size_t)(NS_MAX_LAUNCHES - 3) * NS_SLOT(K);
-        double* fused[ggl_ctx::MAX_PARTS] = {};      // speculative step: the first step's start as 2nd output of the B' launch
-        bool cw_written = false;                     // this step's bound pass left a Collatz-Wielandt vector behind
-        if (c->flags_dirty) {
-            // a step was rejected since the flags were last cleared wholesale: whatever slot carried the 1 (a part that does
-            // not exist in this step's split, the chain's completion check) must not outlive it.  On the main stream BEFORE
-            // the fork, so it is ordered ahead of every part's own zeroing and kernels.
-            HIPCHK(hipMemsetAsync(c->spec_flag, 0, ggl_ctx::MAX_PARTS * sizeof(int), c->stream));
-            for (int h = 0; h < ggl_ctx::MAX_PARTS; ++h) c->spec_flag_h[h] = 0;
-            c->flags_dirty = false;
+        pl.var_parts = (c->symm_variant < 0 && nh > 1 && K >= 16) ? 17 : c->symm_variant;
+        if (S.spec && nh == 1) {
+            std::vector<double> cb(K);
+            for (int k = 0; k < K; ++k) cb[k] = c->spec_c[k] * c->spec_factor;
+            plan_regroup(c, cb.data(), pl);
         }
-        // ---- small matrices: the whole step as ONE launch, one workgroup per instance, the chain resident in LDS ----------
-        // The kernel finds bound and schedule itself, so it needs no host round trip: where the caller can repeat a step
-        // (allow_spec) it runs like a speculative chain -- an instance outside its range (kappa > 300, non-finite data)
-        // raises validation flag 0, the Theta-step leaves the iterate alone and the step is repeated on the launch chain --
-        // elsewhere the flag is read back after a stream synchronisation.
-        c->lds_last = false;
-        const LdsSgl* sgl_req = c->sgl_req;         // (consumed here, whichever route the step takes)
-        c->sgl_req = nullptr;
-        c->sgl_done = false;
-        if (c->lds_omega && c->p <= omega_lds_max_p() && c->ns_force == 0 && c->symm_variant < 0 && !c->chain_mode && !want_A && !resume) {
-            const bool as_spec = allow_spec && c->spec_enable && !latent;
-            if (c->lds_cool > 0) {
-                if (!only_spec) c->lds_cool -= 1;
-            } else if (as_spec || !only_spec) {
-                rc = lds_table(c);
-                if (rc) return rc;
-                // K independent single problems: the same workgroup goes on with the Theta-step and the stopping-test sums
-                LdsSgl sgl;
-                const bool fused = sgl_req && as_spec && c->seq_h && c->spin_wait && !c->prof_on;
-                // ... and takes its three parameters per instance (beta, lambda1 / rho, 1 / rho) straight from the pinned
-                // mirror the caller has just filled: no parameter copy in front of it, the iteration is ONE launch (the
-                // device flag stays zero in this form -- a miss clears it itself, sgl_fused_finish)
-                // The plain form does the same when the pending transfer is nothing but beta (ggl_admm_step): the validation
-                // flags it used to zero with that copy ARE zero unless a step was rejected (flags_dirty, handled above).
-                const bool no_copy = c->lds_pinned && !c->info_dirty && ((fused && pending != nullptr) || (!sgl_req && (pending == nullptr || c->pending_beta_only || c->pending_pinned_ok)));
-                CopySegs sg = first;
-                sg.add(c->spec_flag, nullptr, sizeof(int));
-                sg.add(c->spec_flag + ggl_ctx::MAX_PARTS - 1, nullptr, sizeof(int));
-                c->spec_flag_h[0] = c->spec_flag_h[ggl_ctx::MAX_PARTS - 1] = 0;
-                if (c->info_dirty) sg.add(c->info, nullptr, K * sizeof(int));
-                if (!no_copy) launch_copy_small(c->stream, sg);
-                PB(c, GGL_PH_EIG_OMEGA);
-                unsigned long long* cnt = (unsigned long long*)(c->lds_tab + (size_t)OMEGA_LDS_MAXTAB * OMEGA_LDS_ENT);
-                if (fused) {
-                    sgl = *sgl_req;
-                    sgl.Theta = c->Theta; sgl.X = c->X; sgl.OmegaPrev = c->Om[c->cur];
-                    sgl.norms = c->norms_h; sgl.fail = c->sgl_fail_h;
-                    sgl.seq = c->seq_h; sgl.seq_val = c->seq_wait = ++c->seq_next; sgl.arrive = c->arrive;
-                    memset(c->sgl_fail_h, 0, K * sizeof(int));
-                    if (no_copy) {
-                        sgl.l1K = c->par_h + K;
-                        sgl.invrhoK = c->par_h + 4 * (size_t)K;
-                    }
-                }
-                if (no_copy && first.n > 0) { beta = c->par_h; c->par0_stale = true; }
-                if (!launch_omega_lds(c->stream, c->Theta, latent ? c->L : nullptr, c->X, c->S, beta, c->Om[nxt], c->lds_tab,
-                                      c->lds_ntab, c->lds_lnq, K, c->p, c->spec_flag, c->spec_flag_h, 0, cnt, c->bounds_h, nullptr,
-                                      c->lds_waves, fused ? &sgl : nullptr))
-                    return fail(GGL_E_HIP, "k_omega_lds: p = %d outside the kernel's range, or the LDS attribute was refused", c->p);
-                PE(c, GGL_PH_EIG_OMEGA);
-                c->sgl_done = fused;
-                HIPCHK(hipGetLastError());
-                c->last_parts = 1;
-                c->last_variant = 41;
-                c->lds_calls += 1;
-                c->ns_calls += 1;
-                c->ns_launches_total += 1;
-                c->lds_last = true;
-                if (c->info_dirty) { memset(c->info_h, 0, K * sizeof(int)); c->info_dirty = false; }
-                if (as_spec) {
-                    // validated by the caller after its stream sync (validate_spec) -- the fused SGL form is not speculative in
-                    // that sense: an instance outside the range is redone ALONE by the caller (sgl_fused_finish)
-                    c->spec_pending = !fused;
-                    c->cw_pending = false;
-                    c->dvo_valid = false;
-                    c->cur = nxt;
-                    return GGL_OK;
-                }
-                HIPCHK(hipStreamSynchronize(c->stream));
-                if (c->spec_flag_h[0] == 0) {
-                    sanitize_bounds(c, c->bounds_h, c->par_h, 4.0);
-                    for (int k = 0; k < K; ++k) { c->spec_c[k] = c->bounds_h[k]; c->spec_beta[k] = c->par_h[k]; }
-                    c->spec_have = true;
-                    c->lds_cool_next = 4;
-                    c->dvo_valid = false;
-                    c->cur = nxt;
-                    return GGL_OK;
-                }
-                // outside the kernel's range: this step (and the next few) on the launch chain
-                c->par0_stale = false;                 // (whose parameter copy carries `first`)
-                lds_missed(c);
-                HIPCHK(hipMemsetAsync(c->spec_flag, 0, ggl_ctx::MAX_PARTS * sizeof(int), c->stream));
-                for (int h = 0; h < ggl_ctx::MAX_PARTS; ++h) c->spec_flag_h[h] = 0;
-            }
+    }
+    c->last_parts = pl.nh;
+    c->last_variant = symm_effective_variant(pl.var_parts >= 0 ? pl.var_parts : symm_auto_variant(pl.Kh[0], c->p), c->p);
+}
+
+// ---- the routes -------------------------------------------------------------------------------------------------------------
+// eigendecomposition of W (no matrix-function route for this ctx)
+static int omega_eig_route(ggl_ctx* c, OmegaStep& S, bool only_spec)
+{
+    if (only_spec) return GGL_NOT_LAUNCHED;
+    launch_copy_small(c->stream, S.first);
+    PB(c, GGL_PH_FORM_W);
+    launch_form_W(c->stream, c->W, c->Theta, S.latent ? c->L : nullptr, c->X, c->S, S.beta, c->K, c->p);
+    PE(c, GGL_PH_FORM_W);
+    HIPCHK(hipGetLastError());
+    const int rc = eig_recon(c, c->W, c->Om[S.nxt], c->DvO, MAP_PHIPLUS, S.beta, GGL_PH_EIG_OMEGA, GGL_PH_RECON_OMEGA);
+    if (rc) return rc;
+    c->dvo_valid = true;
+    c->cur = S.nxt;
+    return GGL_OK;
+}
+
+// ---- small matrices: the whole step as ONE launch, one workgroup per instance, the chain resident in LDS ----------
+// The kernel finds bound and schedule itself, so it needs no host round trip: where the caller can repeat a step
+// (allow_spec) it runs like a speculative chain -- an instance outside its range (kappa > 300, non-finite data)
+// raises validation flag 0, the Theta-step leaves the iterate alone and the step is repeated on the launch chain --
+// elsewhere the flag is read back after a stream synchronisation.
+// *done: the step is complete (or failed); otherwise it goes on to the launch chain.
+static int omega_lds_route(ggl_ctx* c, OmegaStep& S, CopySegs* pending, bool allow_spec, bool only_spec, bool* done)
+{
+    const int K = c->K, nxt = S.nxt;
+    *done = false;
+    c->lds_last = false;
+    const LdsSgl* sgl_req = c->sgl_req;         // (consumed here, whichever route the step takes)
+    c->sgl_req = nullptr;
+    c->sgl_done = false;
+    if (!(c->lds_omega && c->p <= omega_lds_max_p() && c->ns_force == 0 && c->symm_variant < 0 && !c->chain_mode && !S.want_A && !S.resume))
+        return GGL_OK;
+    const bool as_spec = allow_spec && c->spec_enable && !S.latent;
+    if (c->lds_cool > 0) {
+        if (!only_spec) c->lds_cool -= 1;
+        return GGL_OK;
+    }
+    if (!(as_spec || !only_spec)) return GGL_OK;
+    *done = true;
+    const int rc = lds_table(c);
+    if (rc) return rc;
+    // K independent single problems: the same workgroup goes on with the Theta-step and the stopping-test sums
+    LdsSgl sgl;
+    const bool sgl_fused = sgl_req && as_spec && c->seq_h && c->spin_wait && !c->prof_on;
+    // ... and takes its three parameters per instance (beta, lambda1 / rho, 1 / rho) straight from the pinned
+    // mirror the caller has just filled: no parameter copy in front of it, the iteration is ONE launch (the
+    // device flag stays zero in this form -- a miss clears it itself, sgl_fused_finish)
+    // The plain form does the same when the pending transfer is nothing but beta (ggl_admm_step): the validation
+    // flags it used to zero with that copy ARE zero unless a step was rejected (flags_dirty, handled by omega_step).
+    const bool no_copy = c->lds_pinned && !c->info_dirty && ((sgl_fused && pending != nullptr) || (!sgl_req && (pending == nullptr || c->pending_beta_only || c->pending_pinned_ok)));
+    CopySegs sg = S.first;
+    sg.add(c->spec_flag, nullptr, sizeof(int));
+    sg.add(c->spec_flag + ggl_ctx::MAX_PARTS - 1, nullptr, sizeof(int));
+    c->spec_flag_h[0] = c->spec_flag_h[ggl_ctx::MAX_PARTS - 1] = 0;
+    if (c->info_dirty) sg.add(c->info, nullptr, K * sizeof(int));
+    if (!no_copy) launch_copy_small(c->stream, sg);
+    PB(c, GGL_PH_EIG_OMEGA);
+    unsigned long long* cnt = (unsigned long long*)(c->lds_tab + (size_t)OMEGA_LDS_MAXTAB * OMEGA_LDS_ENT);
+    if (sgl_fused) {
+        sgl = *sgl_req;
+        sgl.Theta = c->Theta; sgl.X = c->X; sgl.OmegaPrev = c->Om[c->cur];
+        sgl.norms = c->norms_h; sgl.fail = c->sgl_fail_h;
+        sgl.seq = c->seq_h; sgl.seq_val = c->seq_wait = ++c->seq_next; sgl.arrive = c->arrive;
+        memset(c->sgl_fail_h, 0, K * sizeof(int));
+        if (no_copy) {
+            sgl.l1K = c->par_h + K;
+            sgl.invrhoK = c->par_h + 4 * (size_t)K;
         }
-#ifdef GGL_DEV
-        // ---- the whole product chain as ONE persistent launch with per-instance dependencies (k_omega_chain) ----------
-        if (spec && !want_A && !resume && c->chain_mode && c->fused_start && c->fused_bounds && (c->symm_variant < 0 || c->symm_variant == 17) &&
-            chain_tile(K, c->p, c->chain_mode == 2) == 64) {
-            if (!c->nsNX) HIPCHK(malloc_filled(&c->nsNX, 2 * c->n * sizeof(double) + STACK_SLACK, c->stream));
-            if (!c->chain_cnt) HIPCHK(hipMalloc(&c->chain_cnt, (size_t)K * CHAIN_CNT_STRIDE * sizeof(unsigned)));
-            for (int k = 0; k < K; ++k) c->cuse_h[k] = c->spec_c[k] * c->spec_factor;
-            NsPlan& pl = plans[0];
-            SymmOp ops[CHAIN_MAX_OPS];
-            int nops = 0;
-            const int bT = (c->p + 63) / 64;
-            if (ns_plan(c->cuse_h, c->par_h, K, c->coef_h, start_base_h, &pl, c->ns_force, c->ns_degrees, c->ns_tol, c->omega_poly) == 0 &&
-                !pl.stable) {
-                double* f0 = nullptr;
-                for (int k = 0; k < K; ++k)
-                    f0 = ns_fused_start(pl, start_base_h + 5 * (size_t)k, c->nsYP[1], c->nsT, (size_t)K * pp,
-                                        pre + NS_SLOT(K) + (size_t)k * NS_NCOEF);
-                if (f0)
-                    nops = ns_chain_ops(pl, pre_d, pre_d + NS_SLOT(K), c->coef, c->W, c->nsYP[0], c->nsYP[1], c->nsNX, c->nsT,
-                                        c->Om[nxt], K, c->p, 0, f0, c->rowpart, c->fropart, ops, CHAIN_MAX_OPS);
-            }
-            if (nops > 0) {
-                CopySegs sg = first;
-                sg.add(pre_d, pre, (size_t)K * NS_NCOEF * sizeof(double));
-                sg.add(pre_d + NS_SLOT(K), pre + NS_SLOT(K), (size_t)K * NS_NCOEF * sizeof(double));
-                // validation flags of this step: slot 0 the bound check, slot 1 the chain's completion check, last slot the
-                // all-reduced flag of K-sharded runs
-                sg.add(c->spec_flag, nullptr, 2 * sizeof(int));
-                sg.add(c->spec_flag + ggl_ctx::MAX_PARTS - 1, nullptr, sizeof(int));
-                c->spec_flag_h[0] = c->spec_flag_h[1] = c->spec_flag_h[ggl_ctx::MAX_PARTS - 1] = 0;
-                const int nb_launch = pl.products - 2;
-                if (nb_launch > 0) sg.add(c->coef, c->coef_h, (size_t)nb_launch * NS_SLOT(K) * sizeof(double));
-                sg.add(c->cuse, c->cuse_h, (size_t)K * sizeof(double));
-                if (c->info_dirty) sg.add(c->info, nullptr, K * sizeof(int));
-                sg.add(c->chain_cnt, nullptr, (size_t)K * CHAIN_CNT_STRIDE * sizeof(unsigned));
-                launch_copy_small(c->stream, sg);
-                PB(c, GGL_PH_FORM_W);
-                launch_form_W_sym(c->stream, c->W, c->Theta, nullptr, c->X, c->S, beta, K, c->p);
-                PE(c, GGL_PH_FORM_W);
-                PB(c, GGL_PH_EIG_OMEGA);
-                ChainProg P;
-                P.nops = nops; P.K = K; P.p = c->p; P.ntiles = bT * (bT + 1) / 2;
-                P.begin[0] = 0;
-                for (int i = 0; i < nops; ++i) { P.op[i] = ops[i]; P.begin[i + 1] = P.begin[i] + P.ntiles * (ops[i].pair ? 2 : 1); }
-                if (launch_omega_chain(c->stream, P, c->chain_cnt, c->spec_flag + 1, c->spec_flag_h + 1) < 0)
-                    return fail(GGL_E_HIP, "k_omega_chain: launch failed (%s)", hipGetErrorString(hipGetLastError()));
-                // the bound of THIS iteration's A' (validation of the assumed one; next iteration's schedule): B' is intact
-                launch_bound_rows(c->stream, c->rowpart, bT, K, c->p, c->nbrow, c->infpart);
-                launch_cw_final(c->stream, c->nsYP[0] + c->n, c->nbrow, K, c->p, c->infpart, c->fropart, bT * (bT + 1) / 2,
-                                c->cwmax, c->cwcnt, c->bounds_h, c->cuse, c->spec_flag, c->spec_flag_h, 0,
-                                (c->cw_warm && c->cw_have) ? c->cwvec[c->cw_cur] : nullptr,
-                                c->cw_warm ? c->cwvec[c->cw_cur ^ 1] : nullptr);
-                PE(c, GGL_PH_EIG_OMEGA);
-                HIPCHK(hipGetLastError());
-                c->last_parts = 1;
-                c->last_variant = 40;
-                c->chain_calls += 1;
-                c->ns_launches_total += pl.products;
-                note_family(c, pl);
-                c->ns_units_frac += pl.units;
-                c->ns_steps_frac += pl.steps;
-                c->ns_units_total = (long long)(c->ns_units_frac + 0.5);
-                c->ns_steps_total = (long long)(c->ns_steps_frac + 0.5);
-                c->ns_calls += 1;
-                c->spec_calls += 1;
-                c->spec_pending = true;
-                c->cw_pending = c->cw_warm;
-                if (c->info_dirty) { memset(c->info_h, 0, K * sizeof(int)); c->info_dirty = false; }
-                c->dvo_valid = false;
-                c->cur = nxt;
-                return GGL_OK;
-            }
-        }
-#endif   // GGL_DEV (GGL_OPT_CHAIN)
-        if (resume) {
-            for (int h = 0; h < nh; ++h) { plans[h] = c->early.plans[h]; fused[h] = c->early.fused[h]; }
-            c->early_used += 1;
-        } else if (spec) {
-            for (int k = 0; k < K; ++k) c->cuse_h[k] = c->spec_c[k] * c->spec_factor;
-            sanitize_bounds(c, c->cuse_h, c->par_h, 4.0);
-            for (int h = 0; spec && h < nh; ++h) {
-                const int k0 = k0h[h];
-                const int prc = ns_plan(c->cuse_h + k0, c->par_h + k0, Kh[h], c->coef_h + h * region,
-                                        start_base_h + 5 * k0, &plans[h], c->ns_force, c->ns_degrees, c->ns_tol, c->omega_poly);
-                spec = (prc == 0) && !plans[h].stable;
-                for (int k = k0; spec && c->fused_start && k < k0 + Kh[h]; ++k) {
-                    // the bound is assumed known, so the start is a fixed combination of A' and B': {dI, dC, dE} of B' launch
-                    fused[h] = ns_fused_start(plans[h], start_base_h + 5 * (size_t)k, c->nsYP[1] + k0 * pp, c->nsT + k0 * pp,
-                                              nh > 1 ? c->n : (size_t)K * pp, pre + NS_SLOT(K) + (size_t)k * NS_NCOEF);
-                }
-            }
-        }
-        if (only_spec && !spec) return GGL_NOT_LAUNCHED;
-        if (nh > 1 && !c->parts_probed) {
-            rc = probe_part_streams(c);
-            if (rc) return rc;
-        }
-        if (nh > 1 && !resume) {
-            HIPCHK(hipEventRecord(c->ev_fork, c->stream));
-            for (int h = 1; h < nh; ++h) HIPCHK(hipStreamWaitEvent(c->streamx[h - 1], c->ev_fork, 0));
-        }
-        // (The parts' launches are issued part after part.  Issuing them round-robin, so that the parts start together
-        // instead of ~100 us apart, was measured 3 % SLOWER at (32,500): the stagger is what keeps the parts' prologues
-        // and epilogues from coinciding.)
-        for (int hh = 0; hh < nh; ++hh) {
-            // GGL_OPT_PARTS_ORDER: the part on the main stream is queued LAST, so that it is the one that ends last and the
-            // Theta kernel behind it finds the other part's flag set already
-            const int h = (c->parts_order && nh == 2 && c->prof_on == 0) ? nh - 1 - hh : hh;
-            hipStream_t sh = h == 0 ? c->stream : c->streamx[h - 1];
-            const int k0 = k0h[h];
-            // The host's mirrors of the validation flags are cleared when the REST of the chain is launched: the mirrors of an
-            // early part's iteration are still to be read when the part goes into the stream (the device words, cleared by
-            // the part's copy kernel, have been read by then -- the Theta-step that takes them is ahead in the stream).
-            if (!want_A) {
-                c->spec_flag_h[h] = 0;
-                if (h == 0 && nh < ggl_ctx::MAX_PARTS) c->spec_flag_h[ggl_ctx::MAX_PARTS - 1] = 0;
-            }
-            double* Ap = c->nsYP[0] + k0 * pp;
-            double* Bp = c->nsYP[0] + c->n + k0 * pp;
-            const int btile = c->fused_bounds ? symm_bounds_tile(Kh[h], c->p, var_parts) : 0;
-            const int bT = btile ? (c->p + btile - 1) / btile : 0;
-            double* rowp = btile ? c->rowpart + (size_t)k0 * bT * c->p : nullptr;
-            double* frop = btile ? c->fropart + (size_t)k0 * (bT * (bT + 1) / 2) : nullptr;
-            if (!resume) {
-            // ---- first part: parameter tables, W, A', B' (scratch only) ----
-            // the pending parameter transfers are repeated on every part's stream (identical values, a few KB)
-            // GGL_OPT_COPY_RIDER: nothing pending and the device's coefficient rows of A' = W^2 + 4 beta I already those of this
-            // beta (they only change with rho): no launch of its own reads the rest before B', so the tables ride in the A'
-            // launch (symm_set_copy_rider) -- one dependent launch less between the norm reduction and A'
-            // MEASURED (profiles/r5_copy_rider_ab.txt, three interleaved pairs per workload in one box): single launch sequences
-            // K = 4 slab +4 %, (20,200) +4 %, K = 16 +1.4 %, (64,100) +4 %, (32,128) +5 %; TWO concurrent parts lose -- headline
-            // -2.3 %, K = 8 slab -5 %, three of three pairs each (both A' launches end ~7 us earlier in the event timeline and
-            // the iteration is no shorter: the parts are bound by what they share, not by their first launch) -- so: 1 = only
-            // where the chain is one sequence.
-            bool ride_copy = (c->copy_rider == 2 || (c->copy_rider == 1 && nh == 1)) && first.n == 0 && !latent && btile != 0 &&
-                             !c->chain_mode && c->prof_on != 1;
-            for (int k = k0; ride_copy && k < k0 + Kh[h]; ++k) ride_copy = (c->pre0_beta[k] == c->par_h[k]);
-            CopySegs sg = first;
-            if (!ride_copy) {
-                sg.add(pre_d + NS_NCOEF * (size_t)k0, pre + NS_NCOEF * (size_t)k0, (size_t)Kh[h] * NS_NCOEF * sizeof(double));
-                for (int k = k0; k < k0 + Kh[h]; ++k) c->pre0_beta[k] = c->par_h[k];
-            }
-            sg.add(pre_d + NS_SLOT(K) + NS_NCOEF * (size_t)k0, pre + NS_SLOT(K) + NS_NCOEF * (size_t)k0,
-                   (size_t)Kh[h] * NS_NCOEF * sizeof(double));
-            // validation flags of this step: this part's slot, and (part 0) the slot of the all-reduced flag of K-sharded
-            // runs, where a rank must skip and repeat the step when ANY rank's speculation failed -- also a rank that
-            // did not speculate itself
-            sg.add(c->spec_flag + h, nullptr, sizeof(int));
-            if (h == 0 && nh < ggl_ctx::MAX_PARTS) sg.add(c->spec_flag + ggl_ctx::MAX_PARTS - 1, nullptr, sizeof(int));
-            if (spec) {
-                sg.add(start_base_d + 5 * (size_t)k0, start_base_h + 5 * (size_t)k0, (size_t)Kh[h] * 5 * sizeof(double));
-                const int nb_launch = plans[h].products - 2;
-                if (nb_launch > 0)
-                    sg.add(c->coef + h * region, c->coef_h + h * region, (size_t)nb_launch * NS_SLOT(Kh[h]) * sizeof(double));
-                sg.add(c->cuse + k0, c->cuse_h + k0, (size_t)Kh[h] * sizeof(double));
-                if (h == 0 && c->info_dirty) sg.add(c->info, nullptr, K * sizeof(int));
-            }
-            if (h == 0 && c->red_pending.nblk > 0) {
-                // (with anything else in front of A' the reduction goes first, as its own launch)
-                if (w_ready && (c->red_rider == 2 || nh == 1)) {
-                    symm_set_reduce_rider(c->red_pending);
-                    c->red_rides += 1;
-                } else {
-                    launch_reduce_partials(sh, c->red_pending.partials, 1, c->red_pending.nblk, c->red_pending.nv, c->red_pending.out,
-                                           c->red_pending.seq, c->red_pending.seq_val);
-                    trace_mark(c, sh, 21);
-                }
-                c->red_pending = RedRider{};
-            }
-            if (ride_copy) {
-                symm_set_copy_rider(sg);
-                c->copy_rides += 1;
-            } else {
-                launch_copy_small(sh, sg);
-                trace_mark(c, sh, 1);
-            }
-            if (h == 0) PB(c, GGL_PH_FORM_W);
-            if (!w_ready) {
-                launch_form_W_sym(sh, c->W + k0 * pp, c->Theta + k0 * pp, latent ? c->L + k0 * pp : nullptr, c->X + k0 * pp,
-                                  c->S + k0 * pp, beta + k0, Kh[h], c->p);
-                trace_mark(c, sh, 2);
-            } else if (h == 0) c->wf_used += 1;
-            const bool early_ev = want_A && h == 0 && c->prof_on == 2;
-            if (early_ev) {
-                c->ev_early_par ^= 1;
-                (void)hipEventRecord(c->ev_early[c->ev_early_par][0], c->stream);
-            } else if (h == 0 && !want_A) { PE(c, GGL_PH_FORM_W); PB(c, GGL_PH_EIG_OMEGA); }
-            // lambda_max(A')^2 = lambda_max(B') <= min(|B'|_inf, |B'|_F, Collatz-Wielandt ratio), reduced on the
-            // device; only the K_part bounds travel to the (pinned, device-visible) host array.  Where the B' launch is
-            // the direct-to-LDS kernel, its epilogue leaves the row sums and Frobenius shares of B' behind (no norm pass
-            // over B'), and the Collatz-Wielandt pass finishes the bound itself.
-            ns_prepare(sh, pre_d + NS_NCOEF * (size_t)k0, pre_d + NS_SLOT(K) + NS_NCOEF * (size_t)k0, c->W + k0 * pp, Ap, Bp, Kh[h], c->p,
-                       var_parts, spec ? fused[h] : nullptr, rowp, frop, plans[h].direct != 0);
-            symm_flush_rider(sh);
-            if (early_ev) {
-                (void)hipEventRecord(c->ev_early[c->ev_early_par][1], c->stream);
-                c->ev_early_used[c->ev_early_par] = true;
-            }
-            }
-            if (want_A) continue;
-            if (resume && h == 0) PB(c, GGL_PH_EIG_OMEGA);
-            // ---- the rest: bound of this iteration's A' (validation of the assumed one), products, Omega ----
-            // speculative chain of a small launch sequence: the two bound kernels only VALIDATE (the schedule was built from
-            // the previous iteration's bound), so they need not sit in the chain's dependent sequence -- side stream, beside
-            // the first products, joined before B' is overwritten (ns_run) -- where the chip has room (one or two parts of few
-            // tiles; at the headline both parts are bound by throughput and round 3 measured this slower)
-            hipStream_t sb = sh;
-            hipEvent_t bfree = nullptr;
-            const int side_slot = nh + h - 1;                      // part streams 0 .. nh-2 are taken by the parts
-            // measured (profiles/r5_bound_side.txt): three interleaved pairs per workload in one box -- headline (two parts of
-            // 16) +3.0 / +1.5 / +2.2 %; K = 16 and K = 4 within noise; K = 8 (two parts of 4) -1.5 %, C3 -5.5 %, (64,100) -5 %,
-            // (32,128) -4.6 %: a cross-stream wait costs more than the small launches hide -- and six more headline pairs in a
-            // second box: -2.4 / +0.8 / -1.6 % with 50-step regions, -0.1 / +0.8 / +3.1 % with the driver's 20-step regions.
-            // Nine pairs, +0.8 % on average with a run-to-run scatter of +-2 %: not a result.  Off by default.
-            const bool side_on = c->bound_side == 1 || (c->bound_side == 2 && nh > 1 && K >= 16);
-            if (side_on && spec && btile && !c->fused_cw && side_slot < ggl_ctx::MAX_PARTS - 1 && c->streamx[side_slot]) {
-                if (!c->ev_bfork[h]) {
-                    HIPCHK(hipEventCreateWithFlags(&c->ev_bfork[h], hipEventDisableTiming));
-                    HIPCHK(hipEventCreateWithFlags(&c->ev_bjoin[h], hipEventDisableTiming));
-                }
-                sb = c->streamx[side_slot];
-                HIPCHK(hipEventRecord(c->ev_bfork[h], sh));
-                HIPCHK(hipStreamWaitEvent(sb, c->ev_bfork[h], 0));
-                bfree = c->ev_bjoin[h];
-            }
-            // GGL_OPT_CW_RIDER: the validation rides in the first product launch of ns_run (CwRider, kernels.hpp) -- needs the
-            // Collatz-Wielandt vector of the previous iteration
-            const bool ride = c->cw_rider && spec && btile && !c->fused_cw && sb == sh && c->cw_warm && c->cw_have;
-            if (ride) {
-                CwRider r;
-                r.B = Bp; r.rowpart = rowp; r.fropart = frop;
-                r.dprev = c->cwvec[c->cw_cur] + (size_t)k0 * c->p;
-                r.dnext = c->cwvec[c->cw_cur ^ 1] + (size_t)k0 * c->p;
-                r.d_out = c->nbrow + (size_t)k0 * c->p;
-                r.cwmax = c->cwmax + k0; r.cnt = c->cwcnt + k0; r.out = c->bounds_h + k0; r.cuse = c->cuse + k0;
-                r.flag = c->spec_flag; r.flag_host = c->spec_flag_h; r.flag_slot = h;
-                r.T = bT; r.ntile = bT * (bT + 1) / 2; r.p = c->p; r.K = Kh[h]; r.nbx = (c->p + 15) / 16;
-                symm_set_rider(r);
-                if (c->cw_rider == 2) symm_flush_rider(sh);
-                c->cw_rides += 1;
-                cw_written = true;
-            } else if (btile) {
-                if (c->fused_cw) {
-                    launch_bound_cw(sh, Bp, rowp, bT, Kh[h], c->p, c->nbrow + (size_t)k0 * c->p, frop, bT * (bT + 1) / 2,
-                                    c->cwmax + k0, c->cwcnt + k0, c->bounds_h + k0, spec ? c->cuse + k0 : nullptr,
-                                    spec ? c->spec_flag : nullptr, spec ? c->spec_flag_h : nullptr, h,
-                                    (c->cw_warm && c->cw_have) ? c->cwvec[c->cw_cur] + (size_t)k0 * c->p : nullptr,
-                                    c->cw_warm ? c->cwvec[c->cw_cur ^ 1] + (size_t)k0 * c->p : nullptr);
-                } else {
-                const int nib = bound_rows_blocks(c->p);
-                launch_bound_rows(sb, rowp, bT, Kh[h], c->p, c->nbrow + (size_t)k0 * c->p, c->infpart + (size_t)k0 * nib);
-                trace_mark(c, sb, 3);
-                launch_cw_final(sb, Bp, c->nbrow + (size_t)k0 * c->p, Kh[h], c->p, c->infpart + (size_t)k0 * nib, frop,
-                                bT * (bT + 1) / 2, c->cwmax + k0, c->cwcnt + k0, c->bounds_h + k0, spec ? c->cuse + k0 : nullptr,
-                                spec ? c->spec_flag : nullptr, spec ? c->spec_flag_h : nullptr, h,
-                                (c->cw_warm && c->cw_have) ? c->cwvec[c->cw_cur] + (size_t)k0 * c->p : nullptr,
-                                c->cw_warm ? c->cwvec[c->cw_cur ^ 1] + (size_t)k0 * c->p : nullptr);
-                trace_mark(c, sb, 4);
-                }
-                cw_written = c->cw_warm;
-            } else {
-                double* nb2 = c->nbpart + 2 * (size_t)k0 * nbb;
-                double* nbc = c->nbpart + 2 * (size_t)K * nbb + (size_t)k0 * nbb;
-                launch_norm_bounds(sh, Bp, Kh[h], c->p, nb2, c->nbrow + (size_t)k0 * c->p);
-                launch_cw_bounds(sh, Bp, c->nbrow + (size_t)k0 * c->p, Kh[h], c->p, nbc);
-                launch_bound_final(sh, nb2, nbc, nbb, Kh[h], c->bounds_h + k0, 0, spec ? c->cuse + k0 : nullptr,
-                                   spec ? c->spec_flag + h : nullptr, spec ? c->spec_flag_h + h : nullptr);
-            }
-            if (bfree) HIPCHK(hipEventRecord(bfree, sb));
-            if (spec) {
-                ns_run(sh, plans[h], c->coef + h * region, start_base_d + 5 * k0, c->W + k0 * pp, c->nsYP[0] + k0 * pp,
-                       c->nsYP[1] + k0 * pp, c->nsT + k0 * pp, c->Om[nxt] + k0 * pp, Kh[h], c->p,
-                       var_parts, nh > 1 ? c->n : 0, fused[h] != nullptr, bfree);
-                symm_flush_rider(sh);                     // (a chain without a direct-to-LDS product launch: its own launch)
-                c->ns_launches_total += plans[h].products;
-                note_family(c, plans[h]);
-                const double frac = (double)Kh[h] / K;
-                c->ns_units_frac += frac * plans[h].units;
-                c->ns_steps_frac += frac * plans[h].steps;
-            }
-            if (h == 0 && !spec) PE(c, GGL_PH_EIG_OMEGA);
-        }
-        HIPCHK(hipGetLastError());
-        if (want_A) {
-            for (int h = 0; h < nh; ++h) { c->early.plans[h] = plans[h]; c->early.fused[h] = fused[h]; c->early.Kh[h] = Kh[h]; c->early.k0h[h] = k0h[h]; }
-            c->early.nh = nh;
-            c->early.grouped = grouped;
-            c->early.var_parts = var_parts;
-            memcpy(c->early.beta, c->par_h, K * sizeof(double));
-            c->early.valid = true;
-            c->early_launched += 1;
-            return GGL_OK;
-        }
-        if (spec) {
-            // (parts that share a hardware queue keep the event join: a polling wave in front of the kernel it waits for would
-            // sit out its time limit -- the host queues the set before the wait, so this is belt and braces)
-            if (nh > 1 && c->join_flag && !c->parts_serial) {
-                // (see k_wait_flags: the waiting queue idles ~25 us behind a cross-queue event that has fired)
-                c->join_seq += 1;
-                for (int h = 1; h < nh; ++h) launch_set_flag(c->streamx[h - 1], c->join_words + h, c->join_seq);
-                launch_wait_flags(c->stream, c->join_words + 1, nh - 1, c->join_seq, c->spec_flag, c->spec_flag_h, 0, 200.0);
-                HIPCHK(hipGetLastError());
-            } else {
-                for (int h = 1; h < nh; ++h) {
-                    HIPCHK(hipEventRecord(c->ev_join[h - 1], c->streamx[h - 1]));
-                    HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join[h - 1], 0));
-                }
-            }
-            PE(c, GGL_PH_EIG_OMEGA);
-            c->ns_units_total = (long long)(c->ns_units_frac + 0.5);
-            c->ns_steps_total = (long long)(c->ns_steps_frac + 0.5);
-            c->ns_calls += 1;
-            c->spec_calls += 1;
-            note_groups(c, grouped ? nh : 1, Kh, plans);
-            c->spec_pending = true;        // validated by the caller after its stream sync (finish_norms)
-            c->cw_pending = cw_written;
-            if (c->info_dirty) { memset(c->info_h, 0, K * sizeof(int)); c->info_dirty = false; }
-            c->dvo_valid = false;
-            c->cur = nxt;
-            return GGL_OK;
-        }
-        for (int h = 0; h < nh; ++h) HIPCHK(hipStreamSynchronize(h == 0 ? c->stream : c->streamx[h - 1]));
-        sanitize_bounds(c, c->bounds_h, c->par_h, 4.0);          // (GGL_OPT_ISOLATE: lambda_min(A') = 4 beta stands in)
-        // validated bounds: the next step may speculate on them
+    }
+    if (no_copy && S.first.n > 0) { S.beta = c->par_h; c->par0_stale = true; }
+    if (!launch_omega_lds(c->stream, c->Theta, S.latent ? c->L : nullptr, c->X, c->S, S.beta, c->Om[nxt], c->lds_tab,
+                          c->lds_ntab, c->lds_lnq, K, c->p, c->spec_flag, c->spec_flag_h, 0, cnt, c->bounds_h, nullptr,
+                          c->lds_waves, sgl_fused ? &sgl : nullptr))
+        return fail(GGL_E_HIP, "k_omega_lds: p = %d outside the kernel's range, or the LDS attribute was refused", c->p);
+    PE(c, GGL_PH_EIG_OMEGA);
+    c->sgl_done = sgl_fused;
+    HIPCHK(hipGetLastError());
+    c->last_parts = 1;
+    c->last_variant = 41;
+    c->lds_calls += 1;
+    c->ns_calls += 1;
+    c->ns_launches_total += 1;
+    c->lds_last = true;
+    if (c->info_dirty) { memset(c->info_h, 0, K * sizeof(int)); c->info_dirty = false; }
+    if (as_spec) {
+        // validated by the caller after its stream sync (validate_spec) -- the fused SGL form is not speculative in
+        // that sense: an instance outside the range is redone ALONE by the caller (sgl_fused_finish)
+        c->spec_pending = !sgl_fused;
+        c->cw_pending = false;
+        step_advance(c, nxt);
+        return GGL_OK;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->spec_flag_h[0] == 0) {
+        sanitize_bounds(c, c->bounds_h, c->par_h, 4.0);
         for (int k = 0; k < K; ++k) { c->spec_c[k] = c->bounds_h[k]; c->spec_beta[k] = c->par_h[k]; }
         c->spec_have = true;
-        if (cw_written) { c->cw_cur ^= 1; c->cw_have = true; }
-        bool any_stable = false;
-        size_t region_b = region;
-        int var_b = var_parts;
-        if (nh == 1) {
-            // phase A ran as one launch sequence; the products may still run as groups with their own schedules
-            const int G = omega_groups(c, c->bounds_h, c->par_h, K, Kh, k0h, gunits);
-            if (G > 1) {
-                nh = G;
-                grouped = true;
-                region_b = (size_t)(NS_MAX_LAUNCHES - 4) / nh * NS_SLOT(K);
-                var_b = var_grouped;
-                if (!c->parts_probed) {
-                    rc = probe_part_streams(c);
-                    if (rc) return rc;
-                }
-            }
+        c->lds_cool_next = 4;
+        step_advance(c, nxt);
+        return GGL_OK;
+    }
+    // outside the kernel's range: this step (and the next few) on the launch chain
+    c->par0_stale = false;                 // (whose parameter copy carries `first`)
+    lds_missed(c);
+    *done = false;
+    return clear_spec_flags(c);
+}
+
+#ifdef GGL_DEV
+// ---- the whole product chain as ONE persistent launch with per-instance dependencies (k_omega_chain) ----------
+// *done: the step is complete (or failed); otherwise it goes on to the launch chain.
+static int omega_dev_chain(ggl_ctx* c, OmegaStep& S, OmegaChainPlan& plan, bool* done)
+{
+    const int K = c->K, nxt = S.nxt;
+    const size_t pp = S.pp;
+    double *pre = S.pre, *pre_d = S.pre_d;
+    *done = false;
+    if (!(S.spec && !S.want_A && !S.resume && c->chain_mode && c->fused_start && c->fused_bounds && (c->symm_variant < 0 || c->symm_variant == 17) &&
+          chain_tile(K, c->p, c->chain_mode == 2) == 64))
+        return GGL_OK;
+    *done = true;
+    if (!c->nsNX) HIPCHK(malloc_filled(&c->nsNX, 2 * c->n * sizeof(double) + STACK_SLACK, c->stream));
+    if (!c->chain_cnt) HIPCHK(hipMalloc(&c->chain_cnt, (size_t)K * CHAIN_CNT_STRIDE * sizeof(unsigned)));
+    for (int k = 0; k < K; ++k) c->cuse_h[k] = c->spec_c[k] * c->spec_factor;
+    NsPlan& pl = plan.plans[0];
+    SymmOp ops[CHAIN_MAX_OPS];
+    int nops = 0;
+    const int bT = (c->p + 63) / 64;
+    if (ns_plan(c->cuse_h, c->par_h, K, c->coef_h, S.start_base_h, &pl, c->ns_force, c->ns_degrees, c->ns_tol, c->omega_poly) == 0 &&
+        !pl.stable) {
+        double* f0 = nullptr;
+        for (int k = 0; k < K; ++k)
+            f0 = ns_fused_start(pl, S.start_base_h + 5 * (size_t)k, c->nsYP[1], c->nsT, (size_t)K * pp,
+                                pre + NS_SLOT(K) + (size_t)k * NS_NCOEF);
+        if (f0)
+            nops = ns_chain_ops(pl, pre_d, pre_d + NS_SLOT(K), c->coef, c->W, c->nsYP[0], c->nsYP[1], c->nsNX, c->nsT,
+                                c->Om[nxt], K, c->p, 0, f0, c->rowpart, c->fropart, ops, CHAIN_MAX_OPS);
+    }
+    if (nops <= 0) { *done = false; return GGL_OK; }
+    CopySegs sg = S.first;
+    sg.add(pre_d, pre, (size_t)K * NS_NCOEF * sizeof(double));
+    sg.add(pre_d + NS_SLOT(K), pre + NS_SLOT(K), (size_t)K * NS_NCOEF * sizeof(double));
+    // validation flags of this step: slot 0 the bound check, slot 1 the chain's completion check, last slot the
+    // all-reduced flag of K-sharded runs
+    sg.add(c->spec_flag, nullptr, 2 * sizeof(int));
+    sg.add(c->spec_flag + ggl_ctx::MAX_PARTS - 1, nullptr, sizeof(int));
+    c->spec_flag_h[0] = c->spec_flag_h[1] = c->spec_flag_h[ggl_ctx::MAX_PARTS - 1] = 0;
+    const int nb_launch = pl.products - 2;
+    if (nb_launch > 0) sg.add(c->coef, c->coef_h, (size_t)nb_launch * NS_SLOT(K) * sizeof(double));
+    sg.add(c->cuse, c->cuse_h, (size_t)K * sizeof(double));
+    if (c->info_dirty) sg.add(c->info, nullptr, K * sizeof(int));
+    sg.add(c->chain_cnt, nullptr, (size_t)K * CHAIN_CNT_STRIDE * sizeof(unsigned));
+    launch_copy_small(c->stream, sg);
+    PB(c, GGL_PH_FORM_W);
+    launch_form_W_sym(c->stream, c->W, c->Theta, nullptr, c->X, c->S, S.beta, K, c->p);
+    PE(c, GGL_PH_FORM_W);
+    PB(c, GGL_PH_EIG_OMEGA);
+    ChainProg P;
+    P.nops = nops; P.K = K; P.p = c->p; P.ntiles = bT * (bT + 1) / 2;
+    P.begin[0] = 0;
+    for (int i = 0; i < nops; ++i) { P.op[i] = ops[i]; P.begin[i + 1] = P.begin[i] + P.ntiles * (ops[i].pair ? 2 : 1); }
+    if (launch_omega_chain(c->stream, P, c->chain_cnt, c->spec_flag + 1, c->spec_flag_h + 1) < 0)
+        return fail(GGL_E_HIP, "k_omega_chain: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+    // the bound of THIS iteration's A' (validation of the assumed one; next iteration's schedule): B' is intact
+    launch_bound_rows(c->stream, c->rowpart, bT, K, c->p, c->nbrow, c->infpart);
+    launch_cw_final(c->stream, c->nsYP[0] + c->n, c->nbrow, K, c->p, c->infpart, c->fropart, bT * (bT + 1) / 2,
+                    c->cwmax, c->cwcnt, c->bounds_h, c->cuse, c->spec_flag, c->spec_flag_h, 0, cw_prev(c, 0), cw_next(c, 0));
+    PE(c, GGL_PH_EIG_OMEGA);
+    HIPCHK(hipGetLastError());
+    c->last_parts = 1;
+    c->last_variant = 40;
+    c->chain_calls += 1;
+    note_sequence(c, pl, K);
+    c->spec_calls += 1;
+    c->spec_pending = true;
+    c->cw_pending = c->cw_warm;
+    step_epilogue(c, nxt);
+    return GGL_OK;
+}
+#endif   // GGL_DEV (GGL_OPT_CHAIN)
+
+// Speculation: the schedules of the parts from the last validated step's bounds, inflated (cuse_h), and the first step's
+// start as 2nd output of the B' launch.  Clears S.spec where a part has no such schedule.
+static void omega_plan_spec(ggl_ctx* c, OmegaStep& S, OmegaChainPlan& pl)
+{
+    const int K = c->K;
+    const size_t pp = S.pp, region = plan_region(pl, K);
+    for (int k = 0; k < K; ++k) c->cuse_h[k] = c->spec_c[k] * c->spec_factor;
+    sanitize_bounds(c, c->cuse_h, c->par_h, 4.0);
+    for (int h = 0; S.spec && h < pl.nh; ++h) {
+        const int k0 = pl.k0h[h];
+        const int prc = ns_plan(c->cuse_h + k0, c->par_h + k0, pl.Kh[h], c->coef_h + h * region,
+                                S.start_base_h + 5 * k0, &pl.plans[h], c->ns_force, c->ns_degrees, c->ns_tol, c->omega_poly);
+        S.spec = (prc == 0) && !pl.plans[h].stable;
+        for (int k = k0; S.spec && c->fused_start && k < k0 + pl.Kh[h]; ++k) {
+            // the bound is assumed known, so the start is a fixed combination of A' and B': {dI, dC, dE} of B' launch
+            pl.fused[h] = ns_fused_start(pl.plans[h], S.start_base_h + 5 * (size_t)k, c->nsYP[1] + k0 * pp, c->nsT + k0 * pp,
+                                         pl.nh > 1 ? c->n : (size_t)K * pp, S.pre + NS_SLOT(K) + (size_t)k * NS_NCOEF);
         }
-        for (int h = 0; h < nh; ++h) {
-            const int k0 = k0h[h];
-            const int prc = ns_plan(c->bounds_h + k0, c->par_h + k0, Kh[h], c->coef_h + h * region_b, start_base_h + 5 * k0,
-                                    &plans[h], c->ns_force, c->ns_degrees, c->ns_tol, c->omega_poly);
-            if (prc == -1) return fail(GGL_E_SOLVER, "Newton-Schulz Omega-step: non-finite W (diverged iterate?)");
-            if (prc == -2) {
-                // pathological scaling (|W|^2 rho / nk > 1e12): eigendecomposition of the (still intact) W
-                c->ns_eigh_fallbacks += 1;
-                rc = eig_recon(c, c->W, c->Om[nxt], c->DvO, MAP_PHIPLUS, beta, -1, GGL_PH_RECON_OMEGA);
-                if (rc) return rc;
-                c->dvo_valid = true;
-                c->cur = nxt;
-                return GGL_OK;
-            }
-            any_stable = any_stable || plans[h].stable;
+    }
+}
+
+// ---- first part of part h's chain: parameter tables, W, A', B' (scratch only) ----
+static void omega_phase_a(ggl_ctx* c, OmegaStep& S, const OmegaChainPlan& pl, int h, hipStream_t sh)
+{
+    const int K = c->K, nh = pl.nh, k0 = pl.k0h[h], Kp = pl.Kh[h], latent = S.latent;
+    const size_t pp = S.pp, region = plan_region(pl, K);
+    double *pre = S.pre, *pre_d = S.pre_d;
+    const BoundTile bt = plan_bound_tile(c, pl, h);
+    // the pending parameter transfers are repeated on every part's stream (identical values, a few KB)
+    // GGL_OPT_COPY_RIDER: nothing pending and the device's coefficient rows of A' = W^2 + 4 beta I already those of this
+    // beta (they only change with rho): no launch of its own reads the rest before B', so the tables ride in the A'
+    // launch (symm_set_copy_rider) -- one dependent launch less between the norm reduction and A'
+    // MEASURED (profiles/r5_copy_rider_ab.txt, three interleaved pairs per workload in one box): single launch sequences
+    // K = 4 slab +4 %, (20,200) +4 %, K = 16 +1.4 %, (64,100) +4 %, (32,128) +5 %; TWO concurrent parts lose -- headline
+    // -2.3 %, K = 8 slab -5 %, three of three pairs each (both A' launches end ~7 us earlier in the event timeline and
+    // the iteration is no shorter: the parts are bound by what they share, not by their first launch) -- so: 1 = only
+    // where the chain is one sequence.
+    bool ride_copy = (c->copy_rider == 2 || (c->copy_rider == 1 && nh == 1)) && S.first.n == 0 && !latent && bt.bT != 0 &&
+                     !c->chain_mode && c->prof_on != 1;
+    for (int k = k0; ride_copy && k < k0 + Kp; ++k) ride_copy = (c->pre0_beta[k] == c->par_h[k]);
+    CopySegs sg = S.first;
+    if (!ride_copy) {
+        sg.add(pre_d + NS_NCOEF * (size_t)k0, pre + NS_NCOEF * (size_t)k0, (size_t)Kp * NS_NCOEF * sizeof(double));
+        for (int k = k0; k < k0 + Kp; ++k) c->pre0_beta[k] = c->par_h[k];
+    }
+    sg.add(pre_d + NS_SLOT(K) + NS_NCOEF * (size_t)k0, pre + NS_SLOT(K) + NS_NCOEF * (size_t)k0,
+           (size_t)Kp * NS_NCOEF * sizeof(double));
+    // validation flags of this step: this part's slot, and (part 0) the slot of the all-reduced flag of K-sharded
+    // runs, where a rank must skip and repeat the step when ANY rank's speculation failed -- also a rank that
+    // did not speculate itself
+    sg.add(c->spec_flag + h, nullptr, sizeof(int));
+    if (h == 0 && nh < ggl_ctx::MAX_PARTS) sg.add(c->spec_flag + ggl_ctx::MAX_PARTS - 1, nullptr, sizeof(int));
+    if (S.spec) {
+        sg.add(S.start_base_d + 5 * (size_t)k0, S.start_base_h + 5 * (size_t)k0, (size_t)Kp * 5 * sizeof(double));
+        const int nb_launch = pl.plans[h].products - 2;
+        if (nb_launch > 0)
+            sg.add(c->coef + h * region, c->coef_h + h * region, (size_t)nb_launch * NS_SLOT(Kp) * sizeof(double));
+        sg.add(c->cuse + k0, c->cuse_h + k0, (size_t)Kp * sizeof(double));
+        if (h == 0 && c->info_dirty) sg.add(c->info, nullptr, K * sizeof(int));
+    }
+    if (h == 0 && c->red_pending.nblk > 0) {
+        // (with anything else in front of A' the reduction goes first, as its own launch)
+        if (S.w_ready && (c->red_rider == 2 || nh == 1)) {
+            symm_set_reduce_rider(c->red_pending);
+            c->red_rides += 1;
+        } else {
+            launch_reduce_partials(sh, c->red_pending.partials, 1, c->red_pending.nblk, c->red_pending.nv, c->red_pending.out,
+                                   c->red_pending.seq, c->red_pending.seq_val);
+            trace_mark(c, sh, 21);
         }
-        if (nh > 1 && any_stable) {
-            // the stable schedule multiplies a contiguous [Y|P] pair: run the whole batch as one sequence
-            const int prc = ns_plan(c->bounds_h, c->par_h, K, c->coef_h, start_base_h, &plans[0], c->ns_force, c->ns_degrees, c->ns_tol,
-                                    c->omega_poly);
-            if (prc != 0) return fail(GGL_E_SOLVER, "Newton-Schulz Omega-step: plan failed (%d)", prc);
+        c->red_pending = RedRider{};
+    }
+    if (ride_copy) {
+        symm_set_copy_rider(sg);
+        c->copy_rides += 1;
+    } else {
+        launch_copy_small(sh, sg);
+        trace_mark(c, sh, 1);
+    }
+    if (h == 0) PB(c, GGL_PH_FORM_W);
+    if (!S.w_ready) {
+        launch_form_W_sym(sh, c->W + k0 * pp, c->Theta + k0 * pp, latent ? c->L + k0 * pp : nullptr, c->X + k0 * pp,
+                          c->S + k0 * pp, S.beta + k0, Kp, c->p);
+        trace_mark(c, sh, 2);
+    } else if (h == 0) c->wf_used += 1;
+    const bool early_ev = S.want_A && h == 0 && c->prof_on == 2;
+    if (early_ev) {
+        c->ev_early_par ^= 1;
+        (void)hipEventRecord(c->ev_early[c->ev_early_par][0], c->stream);
+    } else if (h == 0 && !S.want_A) { PE(c, GGL_PH_FORM_W); PB(c, GGL_PH_EIG_OMEGA); }
+    // lambda_max(A')^2 = lambda_max(B') <= min(|B'|_inf, |B'|_F, Collatz-Wielandt ratio), reduced on the
+    // device; only the K_part bounds travel to the (pinned, device-visible) host array.  Where the B' launch is
+    // the direct-to-LDS kernel, its epilogue leaves the row sums and Frobenius shares of B' behind (no norm pass
+    // over B'), and the Collatz-Wielandt pass finishes the bound itself.
+    ns_prepare(sh, pre_d + NS_NCOEF * (size_t)k0, pre_d + NS_SLOT(K) + NS_NCOEF * (size_t)k0, c->W + k0 * pp, c->nsYP[0] + k0 * pp,
+               c->nsYP[0] + c->n + k0 * pp, Kp, c->p, pl.var_parts, S.spec ? pl.fused[h] : nullptr, bt.rowp, bt.frop,
+               pl.plans[h].direct != 0);
+    symm_flush_rider(sh);
+    if (early_ev) {
+        (void)hipEventRecord(c->ev_early[c->ev_early_par][1], c->stream);
+        c->ev_early_used[c->ev_early_par] = true;
+    }
+}
+
+// ---- bound of this iteration's A' for part h (a speculative chain: validation of the assumed one) ----
+// *bfree: the event ns_run must wait for before it overwrites B' (null: the bound pass is ahead of it in its own stream)
+static int omega_bound_pass(ggl_ctx* c, OmegaStep& S, const OmegaChainPlan& pl, int h, hipStream_t sh, hipEvent_t* bfree)
+{
+    const int K = c->K, nh = pl.nh, k0 = pl.k0h[h], Kp = pl.Kh[h];
+    const bool spec = S.spec;
+    const BoundTile bt = plan_bound_tile(c, pl, h);
+    const int bT = bt.bT;
+    double* Bp = c->nsYP[0] + c->n + k0 * S.pp;
+    // speculative chain of a small launch sequence: the two bound kernels only VALIDATE (the schedule was built from
+    // the previous iteration's bound), so they need not sit in the chain's dependent sequence -- side stream, beside
+    // the first products, joined before B' is overwritten (ns_run) -- where the chip has room (one or two parts of few
+    // tiles; at the headline both parts are bound by throughput and round 3 measured this slower)
+    hipStream_t sb = sh;
+    *bfree = nullptr;
+    const int side_slot = nh + h - 1;                      // part streams 0 .. nh-2 are taken by the parts
+    // measured (profiles/r5_bound_side.txt): three interleaved pairs per workload in one box -- headline (two parts of
+    // 16) +3.0 / +1.5 / +2.2 %; K = 16 and K = 4 within noise; K = 8 (two parts of 4) -1.5 %, C3 -5.5 %, (64,100) -5 %,
+    // (32,128) -4.6 %: a cross-stream wait costs more than the small launches hide -- and six more headline pairs in a
+    // second box: -2.4 / +0.8 / -1.6 % with 50-step regions, -0.1 / +0.8 / +3.1 % with the driver's 20-step regions.
+    // Nine pairs, +0.8 % on average with a run-to-run scatter of +-2 %: not a result.  Off by default.
+    const bool side_on = c->bound_side == 1 || (c->bound_side == 2 && nh > 1 && K >= 16);
+    if (side_on && spec && bT && !c->fused_cw && side_slot < ggl_ctx::MAX_PARTS - 1 && c->streamx[side_slot]) {
+        if (!c->ev_bfork[h]) {
+            HIPCHK(hipEventCreateWithFlags(&c->ev_bfork[h], hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&c->ev_bjoin[h], hipEventDisableTiming));
         }
-        const int nrun = (nh > 1 && !any_stable) ? nh : 1;
-        if (nrun == 1) { Kh[0] = K; k0h[0] = 0; }
-        c->last_parts = nrun;
-        c->last_variant = symm_effective_variant((nrun > 1 && var_b >= 0) ? var_b
-                          : (c->symm_variant >= 0 ? c->symm_variant : symm_auto_variant(Kh[0], c->p)), c->p);
-        note_groups(c, (grouped && nrun > 1) ? nrun : 1, Kh, plans);
-        PB(c, GGL_PH_EIG_OMEGA2);
-        for (int h = 0; h < nrun; ++h) {
-            const int Kr = Kh[h], k0 = k0h[h];
-            hipStream_t sh = h == 0 ? c->stream : c->streamx[h - 1];
-            CopySegs up;
-            up.add(start_base_d + 5 * (size_t)k0, start_base_h + 5 * (size_t)k0, (size_t)Kr * 5 * sizeof(double));
-            const int nb_launch = plans[h].products - 2;     // launches of phase B
-            if (nb_launch > 0)
-                up.add(c->coef + h * region_b, c->coef_h + h * region_b, (size_t)nb_launch * NS_SLOT(Kr) * sizeof(double));
-            if (h == 0 && c->info_dirty) up.add(c->info, nullptr, K * sizeof(int));   // no eigensolver ran: info = 0
-            launch_copy_small(sh, up);
-            ns_run(sh, plans[h], c->coef + h * region_b, start_base_d + 5 * k0,
-                   c->W + k0 * pp, c->nsYP[0] + k0 * pp, c->nsYP[1] + k0 * pp, c->nsT + k0 * pp, c->Om[nxt] + k0 * pp, Kr,
-                   c->p,
-                   // tile choice by the work of the WHOLE batch: the other parts share the chip (measured +6.7 %);
-                   // with parts, the 3-stage DMA pipeline is 2.8 % ahead of the double buffer (4 % behind without)
-                   nrun > 1 ? var_b : c->symm_variant, nrun > 1 ? c->n : 0);
-            c->ns_stable_calls += plans[h].stable ? 1 : 0;
-            c->ns_launches_total += plans[h].products;
-            note_family(c, plans[h]);
-            // algorithmic work in units of (whole-stack) K p^3 flop
-            const double frac = (double)Kr / K;
-            c->ns_units_frac += frac * plans[h].units;
-            c->ns_steps_frac += frac * plans[h].steps;
+        sb = c->streamx[side_slot];
+        HIPCHK(hipEventRecord(c->ev_bfork[h], sh));
+        HIPCHK(hipStreamWaitEvent(sb, c->ev_bfork[h], 0));
+        *bfree = c->ev_bjoin[h];
+    }
+    // GGL_OPT_CW_RIDER: the validation rides in the first product launch of ns_run (CwRider, kernels.hpp) -- needs the
+    // Collatz-Wielandt vector of the previous iteration
+    const bool ride = c->cw_rider && spec && bT && !c->fused_cw && sb == sh && c->cw_warm && c->cw_have;
+    if (ride) {
+        CwRider r;
+        r.B = Bp; r.rowpart = bt.rowp; r.fropart = bt.frop;
+        r.dprev = cw_prev(c, k0);
+        r.dnext = cw_next(c, k0);
+        r.d_out = c->nbrow + (size_t)k0 * c->p;
+        r.cwmax = c->cwmax + k0; r.cnt = c->cwcnt + k0; r.out = c->bounds_h + k0; r.cuse = c->cuse + k0;
+        r.flag = c->spec_flag; r.flag_host = c->spec_flag_h; r.flag_slot = h;
+        r.T = bT; r.ntile = bT * (bT + 1) / 2; r.p = c->p; r.K = Kp; r.nbx = (c->p + 15) / 16;
+        symm_set_rider(r);
+        if (c->cw_rider == 2) symm_flush_rider(sh);
+        c->cw_rides += 1;
+        S.cw_written = true;
+    } else if (bT) {
+        if (c->fused_cw) {
+            launch_bound_cw(sh, Bp, bt.rowp, bT, Kp, c->p, c->nbrow + (size_t)k0 * c->p, bt.frop, bT * (bT + 1) / 2,
+                            c->cwmax + k0, c->cwcnt + k0, c->bounds_h + k0, spec ? c->cuse + k0 : nullptr,
+                            spec ? c->spec_flag : nullptr, spec ? c->spec_flag_h : nullptr, h, cw_prev(c, k0), cw_next(c, k0));
+        } else {
+            const int nib = bound_rows_blocks(c->p);
+            launch_bound_rows(sb, bt.rowp, bT, Kp, c->p, c->nbrow + (size_t)k0 * c->p, c->infpart + (size_t)k0 * nib);
+            trace_mark(c, sb, 3);
+            launch_cw_final(sb, Bp, c->nbrow + (size_t)k0 * c->p, Kp, c->p, c->infpart + (size_t)k0 * nib, bt.frop,
+                            bT * (bT + 1) / 2, c->cwmax + k0, c->cwcnt + k0, c->bounds_h + k0, spec ? c->cuse + k0 : nullptr,
+                            spec ? c->spec_flag : nullptr, spec ? c->spec_flag_h : nullptr, h, cw_prev(c, k0), cw_next(c, k0));
+            trace_mark(c, sb, 4);
         }
-        for (int h = 1; h < nrun; ++h) {
+        S.cw_written = c->cw_warm;
+    } else {
+        const int nbb = norm_bounds_blocks(c->p);
+        double* nb2 = c->nbpart + 2 * (size_t)k0 * nbb;
+        double* nbc = c->nbpart + 2 * (size_t)K * nbb + (size_t)k0 * nbb;
+        launch_norm_bounds(sh, Bp, Kp, c->p, nb2, c->nbrow + (size_t)k0 * c->p);
+        launch_cw_bounds(sh, Bp, c->nbrow + (size_t)k0 * c->p, Kp, c->p, nbc);
+        launch_bound_final(sh, nb2, nbc, nbb, Kp, c->bounds_h + k0, 0, spec ? c->cuse + k0 : nullptr,
+                           spec ? c->spec_flag + h : nullptr, spec ? c->spec_flag_h + h : nullptr);
+    }
+    if (*bfree) HIPCHK(hipEventRecord(*bfree, sb));
+    return GGL_OK;
+}
+
+// ---- a speculative chain is in the streams: join of the parts, bookkeeping ----
+static int omega_finish_spec(ggl_ctx* c, const OmegaStep& S, const OmegaChainPlan& pl)
+{
+    const int nh = pl.nh;
+    // (parts that share a hardware queue keep the event join: a polling wave in front of the kernel it waits for would
+    // sit out its time limit -- the host queues the set before the wait, so this is belt and braces)
+    if (nh > 1 && c->join_flag && !c->parts_serial) {
+        // (see k_wait_flags: the waiting queue idles ~25 us behind a cross-queue event that has fired)
+        c->join_seq += 1;
+        for (int h = 1; h < nh; ++h) launch_set_flag(c->streamx[h - 1], c->join_words + h, c->join_seq);
+        launch_wait_flags(c->stream, c->join_words + 1, nh - 1, c->join_seq, c->spec_flag, c->spec_flag_h, 0, 200.0);
+        HIPCHK(hipGetLastError());
+    } else {
+        for (int h = 1; h < nh; ++h) {
             HIPCHK(hipEventRecord(c->ev_join[h - 1], c->streamx[h - 1]));
             HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join[h - 1], 0));
         }
-        PE(c, GGL_PH_EIG_OMEGA2);
-        HIPCHK(hipGetLastError());
-        c->ns_units_total = (long long)(c->ns_units_frac + 0.5);
-        c->ns_steps_total = (long long)(c->ns_steps_frac + 0.5);
-        c->ns_calls += 1;
-        c->dvo_valid = false;
-        if (c->info_dirty) { memset(c->info_h, 0, K * sizeof(int)); c->info_dirty = false; }
-        c->cur = nxt;
+    }
+    PE(c, GGL_PH_EIG_OMEGA);
+    c->spec_calls += 1;
+    note_groups(c, pl.grouped ? nh : 1, pl.Kh, pl.plans);
+    c->spec_pending = true;        // validated by the caller after its stream sync (finish_norms)
+    c->cw_pending = S.cw_written;
+    step_epilogue(c, S.nxt);
+    return GGL_OK;
+}
+
+// ---- the bounds are on their way to the host: wait for them, build the schedules from them, launch the products ----
+static int omega_finish_validated(ggl_ctx* c, const OmegaStep& S, OmegaChainPlan& pl)
+{
+    const int K = c->K, nxt = S.nxt;
+    const size_t pp = S.pp;
+    int rc;
+    for (int h = 0; h < pl.nh; ++h) HIPCHK(hipStreamSynchronize(h == 0 ? c->stream : c->streamx[h - 1]));
+    sanitize_bounds(c, c->bounds_h, c->par_h, 4.0);          // (GGL_OPT_ISOLATE: lambda_min(A') = 4 beta stands in)
+    // validated bounds: the next step may speculate on them
+    for (int k = 0; k < K; ++k) { c->spec_c[k] = c->bounds_h[k]; c->spec_beta[k] = c->par_h[k]; }
+    c->spec_have = true;
+    if (S.cw_written) { c->cw_cur ^= 1; c->cw_have = true; }
+    bool any_stable = false;
+    // phase A ran as one launch sequence; the products may still run as groups with their own schedules
+    if (pl.nh == 1 && plan_regroup(c, c->bounds_h, pl) && !c->parts_probed) {
+        rc = probe_part_streams(c);
+        if (rc) return rc;
+    }
+    const int nh = pl.nh;
+    const size_t region = plan_region(pl, K);
+    for (int h = 0; h < nh; ++h) {
+        const int k0 = pl.k0h[h];
+        const int prc = ns_plan(c->bounds_h + k0, c->par_h + k0, pl.Kh[h], c->coef_h + h * region, S.start_base_h + 5 * k0,
+                                &pl.plans[h], c->ns_force, c->ns_degrees, c->ns_tol, c->omega_poly);
+        if (prc == -1) return fail(GGL_E_SOLVER, "Newton-Schulz Omega-step: non-finite W (diverged iterate?)");
+        if (prc == -2) {
+            // pathological scaling (|W|^2 rho / nk > 1e12): eigendecomposition of the (still intact) W
+            c->ns_eigh_fallbacks += 1;
+            rc = eig_recon(c, c->W, c->Om[nxt], c->DvO, MAP_PHIPLUS, S.beta, -1, GGL_PH_RECON_OMEGA);
+            if (rc) return rc;
+            c->dvo_valid = true;
+            c->cur = nxt;
+            return GGL_OK;
+        }
+        any_stable = any_stable || pl.plans[h].stable;
+    }
+    if (nh > 1 && any_stable) {
+        // the stable schedule multiplies a contiguous [Y|P] pair: run the whole batch as one sequence
+        const int prc = ns_plan(c->bounds_h, c->par_h, K, c->coef_h, S.start_base_h, &pl.plans[0], c->ns_force, c->ns_degrees, c->ns_tol,
+                                c->omega_poly);
+        if (prc != 0) return fail(GGL_E_SOLVER, "Newton-Schulz Omega-step: plan failed (%d)", prc);
+    }
+    const int nrun = (nh > 1 && !any_stable) ? nh : 1;
+    if (nrun == 1) { pl.Kh[0] = K; pl.k0h[0] = 0; }
+    c->last_parts = nrun;
+    c->last_variant = symm_effective_variant((nrun > 1 && pl.var_parts >= 0) ? pl.var_parts
+                      : (c->symm_variant >= 0 ? c->symm_variant : symm_auto_variant(pl.Kh[0], c->p)), c->p);
+    note_groups(c, (pl.grouped && nrun > 1) ? nrun : 1, pl.Kh, pl.plans);
+    PB(c, GGL_PH_EIG_OMEGA2);
+    for (int h = 0; h < nrun; ++h) {
+        const int Kr = pl.Kh[h], k0 = pl.k0h[h];
+        hipStream_t sh = h == 0 ? c->stream : c->streamx[h - 1];
+        CopySegs up;
+        up.add(S.start_base_d + 5 * (size_t)k0, S.start_base_h + 5 * (size_t)k0, (size_t)Kr * 5 * sizeof(double));
+        const int nb_launch = pl.plans[h].products - 2;     // launches of phase B
+        if (nb_launch > 0)
+            up.add(c->coef + h * region, c->coef_h + h * region, (size_t)nb_launch * NS_SLOT(Kr) * sizeof(double));
+        if (h == 0 && c->info_dirty) up.add(c->info, nullptr, K * sizeof(int));   // no eigensolver ran: info = 0
+        launch_copy_small(sh, up);
+        ns_run(sh, pl.plans[h], c->coef + h * region, S.start_base_d + 5 * k0,
+               c->W + k0 * pp, c->nsYP[0] + k0 * pp, c->nsYP[1] + k0 * pp, c->nsT + k0 * pp, c->Om[nxt] + k0 * pp, Kr,
+               c->p,
+               // tile choice by the work of the WHOLE batch: the other parts share the chip (measured +6.7 %);
+               // with parts, the 3-stage DMA pipeline is 2.8 % ahead of the double buffer (4 % behind without)
+               nrun > 1 ? pl.var_parts : c->symm_variant, nrun > 1 ? c->n : 0);
+        c->ns_stable_calls += pl.plans[h].stable ? 1 : 0;
+        note_sequence(c, pl.plans[h], Kr);
+    }
+    for (int h = 1; h < nrun; ++h) {
+        HIPCHK(hipEventRecord(c->ev_join[h - 1], c->streamx[h - 1]));
+        HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join[h - 1], 0));
+    }
+    PE(c, GGL_PH_EIG_OMEGA2);
+    HIPCHK(hipGetLastError());
+    step_epilogue(c, nxt);
+    return GGL_OK;
+}
+
+// Omega-step with beta_k in parameter slot 0 (already on the device, or part of the pending transfer)
+int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool only_spec)
+{
+    // only_spec: launch the chain only if it can run speculatively (no host synchronisation inside); else do nothing
+    int rc;
+    const int K = c->K;
+    OmegaStep S;
+    S.latent = latent;
+    S.beta = c->par;
+    S.nxt = c->cur ^ 1;
+    S.pp = (size_t)c->p * c->p;
+    c->step_latent = latent;
+    if (latent && !c->pre0_beta.empty()) std::fill(c->pre0_beta.begin(), c->pre0_beta.end(), std::nan(""));   // (the L-step's tables share the buffer)
+    if (pending) S.first = *pending;
+    // a step whose kernels read their parameters from the pinned mirror never uploaded them: whoever reads the DEVICE copy
+    // next (every other route below does, through `first`) gets it now
+    else if (c->par0_stale) S.first.add(c->par, c->par_h, 8 * (size_t)K * sizeof(double));      // (all eight slots: a few KB)
+    c->par0_stale = false;
+    if (!c->omega_ns) return omega_eig_route(c, S, only_spec);
+    omega_step_flags(c, S, allow_spec, only_spec);
+    omega_step_tables(c, S);
+    OmegaChainPlan pl;
+    omega_split(c, S, pl);
+    if (c->flags_dirty) {
+        // a step was rejected since the flags were last cleared wholesale: whatever slot carried the 1 (a part that does
+        // not exist in this step's split, the chain's completion check) must not outlive it.  On the main stream BEFORE
+        // the fork, so it is ordered ahead of every part's own zeroing and kernels.
+        if ((rc = clear_spec_flags(c))) return rc;
+        c->flags_dirty = false;
+    }
+    bool done;
+    rc = omega_lds_route(c, S, pending, allow_spec, only_spec, &done);
+    if (rc || done) return rc;
+#ifdef GGL_DEV
+    rc = omega_dev_chain(c, S, pl, &done);
+    if (rc || done) return rc;
+#endif
+    if (S.resume) c->early_used += 1;
+    else if (S.spec) omega_plan_spec(c, S, pl);
+    if (only_spec && !S.spec) return GGL_NOT_LAUNCHED;
+    const int nh = pl.nh;
+    if (nh > 1 && !c->parts_probed) {
+        rc = probe_part_streams(c);
+        if (rc) return rc;
+    }
+    if (nh > 1 && !S.resume) {
+        HIPCHK(hipEventRecord(c->ev_fork, c->stream));
+        for (int h = 1; h < nh; ++h) HIPCHK(hipStreamWaitEvent(c->streamx[h - 1], c->ev_fork, 0));
+    }
+    // (The parts' launches are issued part after part.  Issuing them round-robin, so that the parts start together
+    // instead of ~100 us apart, was measured 3 % SLOWER at (32,500): the stagger is what keeps the parts' prologues
+    // and epilogues from coinciding.)
+    const size_t region = plan_region(pl, K);
+    for (int hh = 0; hh < nh; ++hh) {
+        // GGL_OPT_PARTS_ORDER: the part on the main stream is queued LAST, so that it is the one that ends last and the
+        // Theta kernel behind it finds the other part's flag set already
+        const int h = (c->parts_order && nh == 2 && c->prof_on == 0) ? nh - 1 - hh : hh;
+        hipStream_t sh = h == 0 ? c->stream : c->streamx[h - 1];
+        const int k0 = pl.k0h[h];
+        // The host's mirrors of the validation flags are cleared when the REST of the chain is launched: the mirrors of an
+        // early part's iteration are still to be read when the part goes into the stream (the device words, cleared by
+        // the part's copy kernel, have been read by then -- the Theta-step that takes them is ahead in the stream).
+        if (!S.want_A) {
+            c->spec_flag_h[h] = 0;
+            if (h == 0 && nh < ggl_ctx::MAX_PARTS) c->spec_flag_h[ggl_ctx::MAX_PARTS - 1] = 0;
+        }
+        if (!S.resume) omega_phase_a(c, S, pl, h, sh);
+        if (S.want_A) continue;
+        if (S.resume && h == 0) PB(c, GGL_PH_EIG_OMEGA);
+        // ---- the rest: bound of this iteration's A' (validation of the assumed one), products, Omega ----
+        hipEvent_t bfree = nullptr;
+        rc = omega_bound_pass(c, S, pl, h, sh, &bfree);
+        if (rc) return rc;
+        if (S.spec) {
+            ns_run(sh, pl.plans[h], c->coef + h * region, S.start_base_d + 5 * k0, c->W + k0 * S.pp, c->nsYP[0] + k0 * S.pp,
+                   c->nsYP[1] + k0 * S.pp, c->nsT + k0 * S.pp, c->Om[S.nxt] + k0 * S.pp, pl.Kh[h], c->p,
+                   pl.var_parts, nh > 1 ? c->n : 0, pl.fused[h] != nullptr, bfree);
+            symm_flush_rider(sh);                     // (a chain without a direct-to-LDS product launch: its own launch)
+            note_sequence(c, pl.plans[h], pl.Kh[h]);
+        }
+        if (h == 0 && !S.spec) PE(c, GGL_PH_EIG_OMEGA);
+    }
+    HIPCHK(hipGetLastError());
+    if (S.want_A) {
+        c->early.plan = pl;
+        memcpy(c->early.beta, c->par_h, K * sizeof(double));
+        c->early.valid = true;
+        c->early_launched += 1;
         return GGL_OK;
     }
-    if (only_spec) return GGL_NOT_LAUNCHED;
-    launch_copy_small(c->stream, first);
-    PB(c, GGL_PH_FORM_W);
-    launch_form_W(c->stream, c->W, c->Theta, latent ? c->L : nullptr, c->X, c->S, beta, c->K, c->p);
-    PE(c, GGL_PH_FORM_W);
-    HIPCHK(hipGetLastError());
-    rc = eig_recon(c, c->W, c->Om[nxt], c->DvO, MAP_PHIPLUS, beta, GGL_PH_EIG_OMEGA, GGL_PH_RECON_OMEGA);
-    if (rc) return rc;
-    c->dvo_valid = true;
-    c->cur = nxt;
-    return GGL_OK;
+    return S.spec ? omega_finish_spec(c, S, pl) : omega_finish_validated(c, S, pl);
 }
 
 extern "C" int ggl_step_group_partial(ggl_ctx* c, double rho, double lambda1)

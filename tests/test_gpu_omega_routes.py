@@ -1,8 +1,9 @@
-"""Every launch route of the Newton-Schulz Omega-step (omega_step, capi_omega.hip), named, proven taken, and checked against
-eigh.  The route is picked from the shape and from state no drawn shape controls: the split (one launch sequence, two parts of
-a small batch, K >= 16 concurrent parts, or contiguous groups with their own schedules), speculative or validated, a fresh
-chain or the RESUME of an early first part (ggl_ctx::EarlyA) launched behind the previous iteration's Theta-step, and the
-product-kernel variant, which also fixes the tile layout of the bound partials the B' launch leaves behind.
+"""Every launch route of the Newton-Schulz Omega-step (omega_step and its per-route functions, capi_omega.hip), named, proven
+taken, and checked against eigh.  The route is picked from the shape and from state no drawn shape controls: the split
+(omega_split: one launch sequence, two parts of a small batch, K >= 16 concurrent parts, or contiguous groups with their own
+schedules), speculative or validated (omega_finish_spec / omega_finish_validated), a fresh chain or the RESUME of an early
+first part (ggl_ctx::EarlyA, which keeps the part's OmegaChainPlan) launched behind the previous iteration's Theta-step, and
+the product-kernel variant, which also fixes the tile layout of the bound partials the B' launch leaves behind.
 
 Each case runs ggl_admm_step with the reference's rho rule (solver/admm_solver.py:227-233), so that the residual ratio settles
 and early parts fire, on heterogeneous instances (S scaled per instance), and
@@ -211,7 +212,7 @@ def _check_route(case, trail, rhos, odd_dl):
         assert gs["steps"] == 0, info
     if case.rho_change_grouped:
         # a rho change drops the pre-launched chain: the step runs validated (bounds first), and the products as groups
-        # chosen from THOSE bounds (var_b).  Such a call launched validated steps only, or that step plus the next chain:
+        # chosen from THOSE bounds (plan_regroup).  Such a call launched validated steps only, or that step plus the next chain:
         # every Omega-step of the call was grouped.
         hits = [t for t in range(2, len(trail)) if rhos[t - 1] != rhos[t - 2]
                 and _d(trail, t, 0, "calls") > _d(trail, t, 0, "spec_calls")
