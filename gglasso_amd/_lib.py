@@ -98,6 +98,8 @@ _SIGNATURES = {
     "ggl_ext_batch_step": ([_vp, _d, _dp, _dp, _i, _dp, _dp], _i),
     "ggl_objective": ([_vp, _d, _d, _i, _dp], _i),
     "ggl_kkt_residual": ([_vp, _d, _d, _d, _i, _i, _dp, _dp, _dp], _i),
+    "ggl_kkt_terms": ([_vp, _d, _d, _d, _i, _i, _dp, _dp, _dp], _i),
+    "ggl_diag_stats": ([_vp, ctypes.POINTER(ctypes.c_longlong)], _i),
     "ggl_profile_enable": ([_vp, _i], _i),
     "ggl_profile_read": ([_vp, _dp, ctypes.POINTER(ctypes.c_longlong), _i], _i),
     "ggl_dev_symm": ([_i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _i], _i),

@@ -155,10 +155,11 @@ extern "C" int ggl_selection_stats(ggl_ctx* c, double* out)
     HIPCHK(hipGetLastError());
     // eigenvalues of Theta_k: log det and the smallest one (robust_logdet, model_selection.py:884-894)
     HIPCHK(hipMemcpyAsync(c->W, c->snapT, c->n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    int rc = eigvals_only(c, c->W, c->DvO);
+    // (DvL, the eigenvalue scratch of every check between two steps: DvO keeps the eigenvalues of W the last Omega-step left,
+    // which ggl_objective reads -- its log det must not change route, and so its last digits, with what was called before it)
+    int rc = eigvals_only(c, c->W, c->DvL);
     if (rc) return rc;
-    c->dvo_valid = false;
-    HIPCHK(hipMemcpyAsync(d.data(), c->DvO, kp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(d.data(), c->DvL, kp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(c->info_h, c->info, K * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     rc = check_info(c, "selection statistics");
@@ -191,6 +192,7 @@ extern "C" int ggl_objective(ggl_ctx* c, double lambda1, double lambda2, int reg
     std::vector<double> d(kp);
     const bool from_w = c->dvo_valid;
     bool from_chol = false;
+    if (from_w) c->diag_logdet_w += 1;
     if (!from_w) {
         // log det Omega_k = 2 sum_i log R_ii of the Cholesky factor (Omega = phiplus(...) is positive definite by construction):
         // one batched potrf instead of the eigenvalues -- measure=True evaluates this EVERY iteration, and the eigenvalues cost
@@ -204,7 +206,9 @@ extern "C" int ggl_objective(ggl_ctx* c, double lambda1, double lambda2, int reg
         for (int k = 0; k < c->K; ++k) from_chol = from_chol && ok[k];
         if (from_chol) {
             launch_get_diag(c->stream, c->W, c->K, c->p, c->DvO);
+            c->diag_logdet_chol += 1;
         } else {
+            c->diag_logdet_eig += 1;
             HIPCHK(hipMemcpyAsync(c->W, c->Om[c->cur], c->n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
             rc0 = eigvals_only(c, c->W, c->DvO);
             if (rc0) return rc0;
@@ -256,8 +260,10 @@ static int stack_sq(ggl_ctx* c, const double* A, const double* B, double* out)
     return host_reduce(c, c->K, 1, out, false);
 }
 
-extern "C" int ggl_kkt_residual(ggl_ctx* c, double rho, double lambda1, double lambda2, int reg, int latent,
-                                const double* mu1, const double* nk, double* out)
+// The four terms of the KKT residual in the reference's order (admm_solver.py:343-371, single_admm_solver.py:302-317);
+// term 4 is 0 when not latent.  ggl_kkt_residual is their maximum.
+extern "C" int ggl_kkt_terms(ggl_ctx* c, double rho, double lambda1, double lambda2, int reg, int latent,
+                             const double* mu1, const double* nk, double out[4])
 {
     ARGCHK(c && out, "ctx, out");
     ARGCHK(!latent || mu1, "latent needs mu1");
@@ -271,6 +277,7 @@ extern "C" int ggl_kkt_residual(ggl_ctx* c, double rho, double lambda1, double l
     double* T1 = c->W;             // scratch
     double* T2 = c->Om[c->cur ^ 1]; // Omega_{t-1} is dead once the step's norms are out
     double nTheta, nOmega, v;
+    double term[4] = {0.0, 0.0, 0.0, 0.0};
     int rc;
     if ((rc = stack_sq(c, c->Theta, nullptr, &nTheta))) return rc;
     if ((rc = stack_sq(c, Om, nullptr, &nOmega))) return rc;
@@ -279,26 +286,29 @@ extern "C" int ggl_kkt_residual(ggl_ctx* c, double rho, double lambda1, double l
     // term1: |Theta - prox(Theta + rho X)| / (1 + |Theta|)
     launch_axpy(c->stream, T1, c->Theta, rho, c->X, c->n);
     if (reg == GGL_REG_SGL) {
-        // prox_od_1norm with l = lambda1 (scalar or the (p,p) mask array), per instance
+        // prox_od_1norm with l = lambda1 (scalar, the shared (p,p) mask array, or instance k's own of ggl_set_lambda1_mask_k)
+        const size_t pp = (size_t)c->p * c->p;
         for (int k = 0; k < c->K; ++k)
-            launch_prox_od(c->stream, T2 + (size_t)k * c->p * c->p, T1 + (size_t)k * c->p * c->p, lambda1,
-                           c->has_mask ? c->mask : nullptr, c->p);
+            launch_prox_od(c->stream, T2 + k * pp, T1 + k * pp, lambda1,
+                           c->has_maskK ? c->maskK + k * pp : (c->has_mask ? c->mask : nullptr), c->p);
+        if (c->has_maskK) c->diag_kkt_mask_k += 1;
+        else if (c->has_mask) c->diag_kkt_mask += 1;
     } else {
         HIPCHK(launch_prox_p(c->stream, reg, T2, T1, lambda1, lambda2, c->K, c->p, c->sqwork));
     }
     if ((rc = stack_sq(c, c->Theta, T2, &v))) return rc;
-    double res = std::sqrt(v) / (1.0 + nTheta);
+    term[0] = std::sqrt(v) / (1.0 + nTheta);
     // term2: |Theta - Omega - L| / (1 + |Theta|)
     launch_sub(c->stream, T1, c->Theta, Om, c->n);
     if ((rc = stack_sq(c, T1, latent ? c->L : nullptr, &v))) return rc;
-    res = std::max(res, std::sqrt(v) / (1.0 + nTheta));
+    term[1] = std::sqrt(v) / (1.0 + nTheta);
     // term3: |Omega - phiplus(eigh(Omega - nk S - rho X), nk)| / (1 + |Omega|)
     if ((rc = upload_par(c, 3, nk, 1.0, 1.0))) return rc;
     const double* nkd = c->par + 3 * (size_t)c->K;
     launch_kkt_w(c->stream, T1, Om, c->S, c->X, nkd, rho, c->K, c->p);
     if ((rc = eig_recon(c, T1, T2, c->DvL, MAP_PHIPLUS, nkd))) return rc;
     if ((rc = stack_sq(c, Om, T2, &v))) return rc;
-    res = std::max(res, std::sqrt(v) / (1.0 + nOmega));
+    term[2] = std::sqrt(v) / (1.0 + nOmega);
     if (latent) {
         double nL;
         if ((rc = stack_sq(c, c->L, nullptr, &nL))) return rc;
@@ -306,12 +316,47 @@ extern "C" int ggl_kkt_residual(ggl_ctx* c, double rho, double lambda1, double l
         launch_axpy(c->stream, T1, c->L, -rho, c->X, c->n);
         if ((rc = eig_recon(c, T1, T2, c->DvL, MAP_RANK, c->par + 2 * (size_t)c->K))) return rc;
         if ((rc = stack_sq(c, c->L, T2, &v))) return rc;
-        res = std::max(res, std::sqrt(v) / (1.0 + std::sqrt(nL)));
+        term[3] = std::sqrt(v) / (1.0 + std::sqrt(nL));
     }
+    (use_jacobi(c) ? c->diag_kkt_jacobi : c->diag_kkt_rocsolver) += 1;
     HIPCHK(hipMemcpyAsync(c->info_h, c->info, c->K * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if ((rc = check_info(c, "kkt residual"))) return rc;
+    for (int i = 0; i < 4; ++i) out[i] = term[i];
+    return GGL_OK;
+}
+
+extern "C" int ggl_kkt_residual(ggl_ctx* c, double rho, double lambda1, double lambda2, int reg, int latent,
+                                const double* mu1, const double* nk, double* out)
+{
+    ARGCHK(c && out, "ctx, out");
+    double term[4];
+    const int rc = ggl_kkt_terms(c, rho, lambda1, lambda2, reg, latent, mu1, nk, term);
+    if (rc) return rc;
+    // max in the order the terms are formed (a NaN term is dropped by std::max exactly as before)
+    double res = term[0];
+    res = std::max(res, term[1]);
+    res = std::max(res, term[2]);
+    if (latent) res = std::max(res, term[3]);
     *out = res;
+    return GGL_OK;
+}
+
+// What the diagnostics dispatched on this ctx: out = { ggl_objective calls whose log det came from the eigenvalues of W the last
+// Omega-step left, from the Cholesky factor of Omega, from the eigenvalues of Omega behind a failed factorisation;
+// ggl_kkt_terms / ggl_kkt_residual calls on the LDS Jacobi eigensolver, on rocSOLVER, with the shared lambda1 mask, with the
+// per-instance masks; 0 }
+extern "C" int ggl_diag_stats(ggl_ctx* c, long long out[8])
+{
+    ARGCHK(c && out, "ctx, out");
+    out[0] = c->diag_logdet_w;
+    out[1] = c->diag_logdet_chol;
+    out[2] = c->diag_logdet_eig;
+    out[3] = c->diag_kkt_jacobi;
+    out[4] = c->diag_kkt_rocsolver;
+    out[5] = c->diag_kkt_mask;
+    out[6] = c->diag_kkt_mask_k;
+    out[7] = 0;
     return GGL_OK;
 }
 
@@ -394,10 +439,9 @@ extern "C" int ggl_threshold_scan(ggl_ctx* c, const double* tau, int ntau, doubl
     for (int ch = 0; ch < nchunk; ++ch) {
         launch_threshold_write(c->stream, c->snapT, dwsrc + (size_t)ch * K, dwtau.p + (size_t)ch * K, K, p, c->W);
         HIPCHK(hipGetLastError());
-        int rc = eigvals_only(c, c->W, c->DvO);
+        int rc = eigvals_only(c, c->W, c->DvL);      // (DvL: see ggl_selection_stats)
         if (rc) return rc;
-        c->dvo_valid = false;
-        HIPCHK(hipMemcpyAsync(d.data() + (size_t)ch * K * p, c->DvO, (size_t)K * p * sizeof(double), hipMemcpyDeviceToHost,
+        HIPCHK(hipMemcpyAsync(d.data() + (size_t)ch * K * p, c->DvL, (size_t)K * p * sizeof(double), hipMemcpyDeviceToHost,
                               c->stream));
         HIPCHK(hipMemcpyAsync(c->info_h, c->info, K * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -442,11 +486,10 @@ extern "C" int ggl_selection_rank(ggl_ctx* c, double rel_tol, double* out)
     const size_t kp = (size_t)K * p;
     if (!(rel_tol > 0.0)) rel_tol = (double)p * 2.220446049250313e-16;
     HIPCHK(hipMemcpyAsync(c->W, c->snapL, c->n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    int rc = eigvals_only(c, c->W, c->DvO);
+    int rc = eigvals_only(c, c->W, c->DvL);          // (DvL: see ggl_selection_stats)
     if (rc) return rc;
-    c->dvo_valid = false;
     std::vector<double> d(kp);
-    HIPCHK(hipMemcpyAsync(d.data(), c->DvO, kp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(d.data(), c->DvL, kp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(c->info_h, c->info, K * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     rc = check_info(c, "rank of the latent component");

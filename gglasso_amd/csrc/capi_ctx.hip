@@ -756,6 +756,7 @@ extern "C" int ggl_set_state_ex(ggl_ctx* c, const double* Omega, const double* T
     c->spec_have = false;      // bounds of another iterate say nothing about this one
     c->cw_have = false;
     c->cwL_have = false;        // (any positive vector would do, but every solve shall start the same way)
+    if (Omega) c->dvo_valid = false;   // the eigenvalues an Omega-step left belong to the Omega it wrote (ggl_objective)
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);
     const size_t nb = c->n * sizeof(double);
@@ -806,6 +807,7 @@ extern "C" int ggl_state_snapshot(ggl_ctx* c, int restore)
     ARGCHK(c->snap[0], "no snapshot taken");
     for (int i = 0; i < 4; ++i) HIPCHK(hipMemcpyAsync(cur[i], c->snap[i], nb, hipMemcpyDeviceToDevice, c->stream));
     c->state_symmetric = c->snap_symmetric;
+    c->dvo_valid = false;
     c->spec_have = false;
     c->cw_have = false;
     c->cwL_have = false;

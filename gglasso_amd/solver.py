@@ -443,6 +443,23 @@ class HipEngine:
                                         ptr(out)))
         return float(out[0])
 
+    def kkt_terms(self, rho, lambda1, lambda2, reg, latent, mu1, nk):
+        """(4,): the terms ``kkt_residual`` is the maximum of, in the reference's order (admm_solver.py:343-371); term 4 is 0
+        when not latent."""
+        out = np.zeros(4)
+        check(self.lib.ggl_kkt_terms(self.h, rho, lambda1, lambda2, _REG[reg], int(latent), ptr(mu1), ptr(nk), ptr(out)))
+        return out
+
+    def diag_stats(self):
+        """{'logdet_w', 'logdet_chol', 'logdet_eig': ``objective`` calls by the route their log det took (eigenvalues of W from
+        the last Omega-step, Cholesky factor of Omega, eigenvalues of Omega behind a failed factorisation); 'kkt_jacobi',
+        'kkt_rocsolver': KKT calls by eigensolver; 'kkt_mask', 'kkt_mask_k': KKT calls with the shared / per-instance mask}."""
+        import ctypes
+        out = (ctypes.c_longlong * 8)()
+        check(self.lib.ggl_diag_stats(self.h, out))
+        return dict(zip(("logdet_w", "logdet_chol", "logdet_eig", "kkt_jacobi", "kkt_rocsolver", "kkt_mask", "kkt_mask_k"),
+                        (int(v) for v in out)))
+
     def exit_checks(self, latent):
         out = np.zeros(5)
         check(self.lib.ggl_exit_checks(self.h, int(latent), ptr(out)))

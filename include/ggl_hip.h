@@ -26,7 +26,8 @@ extern "C" {
  * the flag at p (p + 1) / 2 (was (p,p) + 1), the int8 entry points live in the development library only, ggl_debug_poison
  * takes a byte pattern.  A binding built against another major version must refuse to load (gglasso_amd/_lib.py does).
  * Entry points and selector values that are only ADDED (GGL_REG_FSGL, ggl_set_block_size, ggl_prox_sum_frob,
- * ggl_frob_norm_per_block, ggl_fsgl_stats, ggl_covariance, ggl_scale_by_diagonal, ggl_set_S_from_data, ggl_get_S) leave every existing layout alone and the number where it is. */
+ * ggl_frob_norm_per_block, ggl_fsgl_stats, ggl_covariance, ggl_scale_by_diagonal, ggl_set_S_from_data, ggl_get_S, ggl_kkt_terms,
+ * ggl_diag_stats) leave every existing layout alone and the number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -503,6 +504,18 @@ int ggl_objective(ggl_ctx *ctx, double lambda1, double lambda2, int reg, double 
  * (opt-in stopping_criterion='kkt').  The dual passed by the reference is rho*X. */
 int ggl_kkt_residual(ggl_ctx *ctx, double rho, double lambda1, double lambda2, int reg, int latent,
                      const double *mu1, const double *nk, double *out);
+/* The four terms ggl_kkt_residual is the maximum of, in the reference's order (admm_solver.py:343-371,
+ * single_admm_solver.py:302-317): |Theta - prox(Theta + rho X)| / (1 + |Theta|), |Theta - Omega - L| / (1 + |Theta|),
+ * |Omega - phiplus(Omega - nk S - rho X)| / (1 + |Omega|), |L - prox_rank(L - rho X, mu1)| / (1 + |L|) (0 when not latent).
+ * GGL_REG_SGL thresholds instance k with lambda1, with the shared mask of ggl_set_lambda1_mask or with its own array of
+ * ggl_set_lambda1_mask_k, as the step does.  Same launches in the same order as ggl_kkt_residual, same refusals. */
+int ggl_kkt_terms(ggl_ctx *ctx, double rho, double lambda1, double lambda2, int reg, int latent,
+                  const double *mu1, const double *nk, double out[4]);
+/* What the diagnostics dispatched on this ctx since it was created: out = { ggl_objective calls whose log det came from the
+ * eigenvalues of W the last Omega-step left, from the Cholesky factor of Omega, from the eigenvalues of Omega behind a failed
+ * factorisation; KKT calls (ggl_kkt_terms / ggl_kkt_residual) on the LDS Jacobi eigensolver, on rocSOLVER, with the shared
+ * lambda1 mask, with per-instance masks; 0 }. */
+int ggl_diag_stats(ggl_ctx *ctx, long long out[8]);
 
 /* ---- per-phase device timing (HIP events on the ctx stream; what bench.py's roofline uses) ------
  * Phases of one iteration; ms[] accumulates elapsed milliseconds, count[] the number of launches. */

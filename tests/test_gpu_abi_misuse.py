@@ -20,3 +20,6 @@ def test_misuse_of_the_c_abi_is_an_error_code_never_a_crash():
     assert r.returncode == 0 and lines and lines[-1] == "ok", r.stdout[-3000:] + r.stderr[-2000:]
     assert not any(ln.startswith("BAD") for ln in lines)
     assert sum(ln.startswith("ok ") for ln in lines) >= 60
+    # ggl_kkt_terms refuses what ggl_kkt_residual refuses
+    for probe in ("ggl_kkt_terms(GGL_REG_FSGL)", "ggl_kkt_terms(latent without mu1)", "ggl_kkt_terms(out=NULL)"):
+        assert any(ln.startswith("ok ") and f" {probe}: rc -1 " in ln for ln in lines), probe

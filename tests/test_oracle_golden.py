@@ -148,6 +148,40 @@ def test_g10_kkt_sgl():
     assert abs(v - float(g["kkt_value"])) <= 1e-12
 
 
+def test_g22_kkt_on_a_state_that_is_no_iterate():
+    """the oracle's KKT criteria against the reference's on a generic state (every term 1e-2 .. 1e-1): GGL / FGL, latent and
+    not, and the single-problem version plain, with an array lambda1 and latent (tests/golden/make_golden_kkt.py)"""
+    g = load_golden("g22_kkt_terms")
+    S, Om, Th, L, X, nk, mu1 = (g[nm] for nm in ("S", "Omega", "Theta", "L", "X", "nk", "mu1"))
+    l1, l2 = g["params"]
+    Z = np.zeros_like(L)
+    for reg in ("GGL", "FGL"):
+        v = orc.kkt_stopping_criterion_mgl(Om, Th, Z, X, S, l1, l2, nk, reg)
+        assert abs(v - float(g[f"mgl_{reg}_nol"])) <= 1e-12 * v
+        v = orc.kkt_stopping_criterion_mgl(Om, Th, L, X, S, l1, l2, nk, reg, latent=True, mu1=mu1)
+        assert abs(v - float(g[f"mgl_{reg}_lat"])) <= 1e-12 * v
+    z = np.zeros_like(L[0])
+    for tag, args, kw in (("plain", (z, X[0], S[0], l1), {}), ("array", (z, X[0], S[0], g["sgl_lambda1_array"]), {}),
+                          ("lat", (L[0], X[0], S[0], l1), {"latent": True, "mu1": 0.15})):
+        v = orc.kkt_stopping_criterion_sgl(Om[0], Th[0], *args, **kw)
+        assert abs(v - float(g[f"sgl_{tag}"])) <= 1e-12 * v, tag
+    assert min(float(g[k]) for k in g.files if g[k].ndim == 0) >= 1e-2
+    # term by term: the reference of tests/diag_ref.py (which the GPU diagnostics are held against) on the same state
+    import diag_ref as dr
+    for reg in ("GGL", "FGL"):
+        for tag, Lx, lat in (("nol", Z, False), ("lat", L, True)):
+            t = dr.kkt_ref(reg, Om, Th, Lx, X, S, 1.0, l1, l2, nk[:, 0, 0], lat, mu1).terms.astype(np.float64)
+            want = g[f"mgl_{reg}_{tag}_terms"]
+            assert np.all(np.abs(t - want) <= 1e-12 * want), (reg, tag, t, want)
+    assert abs(g["mgl_GGL_nol_terms"][0] - g["mgl_FGL_nol_terms"][0]) >= 1e-3       # the penalties differ in term 1 only
+    for tag, Lx, kw in (("plain", z, {}), ("array", z, {"mask": g["sgl_lambda1_array"]}), ("lat", L[0], {})):
+        t = dr.kkt_ref("SGL", Om[:1], Th[:1], Lx[None], X[:1], S[:1], 1.0, l1, 0.0, None, tag == "lat", np.full(1, 0.15),
+                       **kw).terms.astype(np.float64)
+        want = g[f"sgl_{tag}_terms"]
+        assert np.all(np.abs(t - want) <= 1e-12 * np.maximum(want, 1e-300)), (tag, t, want)
+    assert abs(g["sgl_plain_terms"][0] - g["sgl_array_terms"][0]) >= 1e-3
+
+
 def test_g11_block_sgl():
     g = load_golden("g11_block_sgl")
     S, lam = g["S"], float(g["lam"])

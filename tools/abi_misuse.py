@@ -148,6 +148,15 @@ expect_error("ggl_set_block_size(M=-2)", lib.ggl_set_block_size(h, -2))
 assert lib.ggl_set_block_size(h, 4) == 0, last()
 expect_error("ggl_kkt_residual(GGL_REG_FSGL)", lib.ggl_kkt_residual(h, ctypes.c_double(1.0), ctypes.c_double(0.1), ctypes.c_double(0.0), 3, 0,
                                                                     None, ptr(r4), ptr(np.zeros(1))))
+kt = lambda reg, latent=0, mu=None, out=np.zeros(4): lib.ggl_kkt_terms(h, ctypes.c_double(1.0), ctypes.c_double(0.1), ctypes.c_double(0.05), reg,
+                                                                       latent, mu, ptr(r4), None if out is None else ptr(out))
+expect_error("ggl_kkt_terms(GGL_REG_FSGL)", kt(3))
+expect_error("ggl_kkt_terms(latent without mu1)", kt(1, latent=1))
+expect_error("ggl_kkt_terms(out=NULL)", kt(1, out=None))
+expect_error("ggl_kkt_terms(reg=9)", kt(9))
+expect_error("ggl_kkt_terms(NULL ctx)", lib.ggl_kkt_terms(None, ctypes.c_double(1.0), ctypes.c_double(0.1), ctypes.c_double(0.05), 1, 0, None,
+                                                          ptr(r4), ptr(np.zeros(4))))
+expect_error("ggl_diag_stats(out=NULL)", lib.ggl_diag_stats(h, None))
 expect_error("ggl_admm_step(GGL_REG_FSGL, lambda1=0)", lib.ggl_admm_step(h, ctypes.c_double(1.0), ctypes.c_double(0.0), ctypes.c_double(0.0), 3, 0,
                                                                          None, None, ptr(n5)))
 assert lib.ggl_set_lambda1_mask(h, ptr(np.ones((8, 8)))) == 0, last()
