@@ -154,6 +154,9 @@ _SIGNATURES = {
     "ggl_scale_by_diagonal": ([_i, _i, _i, _dp, _dp, _dp, _dp], _i),
     "ggl_set_S_from_data": ([_vp, ctypes.POINTER(_dp), _ip, _i], _i),
     "ggl_get_S": ([_vp, _dp, _dp], _i),
+    "ggl_covariance_subsets": ([_i, _i, _i, _dp, _i, _i, _ip, _i, _dp, _dp], _i),
+    "ggl_set_S_from_subsets": ([_vp, _dp, _i, _i, _i, _ip, _i], _i),
+    "ggl_edge_stability": ([_vp, _i, _d, _ip, ctypes.POINTER(ctypes.c_longlong)], _i),
 }
 
 # libggl_hip_dev.so only (-DGGL_DEV)

@@ -48,9 +48,13 @@ def ADMM_SGL_batch(S, lambda1, Omega_0=None, Theta_0=None, X_0=None, rho=1., max
 
 
 def _sgl_batch_impl(S, lambda1, Omega_0, Theta_0, X_0, rho, max_iter, tol, rtol, update_rho, verbose, latent, mu1, lambda1_mask,
-                    selection_stats, dims, tau_range, compact, fetch, select, _block_size):
+                    selection_stats, dims, tau_range, compact, fetch, select, _block_size, _on_device=None):
     """Body of ``ADMM_SGL_batch`` and ``ADMM_FSGL_batch``; ``_block_size``: every point is a Functional SGL problem with
-    blocks of this size (the block penalty in the Theta-step), None: element-wise penalty."""
+    blocks of this size (the block penalty in the Theta-step), None: element-wise penalty.  ``_on_device``: a pair of
+    callables around the iterations for a driver whose data stay on the device (``model_selection.stars_search``):
+    ``before(eng)`` right after the engine exists (it may write the S of the ctx there; the ``S`` argument is then only a
+    placeholder of the right shape), ``after(eng, results)`` once every point has its result and snapshot, before the
+    engine closes."""
     S = as_c(S)
     assert S.ndim in (2, 3) and S.shape[-1] == S.shape[-2]
     p = S.shape[-1]
@@ -98,6 +102,8 @@ def _sgl_batch_impl(S, lambda1, Omega_0, Theta_0, X_0, rho, max_iter, tol, rtol,
     eng = _solver.ENGINE(np.broadcast_to(S, (K, p, p)), Om0, Th0, X0)
     engines = [eng]                  # eng: the original ctx (snapshots, statistics); cur: where the live points iterate
     try:
+        if _on_device is not None:
+            _on_device[0](eng)
         if _block_size:
             # (a compacted ctx takes the block size over from the one it is cut out of)
             assert lambda1_mask is None and dims is None, "the block penalty takes neither a mask nor per-instance dimensions"
@@ -119,7 +125,7 @@ def _sgl_batch_impl(S, lambda1, Omega_0, Theta_0, X_0, rho, max_iter, tol, rtol,
         results = [None] * K
         last = np.zeros((K, 4))                                         # r_t, s_t, e_pri, e_dual of every point's last iteration
         dimk = (pk ** 2 + pk) / 2                                       # single_admm_solver.py:279, of the block itself
-        keep_snapshots = selection_stats or latent
+        keep_snapshots = selection_stats or latent or _on_device is not None
         cur, slots = eng, np.arange(K)                                   # slots[s]: the point in slot s of cur
         carried = np.zeros(K, dtype=np.int64)
 
@@ -205,6 +211,8 @@ def _sgl_batch_impl(S, lambda1, Omega_0, Theta_0, X_0, rho, max_iter, tol, rtol,
                                           (v if nm == 'threshold_eig_problems' else float('nan')))
                                      for nm, v in info['selection'].items()}
                 info['selection']['failed'] = True
+        if _on_device is not None:
+            _on_device[1](eng, results)
         if select is not None:
             k_sel, target = select(results)
             if k_sel is not None:

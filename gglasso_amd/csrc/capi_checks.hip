@@ -179,6 +179,43 @@ extern "C" int ggl_selection_stats(ggl_ctx* c, double* out)
     return GGL_OK;
 }
 
+// StARS over the snapshots of a batch of K = L * B points, instance l * B + r = subsample r at lambda l (k_edge_stability,
+// stars.hip): per lambda the exact integer sum_{i<j} c (B - c) of the selection counts c, and the count tables on request
+extern "C" int ggl_edge_stability(ggl_ctx* c, int B, double t, int* counts_out, long long* num_out)
+{
+    ARGCHK(c && num_out, "ctx, num_out");
+    if (B < 1 || c->K % B != 0)
+        return fail(GGL_E_ARG, "bad argument: B = %d subsamples per lambda do not divide the K = %d instances of the ctx", B, c->K);
+    if (!(t >= 0.0) || !(t <= 1.79769313486231570815e308))
+        return fail(GGL_E_ARG, "bad argument: the edge threshold t = %g must be finite and not negative", t);
+    ARGCHK(c->snapT, "no snapshot taken (ggl_snapshot_k)");
+    const int L = c->K / B, p = c->p;
+    ARGCHK(L <= 65535, "more than 65535 lambdas in one ctx");
+    // num[l] <= p (p - 1) / 2 * B^2 / 4 must fit a signed 64-bit integer
+    ARGCHK((double)p * (double)p * (double)B * (double)B < 7e19, "p * B too large for exact 64-bit sums");
+    HIPCHK(hipSetDevice(c->device));
+    DROP_PRE(c);
+    const size_t pp = (size_t)p * p;
+    // num: the first L words of the ctx's scratch c->norms (at least 8 K doubles, free between two steps as in
+    // ggl_selection_stats) REINTERPRETED as 64-bit integers: after this call they hold no doubles, and whoever reads norms
+    // must have written it first (every user does).  Only the optional count tables are allocated here.
+    unsigned long long* dNum = reinterpret_cast<unsigned long long*>(c->norms);
+    int* dCnt = nullptr;
+    hipError_t e = counts_out ? hipMalloc(&dCnt, (size_t)L * pp * sizeof(int)) : hipSuccess;
+    if (e == hipSuccess) e = hipMemsetAsync(dNum, 0, L * sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess) {
+        launch_edge_stability(c->stream, c->snapT, L, B, p, t, dCnt, dNum);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(num_out, dNum, L * sizeof(long long), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && counts_out)
+        e = hipMemcpyAsync(counts_out, dCnt, (size_t)L * pp * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (dCnt) (void)hipFree(dCnt);
+    HIPCHK(e);
+    return GGL_OK;
+}
+
 extern "C" int ggl_objective(ggl_ctx* c, double lambda1, double lambda2, int reg, double out[3])
 {
     ARGCHK(c && out, "ctx, out");

@@ -41,32 +41,22 @@ int diag_error(hipStream_t st, const int* err_d, int p, const double* d_host, co
                 what, k, i, v);
 }
 
-// S_dev (K,p,p) from the host data on stream st; with GGL_COV_SCALE the correlations, and the variances in var_dev (K,p)
-int covariance_to_device(hipStream_t st, int K, int p, const int* N, const double* const* X_host, int flags, double* S_dev,
-                         double* var_dev)
+// S_dev (K,p,p) from the arena X_dev (instance k the packed row-major (p, N[k]) array at off[k]; off_dev, N_dev: the tables
+// on the device) on stream st; with GGL_COV_SCALE the correlations, and the variances in var_dev (K,p).  Waits for the
+// stream: the caller may free the arena on return.
+int covariance_of_arena(hipStream_t st, int K, int p, const double* X_dev, const long long* off_dev, const int* N_dev, int flags,
+                        double* S_dev, double* var_dev)
 {
-    std::vector<long long> off(K);
-    size_t total = 0;
-    for (int k = 0; k < K; ++k) { off[k] = (long long)total; total += (size_t)p * N[k]; }
-    // the data go up once, into one arena of sum_k p N_k doubles (instance k packed at off[k], row length N_k)
-    DevArr<double> dX, dMean, dSd;
-    DevArr<long long> dOff;
-    DevArr<int> dN, dErr;
-    HIPCHK(dX.alloc(total));
-    HIPCHK(dOff.alloc(K));
-    HIPCHK(dN.alloc(K));
-    HIPCHK(hipMemcpyAsync(dOff.p, off.data(), K * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dN.p, N, K * sizeof(int), hipMemcpyHostToDevice, st));
-    for (int k = 0; k < K; ++k)
-        HIPCHK(hipMemcpyAsync(dX.p + off[k], X_host[k], (size_t)p * N[k] * sizeof(double), hipMemcpyHostToDevice, st));
+    DevArr<double> dMean, dSd;
+    DevArr<int> dErr;
     const bool center = (flags & GGL_COV_CENTER) != 0;
     if (center) {
         HIPCHK(dMean.alloc((size_t)K * p));
-        launch_row_means(st, dX.p, dOff.p, dN.p, 0, dMean.p, K, p);
+        launch_row_means(st, X_dev, off_dev, N_dev, 0, dMean.p, K, p);
         HIPCHK(hipGetLastError());
     }
     const int tile = (flags & GGL_COV_TILE64) ? 64 : ((flags & GGL_COV_TILE32) ? 32 : 0);
-    launch_gram_nt(st, dX.p, dOff.p, dN.p, 0, center ? dMean.p : nullptr, S_dev, K, p, tile);
+    launch_gram_nt(st, X_dev, off_dev, N_dev, 0, center ? dMean.p : nullptr, S_dev, K, p, tile);
     HIPCHK(hipGetLastError());
     if (flags & GGL_COV_SCALE) {
         HIPCHK(dSd.alloc((size_t)K * p));
@@ -77,8 +67,29 @@ int covariance_to_device(hipStream_t st, int K, int p, const int* N, const doubl
         int rc = diag_error(st, dErr.p, p, nullptr, S_dev, "the variance");
         if (rc) return rc;
     }
-    HIPCHK(hipStreamSynchronize(st));      // the arena is freed on return
+    HIPCHK(hipStreamSynchronize(st));
     return GGL_OK;
+}
+
+// ... from the host data
+int covariance_to_device(hipStream_t st, int K, int p, const int* N, const double* const* X_host, int flags, double* S_dev,
+                         double* var_dev)
+{
+    std::vector<long long> off(K);
+    size_t total = 0;
+    for (int k = 0; k < K; ++k) { off[k] = (long long)total; total += (size_t)p * N[k]; }
+    // the data go up once, into one arena of sum_k p N_k doubles (instance k packed at off[k], row length N_k)
+    DevArr<double> dX;
+    DevArr<long long> dOff;
+    DevArr<int> dN;
+    HIPCHK(dX.alloc(total));
+    HIPCHK(dOff.alloc(K));
+    HIPCHK(dN.alloc(K));
+    HIPCHK(hipMemcpyAsync(dOff.p, off.data(), K * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dN.p, N, K * sizeof(int), hipMemcpyHostToDevice, st));
+    for (int k = 0; k < K; ++k)
+        HIPCHK(hipMemcpyAsync(dX.p + off[k], X_host[k], (size_t)p * N[k] * sizeof(double), hipMemcpyHostToDevice, st));
+    return covariance_of_arena(st, K, p, dX.p, dOff.p, dN.p, flags, S_dev, var_dev);      // (the arena is freed on return)
 }
 }  // namespace
 
@@ -172,5 +183,124 @@ extern "C" int ggl_get_S(ggl_ctx* c, double* S_out, double* scale_out)
     int rc = download_stacks(c, {{S_out, c->S, c->n * sizeof(double)}});
     if (rc) return rc;
     if (scale_out) std::memcpy(scale_out, c->cov_scale.data(), c->cov_scale.size() * sizeof(double));
+    return GGL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// covariances of B column subsets of one X (the subsamples of StARS stability selection): X goes up once, the columns
+// are gathered on the device (k_gather_cols, stars.hip) into the arena the kernels above read as a K = B call
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+int check_subset_args(int p, int N, const double* X_host, int B, int b, const int* idx, int flags)
+{
+    ARGCHK(p >= 1 && N >= 1, "p >= 1, N >= 1");
+    ARGCHK(X_host && idx, "X, idx");
+    ARGCHK((flags & ~COV_FLAGS) == 0, "flags: unknown bits (GGL_COV_CENTER | GGL_COV_SCALE | GGL_COV_TILE32 | GGL_COV_TILE64)");
+    ARGCHK(!((flags & GGL_COV_TILE32) && (flags & GGL_COV_TILE64)), "flags: GGL_COV_TILE32 and GGL_COV_TILE64 exclude each other");
+    if (B < 1 || B > 65535) return fail(GGL_E_ARG, "bad argument: B = %d subsets, 1 .. 65535 are possible", B);
+    if (b < 1) return fail(GGL_E_ARG, "bad argument: b = %d, every subset needs at least one sample", b);
+    ARGCHK((size_t)B * p < (size_t)GGL_DIAG_OK, "B * p too large");
+    for (int r = 0; r < B; ++r)
+        for (int q = 0; q < b; ++q) {
+            const int n = idx[(size_t)r * b + q];
+            if (n < 0 || n >= N)
+                return fail(GGL_E_ARG, "bad argument: subset %d, position %d holds the index %d, outside [0, %d)", r, q, n, N);
+        }
+    return GGL_OK;
+}
+
+// S_dev (B,p,p) and var_dev (B,p) of the subsets on stream st; the arguments have been checked
+int subsets_to_device(hipStream_t st, int p, int N, const double* X_host, int B, int b, const int* idx, int flags,
+                      double* S_dev, double* var_dev)
+{
+    std::vector<long long> off(B);
+    std::vector<int> Nb(B, b);
+    for (int r = 0; r < B; ++r) off[r] = (long long)r * p * b;
+    DevArr<double> dX, dA;
+    DevArr<long long> dOff;
+    DevArr<int> dN, dIdx;
+    HIPCHK(dX.alloc((size_t)p * N));
+    HIPCHK(dA.alloc((size_t)B * p * b));
+    HIPCHK(dOff.alloc(B));
+    HIPCHK(dN.alloc(B));
+    HIPCHK(dIdx.alloc((size_t)B * b));
+    HIPCHK(hipMemcpyAsync(dX.p, X_host, (size_t)p * N * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dIdx.p, idx, (size_t)B * b * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dOff.p, off.data(), B * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dN.p, Nb.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
+    launch_gather_cols(st, dX.p, dIdx.p, dA.p, p, N, B, b);
+    HIPCHK(hipGetLastError());
+    // (waits for the stream before it returns: the host tables and the arenas go away behind it)
+    return covariance_of_arena(st, B, p, dA.p, dOff.p, dN.p, flags, S_dev, var_dev);
+}
+}  // namespace
+
+extern "C" int ggl_covariance_subsets(int device, int p, int N, const double* X_host, int B, int b, const int* idx, int flags,
+                                      double* S_out, double* scale_out)
+{
+    int rc = check_subset_args(p, N, X_host, B, b, idx, flags);
+    if (rc) return rc;
+    ARGCHK(S_out, "S_out");
+    ARGCHK(!(flags & GGL_COV_SCALE) || scale_out, "GGL_COV_SCALE needs scale_out");
+    HIPCHK(hipSetDevice(device));
+    const size_t n = (size_t)B * p * p;
+    DevBuf dS, dVar;
+    HIPCHK(dS.alloc(n));
+    HIPCHK(dVar.alloc((size_t)B * p));
+    rc = subsets_to_device(nullptr, p, N, X_host, B, b, idx, flags, dS.p, dVar.p);
+    if (rc) return rc;
+    DOWN(S_out, dS.p, n);
+    if (flags & GGL_COV_SCALE) DOWN(scale_out, dVar.p, (size_t)B * p);
+    return GGL_OK;
+}
+
+extern "C" int ggl_set_S_from_subsets(ggl_ctx* c, const double* X_host, int N, int B, int b, const int* idx, int flags)
+{
+    ARGCHK(c, "ctx");
+    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) takes its S from ggl_set_S");
+    int rc = check_subset_args(c->p, N, X_host, B, b, idx, flags);
+    if (rc) return rc;
+    if (c->K % B != 0) return fail(GGL_E_ARG, "bad argument: B = %d subsets do not divide the K = %d instances of the ctx", B, c->K);
+    HIPCHK(hipSetDevice(c->device));
+    DROP_PRE(c);
+    // The B matrices are built beside the ctx's S, which is overwritten only once they are complete: a call that is refused
+    // (here or by the variance check of GGL_COV_SCALE) leaves S, and what was built for it, as it was.
+    const size_t pp = (size_t)c->p * c->p, bp = (size_t)B * c->p;
+    DevBuf dS, dVar;
+    HIPCHK(dS.alloc((size_t)B * pp));
+    HIPCHK(dVar.alloc(bp));
+    rc = subsets_to_device(c->stream, c->p, N, X_host, B, b, idx, flags, dS.p, dVar.p);
+    if (rc) return rc;
+    std::vector<double> var;
+    if (flags & GGL_COV_SCALE) {
+        var.resize(bp);
+        HIPCHK(hipMemcpyAsync(var.data(), dVar.p, bp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    c->spec_have = false;
+    c->cw_have = false;
+    c->cwL_have = false;
+    c->wf_ready = false;
+    c->S_symmetric = false;
+    c->cov_scale.clear();
+    // instance k = subset k % B (the layout of ggl_set_S_ex with period B), replicated device to device
+    HIPCHK(hipMemcpyAsync(c->S, dS.p, (size_t)B * pp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    for (size_t have = (size_t)B; have < (size_t)c->K; have *= 2) {
+        const size_t take = std::min(have, (size_t)c->K - have);
+        HIPCHK(hipMemcpyAsync(c->S + have * pp, c->S, take * pp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    }
+    if (flags & GGL_COV_SCALE) {
+        c->cov_scale.resize((size_t)c->K * c->p);
+        for (int k = 0; k < c->K; ++k)
+            std::memcpy(c->cov_scale.data() + (size_t)k * c->p, var.data() + (size_t)(k % B) * c->p, c->p * sizeof(double));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));      // (dS is freed on return)
+    // as ggl_set_S: exact symmetry of S decides whether a Theta kernel may form the next W per element
+    launch_asym_max(c->stream, c->S, c->K, c->p, c->norms);
+    HIPCHK(hipGetLastError());
+    double asym = 1.0;
+    rc = host_reduce(c, c->K, 1, &asym, true);
+    if (rc) return rc;
+    c->S_symmetric = (asym == 0.0);
     return GGL_OK;
 }

@@ -9,12 +9,13 @@
 //   capi_lstep.hip      the L-step (sign iteration, deflation, continuation) and ggl_finalize_L
 //   capi_batch.hip      batches of independent problems: steps, the loop in C, isolation, compaction
 //   capi_snapshots.hip  per-instance snapshots of finished points
-//   capi_checks.hip     exit checks, objective, KKT, selection statistics, thresholds, rank
+//   capi_checks.hip     exit checks, objective, KKT, selection statistics, thresholds, rank, edge stability (StARS)
 //   capi_stats.hip      counters, profiling, event timeline
 //   capi_comm.hip       RCCL behind the C ABI (K-sharded step)
 //   capi_ext.hip        ext_ADMM_MGL (instances of different dimension)
 //   capi_ops.hip        stateless operator entry points, development probes
-//   capi_data.hip       sample covariance from data, scaling by a diagonal (stateless and into a ctx's S)
+//   capi_data.hip       sample covariance from data and from column subsets of one data array, scaling by a diagonal
+//                       (stateless and into a ctx's S)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>

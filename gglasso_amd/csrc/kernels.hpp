@@ -518,4 +518,12 @@ static constexpr int GGL_DIAG_OK = 0x7f7f7f7f;
 void launch_scale_by_diag(hipStream_t st, const double* X, const double* d, double* Y, double* d_out, double* sd, int* err,
                           int K, int p);
 
+// StARS stability selection (stars.hip).  arena[r,i,c] = X[i, idx[r,c]]: X (p,N) row-major, idx (B,b) with every entry in
+// [0,N) (the caller checked), arena the packed stack of B (p,b) instances the covariance kernels above read
+void launch_gather_cols(hipStream_t st, const double* X, const int* idx, double* arena, int p, int N, int B, int b);
+// T (L*B,p,p), instance l * B + r: counts (L,p,p) int32 (may be null) = #{r : |T[l*B+r,i,j]| >= t} for i < j, mirrored, zero
+// diagonal; num[l] (zeroed by the caller) += sum_{i<j} c (B - c)
+void launch_edge_stability(hipStream_t st, const double* T, int L, int B, int p, double t, int* counts,
+                           unsigned long long* num);
+
 }  // namespace ggl

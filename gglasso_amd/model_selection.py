@@ -627,3 +627,161 @@ def grid_search(solver, S, N, p, reg, l1, l2=None, w2=None, method='eBIC', gamma
         stats['NO_THRESHOLDING_SOL'] = no_thr_best
         stats['NO_THRESHOLDING_BEST'] = no_thr_params
     return stats, ix, curr_best
+
+
+# -----------------------------------------------------------------------------------------------------------------
+# StARS: stability selection of lambda1 from data (Liu, Roeder, Wasserman 2010, "Stability Approach to Regularization
+# Selection"; the default of R's huge).  B subsamples x L lambdas are B * L independent single problems of one dimension:
+# ONE batch (``ADMM_SGL_batch``'s machinery), instance l * B + r = subsample r at lambda l.  The data go to the device
+# once, the B subset covariances are computed and replicated there, and what comes back is one integer per lambda.
+# -----------------------------------------------------------------------------------------------------------------
+def stars_subsamples(N, n_subsamples, subsample_size=None, seed=0):
+    """The (n_subsamples, b) int32 array of sorted draws without replacement from range(N): row r comes from
+    ``numpy.random.default_rng([seed, r])``.  Default b: ``int(10 sqrt(N))`` for N > 144, else ``int(0.8 N)`` (the rule of
+    huge), at least 1."""
+    N, B = int(N), int(n_subsamples)
+    assert N >= 1 and B >= 1, "N and n_subsamples must be at least 1"
+    if subsample_size is None:
+        subsample_size = int(10 * np.sqrt(N)) if N > 144 else int(0.8 * N)
+    b = max(1, int(subsample_size))
+    assert b <= N, f"a subsample of {b} out of {N} observations cannot be drawn without replacement"
+    return np.stack([np.sort(np.random.default_rng([int(seed), r]).choice(N, b, replace=False))
+                     for r in range(B)]).astype(np.int32)
+
+
+def stars_select(D, beta):
+    """StARS' choice on the instabilities ``D`` of a grid in descending order (sparse to dense): ``(index, Dbar)`` with
+    ``Dbar`` the running maximum of D and ``index`` the largest one with ``Dbar <= beta`` -- the densest graph that is still
+    stable.  A NaN in D (a lambda with a failed point) is never chosen and does not enter the running maximum.  If no
+    lambda qualifies: index 0 and a RuntimeWarning."""
+    import warnings
+    D = np.asarray(D, dtype=np.float64).reshape(-1)
+    assert D.size >= 1
+    Dbar = np.fmax.accumulate(D)
+    ok = np.flatnonzero(~np.isnan(D) & (Dbar <= beta))
+    if ok.size == 0:
+        warnings.warn(f"StARS: no lambda1 of the grid has an instability of at most beta = {beta} (the smallest is "
+                      f"{np.nanmin(D) if not np.all(np.isnan(D)) else np.nan}); the sparsest point of the grid is returned. "
+                      f"Extend the grid to larger lambda1.", RuntimeWarning, stacklevel=2)
+        return 0, Dbar
+    return int(ok[-1]), Dbar
+
+
+def _host_subset_covariances(X, idx, center, scale):
+    """numpy counterpart of ``utils.sample_covariance_subsets`` for engines without the device route."""
+    out = []
+    for r in range(idx.shape[0]):
+        Xr = X[:, idx[r]]
+        S = np.atleast_2d(np.cov(Xr, bias=True)) if center else Xr @ Xr.T / Xr.shape[1]
+        if scale:
+            sd = np.sqrt(np.diag(S))
+            S = S / (sd[:, None] * sd[None, :])
+        out.append(S)
+    return np.stack(out)
+
+
+def _host_edge_counts(Theta, t):
+    """(L,p,p) int32 counts and (L,) int64 sums of StARS from a (L,B,p,p) stack: numpy counterpart of
+    ``HipEngine.edge_stability`` (only the upper triangle of a Theta is read, a NaN is no edge)."""
+    L, B, p, _ = Theta.shape
+    with np.errstate(invalid='ignore'):
+        up = np.triu(np.abs(Theta) >= t, 1).sum(axis=1).astype(np.int64)
+    num = (up * (B - up)).sum(axis=(1, 2))
+    return (up + up.transpose(0, 2, 1)).astype(np.int32), num.astype(np.int64)
+
+
+def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.05, seed=0, indices=None, t=1e-8, center=True,
+                 scale=False, tol=1e-7, rtol=1e-7, max_iter=1000, store_all=False, lambdas_per_batch=None):
+    """StARS for the Single Graphical Lasso from observations ``X`` (p,N), variables in rows.  Returns ``(sol, stats)``.
+
+    * Subsamples: ``stars_subsamples(N, n_subsamples, subsample_size, seed)``, or ``indices`` (B,b) given by the caller
+      (duplicates allowed: a bootstrap draw).  The grid is used in descending order, ``stats['LAMBDA']``.
+    * ``S_r`` = ``numpy.cov(X[:, indices[r]], bias=True)`` (``scale``: each subsample's correlations); ``Theta[l,r]`` solves
+      ``ADMM_SGL(S_r, lambda[l])`` from ``Omega_0 = X_0 = identity``; all B * L points run as one batch.
+    * ``c[l,i,j]`` = #{r : |Theta[l,r,i,j]| >= t} for i < j; ``NUM[l] = sum_{i<j} c (B - c)`` (exact integers);
+      ``INSTABILITY[l] = 2 NUM[l] / (B^2 p (p - 1) / 2)``; ``INSTABILITY_MONOTONE`` its running maximum along the grid;
+      ``IX`` the largest index whose running maximum is at most ``beta`` (``stars_select``).
+    * A lambda with a point that ended as 'solver error' gets NaN, is never chosen and is listed in ``FAILED``.
+    * ``sol``: ``ADMM_SGL`` on the covariance of all N observations at the chosen lambda1 (``stats['BEST']``).
+
+    With the device engine the data are uploaded once, the covariances never exist on the host and only the L integers come
+    back; ``store_all`` also returns ``COUNTS`` (L,p,p) and ``THETA`` (L,B,p,p).  ``lambdas_per_batch``: run that many
+    lambdas per batch (each its own ctx) where the whole grid does not fit in device memory.  An engine without
+    ``set_data_subsets`` / ``edge_stability`` takes the same batch call on numpy covariances and counts on the host."""
+    import warnings
+    from . import solver as _solver, utils
+    from .batch import _sgl_batch_impl
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    assert X.ndim == 2, f"data must be a (p,N) array with variables in rows, has shape {X.shape}"
+    p, N = X.shape
+    lam = np.sort(np.atleast_1d(np.asarray(lambda_range, dtype=np.float64)).reshape(-1))[::-1].copy()
+    assert lam.size >= 1 and np.all(lam > 0), "lambda1 should be positive"
+    assert t >= 0 and np.isfinite(t), "the edge threshold t must be finite and not negative"
+    if indices is None:
+        idx = stars_subsamples(N, n_subsamples, subsample_size, seed)
+    else:
+        idx = utils._subset_indices(indices)
+        assert idx.shape[0] >= 1 and idx.shape[1] >= 1, "indices must hold at least one subsample of at least one observation"
+        # (the library checks the range on the device route; the host route indexes numpy arrays, which would wrap)
+        assert idx.min() >= 0 and idx.max() < N, f"indices must lie in [0, {N})"
+    B, b = idx.shape
+    L = lam.size
+    per = L if lambdas_per_batch is None else max(1, int(lambdas_per_batch))
+    on_device = hasattr(_solver.ENGINE, "set_data_subsets") and hasattr(_solver.ENGINE, "edge_stability")
+    eye = np.eye(p)
+    NUM = np.zeros(L, dtype=np.int64)
+    failed = np.zeros(L, dtype=bool)
+    COUNTS = np.zeros((L, p, p), dtype=np.int32) if store_all else None
+    THETA = np.zeros((L, B, p, p)) if store_all else None
+    S_host = None if on_device else _host_subset_covariances(X, idx, center, scale)
+    for l0 in range(0, L, per):
+        sl = slice(l0, min(L, l0 + per))
+        nl = sl.stop - sl.start
+        lam_k = np.repeat(lam[sl], B)                                   # instance (l - l0) * B + r
+        got = {}
+
+        def before(eng):
+            eng.set_data_subsets(X, idx, center=center, scale=scale)
+
+        def after(eng, results):
+            got['edges'] = eng.edge_stability(B, t, counts=store_all)
+
+        if on_device:
+            # the S argument only shapes the ctx: ONE (p,p) matrix, which the batch hands to the engine as a broadcast view
+            # (uploaded once, replicated on the device); `before` then writes the real S there
+            res = _sgl_batch_impl(eye, lam_k, eye, None, eye, 1., max_iter, tol, rtol, True,
+                                  False, False, None, None, False, None, None, True, ('Theta',) if store_all else (), None,
+                                  None, _on_device=(before, after))
+            if store_all:
+                NUM[sl], COUNTS[sl] = got['edges']
+            else:
+                NUM[sl] = got['edges']
+        else:
+            res = _sgl_batch_impl(np.tile(S_host, (nl, 1, 1)), lam_k, eye, None, eye, 1., max_iter, tol, rtol, True, False,
+                                  False, None, None, False, None, None, True, None, None, None)
+            Th = np.stack([sol['Theta'] for sol, _ in res]).reshape(nl, B, p, p)
+            cnt, NUM[sl] = _host_edge_counts(Th, t)
+            if store_all:
+                COUNTS[sl] = cnt
+        if store_all:
+            THETA[sl] = np.stack([sol['Theta'] for sol, _ in res]).reshape(nl, B, p, p)
+        failed[sl] = np.array([info['status'] == 'solver error' for _, info in res]).reshape(nl, B).any(axis=1)
+    pairs = p * (p - 1) // 2
+    D = np.array([2 * int(n) / (B * B * pairs) for n in NUM]) if pairs else np.zeros(L)
+    D[failed] = np.nan
+    if failed.any():
+        warnings.warn(f"StARS: a subsample failed at lambda1 = {[float(v) for v in lam[failed]]}; these grid points have no instability "
+                      f"and are not chosen", RuntimeWarning, stacklevel=2)
+    ix, Dbar = stars_select(D, beta)
+    if on_device:
+        S_full = utils.sample_covariance(X, center=center, scale=scale)
+        S_full = S_full[0] if scale else S_full
+    else:
+        S_full = _host_subset_covariances(X, np.arange(N)[None], center, scale)[0]
+    sol, _ = _solver.ADMM_SGL(S_full, lam[ix], eye, X_0=eye, tol=tol, rtol=rtol, max_iter=max_iter, verbose=False)
+    stats = {'LAMBDA': lam, 'INSTABILITY': D, 'INSTABILITY_MONOTONE': Dbar, 'NUM': [int(n) for n in NUM], 'IX': ix,
+             'BEST': {'lambda1': lam[ix]}, 'INDICES': idx, 'subsample_size': b, 'n_subsamples': B,
+             'FAILED': [int(l) for l in np.flatnonzero(failed)]}
+    if store_all:
+        stats['COUNTS'], stats['THETA'] = COUNTS, THETA
+    return sol, stats

@@ -153,7 +153,9 @@ class glasso_problem:
             S = np.stack([S[k] for k in range(len(S))])       # a list of instances of ONE dimension is a conforming stack
         if isinstance(S, np.ndarray) and S.ndim == 2:
             N = int(N[0])
-        return cls(S, N, reg=reg, reg_params=reg_params, latent=latent, G=G, do_scaling=do_scaling)
+        prob = cls(S, N, reg=reg, reg_params=reg_params, latent=latent, G=G, do_scaling=do_scaling)
+        prob._observations, prob._center = Xs, center       # kept for resampling (stability_selection)
+        return prob
 
     def __repr__(self):
         name = {None: "SINGLE", "GGL": "GROUP", "FGL": "FUSED"}[self.reg]
@@ -275,6 +277,27 @@ class glasso_problem:
         criterion = dict(method=method, gamma=gamma, tol=tol, rtol=rtol)
         select = self._select_multiple if self.multiple else self._select_single
         sol, stats = select(criterion, store_all)
+        self._keep(sol)
+        self.modelselect_stats = dict(stats)
+
+    def stability_selection(self, modelselect_params=None, n_subsamples=20, subsample_size=None, beta=0.05, seed=0, tol=1e-7,
+                            rtol=1e-7, store_all=False):
+        """Pick ``lambda1`` of a Single Graphical Lasso problem built by ``from_data`` by StARS (stability across
+        subsamples of the observations, ``model_selection.stars_search``) over ``modelselect_params['lambda1_range']``.
+        ``self.reg_params['lambda1']`` is set to the choice, the estimate on all observations goes to ``self.solution`` and
+        the instabilities to ``self.modelselect_stats``.  With ``do_scaling`` every subsample is scaled to its own
+        correlations and the solution goes back to the covariances' scale, as in ``solve``."""
+        assert getattr(self, '_observations', None) is not None, \
+            "Stability selection resamples the observations: build the problem with glasso_problem.from_data(X)."
+        assert not self.multiple, "Stability selection is implemented for Single Graphical Lasso problems only."
+        assert not self.latent, "Stability selection is not implemented for problems with latent variables."
+        self.set_modelselect_params(modelselect_params)
+        assert self.modelselect_params.get('lambda1_mask') is None and self.reg_params.get('lambda1_mask') is None, \
+            "Stability selection is not implemented with a lambda1_mask."
+        sol, stats = _ms.stars_search(self._observations[0], self.modelselect_params['lambda1_range'],
+                                      n_subsamples=n_subsamples, subsample_size=subsample_size, beta=beta, seed=seed,
+                                      center=self._center, scale=bool(self.do_scaling), tol=tol, rtol=rtol, store_all=store_all)
+        self.set_reg_params(stats['BEST'])
         self._keep(sol)
         self.modelselect_stats = dict(stats)
 

@@ -123,6 +123,31 @@ class HipEngine:
                                            flags))
         self._S_scaled = bool(scale)
 
+    def set_data_subsets(self, X, indices, center=True, scale=False):
+        """The ctx's S from column subsets of ONE data array, computed on the device (``ggl_set_S_from_subsets``): X (p,N),
+        variables in rows, ``indices`` (B,b) ints with B a divisor of K; instance k gets ``cov(X[:, indices[k % B]])``.
+        A refused call (an index outside [0,N), say) leaves S as it was."""
+        from .utils import _subset_indices
+        X = as_c(X)
+        assert X.ndim == 2 and X.shape[0] == self.p, f"data must be a ({self.p}, N) array"
+        idx = _subset_indices(indices)
+        flags = (_lib.COV_CENTER if center else 0) | (_lib.COV_SCALE if scale else 0)
+        check(self.lib.ggl_set_S_from_subsets(self.h, ptr(X), X.shape[1], idx.shape[0], idx.shape[1],
+                                              idx.ctypes.data_as(_lib._ip), flags))
+        self._S_scaled = bool(scale)
+
+    def edge_stability(self, B, t=1e-8, counts=False):
+        """StARS over the Theta snapshots of a batch of K = L * B points (instance l * B + r: subsample r at lambda l):
+        the (L,) int64 array ``sum_{i<j} c (B - c)`` of the selection counts ``c[l,i,j] = #{r : |Theta| >= t}``, exact; with
+        ``counts`` also the (L,p,p) int32 tables of c (mirrored, zero diagonal)."""
+        import ctypes
+        L = self.K // int(B) if int(B) >= 1 and self.K % int(B) == 0 else 1        # (otherwise the library refuses the call)
+        num = np.zeros(L, dtype=np.int64)
+        tab = np.empty((L, self.p, self.p), dtype=np.int32) if counts else None
+        check(self.lib.ggl_edge_stability(self.h, int(B), float(t), None if tab is None else tab.ctypes.data_as(_lib._ip),
+                                          num.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        return (num, tab) if counts else num
+
     def get_S(self):
         """S (K,p,p) as it lies on the device; after ``set_data(..., scale=True)`` the pair (S, variances (K,p))."""
         S = np.empty((self.K, self.p, self.p))

@@ -84,3 +84,37 @@ def sample_covariance(X, center=True, scale=False, device=0):
         S = {k: np.array(S[k]) for k in range(len(Xs))}
         var = {k: np.array(var[k]) for k in range(len(Xs))} if scale else None
     return (S, var) if scale else S
+
+
+def _subset_indices(indices):
+    """The (B, b) int32 array of column indices of ``sample_covariance_subsets`` (the library checks B, b and the range)."""
+    idx = np.asarray(indices)
+    assert idx.ndim == 2 and np.issubdtype(idx.dtype, np.integer), \
+        f"indices must be a (B, b) integer array, is {idx.dtype} of shape {idx.shape}"
+    assert idx.size == 0 or (idx.min() >= -2 ** 31 and idx.max() < 2 ** 31), "indices do not fit 32 bits"
+    return np.ascontiguousarray(idx, dtype=np.int32)
+
+
+def _covariance_subsets_call(X, idx, flags, device=0):
+    """One ``ggl_covariance_subsets`` call: X C-contiguous float64 (p, N), idx C-contiguous int32 (B, b).  Returns
+    (S (B,p,p), variances (B,p) or None)."""
+    (p, N), (B, b) = X.shape, idx.shape
+    S = np.empty((B, p, p))
+    var = np.empty((B, p)) if flags & _lib.COV_SCALE else None
+    _lib.require_gpu()
+    check(_lib.load().ggl_covariance_subsets(int(device), p, N, ptr(X), B, b, idx.ctypes.data_as(_lib._ip), int(flags), ptr(S),
+                                             ptr(var)))
+    return S, var
+
+
+def sample_covariance_subsets(X, indices, center=True, scale=False, device=0):
+    """``numpy.cov(X[:, indices[r]], bias=True)`` for every row r of ``indices`` (B, b) on the device: X (p, N), variables in
+    rows, goes up once and the columns are gathered there -- the subsamples of ``model_selection.stars_search``.  Duplicate
+    indices are allowed (a bootstrap draw).  Returns S (B,p,p), bitwise what ``sample_covariance`` gives for the B gathered
+    arrays as one (B,p,b) stack; ``scale=True``: each subset's own correlations, and as a second value the variances (B,p)."""
+    X = as_c(X)
+    assert X.ndim == 2 and X.shape[0] >= 1 and X.shape[1] >= 1, \
+        f"data must be a (p,N) array with variables in rows, has shape {X.shape}"
+    flags = (_lib.COV_CENTER if center else 0) | (_lib.COV_SCALE if scale else 0)
+    S, var = _covariance_subsets_call(X, _subset_indices(indices), flags, device)
+    return (S, var) if scale else S

@@ -27,7 +27,7 @@ extern "C" {
  * takes a byte pattern.  A binding built against another major version must refuse to load (gglasso_amd/_lib.py does).
  * Entry points and selector values that are only ADDED (GGL_REG_FSGL, ggl_set_block_size, ggl_prox_sum_frob,
  * ggl_frob_norm_per_block, ggl_fsgl_stats, ggl_covariance, ggl_scale_by_diagonal, ggl_set_S_from_data, ggl_get_S, ggl_kkt_terms,
- * ggl_diag_stats) leave every existing layout alone and the number where it is. */
+ * ggl_diag_stats, ggl_covariance_subsets, ggl_set_S_from_subsets, ggl_edge_stability) leave every existing layout alone and the number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -740,6 +740,26 @@ int ggl_scale_by_diagonal(int device, int K, int p, const double *X_host, const 
 int ggl_set_S_from_data(ggl_ctx *ctx, const double *const *X_host, const int *N, int flags);
 /* S_out (K,p,p); scale_out (K,p): the variances, NULL unless the ctx's S came from data with GGL_COV_SCALE */
 int ggl_get_S(ggl_ctx *ctx, double *S_out, double *scale_out);
+
+/* ---- StARS stability selection from data (Liu, Roeder, Wasserman 2010): both ends of a batch of B subsamples x L lambdas
+ * on the device (stars.hip).  Entry points that are only ADDED: GGL_VERSION stays where it is.
+ *
+ * Covariances of B column subsets of ONE data array: X_host the row-major (p,N) array, variables in rows, idx the (B,b)
+ * int array of sample indices in [0,N) (duplicates allowed: a bootstrap draw; any order).  X goes up once, the columns are
+ * gathered on the device, and subset r's matrix is bitwise what the covariance call above returns for the gathered (p,b) array
+ * in a call of K = B instances.  S_out (B,p,p), scale_out (B,p) or NULL, flags as above.  GGL_E_ARG, found before any device
+ * work: an index outside [0,N) (the message names subset and position), b < 1, B < 1. */
+int ggl_covariance_subsets(int device, int p, int N, const double *X_host, int B, int b, const int *idx, int flags,
+                           double *S_out, double *scale_out);
+/* ... straight into the S of a ctx whose K is a multiple of B: instance k gets subset k % B (the layout of the S upload
+ * with period B), replicated on the device.  Bookkeeping as the data call above (what earlier iterations carried is forgotten,
+ * the variances are kept with GGL_COV_SCALE); a refused call leaves the ctx's S as it was. */
+int ggl_set_S_from_subsets(ggl_ctx *ctx, const double *X_host, int N, int B, int b, const int *idx, int flags);
+/* Edge stability over the Theta snapshots of a ctx with K = L * B instances, instance l * B + r = subsample r at lambda l:
+ * c[l,i,j] = #{ r : |Theta[l*B+r,i,j]| >= t } for i < j (a NaN is no edge; only the upper triangle of a Theta is read),
+ * num_out[l] = sum_{i<j} c (B - c), an exact integer (L values); counts_out (L,p,p) int32 or NULL: c mirrored, zero diagonal.
+ * Integer sums: two calls return the same bits.  GGL_E_ARG: B < 1 or not dividing K, t negative or not finite, no snapshot. */
+int ggl_edge_stability(ggl_ctx *ctx, int B, double t, int *counts_out, long long *num_out);
 
 #ifdef __cplusplus
 }
