@@ -233,6 +233,39 @@ int subsets_to_device(hipStream_t st, int p, int N, const double* X_host, int B,
     // (waits for the stream before it returns: the host tables and the arenas go away behind it)
     return covariance_of_arena(st, B, p, dA.p, dOff.p, dN.p, flags, S_dev, var_dev);
 }
+
+// The B complete matrices dS (B,p,p) become the S of the ctx, instance k = subset k % B (the layout of ggl_set_S_ex with period
+// B), replicated device to device; var: the (B,p) variances that go with them, or empty.  What earlier iterations carried is
+// forgotten, as in ggl_set_S.
+int install_subset_S(ggl_ctx* c, const double* dS, int B, const std::vector<double>& var)
+{
+    const size_t pp = (size_t)c->p * c->p;
+    c->spec_have = false;
+    c->cw_have = false;
+    c->cwL_have = false;
+    c->wf_ready = false;
+    c->S_symmetric = false;
+    c->cov_scale.clear();
+    HIPCHK(hipMemcpyAsync(c->S, dS, (size_t)B * pp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    for (size_t have = (size_t)B; have < (size_t)c->K; have *= 2) {
+        const size_t take = std::min(have, (size_t)c->K - have);
+        HIPCHK(hipMemcpyAsync(c->S + have * pp, c->S, take * pp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    }
+    if (!var.empty()) {
+        c->cov_scale.resize((size_t)c->K * c->p);
+        for (int k = 0; k < c->K; ++k)
+            std::memcpy(c->cov_scale.data() + (size_t)k * c->p, var.data() + (size_t)(k % B) * c->p, c->p * sizeof(double));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));      // (the caller frees dS on return)
+    // as ggl_set_S: exact symmetry of S decides whether a Theta kernel may form the next W per element
+    launch_asym_max(c->stream, c->S, c->K, c->p, c->norms);
+    HIPCHK(hipGetLastError());
+    double asym = 1.0;
+    int rc = host_reduce(c, c->K, 1, &asym, true);
+    if (rc) return rc;
+    c->S_symmetric = (asym == 0.0);
+    return GGL_OK;
+}
 }  // namespace
 
 extern "C" int ggl_covariance_subsets(int device, int p, int N, const double* X_host, int B, int b, const int* idx, int flags,
@@ -277,30 +310,123 @@ extern "C" int ggl_set_S_from_subsets(ggl_ctx* c, const double* X_host, int N, i
         HIPCHK(hipMemcpyAsync(var.data(), dVar.p, bp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
-    c->spec_have = false;
-    c->cw_have = false;
-    c->cwL_have = false;
-    c->wf_ready = false;
-    c->S_symmetric = false;
-    c->cov_scale.clear();
-    // instance k = subset k % B (the layout of ggl_set_S_ex with period B), replicated device to device
-    HIPCHK(hipMemcpyAsync(c->S, dS.p, (size_t)B * pp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    for (size_t have = (size_t)B; have < (size_t)c->K; have *= 2) {
-        const size_t take = std::min(have, (size_t)c->K - have);
-        HIPCHK(hipMemcpyAsync(c->S + have * pp, c->S, take * pp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    }
-    if (flags & GGL_COV_SCALE) {
-        c->cov_scale.resize((size_t)c->K * c->p);
-        for (int k = 0; k < c->K; ++k)
-            std::memcpy(c->cov_scale.data() + (size_t)k * c->p, var.data() + (size_t)(k % B) * c->p, c->p * sizeof(double));
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));      // (dS is freed on return)
-    // as ggl_set_S: exact symmetry of S decides whether a Theta kernel may form the next W per element
-    launch_asym_max(c->stream, c->S, c->K, c->p, c->norms);
-    HIPCHK(hipGetLastError());
-    double asym = 1.0;
-    rc = host_reduce(c, c->K, 1, &asym, true);
-    if (rc) return rc;
-    c->S_symmetric = (asym == 0.0);
+    return install_subset_S(c, dS.p, B, var);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Kendall's tau-b and the skeptic matrix sin(pi/2 tau) from dense ranks (kernels: kendall.hip): the ranks go up once, the
+// columns of the B subsets are gathered on the device, the counts G = Z Z^T are exact 64-bit integers
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+int check_kendall_args(int p, int N, const int* ranks_host, int B, int b, const int* idx)
+{
+    ARGCHK(p >= 1 && N >= 1, "p >= 1, N >= 1");
+    ARGCHK(ranks_host, "ranks");
+    if (B < 1 || B > 65535) return fail(GGL_E_ARG, "bad argument: B = %d subsets, 1 .. 65535 are possible", B);
+    if (!idx && (B != 1 || b != N))
+        return fail(GGL_E_ARG, "bad argument: idx = NULL takes all N = %d samples as one subset: B = 1, b = N (B = %d, b = %d)", N, B, b);
+    if (b < 2) return fail(GGL_E_ARG, "bad argument: b = %d, a subset needs at least two samples to form a pair", b);
+    ARGCHK((size_t)B * p < (size_t)GGL_DIAG_OK, "B * p too large");
+    ARGCHK(kendall_counts_fit(p, b, B), "p and b are beyond what one launch takes (p * b < 2^31, p <= 23104, b below about one million)");
+    if (idx)
+        for (int r = 0; r < B; ++r)
+            for (int q = 0; q < b; ++q) {
+                const int n = idx[(size_t)r * b + q];
+                if (n < 0 || n >= N)
+                    return fail(GGL_E_ARG, "bad argument: subset %d, position %d holds the index %d, outside [0, %d)", r, q, n, N);
+            }
+    // dense ranks lie in [0, N): their differences then fit 32 bits
+    for (size_t e = 0; e < (size_t)p * N; ++e)
+        if (ranks_host[e] < 0 || ranks_host[e] >= N)
+            return fail(GGL_E_ARG, "bad argument: variable %d, sample %d holds the rank %d, outside [0, %d)", (int)(e / N), (int)(e % N),
+                        ranks_host[e], N);
     return GGL_OK;
+}
+
+// G_dev (B,p,p) int64 on stream st, and with S_dev the skeptic matrices (B,p,p) -- GGL_E_ARG naming subset and variable where
+// a variable is constant over a subset, S_dev is not written then.  The arguments have been checked.  Waits for the stream.
+int kendall_to_device(hipStream_t st, int p, int N, const int* ranks_host, int B, int b, const int* idx, long long* G_dev,
+                      double* S_dev)
+{
+    DevArr<int> dR, dA, dIdx, dErr;
+    HIPCHK(dR.alloc((size_t)p * N));
+    HIPCHK(hipMemcpyAsync(dR.p, ranks_host, (size_t)p * N * sizeof(int), hipMemcpyHostToDevice, st));
+    const int* Rg = dR.p;
+    if (idx) {
+        HIPCHK(dA.alloc((size_t)B * p * b));
+        HIPCHK(dIdx.alloc((size_t)B * b));
+        HIPCHK(hipMemcpyAsync(dIdx.p, idx, (size_t)B * b * sizeof(int), hipMemcpyHostToDevice, st));
+        launch_gather_ranks(st, dR.p, dIdx.p, dA.p, p, N, B, b);
+        HIPCHK(hipGetLastError());
+        Rg = dA.p;
+    }
+    launch_kendall_counts(st, Rg, G_dev, B, p, b);
+    HIPCHK(hipGetLastError());
+    if (S_dev) {
+        HIPCHK(dErr.alloc(1));
+        HIPCHK(hipMemsetAsync(dErr.p, 0x7f, sizeof(int), st));
+        launch_kendall_skeptic(st, G_dev, S_dev, dErr.p, B, p);
+        HIPCHK(hipGetLastError());
+        int err = GGL_DIAG_OK;
+        HIPCHK(hipMemcpyAsync(&err, dErr.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (err != GGL_DIAG_OK)
+            return fail(GGL_E_ARG, "bad argument: variable %d is constant over subset %d (no untied pair of samples); the rank "
+                        "correlation needs every variable to vary", err % p, err / p);
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return GGL_OK;
+}
+
+int kendall_call(int device, int p, int N, const int* ranks_host, int B, int b, const int* idx, double* S_out, long long* G_out)
+{
+    HIPCHK(hipSetDevice(device));
+    const size_t n = (size_t)B * p * p;
+    DevArr<long long> dG;
+    DevBuf dS;
+    HIPCHK(dG.alloc(n));
+    if (S_out) HIPCHK(dS.alloc(n));
+    int rc = kendall_to_device(nullptr, p, N, ranks_host, B, b, idx, dG.p, S_out ? dS.p : nullptr);
+    if (rc) return rc;
+    if (G_out) HIPCHK(hipMemcpy(G_out, dG.p, n * sizeof(long long), hipMemcpyDeviceToHost));
+    if (S_out) DOWN(S_out, dS.p, n);
+    return GGL_OK;
+}
+}  // namespace
+
+extern "C" int ggl_kendall_counts(int device, int p, int N, const int* ranks_host, int B, int b, const int* idx, long long* G_out)
+{
+    int rc = check_kendall_args(p, N, ranks_host, B, b, idx);
+    if (rc) return rc;
+    ARGCHK(G_out, "G_out");
+    return kendall_call(device, p, N, ranks_host, B, b, idx, nullptr, G_out);
+}
+
+extern "C" int ggl_kendall_skeptic(int device, int p, int N, const int* ranks_host, int B, int b, const int* idx, double* S_out,
+                                   long long* G_out)
+{
+    int rc = check_kendall_args(p, N, ranks_host, B, b, idx);
+    if (rc) return rc;
+    ARGCHK(S_out, "S_out");
+    return kendall_call(device, p, N, ranks_host, B, b, idx, S_out, G_out);
+}
+
+extern "C" int ggl_set_S_from_kendall(ggl_ctx* c, const int* ranks_host, int N, int B, int b, const int* idx)
+{
+    ARGCHK(c, "ctx");
+    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) takes its S from ggl_set_S");
+    int rc = check_kendall_args(c->p, N, ranks_host, B, b, idx);
+    if (rc) return rc;
+    if (c->K % B != 0) return fail(GGL_E_ARG, "bad argument: B = %d subsets do not divide the K = %d instances of the ctx", B, c->K);
+    HIPCHK(hipSetDevice(c->device));
+    DROP_PRE(c);
+    // as ggl_set_S_from_subsets: the B matrices are built beside the ctx's S; a refused call (a constant variable) leaves S alone
+    const size_t n = (size_t)B * c->p * c->p;
+    DevArr<long long> dG;
+    DevBuf dS;
+    HIPCHK(dG.alloc(n));
+    HIPCHK(dS.alloc(n));
+    rc = kendall_to_device(c->stream, c->p, N, ranks_host, B, b, idx, dG.p, dS.p);
+    if (rc) return rc;
+    return install_subset_S(c, dS.p, B, {});
 }

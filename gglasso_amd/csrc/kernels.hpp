@@ -526,4 +526,15 @@ void launch_gather_cols(hipStream_t st, const double* X, const int* idx, double*
 void launch_edge_stability(hipStream_t st, const double* T, int L, int B, int p, double t, int* counts,
                            unsigned long long* num);
 
+// Kendall's tau-b and the skeptic matrix on the int8 matrix cores (kendall.hip).  out[r,i,c] = R[i, idx[r,c]]: R (p,N) int32
+// dense ranks, idx (B,b) with every entry in [0,N) (the caller checked)
+void launch_gather_ranks(hipStream_t st, const int* R, const int* idx, int* out, int p, int N, int B, int b);
+// Rg: B packed (p,n) rank arrays; G (B,p,p) int64 = sum over sample pairs a < b of sgn(Rg[r,i,a] - Rg[r,i,b]) sgn(Rg[r,j,a] -
+// Rg[r,j,b]), exact and symmetric (zeroed here).  kendall_counts_fit: the sizes the launch takes
+bool kendall_counts_fit(int p, int n, int B);
+void launch_kendall_counts(hipStream_t st, const int* Rg, long long* G, int B, int p, int n);
+// S[r,i,j] = sin(pi/2 G_ij / sqrt(G_ii G_jj)), diagonal 1; *err (set to GGL_DIAG_OK by the caller) = smallest r * p + i with
+// G[r,i,i] = 0 (a variable constant over the subset), then S is not written
+void launch_kendall_skeptic(hipStream_t st, const long long* G, double* S, int* err, int B, int p);
+
 }  // namespace ggl

@@ -691,7 +691,7 @@ def _host_edge_counts(Theta, t):
 
 
 def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.05, seed=0, indices=None, t=1e-8, center=True,
-                 scale=False, tol=1e-7, rtol=1e-7, max_iter=1000, store_all=False, lambdas_per_batch=None):
+                 scale=False, tol=1e-7, rtol=1e-7, max_iter=1000, store_all=False, lambdas_per_batch=None, correlation=None):
     """StARS for the Single Graphical Lasso from observations ``X`` (p,N), variables in rows.  Returns ``(sol, stats)``.
 
     * Subsamples: ``stars_subsamples(N, n_subsamples, subsample_size, seed)``, or ``indices`` (B,b) given by the caller
@@ -707,10 +707,19 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     With the device engine the data are uploaded once, the covariances never exist on the host and only the L integers come
     back; ``store_all`` also returns ``COUNTS`` (L,p,p) and ``THETA`` (L,B,p,p).  ``lambdas_per_batch``: run that many
     lambdas per batch (each its own ctx) where the whole grid does not fit in device memory.  An engine without
-    ``set_data_subsets`` / ``edge_stability`` takes the same batch call on numpy covariances and counts on the host."""
+    ``set_data_subsets`` / ``edge_stability`` takes the same batch call on numpy covariances and counts on the host.
+
+    ``correlation='kendall'``: every ``S_r``, and the matrix of the final fit, is the nonparanormal skeptic matrix
+    ``sin(pi/2 tau-b)`` of the observations (``utils.skeptic_correlation``; on the device ``ggl_set_S_from_kendall``) instead of
+    the Pearson covariance -- invariant under monotone transforms of the variables, robust to outliers and ties.  ``center`` and
+    ``scale`` have no meaning then and must be left at their defaults.  The matrix may be indefinite; it is used as it is."""
     import warnings
     from . import solver as _solver, utils
     from .batch import _sgl_batch_impl
+    assert correlation in (None, 'kendall'), "correlation must be None (Pearson) or 'kendall'"
+    kendall = correlation == 'kendall'
+    if kendall:
+        assert center is True and scale is False, "correlation='kendall' has no use for center / scale: leave them at their defaults"
     X = np.ascontiguousarray(X, dtype=np.float64)
     assert X.ndim == 2, f"data must be a (p,N) array with variables in rows, has shape {X.shape}"
     p, N = X.shape
@@ -727,13 +736,17 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     B, b = idx.shape
     L = lam.size
     per = L if lambdas_per_batch is None else max(1, int(lambdas_per_batch))
-    on_device = hasattr(_solver.ENGINE, "set_data_subsets") and hasattr(_solver.ENGINE, "edge_stability")
+    on_device = hasattr(_solver.ENGINE, "set_kendall_subsets" if kendall else "set_data_subsets") and \
+        hasattr(_solver.ENGINE, "edge_stability")
     eye = np.eye(p)
     NUM = np.zeros(L, dtype=np.int64)
     failed = np.zeros(L, dtype=bool)
     COUNTS = np.zeros((L, p, p), dtype=np.int32) if store_all else None
     THETA = np.zeros((L, B, p, p)) if store_all else None
-    S_host = None if on_device else _host_subset_covariances(X, idx, center, scale)
+    if on_device:
+        S_host = None
+    else:
+        S_host = utils.host_skeptic_correlation(X, idx) if kendall else _host_subset_covariances(X, idx, center, scale)
     for l0 in range(0, L, per):
         sl = slice(l0, min(L, l0 + per))
         nl = sl.stop - sl.start
@@ -741,7 +754,10 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
         got = {}
 
         def before(eng):
-            eng.set_data_subsets(X, idx, center=center, scale=scale)
+            if kendall:
+                eng.set_kendall_subsets(X, idx)
+            else:
+                eng.set_data_subsets(X, idx, center=center, scale=scale)
 
         def after(eng, results):
             got['edges'] = eng.edge_stability(B, t, counts=store_all)
@@ -773,7 +789,9 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
         warnings.warn(f"StARS: a subsample failed at lambda1 = {[float(v) for v in lam[failed]]}; these grid points have no instability "
                       f"and are not chosen", RuntimeWarning, stacklevel=2)
     ix, Dbar = stars_select(D, beta)
-    if on_device:
+    if kendall:
+        S_full = utils.skeptic_correlation(X) if on_device else utils.host_skeptic_correlation(X)
+    elif on_device:
         S_full = utils.sample_covariance(X, center=center, scale=scale)
         S_full = S_full[0] if scale else S_full
     else:

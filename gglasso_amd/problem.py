@@ -8,7 +8,8 @@ implementation is this package's own:
 * ``model_selection()`` calls this package's ``single_grid_search`` / ``K_single_grid`` / ``grid_search``, so a grid is
   solved as batches (``ADMM_SGL_batch`` / ``ADMM_MGL_batch`` / ``ext_ADMM_MGL_batch``) instead of a sequential walk.
 * ``do_scaling`` (covariances -> correlations, and Theta, L back) goes through the device kernel (``ggl_scale_by_diagonal``).
-* ``glasso_problem.from_data(X, ...)`` starts from observations: S comes from ``utils.sample_covariance``.
+* ``glasso_problem.from_data(X, ...)`` starts from observations: S comes from ``utils.sample_covariance``, or with
+  ``correlation='kendall'`` from ``utils.skeptic_correlation`` (rank based).
 """
 import numbers
 import warnings
@@ -143,19 +144,41 @@ class glasso_problem:
             self._to_correlations()
 
     @classmethod
-    def from_data(cls, X, *, reg="GGL", reg_params=None, latent=False, G=None, do_scaling=False, center=True):
+    def from_data(cls, X, *, reg="GGL", reg_params=None, latent=False, G=None, do_scaling=False, center=True, correlation=None):
         """The problem of observations ``X``: (p,N), (K,p,N) or a list / dict of (p_k,N_k) arrays, variables in rows.
-        ``N`` is read off the data and S is computed on the device (``utils.sample_covariance``)."""
+        ``N`` is read off the data and S is computed on the device (``utils.sample_covariance``).
+
+        ``correlation='kendall'``: S is every instance's nonparanormal skeptic matrix ``sin(pi/2 tau-b)``
+        (``utils.skeptic_correlation``: Kendall's tau-b on the int8 matrix cores) -- for data that are not Gaussian (counts,
+        skewed or heavy-tailed measurements, ties).  It is a correlation matrix (unit diagonal; ``center`` has no meaning and
+        must be left at its default) and it can be indefinite: the ADMM's log-det prox does not need a positive semidefinite
+        input, so the matrix is used as it is and no projection is applied."""
+        assert correlation in (None, 'kendall'), "correlation must be None (Pearson) or 'kendall'"
         _, Xs = utils._data_list(X)
         N = np.array([x.shape[1] for x in Xs])
-        S = utils.sample_covariance(X, center=center)
+        if correlation == 'kendall':
+            assert center is True, "correlation='kendall' has no use for center: leave it at its default"
+            S = cls._skeptic(X)
+        else:
+            S = utils.sample_covariance(X, center=center)
         if isinstance(S, dict) and G is None and len({s.shape[0] for s in S.values()}) == 1:
             S = np.stack([S[k] for k in range(len(S))])       # a list of instances of ONE dimension is a conforming stack
         if isinstance(S, np.ndarray) and S.ndim == 2:
             N = int(N[0])
         prob = cls(S, N, reg=reg, reg_params=reg_params, latent=latent, G=G, do_scaling=do_scaling)
         prob._observations, prob._center = Xs, center       # kept for resampling (stability_selection)
+        prob._correlation = correlation
         return prob
+
+    @staticmethod
+    def _skeptic(X):
+        """The skeptic matrices of the observations, of the kind ``utils.sample_covariance`` returns; an engine without the
+        device route (``set_kendall_subsets``) takes the numpy brute force."""
+        if hasattr(_solver.ENGINE, "set_kendall_subsets"):
+            return utils.skeptic_correlation(X)
+        kind, Xs = utils._data_list(X)
+        S = [utils.host_skeptic_correlation(x) for x in Xs]
+        return S[0] if kind == "2d" else (np.stack(S) if kind == "3d" else dict(enumerate(S)))
 
     def __repr__(self):
         name = {None: "SINGLE", "GGL": "GROUP", "FGL": "FUSED"}[self.reg]
@@ -286,7 +309,8 @@ class glasso_problem:
         subsamples of the observations, ``model_selection.stars_search``) over ``modelselect_params['lambda1_range']``.
         ``self.reg_params['lambda1']`` is set to the choice, the estimate on all observations goes to ``self.solution`` and
         the instabilities to ``self.modelselect_stats``.  With ``do_scaling`` every subsample is scaled to its own
-        correlations and the solution goes back to the covariances' scale, as in ``solve``."""
+        correlations and the solution goes back to the covariances' scale, as in ``solve``.  A problem built with
+        ``correlation='kendall'`` resamples the skeptic matrix instead (``do_scaling`` has nothing to scale then)."""
         assert getattr(self, '_observations', None) is not None, \
             "Stability selection resamples the observations: build the problem with glasso_problem.from_data(X)."
         assert not self.multiple, "Stability selection is implemented for Single Graphical Lasso problems only."
@@ -294,9 +318,11 @@ class glasso_problem:
         self.set_modelselect_params(modelselect_params)
         assert self.modelselect_params.get('lambda1_mask') is None and self.reg_params.get('lambda1_mask') is None, \
             "Stability selection is not implemented with a lambda1_mask."
+        how = dict(correlation='kendall') if getattr(self, '_correlation', None) == 'kendall' else \
+            dict(center=self._center, scale=bool(self.do_scaling))
         sol, stats = _ms.stars_search(self._observations[0], self.modelselect_params['lambda1_range'],
                                       n_subsamples=n_subsamples, subsample_size=subsample_size, beta=beta, seed=seed,
-                                      center=self._center, scale=bool(self.do_scaling), tol=tol, rtol=rtol, store_all=store_all)
+                                      tol=tol, rtol=rtol, store_all=store_all, **how)
         self.set_reg_params(stats['BEST'])
         self._keep(sol)
         self.modelselect_stats = dict(stats)

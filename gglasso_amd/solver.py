@@ -136,6 +136,21 @@ class HipEngine:
                                               idx.ctypes.data_as(_lib._ip), flags))
         self._S_scaled = bool(scale)
 
+    def set_kendall_subsets(self, X, indices=None):
+        """The ctx's S as skeptic matrices ``sin(pi/2 tau-b)`` of column subsets of ONE data array, computed on the device
+        (``ggl_set_S_from_kendall``): X (p,N), variables in rows, ``indices`` (B,b) ints with B a divisor of K (None: all
+        samples, B = 1); instance k gets the matrix of ``X[:, indices[k % B]]``.  A refused call (a variable constant over a
+        subset, an index outside [0,N)) leaves S as it was."""
+        from .utils import _subset_indices, dense_ranks
+        X = as_c(X)
+        assert X.ndim == 2 and X.shape[0] == self.p, f"data must be a ({self.p}, N) array"
+        R = dense_ranks(X)
+        idx = None if indices is None else _subset_indices(indices)
+        B, b = (1, X.shape[1]) if idx is None else idx.shape
+        check(self.lib.ggl_set_S_from_kendall(self.h, R.ctypes.data_as(_lib._ip), X.shape[1], B, b,
+                                              None if idx is None else idx.ctypes.data_as(_lib._ip)))
+        self._S_scaled = False
+
     def edge_stability(self, B, t=1e-8, counts=False):
         """StARS over the Theta snapshots of a batch of K = L * B points (instance l * B + r: subsample r at lambda l):
         the (L,) int64 array ``sum_{i<j} c (B - c)`` of the selection counts ``c[l,i,j] = #{r : |Theta| >= t}``, exact; with

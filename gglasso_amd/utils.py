@@ -118,3 +118,122 @@ def sample_covariance_subsets(X, indices, center=True, scale=False, device=0):
     flags = (_lib.COV_CENTER if center else 0) | (_lib.COV_SCALE if scale else 0)
     S, var = _covariance_subsets_call(X, _subset_indices(indices), flags, device)
     return (S, var) if scale else S
+
+
+# -----------------------------------------------------------------------------------------------------------------
+# Rank correlation: Kendall's tau-b and the nonparanormal skeptic matrix sin(pi/2 tau) (Liu, Han, Yuan, Lafferty, Wasserman
+# 2012; the other input statistic of R's huge).  With Z[i,(a,b)] = sgn(x_ia - x_ib) over the sample pairs a < b, G = Z Z^T
+# holds exact integers, G_ij = concordant - discordant pairs and G_ii = the pairs not tied in i, and tau-b = G_ij / sqrt(G_ii
+# G_jj) with ties handled.  The library forms G on the int8 matrix cores from dense ranks (csrc/kendall.hip).
+# -----------------------------------------------------------------------------------------------------------------
+_llp = ctypes.POINTER(ctypes.c_longlong)
+
+
+def dense_ranks(X):
+    """The (p,N) int32 array of dense ranks of every row of ``X`` (p,N): equal values get equal ranks, 0 for the smallest.
+    The sign of a rank difference is the sign of the value difference.  NaN and inf are refused."""
+    X = np.asarray(X, dtype=np.float64)
+    assert X.ndim == 2 and X.shape[0] >= 1 and X.shape[1] >= 1, \
+        f"data must be a (p,N) array with variables in rows, has shape {X.shape}"
+    assert np.isfinite(X).all(), "rank correlation needs finite data (NaN or inf found)"
+    R = np.empty(X.shape, dtype=np.int32)
+    for i in range(X.shape[0]):
+        R[i] = np.unique(X[i], return_inverse=True)[1].reshape(-1)
+    return R
+
+
+def _kendall_call(R, idx, skeptic, device=0):
+    """One ``ggl_kendall_counts`` / ``ggl_kendall_skeptic`` call: R C-contiguous int32 (p,N) dense ranks, idx C-contiguous
+    int32 (B,b) or None (all samples, B = 1).  Returns (G (B,p,p) int64, S (B,p,p) or None)."""
+    p, N = R.shape
+    B, b = (1, N) if idx is None else idx.shape
+    G = np.empty((B, p, p), dtype=np.int64)
+    S = np.empty((B, p, p)) if skeptic else None
+    ip = None if idx is None else idx.ctypes.data_as(_lib._ip)
+    _lib.require_gpu()
+    lib = _lib.load()
+    if skeptic:
+        check(lib.ggl_kendall_skeptic(int(device), p, N, R.ctypes.data_as(_lib._ip), B, b, ip, ptr(S), G.ctypes.data_as(_llp)))
+    else:
+        check(lib.ggl_kendall_counts(int(device), p, N, R.ctypes.data_as(_lib._ip), B, b, ip, G.ctypes.data_as(_llp)))
+    return G, S
+
+
+def host_kendall_counts(X, indices=None, chunk=1 << 22):
+    """numpy counterpart of ``kendall_counts`` for one (p,N) array (engines without the device route): a brute force over the
+    sample pairs, ``chunk`` sign entries at a time, summed in int64.  Returns (B,p,p), or (p,p) without ``indices``."""
+    X = np.asarray(X, dtype=np.float64)
+    assert X.ndim == 2 and np.isfinite(X).all(), "rank correlation needs a finite (p,N) array"
+    p = X.shape[0]
+    subsets = [X] if indices is None else [X[:, np.asarray(ix)] for ix in np.asarray(indices)]
+    out = np.zeros((len(subsets), p, p), dtype=np.int64)
+    for r, Xr in enumerate(subsets):
+        n = Xr.shape[1]
+        rows = max(1, int(chunk // max(1, p * n)))                    # a-samples per chunk
+        for a0 in range(0, n - 1, rows):
+            a = np.arange(a0, min(n - 1, a0 + rows))
+            Z = np.sign(Xr[:, a, None] - Xr[:, None, :])               # (p, a, b)
+            Z *= (np.arange(n)[None, :] > a[:, None])[None]            # pairs a < b only
+            Z = Z.reshape(p, -1).astype(np.int64)
+            out[r] += Z @ Z.T
+    return out[0] if indices is None else out
+
+
+def _tau_from_counts(G, skeptic):
+    """tau-b (or sin(pi/2 tau-b)) from the integers, diagonal exactly 1; a constant variable is refused."""
+    G = np.asarray(G)
+    d = np.diagonal(G, axis1=-2, axis2=-1).astype(np.float64)
+    assert np.all(d > 0), "rank correlation: a variable is constant (no untied pair of samples)"
+    T = G / np.sqrt(d[..., :, None] * d[..., None, :])
+    if skeptic:
+        T = np.sin(np.pi / 2 * T)
+    i = np.arange(G.shape[-1])
+    T[..., i, i] = 1.0
+    return T
+
+
+def host_skeptic_correlation(X, indices=None):
+    """numpy counterpart of ``skeptic_correlation`` for one (p,N) array."""
+    return _tau_from_counts(host_kendall_counts(X, indices), True)
+
+
+def _kendall_per_instance(X, indices, fn):
+    """``fn(ranks of instance, idx)`` for every instance of what ``sample_covariance`` accepts, returned as the same kind (with
+    ``indices`` every result carries a leading axis of B subsets)."""
+    kind, Xs = _data_list(X)
+    idx = None if indices is None else _subset_indices(indices)
+    out = [fn(dense_ranks(x), idx) for x in Xs]
+    if indices is None:
+        out = [o[0] for o in out]
+    if kind == "2d":
+        return out[0]
+    if kind == "3d":
+        return np.stack(out)
+    return {k: out[k] for k in range(len(out))}
+
+
+def kendall_counts(X, indices=None, device=0):
+    """The exact int64 matrix ``G = Z Z^T`` of Kendall's tau on the device (int8 matrix cores):
+    ``G[i,j] = sum_{a<b} sgn(x_ia - x_ib) sgn(x_ja - x_jb)`` -- concordant minus discordant pairs of (i,j) off the diagonal,
+    the pairs not tied in i on it.  Exactly symmetric, the same bits on every call, and invariant under any increasing
+    transform of a variable.
+
+    X: (p,N), (K,p,N), or a list / dict (keys 0..K-1) of (p_k,N_k) arrays, variables in rows; one kernel call per instance.
+    ``indices`` (B,b): G of the column subsets ``X[:, indices[r]]`` (one upload of the ranks; duplicates allowed) -- every
+    instance's result then is (B,p,p)."""
+    return _kendall_per_instance(X, indices, lambda R, idx: _kendall_call(R, idx, False, device)[0])
+
+
+def kendall_tau(X, indices=None, device=0):
+    """Kendall's tau-b between every pair of variables, ``G_ij / sqrt(G_ii G_jj)`` of ``kendall_counts`` (ties handled; what
+    ``scipy.stats.kendalltau`` returns per pair); the diagonal is 1.  A constant variable is refused.  Arguments and the kind
+    of the result as ``kendall_counts``."""
+    return _kendall_per_instance(X, indices, lambda R, idx: _tau_from_counts(_kendall_call(R, idx, False, device)[0], False))
+
+
+def skeptic_correlation(X, indices=None, device=0):
+    """The nonparanormal skeptic matrix ``sin(pi/2 tau-b)`` on the device: a correlation estimate that is invariant under
+    monotone transforms of the variables and robust to outliers and ties.  Diagonal exactly 1, exactly symmetric; it need not
+    be positive semidefinite.  A variable that is constant (over a subset) is refused, naming it.  Arguments and the kind of
+    the result as ``kendall_counts``."""
+    return _kendall_per_instance(X, indices, lambda R, idx: _kendall_call(R, idx, True, device)[1])

@@ -27,7 +27,8 @@ extern "C" {
  * takes a byte pattern.  A binding built against another major version must refuse to load (gglasso_amd/_lib.py does).
  * Entry points and selector values that are only ADDED (GGL_REG_FSGL, ggl_set_block_size, ggl_prox_sum_frob,
  * ggl_frob_norm_per_block, ggl_fsgl_stats, ggl_covariance, ggl_scale_by_diagonal, ggl_set_S_from_data, ggl_get_S, ggl_kkt_terms,
- * ggl_diag_stats, ggl_covariance_subsets, ggl_set_S_from_subsets, ggl_edge_stability) leave every existing layout alone and the number where it is. */
+ * ggl_diag_stats, ggl_covariance_subsets, ggl_set_S_from_subsets, ggl_edge_stability, ggl_kendall_counts, ggl_kendall_skeptic,
+ * ggl_set_S_from_kendall) leave every existing layout alone and the number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -760,6 +761,29 @@ int ggl_set_S_from_subsets(ggl_ctx *ctx, const double *X_host, int N, int B, int
  * num_out[l] = sum_{i<j} c (B - c), an exact integer (L values); counts_out (L,p,p) int32 or NULL: c mirrored, zero diagonal.
  * Integer sums: two calls return the same bits.  GGL_E_ARG: B < 1 or not dividing K, t negative or not finite, no snapshot. */
 int ggl_edge_stability(ggl_ctx *ctx, int B, double t, int *counts_out, long long *num_out);
+
+/* ---- Rank correlation from data: Kendall's tau-b between every pair of variables and the nonparanormal skeptic matrix
+ * sin(pi/2 tau) (Liu, Han, Yuan, Lafferty, Wasserman 2012) on the int8 matrix cores (kendall.hip).  Entry points that are only
+ * ADDED: GGL_VERSION stays where it is.
+ *
+ * ranks_host: the row-major (p,N) int array of DENSE ranks of every variable (equal values, equal ranks; every entry in
+ * [0,N)), variables in rows.  idx: the (B,b) int array of sample indices in [0,N) of B subsets (duplicates allowed: they
+ * form tied pairs; any order), or NULL = all N samples as one subset (B = 1, b = N).
+ * G_out (B,p,p) 64-bit integers: G[r,i,j] = sum over the pairs a < b of positions of subset r of
+ * sgn(R[i,idx[r,a]] - R[i,idx[r,b]]) * sgn(R[j,idx[r,a]] - R[j,idx[r,b]]) -- concordant minus discordant pairs off the
+ * diagonal, the pairs not tied in i on it; tau-b is G_ij / sqrt(G_ii G_jj).  Exact, exactly symmetric, and the same bits on
+ * every call.  GGL_E_ARG, found before any device work: an index outside [0,N) (the message names subset and position),
+ * b < 2, B < 1, a rank outside [0,N), a shape beyond what one launch takes (p * b < 2^31, p <= 23104, ceil(b/64) * ceil(b/1024)
+ * < 2^24: b up to about one million). */
+int ggl_kendall_counts(int device, int p, int N, const int *ranks_host, int B, int b, const int *idx, long long *G_out);
+/* S_out (B,p,p) = sin(pi/2 tau-b), diagonal exactly 1, exactly symmetric; G_out as above or NULL.  A variable that is constant
+ * over a subset (G_ii = 0) is GGL_E_ARG naming subset and variable; nothing is written then. */
+int ggl_kendall_skeptic(int device, int p, int N, const int *ranks_host, int B, int b, const int *idx, double *S_out,
+                        long long *G_out);
+/* ... straight into the S of a ctx whose K is a multiple of B: instance k gets the skeptic matrix of subset k % B, bitwise
+ * that of the call above (layout and bookkeeping of ggl_set_S_from_subsets; the ctx keeps no variances).  GGL_E_ARG also for
+ * a B that does not divide K and for a ctx with instance dimensions; a refused call leaves the ctx's S as it was. */
+int ggl_set_S_from_kendall(ggl_ctx *ctx, const int *ranks_host, int N, int B, int b, const int *idx);
 
 #ifdef __cplusplus
 }
