@@ -175,6 +175,9 @@ _DEV_SIGNATURES = {
     "ggl_dev_chain_run": ([_i, _i, _i, _i, _dp], _i),
     "ggl_dev_switch_bench": ([_i, _i, _i, _i, _i, _dp], _i),
     "ggl_dev_vendor_bench": ([_i, _i, _i, _i, _dp], _i),
+    "ggl_dev_set_symm_epilogue": ([_i], _i),
+    "ggl_dev_symm_bench_ops": ([_i, _i, _i, _i, _i, _dp], _i),
+    "ggl_dev_symm_full": ([_i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _i], _i),
     "ggl_dev_fill_copy_probe": ([_i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_longlong)], _i),
 }
 

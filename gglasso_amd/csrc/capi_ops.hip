@@ -180,6 +180,87 @@ extern "C" int ggl_dev_symm_bench(int K, int p, int variant, int iters, double* 
 }
 
 #ifdef GGL_DEV
+extern "C" int ggl_dev_set_symm_epilogue(int serial) { return symm_set_serial_epilogue(serial != 0) ? 1 : 0; }
+
+// ggl_dev_symm_bench with the epilogue's operands: E and E2 symmetric stacks (as in the solvers), coefficients that use them
+extern "C" int ggl_dev_symm_bench_ops(int K, int p, int variant, int iters, int ops, double* ms_out)
+{
+    ARGCHK(K >= 1 && p >= 1 && iters >= 1 && ms_out && ops >= 0 && ops <= 7, "arguments");
+    ARGCHK(variant < 0 || symm_variant_built(variant), "product-kernel variant not in this build");
+    const size_t n = (size_t)K * p * p;
+    std::vector<double> h(n), coef((size_t)K * NS_NCOEF, 0.0);
+    unsigned long long s = 88172645463325252ull;
+    for (size_t i = 0; i < n; ++i) {
+        s ^= s << 13; s ^= s >> 7; s ^= s << 17;
+        h[i] = (double)(s >> 11) / 9007199254740992.0 - 0.5;
+    }
+    for (int k = 0; k < K; ++k)
+        for (int i = 0; i < p; ++i)
+            for (int j = 0; j < i; ++j) h[((size_t)k * p + i) * p + j] = h[((size_t)k * p + j) * p + i];
+    for (int k = 0; k < K; ++k) {
+        double* c = coef.data() + (size_t)k * NS_NCOEF;
+        c[0] = 1.5; c[1] = 1.0 / p; c[2] = -0.5; c[3] = 0.25; c[4] = 0.5; c[5] = 0.125; c[6] = 0.75; c[7] = -0.375;
+    }
+    DevBuf dA, dB, dC, dC2, dcoef;
+    HIPCHK(dA.alloc(n));
+    HIPCHK(dB.alloc(n));
+    HIPCHK(dC.alloc(n));
+    HIPCHK(dC2.alloc(n));
+    HIPCHK(dcoef.alloc(coef.size()));
+    UP(dA.p, h.data(), n);
+    UP(dB.p, h.data(), n);
+    UP(dcoef.p, coef.data(), coef.size());
+    const double* E = (ops & 1) ? dA.p : nullptr;
+    const double* E2 = (ops & 2) ? dB.p : nullptr;
+    double* C2 = (ops & 4) ? dC2.p : nullptr;
+    struct Events {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    } ev;
+    HIPCHK(hipEventCreate(&ev.e0));
+    HIPCHK(hipEventCreate(&ev.e1));
+    for (int i = 0; i < 3; ++i) launch_symm(nullptr, dA.p, dB.p, dC.p, C2, E, dcoef.p, K, p, variant, nullptr, nullptr, nullptr, E2);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipEventRecord(ev.e0, nullptr));
+    for (int i = 0; i < iters; ++i) launch_symm(nullptr, dA.p, dB.p, dC.p, C2, E, dcoef.p, K, p, variant, nullptr, nullptr, nullptr, E2);
+    HIPCHK(hipEventRecord(ev.e1, nullptr));
+    HIPCHK(hipEventSynchronize(ev.e1));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    HIPCHK(hipGetLastError());
+    *ms_out = ms / iters;
+    return GGL_OK;
+}
+
+// ggl_dev_symm with every operand of the epilogue (kernel unit test of the batched epilogue: the second affine operand and
+// the second output's E / E2 terms, which the five-coefficient entry point leaves at zero)
+extern "C" int ggl_dev_symm_full(int K, int p, const double* A, const double* B, const double* E, const double* E2,
+                                 const double* coef8K, double* C, double* C2, int variant)
+{
+    ARGCHK(K >= 1 && p >= 1 && A && B && coef8K && C, "arguments");
+    ARGCHK(variant < 0 || symm_variant_built(variant), "product-kernel variant not in this build");
+    const size_t n = (size_t)K * p * p;
+    DevBuf dA, dB, dE, dE2, dC, dC2, dcoef;
+    HIPCHK(dA.alloc(n));
+    HIPCHK(dB.alloc(n));
+    HIPCHK(dC.alloc(n));
+    HIPCHK(dcoef.alloc((size_t)K * NS_NCOEF));
+    UP(dA.p, A, n);
+    UP(dB.p, B, n);
+    UP(dcoef.p, coef8K, (size_t)K * NS_NCOEF);
+    if (E) { HIPCHK(dE.alloc(n)); UP(dE.p, E, n); }
+    if (E2) { HIPCHK(dE2.alloc(n)); UP(dE2.p, E2, n); }
+    if (C2) HIPCHK(dC2.alloc(n));
+    launch_symm(nullptr, dA.p, dB.p, dC.p, C2 ? dC2.p : nullptr, E ? dE.p : nullptr, dcoef.p, K, p, variant, nullptr, nullptr,
+                nullptr, E2 ? dE2.p : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    DOWN(C, dC.p, n);
+    if (C2) DOWN(C2, dC2.p, n);
+    return GGL_OK;
+}
+
 // What does a change of kernel between dependent launches cost?  mode 0: `iters` products; 1: `iters` x (product, then a
 // one-thread kernel that stores a word); 2: `iters` of the one-thread kernel; 3: `iters` x (product, elementwise scale by 1 of
 // the output: an LDS-free kernel over the same data).  ms per repetition (tools/kernel_switch_cost.py).

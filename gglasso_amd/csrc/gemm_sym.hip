@@ -293,6 +293,8 @@ template <int N> __device__ __forceinline__ void wait_vmcnt()
 // NW: waves per workgroup (4: 2 x 2 waves of BM/2 x BM/2; 8: 4 x 2 waves of BM/4 x BM/2 -- two waves per SIMD, for batches
 // so small that only one workgroup lands on a CU and a lone wave per SIMD cannot hide its LDS round trips and barriers)
 // symm_dl_tile: one output tile (instance k of the combined batch, tile pair b) -- the whole body of k_symm_dl
+// SER 1: the serial epilogue instead of the batched one (development library only); XREG: VGPRs the caller keeps
+// live across the tile (the persistent chain's loop state), taken off the batched epilogue's register budget
 // AUX: cache policy of every global READ of the tile body (operand DMA and the E term): 0 = default; 16 = sc1, i.e. served by
 // the XCD's L2 past this CU's vector L1 -- what a persistent kernel needs to read tiles that ANOTHER CU of the same XCD
 // wrote earlier in the same launch (a CU's L1 is never refreshed by other CUs' stores; MI355X_MICROARCH.md).
@@ -302,7 +304,51 @@ template <int AUX> __device__ __forceinline__ double ld_pol(const double* p)
     else return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // global_load_dwordx2 ... sc1
 }
 
-template <int BK, int NSTG, int ABL, int BM, int NW, int AUX = 0>
+// the bound partials of one staged tile (symm_dl_tile: rowpart / fropart), by the first 2 BM threads of the workgroup
+template <int BM>
+__device__ __forceinline__ void symm_dl_partials(const double* smem, double* __restrict__ rowpart, double* __restrict__ fropart,
+                                                 int k, int p, int T, int blockTile, int I, int J, int I0, int J0, int tid)
+{
+    // threads 0..BM-1: row t of the staged tile; threads BM..2BM-1 (off-diagonal tiles): column t of it, i.e. row
+    // J0+t of the mirrored tile.  A diagonal tile holds its upper triangle U only: row t of the full symmetric tile
+    // is row t of U plus column t of U minus the diagonal entry.
+    const int t = tid & (BM - 1);
+    const bool second = tid >= BM;
+    const size_t slot_stride = (size_t)p;
+    double rs = 0.0, sq = 0.0;
+    if (!second) {
+#pragma unroll 8
+        for (int c = 0; c < BM; ++c) { const double x = smem[t * BM + (c ^ t)]; rs += fabs(x); sq += x * x; }
+    }
+    if (second || I == J) {
+        double cs = 0.0;
+#pragma unroll 8
+        for (int r = 0; r < BM; ++r) cs += fabs(smem[r * BM + (t ^ r)]);
+        if (I == J) {
+            if (!second) {
+                const double dg = smem[t * BM];
+                rs = (rs + cs) - fabs(dg);
+                sq = 2.0 * sq - dg * dg;
+            }
+        } else {
+            rs = cs;
+        }
+    } else {
+        sq *= 2.0;            // off-diagonal tile: its mirror has the same squares
+    }
+    if (I != J || !second) {
+        const int T2 = (p + BM - 1) / BM;
+        const int slot = second ? I : J, gi = (second ? J0 : I0) + t;
+        if (gi < p) rowpart[((size_t)k * T2 + slot) * slot_stride + gi] = rs;
+    }
+    if (tid < 64) {                      // wave 0 holds the BM row threads
+        sq = wave_sum((tid < BM) ? sq : 0.0);
+        if (tid == 0) fropart[(size_t)k * (T * (T + 1) / 2) + blockTile] = sq;
+    }
+
+}
+
+template <int BK, int NSTG, int ABL, int BM, int NW, int AUX = 0, int SER = 0, int XREG = 0>
 __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const double* __restrict__ B,
                                              double* __restrict__ C, double* __restrict__ C2,
                                              const double* __restrict__ E, const double* __restrict__ E2,
@@ -423,6 +469,20 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
         else if (wave == 2) { rbk[0] = 16; rbk[TI - 1] = 0; cbk[0] = WN + 16; cbk[TJ - 1] = WN; nval = 1; }   // X=(1,3)
     }
     const bool dead_wave = !REBAL && (I == J) && (wr >= wc + WN);
+    // Epilogue operands.  The batched epilogue (SER == 0) fetches its coefficients HERE, ahead of the slab loop: eight scalar
+    // loads whose latency the loop hides, instead of a scalar round trip between the last MFMA and the first epilogue load.
+    double cI = 0.0, cAcc = 0.0, cE = 0.0, dI = 0.0, dC = 0.0, dE = 0.0, cE2 = 0.0, dE2 = 0.0;
+    double* Ck = (second ? C1 : C) + (size_t)kk * pp;
+    double* C2k = (C2 && !second) ? C2 + (size_t)kk * pp : nullptr;
+    const double* Ek = (E && !second) ? E + (size_t)kk * pp : nullptr;
+    // second affine operand (E2, coefficients cE2 / dE2): added after the E term, so a launch without it keeps its bits
+    const double* E2k = (E2 && !second) ? E2 + (size_t)kk * pp : nullptr;
+    auto load_coefs = [&] {
+        cI = coef[k * NS_NCOEF + 0]; cAcc = coef[k * NS_NCOEF + 1]; cE = coef[k * NS_NCOEF + 2];
+        dI = coef[k * NS_NCOEF + 3]; dC = coef[k * NS_NCOEF + 4]; dE = coef[k * NS_NCOEF + 5];
+        cE2 = E2k ? coef[k * NS_NCOEF + 6] : 0.0; dE2 = E2k ? coef[k * NS_NCOEF + 7] : 0.0;
+    };
+    if constexpr (SER == 0 && ABL != 4) load_coefs();
     const int S = (p + BK - 1) / BK;
 #pragma unroll
     for (int q = 0; q < NSTG - 1; ++q)
@@ -513,7 +573,9 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
         else if constexpr (NSTG == 4) stages(s0, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{});
         else stages(s0, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 5>{});
     }
-    __syncthreads();     // all fragment reads done before the slabs are reused as the mirror tile
+    // all fragment reads done before the slabs are reused as the mirror tile (the batched epilogue has this barrier behind
+    // its first loads, see there)
+    if constexpr (ABL == 4 || SER != 0) __syncthreads();
 #if defined(GGL_EXP_SETPRIO) && GGL_EXP_SETPRIO == 2
     __builtin_amdgcn_s_setprio(2);                                       // experiment: the epilogue outranks the other workgroups' slab loops
 #endif
@@ -527,22 +589,251 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
         return;
     }
 
-    const double cI = coef[k * NS_NCOEF + 0], cAcc = coef[k * NS_NCOEF + 1], cE = coef[k * NS_NCOEF + 2];
-    const double dI = coef[k * NS_NCOEF + 3], dC = coef[k * NS_NCOEF + 4], dE = coef[k * NS_NCOEF + 5];
-    double* Ck = (second ? C1 : C) + (size_t)kk * pp;
-    double* C2k = (C2 && !second) ? C2 + (size_t)kk * pp : nullptr;
-    const double* Ek = (E && !second) ? E + (size_t)kk * pp : nullptr;
-    // second affine operand (E2, coefficients cE2 / dE2): added after the E term, so a launch without it keeps its bits
-    const double* E2k = (E2 && !second) ? E2 + (size_t)kk * pp : nullptr;
-    const double cE2 = E2k ? coef[k * NS_NCOEF + 6] : 0.0, dE2 = E2k ? coef[k * NS_NCOEF + 7] : 0.0;
+#ifdef GGL_DEV
+    if constexpr (SER != 0) {
+        // the serial epilogue (development library, ggl_dev_set_symm_epilogue): the bitwise yardstick of
+        // the batched one below and the other side of its A/B -- one global round trip per trip of every pass
+        load_coefs();
+        double dev = 0.0;
+        // Off-diagonal tiles: the accumulators go to the (XOR-swizzled) LDS tile first and BOTH copies -- the tile and its
+        // mirror -- are written from there with 16-byte accesses, two consecutive columns per lane (p is even, tile columns start
+        // on even indices): half the global store / E-load instructions of the layout the MFMA leaves the values in (one column
+        // per lane: 8-byte accesses, which run at 0.54-0.70x the 16-byte rate on this chip).  Same arithmetic per element
+        // (cAcc * acc, then + cE * E): same bits.  Diagonal tiles keep the direct path (upper triangle only, in-tile mirror).
+        const bool wide = (I != J) && ABL != 1;
+        if (wide) {
+    #pragma unroll
+            for (int ti = 0; ti < TI; ++ti)
+    #pragma unroll
+                for (int tj = 0; tj < TJ; ++tj)
+    #pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = wr + ti * 16 + (lane >> 4) + 4 * r;
+                        const int col = wc + tj * 16 + (lane & 15);
+                        smem[row * BM + (col ^ row)] = cAcc * acc[ti][tj][r];
+                    }
+            __syncthreads();
+            auto ld2 = [](const double* q) { return *reinterpret_cast<const double2*>(q); };
+            auto lde2 = [&](const double* q) {
+                if constexpr (AUX == 0) return *reinterpret_cast<const double2*>(q);
+                else { double2 e; e.x = ld_pol<AUX>(q); e.y = ld_pol<AUX>(q + 1); return e; }
+            };
+            for (int e2 = tid; e2 < BM * BM / 2; e2 += NT) {
+                const int row = e2 / (BM / 2), c2 = (e2 % (BM / 2)) * 2;
+                const int gi = I0 + row, gj = J0 + c2;
+                // columns c2, c2 + 1 of row `row` sit at (c2 ^ row), (c2 ^ row) ^ 1: one aligned pair, swapped for odd rows
+                double2 t = ld2(smem + row * BM + ((c2 ^ row) & ~1));
+                if (row & 1) { const double h = t.x; t.x = t.y; t.y = h; }
+                if (gi < p && gj + 1 < p) {
+                    double2 e = {0.0, 0.0}, f = {0.0, 0.0};
+                    if (Ek) e = lde2(Ek + (size_t)gi * p + gj);
+                    if (E2k) f = lde2(E2k + (size_t)gi * p + gj);
+                    double2 v;
+                    v.x = t.x + cE * e.x;
+                    v.y = t.y + cE * e.y;
+                    if (E2k) { v.x += cE2 * f.x; v.y += cE2 * f.y; }
+                    dev = fmax(dev, fmax(fabs(v.x), fabs(v.y)));
+                    *reinterpret_cast<double2*>(Ck + (size_t)gi * p + gj) = v;
+                    if (C2k) {
+                        double2 w;
+                        w.x = c2val(dC, v.x, dE, e.x);
+                        w.y = c2val(dC, v.y, dE, e.y);
+                        if (E2k) { w.x = __builtin_fma(dE2, f.x, w.x); w.y = __builtin_fma(dE2, f.y, w.y); }
+                        *reinterpret_cast<double2*>(C2k + (size_t)gi * p + gj) = w;
+                    }
+                    if (rowpart) {          // the bound partials (and then the mirror) read the FINAL values from the tile
+                        if (row & 1) { const double h = v.x; v.x = v.y; v.y = h; }
+                        *reinterpret_cast<double2*>(smem + row * BM + ((c2 ^ row) & ~1)) = v;
+                    }
+                } else if (gi < p && gj < p) {
+                    // odd p: the last column is the first half of a pair whose second half lies outside the matrix
+                    const double e0 = Ek ? ld_pol<AUX>(Ek + (size_t)gi * p + gj) : 0.0;
+                    const double f0 = E2k ? ld_pol<AUX>(E2k + (size_t)gi * p + gj) : 0.0;
+                    double v0 = t.x + cE * e0;
+                    if (E2k) v0 += cE2 * f0;
+                    dev = fmax(dev, fabs(v0));
+                    Ck[(size_t)gi * p + gj] = v0;
+                    if (C2k) C2k[(size_t)gi * p + gj] = c2val2(dC, v0, dE, e0, E2k != nullptr, dE2, f0);
+                    if (rowpart) {
+                        double2 v = {v0, 0.0};
+                        if (row & 1) { v.x = 0.0; v.y = v0; }
+                        *reinterpret_cast<double2*>(smem + row * BM + ((c2 ^ row) & ~1)) = v;
+                    }
+                } else if (rowpart) {
+                    *reinterpret_cast<double2*>(smem + row * BM + ((c2 ^ row) & ~1)) = double2{0.0, 0.0};
+                }
+            }
+        } else {
+        if (REBAL && I == J && rowpart && ABL != 1) {
+            // the staged tile of the bound partials wants zeros below the diagonal: the six blocks no wave owns any more
+            for (int e = tid; e < 6 * 256; e += NT) {
+                const int blk = e >> 8, br = (blk < 1) ? 1 : (blk < 3 ? 2 : 3), bc = blk - (br == 1 ? 0 : (br == 2 ? 1 : 3));
+                const int row = br * 16 + ((e >> 4) & 15), col = bc * 16 + (e & 15);
+                smem[row * BM + (col ^ row)] = 0.0;
+            }
+        }
+    #pragma unroll
+        for (int ti = 0; ti < TI; ++ti)
+    #pragma unroll
+            for (int tj = 0; tj < TJ; ++tj) {
+                if (REBAL && ((ti != tj && tj == 0 && nval <= 3) || ((ti | tj) != 0 && nval <= 1))) continue;   // not a block of the tile
+    #pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = rbk[ti] + (lane >> 4) + 4 * r;
+                    const int col = cbk[tj] + (lane & 15);
+                    const int gi = I0 + row, gj = J0 + col;
+                    double v = cAcc * acc[ti][tj][r];
+                    const bool keep = gi < p && gj < p && (I != J || gi <= gj);
+                    if (keep) {
+                        if (gi == gj) v += cI;
+                        const double e0 = Ek ? ld_pol<AUX>(Ek + (size_t)gi * p + gj) : 0.0;
+                        v += cE * e0;
+                        const double f0 = E2k ? ld_pol<AUX>(E2k + (size_t)gi * p + gj) : 0.0;
+                        if (E2k) v += cE2 * f0;
+                        dev = fmax(dev, fabs(v - (gi == gj ? 1.0 : 0.0)));
+                        Ck[(size_t)gi * p + gj] = v;
+                        if (C2k) C2k[(size_t)gi * p + gj] = c2val2(dC, v, dE, e0, E2k != nullptr, dE2, f0) + (gi == gj ? dI : 0.0);
+                        if (I == J && gi != gj) {
+                            Ck[(size_t)gj * p + gi] = v;
+                            if (C2k) C2k[(size_t)gj * p + gi] = c2val2(dC, v, dE, e0, E2k != nullptr, dE2, f0);
+                        }
+                    }
+                    // XOR-swizzled BM x BM tile in LDS: the mirror pass of an off-diagonal tile reads it transposed; with
+                    // bound partials every tile is staged (entries that are not stored count as zero)
+                    if ((I != J || rowpart) && ABL != 1) smem[row * BM + (col ^ row)] = (rowpart && !keep) ? 0.0 : v;
+                }
+            }
+        }
+        if (maxdev) {
+            dev = wave_max(dev);
+            if (lane == 0 && dev > 0.0)
+                atomicMax(reinterpret_cast<unsigned long long*>(maxdev + k), (unsigned long long)__double_as_longlong(dev));
+        }
+        if (((I != J && !wide) || rowpart) && ABL != 1) __syncthreads();
+        if (rowpart && ABL != 1 && tid < 2 * BM) symm_dl_partials<BM>(smem, rowpart, fropart, k, p, T, blockTile, I, J, I0, J0, tid);
+        if (wide) {
+            // the mirror: row a of it is column a of the staged tile; two consecutive columns c2, c2 + 1 per lane.  Without bound
+            // partials the tile still holds cAcc * acc and the E term is added here as well (E is bitwise symmetric -- an output
+            // of this kernel family -- so its mirrored entries ARE the upper ones); with them it holds the final values.
+            auto lde2 = [&](const double* q) {
+                if constexpr (AUX == 0) return *reinterpret_cast<const double2*>(q);
+                else { double2 e; e.x = ld_pol<AUX>(q); e.y = ld_pol<AUX>(q + 1); return e; }
+            };
+            for (int e2 = tid; e2 < BM * BM / 2; e2 += NT) {
+                const int a = e2 / (BM / 2), c2 = (e2 % (BM / 2)) * 2;      // out[J0+a][I0+c2 .. +1] = tile[c2 .. +1][a]
+                if (J0 + a < p && I0 + c2 + 1 < p) {
+                    double2 v;
+                    v.x = smem[c2 * BM + (a ^ c2)];
+                    v.y = smem[(c2 + 1) * BM + (a ^ (c2 + 1))];
+                    double2 e = {0.0, 0.0}, f = {0.0, 0.0};
+                    const bool need_e = Ek && (!rowpart || (C2k && dE != 0.0));
+                    if (need_e) e = lde2(Ek + (size_t)(J0 + a) * p + I0 + c2);
+                    const bool need_f = E2k && (!rowpart || (C2k && dE2 != 0.0));
+                    if (need_f) f = lde2(E2k + (size_t)(J0 + a) * p + I0 + c2);
+                    if (!rowpart) {
+                        v.x += cE * e.x; v.y += cE * e.y;
+                        if (E2k) { v.x += cE2 * f.x; v.y += cE2 * f.y; }
+                    }
+                    *reinterpret_cast<double2*>(Ck + (size_t)(J0 + a) * p + I0 + c2) = v;
+                    if (C2k) {
+                        double2 w;
+                        w.x = c2val(dC, v.x, dE, e.x);
+                        w.y = c2val(dC, v.y, dE, e.y);
+                        if (E2k) { w.x = __builtin_fma(dE2, f.x, w.x); w.y = __builtin_fma(dE2, f.y, w.y); }
+                        *reinterpret_cast<double2*>(C2k + (size_t)(J0 + a) * p + I0 + c2) = w;
+                    }
+                } else if (J0 + a < p && I0 + c2 < p) {
+                    // (never taken: I < J, so the rows I0 .. I0 + BM - 1 of an off-diagonal tile all lie inside the matrix and an
+                    // odd last column can only belong to tile column J; kept so that the pair test above stands on its own)
+                    double v0 = smem[c2 * BM + (a ^ c2)];
+                    const bool need_e = Ek && (!rowpart || (C2k && dE != 0.0));
+                    const double e0 = need_e ? ld_pol<AUX>(Ek + (size_t)(J0 + a) * p + I0 + c2) : 0.0;
+                    const bool need_f = E2k && (!rowpart || (C2k && dE2 != 0.0));
+                    const double f0 = need_f ? ld_pol<AUX>(E2k + (size_t)(J0 + a) * p + I0 + c2) : 0.0;
+                    if (!rowpart) { v0 += cE * e0; if (E2k) v0 += cE2 * f0; }
+                    Ck[(size_t)(J0 + a) * p + I0 + c2] = v0;
+                    if (C2k) C2k[(size_t)(J0 + a) * p + I0 + c2] = c2val2(dC, v0, dE, e0, E2k != nullptr, dE2, f0);
+                }
+            }
+        }
+        return;
+    }
+#endif
+    // The batched epilogue.  The serial one paid a dependent global round trip per trip of every pass -- load E, load E2,
+    // s_waitcnt vmcnt(0) (which also waits for the previous trip's store acknowledgements), store -- about 16 of them per
+    // tile, its four waves holding a third of the CU's LDS and issuing no MFMA meanwhile.  Here
+    //   * the E / E2 loads of a whole batch of trips are issued back to back (NB trips of an off-diagonal tile, DB 16x16
+    //     blocks of a diagonal one: as many as fit the register budget of the kernel's residency, VBUD), the FIRST batch
+    //     ahead of the barrier that closes the slab loop, so that its latency runs under the barrier, the staging of the
+    //     accumulators and the barrier behind it.  (It is issued after the slab loop, i.e. after the last slab's vmcnt(0):
+    //     the loop's counted wait_vmcnt<N> never see it.  Ahead of the last slab's MFMAs it would have to be counted into
+    //     every immediate of the loop.)
+    //   * the stores follow without a wait of their own: the compiler's counted vmcnt in front of a trip's arithmetic
+    //     leaves the stores of the earlier trips in flight;
+    //   * the barriers are LDS-only (lds_barrier): __syncthreads() drains vmcnt(0), i.e. loads AND store acknowledgements;
+    //   * the direct pass writes the final values back to the staged tile and the mirror pass reads them from there: no
+    //     second pass over E / E2 (they are bitwise symmetric -- outputs of this kernel family -- so the mirrored entry of
+    //     the sum IS the upper one), except where the second output needs them, batched in the same way.
+    // Same operations per element in the same order (the fused multiply-adds pinned with __builtin_fma): same bits.
+    constexpr int LDSB = NSTG * 2 * SLAB * 8;
+    constexpr int WGCU = (160 * 1024 / LDSB) < (8 / (NW / 4)) ? (160 * 1024 / LDSB) : (8 / (NW / 4));   // workgroups per CU
+    constexpr int VBUD = (512 / (WGCU * (NW / 4))) & ~7;          // VGPRs per lane that keep that residency
+    // of them, for loads in flight: what the accumulators, ~48 registers of addresses and values in work and the caller's
+    // own live registers (XREG) leave
+    constexpr int BREG = VBUD - TI * TJ * 8 - 48 - XREG;
+    constexpr int NTRIP = BM * BM / 2 / NT;                       // trips of a pass over an off-diagonal tile
+    constexpr int NB = (BREG / 8 >= NTRIP) ? NTRIP : (BREG / 8 >= NTRIP / 2 && NTRIP >= 2) ? NTRIP / 2 : 1;   // trips per batch (8 VGPRs each)
+    constexpr int NBLK = TI * TJ;                                 // 16x16 blocks of a wave
+    constexpr int DB = (BREG / 16 >= NBLK) ? NBLK : (BREG / 16 >= NBLK / 2 && NBLK >= 2) ? NBLK / 2 : 1;      // blocks per batch (16 VGPRs each)
+    static_assert(NTRIP * NT * 2 == BM * BM && NTRIP % NB == 0 && NBLK % DB == 0, "epilogue batches");
+    auto lds_barrier = [] {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    };
+    // The ONE wait of a batch: an empty statement that reads the batch's registers, in workgroup-uniform control flow.  Left
+    // to itself the compiler waits at the first use, which sits inside a lane-predicated region; behind such a region it no
+    // longer knows what has landed and drains vmcnt(0) -- store acknowledgements included -- at every later trip.
+    auto landed = [](const double& x) { asm volatile("" ::"v"(x)); };
+    auto landed2 = [&](const double2& x) { landed(x.x); landed(x.y); };
+    auto ld2 = [](const double* q) { return *reinterpret_cast<const double2*>(q); };
+    auto lde2 = [&](const double* q) {
+        if constexpr (AUX == 0) return *reinterpret_cast<const double2*>(q);
+        else { double2 e; e.x = ld_pol<AUX>(q); e.y = ld_pol<AUX>(q + 1); return e; }
+    };
     double dev = 0.0;
     // Off-diagonal tiles: the accumulators go to the (XOR-swizzled) LDS tile first and BOTH copies -- the tile and its
-    // mirror -- are written from there with 16-byte accesses, two consecutive columns per lane (p is even, tile columns start
-    // on even indices): half the global store / E-load instructions of the layout the MFMA leaves the values in (one column
-    // per lane: 8-byte accesses, which run at 0.54-0.70x the 16-byte rate on this chip).  Same arithmetic per element
-    // (cAcc * acc, then + cE * E): same bits.  Diagonal tiles keep the direct path (upper triangle only, in-tile mirror).
+    // mirror -- are written from there with 16-byte accesses, two consecutive columns per lane (tile columns start on even
+    // indices): half the global store / E-load instructions of the layout the MFMA leaves the values in (one column per
+    // lane: 8-byte accesses, which run at 0.54-0.70x the 16-byte rate on this chip).  Diagonal tiles keep the direct path
+    // (upper triangle only, in-tile mirror).
     const bool wide = (I != J) && ABL != 1;
     if (wide) {
+        double2 pe[NB], pf[NB];
+        // trip u of the direct pass: lane -> row `row`, columns c2, c2 + 1 of the tile; the edge guards as ONE predicate per
+        // trip.  (One load instruction per operand and trip, whatever the lane's case: a second one into the same registers
+        // on another branch -- 8 bytes for the odd last column -- makes the compiler drain vmcnt(0) between the trips, a
+        // write-after-write hazard it tracks per register, not per lane.)  Odd p: the last column is the first half of a
+        // pair whose second half lies outside the matrix; its lane loads the pair ONE COLUMN TO THE LEFT (inside the row,
+        // 4-byte aligned as the queues' unaligned-access mode allows) and takes the second half.
+        auto direct_loads = [&](const int u0) {
+#pragma unroll
+            for (int q = 0; q < NB; ++q) {
+                const int e2 = tid + (u0 + q) * NT;
+                const int row = e2 / (BM / 2), c2 = (e2 % (BM / 2)) * 2;
+                const int gi = I0 + row, gj = J0 + c2;
+                const bool any = gi < p && gj < p, half = any && gj + 1 >= p;
+                const size_t o = (size_t)gi * p + gj - (half ? 1 : 0);
+                pe[q] = double2{0.0, 0.0};
+                pf[q] = double2{0.0, 0.0};
+                if (any) {
+                    if (Ek) pe[q] = lde2(Ek + o);
+                    if (E2k) pf[q] = lde2(E2k + o);
+                }
+            }
+        };
+        direct_loads(0);
+        lds_barrier();       // all fragment reads done before the slabs are reused as the mirror tile
 #pragma unroll
         for (int ti = 0; ti < TI; ++ti)
 #pragma unroll
@@ -553,95 +844,123 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
                     const int col = wc + tj * 16 + (lane & 15);
                     smem[row * BM + (col ^ row)] = cAcc * acc[ti][tj][r];
                 }
-        __syncthreads();
-        auto ld2 = [](const double* q) { return *reinterpret_cast<const double2*>(q); };
-        auto lde2 = [&](const double* q) {
-            if constexpr (AUX == 0) return *reinterpret_cast<const double2*>(q);
-            else { double2 e; e.x = ld_pol<AUX>(q); e.y = ld_pol<AUX>(q + 1); return e; }
-        };
-        for (int e2 = tid; e2 < BM * BM / 2; e2 += NT) {
-            const int row = e2 / (BM / 2), c2 = (e2 % (BM / 2)) * 2;
-            const int gi = I0 + row, gj = J0 + c2;
-            // columns c2, c2 + 1 of row `row` sit at (c2 ^ row), (c2 ^ row) ^ 1: one aligned pair, swapped for odd rows
-            double2 t = ld2(smem + row * BM + ((c2 ^ row) & ~1));
-            if (row & 1) { const double h = t.x; t.x = t.y; t.y = h; }
-            if (gi < p && gj + 1 < p) {
-                double2 e = {0.0, 0.0}, f = {0.0, 0.0};
-                if (Ek) e = lde2(Ek + (size_t)gi * p + gj);
-                if (E2k) f = lde2(E2k + (size_t)gi * p + gj);
-                double2 v;
-                v.x = t.x + cE * e.x;
-                v.y = t.y + cE * e.y;
-                if (E2k) { v.x += cE2 * f.x; v.y += cE2 * f.y; }
-                dev = fmax(dev, fmax(fabs(v.x), fabs(v.y)));
-                *reinterpret_cast<double2*>(Ck + (size_t)gi * p + gj) = v;
-                if (C2k) {
-                    double2 w;
-                    w.x = c2val(dC, v.x, dE, e.x);
-                    w.y = c2val(dC, v.y, dE, e.y);
-                    if (E2k) { w.x = __builtin_fma(dE2, f.x, w.x); w.y = __builtin_fma(dE2, f.y, w.y); }
-                    *reinterpret_cast<double2*>(C2k + (size_t)gi * p + gj) = w;
-                }
-                if (rowpart) {          // the bound partials (and then the mirror) read the FINAL values from the tile
+        lds_barrier();
+#pragma unroll
+        for (int u0 = 0; u0 < NTRIP; u0 += NB) {
+            if (u0 > 0) direct_loads(u0);
+#pragma unroll
+            for (int q = 0; q < NB; ++q) { landed2(pe[q]); landed2(pf[q]); }
+#pragma unroll
+            for (int q = 0; q < NB; ++q) {
+                const int e2 = tid + (u0 + q) * NT;
+                const int row = e2 / (BM / 2), c2 = (e2 % (BM / 2)) * 2;
+                const int gi = I0 + row, gj = J0 + c2;
+                // columns c2, c2 + 1 of row `row` sit at (c2 ^ row), (c2 ^ row) ^ 1: one aligned pair, swapped for odd rows
+                double* tp = smem + row * BM + ((c2 ^ row) & ~1);
+                double2 t = ld2(tp);
+                if (row & 1) { const double h = t.x; t.x = t.y; t.y = h; }
+                double2 e = pe[q], f = pf[q];
+                if (gi < p && gj < p && gj + 1 >= p) { e.x = e.y; f.x = f.y; }      // the odd last column, see direct_loads
+                // the final values go back to the tile: the bound partials and the mirror pass read them from there
+                if (gi < p && gj + 1 < p) {
+                    double2 v;
+                    v.x = __builtin_fma(cE, e.x, t.x);
+                    v.y = __builtin_fma(cE, e.y, t.y);
+                    if (E2k) { v.x = __builtin_fma(cE2, f.x, v.x); v.y = __builtin_fma(cE2, f.y, v.y); }
+                    dev = fmax(dev, fmax(fabs(v.x), fabs(v.y)));
+                    *reinterpret_cast<double2*>(Ck + (size_t)gi * p + gj) = v;
+                    if (C2k) {
+                        double2 w;
+                        w.x = c2val(dC, v.x, dE, e.x);
+                        w.y = c2val(dC, v.y, dE, e.y);
+                        if (E2k) { w.x = __builtin_fma(dE2, f.x, w.x); w.y = __builtin_fma(dE2, f.y, w.y); }
+                        *reinterpret_cast<double2*>(C2k + (size_t)gi * p + gj) = w;
+                    }
                     if (row & 1) { const double h = v.x; v.x = v.y; v.y = h; }
-                    *reinterpret_cast<double2*>(smem + row * BM + ((c2 ^ row) & ~1)) = v;
-                }
-            } else if (gi < p && gj < p) {
-                // odd p: the last column is the first half of a pair whose second half lies outside the matrix
-                const double e0 = Ek ? ld_pol<AUX>(Ek + (size_t)gi * p + gj) : 0.0;
-                const double f0 = E2k ? ld_pol<AUX>(E2k + (size_t)gi * p + gj) : 0.0;
-                double v0 = t.x + cE * e0;
-                if (E2k) v0 += cE2 * f0;
-                dev = fmax(dev, fabs(v0));
-                Ck[(size_t)gi * p + gj] = v0;
-                if (C2k) C2k[(size_t)gi * p + gj] = c2val2(dC, v0, dE, e0, E2k != nullptr, dE2, f0);
-                if (rowpart) {
+                    *reinterpret_cast<double2*>(tp) = v;
+                } else if (gi < p && gj < p) {
+                    double v0 = __builtin_fma(cE, e.x, t.x);
+                    if (E2k) v0 = __builtin_fma(cE2, f.x, v0);
+                    dev = fmax(dev, fabs(v0));
+                    Ck[(size_t)gi * p + gj] = v0;
+                    if (C2k) C2k[(size_t)gi * p + gj] = c2val2(dC, v0, dE, e.x, E2k != nullptr, dE2, f.x);
                     double2 v = {v0, 0.0};
                     if (row & 1) { v.x = 0.0; v.y = v0; }
-                    *reinterpret_cast<double2*>(smem + row * BM + ((c2 ^ row) & ~1)) = v;
+                    *reinterpret_cast<double2*>(tp) = v;
+                } else if (rowpart) {
+                    *reinterpret_cast<double2*>(tp) = double2{0.0, 0.0};
                 }
-            } else if (rowpart) {
-                *reinterpret_cast<double2*>(smem + row * BM + ((c2 ^ row) & ~1)) = double2{0.0, 0.0};
             }
         }
     } else {
-    if (REBAL && I == J && rowpart && ABL != 1) {
-        // the staged tile of the bound partials wants zeros below the diagonal: the six blocks no wave owns any more
-        for (int e = tid; e < 6 * 256; e += NT) {
-            const int blk = e >> 8, br = (blk < 1) ? 1 : (blk < 3 ? 2 : 3), bc = blk - (br == 1 ? 0 : (br == 2 ? 1 : 3));
-            const int row = br * 16 + ((e >> 4) & 15), col = bc * 16 + (e & 15);
-            smem[row * BM + (col ^ row)] = 0.0;
-        }
-    }
+        double de[DB * 4], df[DB * 4];
+        // not a block of the tile (the diagonal tiles' rebalanced waves, see rbk / cbk above)
+        auto no_block = [&](const int ti, const int tj) {
+            return REBAL && ((ti != tj && tj == 0 && nval <= 3) || ((ti | tj) != 0 && nval <= 1));
+        };
+        auto diag_loads = [&](const int b0) {
 #pragma unroll
-    for (int ti = 0; ti < TI; ++ti)
+            for (int q = 0; q < DB; ++q) {
+                const int ti = (b0 + q) / TJ, tj = (b0 + q) % TJ;
 #pragma unroll
-        for (int tj = 0; tj < TJ; ++tj) {
-            if (REBAL && ((ti != tj && tj == 0 && nval <= 3) || ((ti | tj) != 0 && nval <= 1))) continue;   // not a block of the tile
+                for (int r = 0; r < 4; ++r) {
+                    de[q * 4 + r] = 0.0;
+                    df[q * 4 + r] = 0.0;
+                }
+                if (no_block(ti, tj)) continue;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = rbk[ti] + (lane >> 4) + 4 * r;
-                const int col = cbk[tj] + (lane & 15);
-                const int gi = I0 + row, gj = J0 + col;
-                double v = cAcc * acc[ti][tj][r];
-                const bool keep = gi < p && gj < p && (I != J || gi <= gj);
-                if (keep) {
-                    if (gi == gj) v += cI;
-                    const double e0 = Ek ? ld_pol<AUX>(Ek + (size_t)gi * p + gj) : 0.0;
-                    v += cE * e0;
-                    const double f0 = E2k ? ld_pol<AUX>(E2k + (size_t)gi * p + gj) : 0.0;
-                    if (E2k) v += cE2 * f0;
-                    dev = fmax(dev, fabs(v - (gi == gj ? 1.0 : 0.0)));
-                    Ck[(size_t)gi * p + gj] = v;
-                    if (C2k) C2k[(size_t)gi * p + gj] = c2val2(dC, v, dE, e0, E2k != nullptr, dE2, f0) + (gi == gj ? dI : 0.0);
-                    if (I == J && gi != gj) {
-                        Ck[(size_t)gj * p + gi] = v;
-                        if (C2k) C2k[(size_t)gj * p + gi] = c2val2(dC, v, dE, e0, E2k != nullptr, dE2, f0);
+                for (int r = 0; r < 4; ++r) {
+                    const int gi = I0 + rbk[ti] + (lane >> 4) + 4 * r, gj = J0 + cbk[tj] + (lane & 15);
+                    if (gi < p && gj < p && (I != J || gi <= gj)) {
+                        if (Ek) de[q * 4 + r] = ld_pol<AUX>(Ek + (size_t)gi * p + gj);
+                        if (E2k) df[q * 4 + r] = ld_pol<AUX>(E2k + (size_t)gi * p + gj);
                     }
                 }
-                // XOR-swizzled BM x BM tile in LDS: the mirror pass of an off-diagonal tile reads it transposed; with
-                // bound partials every tile is staged (entries that are not stored count as zero)
-                if ((I != J || rowpart) && ABL != 1) smem[row * BM + (col ^ row)] = (rowpart && !keep) ? 0.0 : v;
+            }
+        };
+        diag_loads(0);
+        lds_barrier();       // all fragment reads done before the slabs are reused as the mirror tile
+        if (REBAL && I == J && rowpart && ABL != 1) {
+            // the staged tile of the bound partials wants zeros below the diagonal: the six blocks no wave owns any more
+            for (int e = tid; e < 6 * 256; e += NT) {
+                const int blk = e >> 8, br = (blk < 1) ? 1 : (blk < 3 ? 2 : 3), bc = blk - (br == 1 ? 0 : (br == 2 ? 1 : 3));
+                const int row = br * 16 + ((e >> 4) & 15), col = bc * 16 + (e & 15);
+                smem[row * BM + (col ^ row)] = 0.0;
+            }
+        }
+#pragma unroll
+        for (int b0 = 0; b0 < NBLK; b0 += DB) {
+            if (b0 > 0) diag_loads(b0);
+#pragma unroll
+            for (int q = 0; q < DB * 4; ++q) { landed(de[q]); landed(df[q]); }
+#pragma unroll
+            for (int q = 0; q < DB; ++q) {
+                const int ti = (b0 + q) / TJ, tj = (b0 + q) % TJ;
+                if (no_block(ti, tj)) continue;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = rbk[ti] + (lane >> 4) + 4 * r;
+                    const int col = cbk[tj] + (lane & 15);
+                    const int gi = I0 + row, gj = J0 + col;
+                    double v = cAcc * acc[ti][tj][r];
+                    const bool keep = gi < p && gj < p && (I != J || gi <= gj);
+                    if (keep) {
+                        if (gi == gj) v += cI;
+                        const double e0 = de[q * 4 + r], f0 = df[q * 4 + r];
+                        v = __builtin_fma(cE, e0, v);
+                        if (E2k) v = __builtin_fma(cE2, f0, v);
+                        dev = fmax(dev, fabs(v - (gi == gj ? 1.0 : 0.0)));
+                        Ck[(size_t)gi * p + gj] = v;
+                        if (C2k) C2k[(size_t)gi * p + gj] = c2val2(dC, v, dE, e0, E2k != nullptr, dE2, f0) + (gi == gj ? dI : 0.0);
+                        if (I == J && gi != gj) {
+                            Ck[(size_t)gj * p + gi] = v;
+                            if (C2k) C2k[(size_t)gj * p + gi] = c2val2(dC, v, dE, e0, E2k != nullptr, dE2, f0);
+                        }
+                    }
+                    // XOR-swizzled BM x BM tile in LDS: with bound partials every tile is staged (entries that are not stored
+                    // count as zero); an off-diagonal tile comes here only without its mirror (ABL 1)
+                    if ((I != J || rowpart) && ABL != 1) smem[row * BM + (col ^ row)] = (rowpart && !keep) ? 0.0 : v;
+                }
             }
         }
     }
@@ -650,87 +969,58 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
         if (lane == 0 && dev > 0.0)
             atomicMax(reinterpret_cast<unsigned long long*>(maxdev + k), (unsigned long long)__double_as_longlong(dev));
     }
-    if (((I != J && !wide) || rowpart) && ABL != 1) __syncthreads();
-    if (rowpart && ABL != 1 && tid < 2 * BM) {
-        // threads 0..BM-1: row t of the staged tile; threads BM..2BM-1 (off-diagonal tiles): column t of it, i.e. row
-        // J0+t of the mirrored tile.  A diagonal tile holds its upper triangle U only: row t of the full symmetric tile
-        // is row t of U plus column t of U minus the diagonal entry.
-        const int t = tid & (BM - 1);
-        const bool second = tid >= BM;
-        const size_t slot_stride = (size_t)p;
-        double rs = 0.0, sq = 0.0;
-        if (!second) {
-#pragma unroll 8
-            for (int c = 0; c < BM; ++c) { const double x = smem[t * BM + (c ^ t)]; rs += fabs(x); sq += x * x; }
-        }
-        if (second || I == J) {
-            double cs = 0.0;
-#pragma unroll 8
-            for (int r = 0; r < BM; ++r) cs += fabs(smem[r * BM + (t ^ r)]);
-            if (I == J) {
-                if (!second) {
-                    const double dg = smem[t * BM];
-                    rs = (rs + cs) - fabs(dg);
-                    sq = 2.0 * sq - dg * dg;
-                }
-            } else {
-                rs = cs;
-            }
-        } else {
-            sq *= 2.0;            // off-diagonal tile: its mirror has the same squares
-        }
-        if (I != J || !second) {
-            const int T2 = (p + BM - 1) / BM;
-            const int slot = second ? I : J, gi = (second ? J0 : I0) + t;
-            if (gi < p) rowpart[((size_t)k * T2 + slot) * slot_stride + gi] = rs;
-        }
-        if (tid < 64) {                      // wave 0 holds the BM row threads
-            sq = wave_sum((tid < BM) ? sq : 0.0);
-            if (tid == 0) fropart[(size_t)k * (T * (T + 1) / 2) + blockTile] = sq;
-        }
-    }
+    if ((I != J || rowpart) && ABL != 1) lds_barrier();      // the staged tile holds the final values
+    if (rowpart && ABL != 1 && tid < 2 * BM) symm_dl_partials<BM>(smem, rowpart, fropart, k, p, T, blockTile, I, J, I0, J0, tid);
     if (wide) {
-        // the mirror: row a of it is column a of the staged tile; two consecutive columns c2, c2 + 1 per lane.  Without bound
-        // partials the tile still holds cAcc * acc and the E term is added here as well (E is bitwise symmetric -- an output
-        // of this kernel family -- so its mirrored entries ARE the upper ones); with them it holds the final values.
-        auto lde2 = [&](const double* q) {
-            if constexpr (AUX == 0) return *reinterpret_cast<const double2*>(q);
-            else { double2 e; e.x = ld_pol<AUX>(q); e.y = ld_pol<AUX>(q + 1); return e; }
-        };
-        for (int e2 = tid; e2 < BM * BM / 2; e2 += NT) {
-            const int a = e2 / (BM / 2), c2 = (e2 % (BM / 2)) * 2;      // out[J0+a][I0+c2 .. +1] = tile[c2 .. +1][a]
-            if (J0 + a < p && I0 + c2 + 1 < p) {
-                double2 v;
-                v.x = smem[c2 * BM + (a ^ c2)];
-                v.y = smem[(c2 + 1) * BM + (a ^ (c2 + 1))];
-                double2 e = {0.0, 0.0}, f = {0.0, 0.0};
-                const bool need_e = Ek && (!rowpart || (C2k && dE != 0.0));
-                if (need_e) e = lde2(Ek + (size_t)(J0 + a) * p + I0 + c2);
-                const bool need_f = E2k && (!rowpart || (C2k && dE2 != 0.0));
-                if (need_f) f = lde2(E2k + (size_t)(J0 + a) * p + I0 + c2);
-                if (!rowpart) {
-                    v.x += cE * e.x; v.y += cE * e.y;
-                    if (E2k) { v.x += cE2 * f.x; v.y += cE2 * f.y; }
+        // the mirror: row a of it is column a of the staged tile, two consecutive columns c2, c2 + 1 per lane -- final values,
+        // no arithmetic left but the second output's, whose E / E2 terms are loaded at the mirrored addresses
+        // (loaded under the serial epilogue's condition -- without bound partials also where dE or dE2 is zero: fma(0, e, x)
+        // is x only up to the sign of a zero and for finite e, and the second output keeps its bits exactly)
+        const bool need_e = Ek && C2k && (!rowpart || dE != 0.0), need_f = E2k && C2k && (!rowpart || dE2 != 0.0);
+        double2 me[NB], mf[NB];
+#pragma unroll
+        for (int u0 = 0; u0 < NTRIP; u0 += NB) {
+#pragma unroll
+            for (int q = 0; q < NB; ++q) {
+                const int e2 = tid + (u0 + q) * NT;
+                const int a = e2 / (BM / 2), c2 = (e2 % (BM / 2)) * 2;
+                const size_t o = (size_t)(J0 + a) * p + I0 + c2;
+                const bool any = J0 + a < p && I0 + c2 < p, half = any && I0 + c2 + 1 >= p;
+                me[q] = double2{0.0, 0.0};
+                mf[q] = double2{0.0, 0.0};
+                if (any) {                       // (one load per operand and trip, as in direct_loads)
+                    if (need_e) me[q] = lde2(Ek + o - (half ? 1 : 0));
+                    if (need_f) mf[q] = lde2(E2k + o - (half ? 1 : 0));
                 }
-                *reinterpret_cast<double2*>(Ck + (size_t)(J0 + a) * p + I0 + c2) = v;
-                if (C2k) {
-                    double2 w;
-                    w.x = c2val(dC, v.x, dE, e.x);
-                    w.y = c2val(dC, v.y, dE, e.y);
-                    if (E2k) { w.x = __builtin_fma(dE2, f.x, w.x); w.y = __builtin_fma(dE2, f.y, w.y); }
-                    *reinterpret_cast<double2*>(C2k + (size_t)(J0 + a) * p + I0 + c2) = w;
+            }
+#pragma unroll
+            for (int q = 0; q < NB; ++q) { landed2(me[q]); landed2(mf[q]); }
+#pragma unroll
+            for (int q = 0; q < NB; ++q) {
+                const int e2 = tid + (u0 + q) * NT;
+                const int a = e2 / (BM / 2), c2 = (e2 % (BM / 2)) * 2;      // out[J0+a][I0+c2 .. +1] = tile[c2 .. +1][a]
+                const size_t o = (size_t)(J0 + a) * p + I0 + c2;
+                double2 e = me[q], f = mf[q];
+                if (J0 + a < p && I0 + c2 < p && I0 + c2 + 1 >= p) { e.x = e.y; f.x = f.y; }
+                if (J0 + a < p && I0 + c2 + 1 < p) {
+                    double2 v;
+                    v.x = smem[c2 * BM + (a ^ c2)];
+                    v.y = smem[(c2 + 1) * BM + (a ^ (c2 + 1))];
+                    *reinterpret_cast<double2*>(Ck + o) = v;
+                    if (C2k) {
+                        double2 w;
+                        w.x = c2val(dC, v.x, dE, e.x);
+                        w.y = c2val(dC, v.y, dE, e.y);
+                        if (E2k) { w.x = __builtin_fma(dE2, f.x, w.x); w.y = __builtin_fma(dE2, f.y, w.y); }
+                        *reinterpret_cast<double2*>(C2k + o) = w;
+                    }
+                } else if (J0 + a < p && I0 + c2 < p) {
+                    // (never taken: I < J, so the rows I0 .. I0 + BM - 1 of an off-diagonal tile all lie inside the matrix and an
+                    // odd last column can only belong to tile column J; kept so that the pair test above stands on its own)
+                    const double v0 = smem[c2 * BM + (a ^ c2)];
+                    Ck[o] = v0;
+                    if (C2k) C2k[o] = c2val2(dC, v0, dE, e.x, E2k != nullptr, dE2, f.x);
                 }
-            } else if (J0 + a < p && I0 + c2 < p) {
-                // (never taken: I < J, so the rows I0 .. I0 + BM - 1 of an off-diagonal tile all lie inside the matrix and an
-                // odd last column can only belong to tile column J; kept so that the pair test above stands on its own)
-                double v0 = smem[c2 * BM + (a ^ c2)];
-                const bool need_e = Ek && (!rowpart || (C2k && dE != 0.0));
-                const double e0 = need_e ? ld_pol<AUX>(Ek + (size_t)(J0 + a) * p + I0 + c2) : 0.0;
-                const bool need_f = E2k && (!rowpart || (C2k && dE2 != 0.0));
-                const double f0 = need_f ? ld_pol<AUX>(E2k + (size_t)(J0 + a) * p + I0 + c2) : 0.0;
-                if (!rowpart) { v0 += cE * e0; if (E2k) v0 += cE2 * f0; }
-                Ck[(size_t)(J0 + a) * p + I0 + c2] = v0;
-                if (C2k) C2k[(size_t)(J0 + a) * p + I0 + c2] = c2val2(dC, v0, dE, e0, E2k != nullptr, dE2, f0);
             }
         }
     }
@@ -890,7 +1180,8 @@ __global__ __launch_bounds__(256) void k_cw_rider(const CwRider rider)
     cw_rider_body(rider, (int)blockIdx.x, sh);
 }
 
-template <int BK, int NSTG, int ABL = 0, int BM = 64, int NW = 4>
+// SER 1: the serial epilogue (development library only, see symm_dl_tile)
+template <int BK, int NSTG, int ABL = 0, int BM = 64, int NW = 4, int SER = 0>
 __global__ __launch_bounds__(NW * 64) void k_symm_dl(const double* __restrict__ A, const double* __restrict__ B,
                                                  double* __restrict__ C, double* __restrict__ C2,
                                                  const double* __restrict__ E, const double* __restrict__ E2,
@@ -945,7 +1236,7 @@ __global__ __launch_bounds__(NW * 64) void k_symm_dl(const double* __restrict__ 
     }
     int k, b;
     if (!decode_block_xcd(T * (T + 1) / 2, K + K1, k, b, bid)) return;
-    symm_dl_tile<BK, NSTG, ABL, BM, NW>(A, B, C, C2, E, E2, coef, K, p, A1, B1, C1, K1, maxdev, rowpart, fropart, k, b, smem);
+    symm_dl_tile<BK, NSTG, ABL, BM, NW, 0, SER>(A, B, C, C2, E, E2, coef, K, p, A1, B1, C1, K1, maxdev, rowpart, fropart, k, b, smem);
 }
 
 #ifdef GGL_DEV
@@ -1273,6 +1564,13 @@ __global__ __launch_bounds__(256) void k_symm_sk(const double* __restrict__ A, c
 
 #endif   // GGL_DEV (k_symm_sk)
 
+#ifdef GGL_DEV
+// which epilogue the direct-to-LDS launches of the development library run: the batched one (false) or the serial one
+// (ggl_dev_set_symm_epilogue; the product library compiles the batched one only)
+static bool g_symm_serial = false;
+bool symm_set_serial_epilogue(bool on) { const bool was = g_symm_serial; g_symm_serial = on; return was; }
+#endif
+
 #ifdef GGL_DEV      // (round 6: the persistent chain is an option of the development library only -- measured slower)
 // ---------------------------------------------------------------------------------------------
 // k_omega_chain: the WHOLE product chain of an Omega-step (A', B', the Newton-Schulz products, Omega) of a batch in ONE
@@ -1297,7 +1595,7 @@ __global__ __launch_bounds__(256) void k_symm_sk(const double* __restrict__ A, c
 // handed out of product s.  A claim is ONE fetch_add on the ticket word of the product the workgroup last saw ready for
 // that instance (a ticket beyond the product's tiles is void: nothing is lost, nobody waits); only when a product is
 // exhausted does the workgroup read the completion word to see whether the next one may start.
-template <int BK, int NSTG, int BM, int AUX>
+template <int BK, int NSTG, int BM, int AUX, int SER = 0>
 __global__ __launch_bounds__(256) void k_omega_chain(const ChainProg P, unsigned* __restrict__ state)
 {
     __shared__ __attribute__((aligned(16))) double smem[NSTG * 2 * BK * BM];
@@ -1370,7 +1668,7 @@ __global__ __launch_bounds__(256) void k_omega_chain(const ChainProg P, unsigned
         const SymmOp& o = P.op[js];
         int kk = jk;
         if (o.pair && jb >= P.ntiles) { kk = P.K + jk; jb -= P.ntiles; }
-        symm_dl_tile<BK, NSTG, 0, BM, 4, AUX>(o.A, o.B, o.C, o.C2, o.E, o.E2, o.coef, P.K, P.p, o.A1, o.B1, o.C1, o.pair ? P.K : 0,
+        symm_dl_tile<BK, NSTG, 0, BM, 4, AUX, SER, 32>(o.A, o.B, o.C, o.C2, o.E, o.E2, o.coef, P.K, P.p, o.A1, o.B1, o.C1, o.pair ? P.K : 0,
                                                nullptr, o.rowpart, o.fropart, kk, jb, smem);
         // this tile's stores are in the XCD's L2 before the arrival is counted; the barrier also frees the LDS image
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1415,6 +1713,7 @@ int launch_omega_chain(hipStream_t st, const ChainProg& P, unsigned* state, int*
         slots -= slots % NXCD;
     }
     if (aux == 0) hipLaunchKernelGGL((k_omega_chain<16, 3, 64, 0>), dim3(slots), dim3(256), 0, st, P, state);   // measurement only
+    else if (g_symm_serial) hipLaunchKernelGGL((k_omega_chain<16, 3, 64, 16, 1>), dim3(slots), dim3(256), 0, st, P, state);
     else
     hipLaunchKernelGGL((k_omega_chain<16, 3, 64, 16>), dim3(slots), dim3(256), 0, st, P, state);
     hipLaunchKernelGGL(k_chain_check, dim3(1), dim3(64), 0, st, state, P.K, (unsigned)P.begin[P.nops], flag, flag_h);
@@ -1490,7 +1789,7 @@ __global__ __launch_bounds__(256) void k_symm_chain_probe(double* X0, double* X1
         for (int L = blockIdx.x; L < total; L += gridDim.x) {       // gridDim.x is a multiple of 8: L % 8 = this XCD
             int k, b;
             if (decode_block_xcd(ntiles, K, k, b, L))
-                symm_dl_tile<BK, NSTG, 0, BM, 4>(src, src, dst, nullptr, nullptr, nullptr, coef, K, p, nullptr, nullptr, nullptr, 0,
+                symm_dl_tile<BK, NSTG, 0, BM, 4, 0, 0, 32>(src, src, dst, nullptr, nullptr, nullptr, coef, K, p, nullptr, nullptr, nullptr, 0,
                                                  nullptr, nullptr, nullptr, k, b, smem);
             __syncthreads();                                         // the slab storage is reused by the next tile
         }
@@ -1566,7 +1865,21 @@ static void launch_dl(hipStream_t st, const double* A, const double* B, double* 
     int ncopy = red.nblk > 0 ? NXCD : 0;          // (in front of the tiles, see k_symm_dl)
     for (int i = 0; i < cps.n; ++i) ncopy += (int)((cps.words[i] + 1023u) / 1024u);
     const int nride = rider.K * rider.nbx + ncopy;
-#define GGL_DL(...) hipLaunchKernelGGL((k_symm_dl<__VA_ARGS__>), grid, dim3(256), 0, st, A, B, C, C2, E, E2, coef, K, p, A1, B1, C1, K1, maxdev, rowpart, fropart, rider, cps, red)
+#define GGL_DL_ARGS A, B, C, C2, E, E2, coef, K, p, A1, B1, C1, K1, maxdev, rowpart, fropart, rider, cps, red
+#ifdef GGL_DEV
+    // GGL_DL(BK, NSTG, ABL, BM): the instance with the epilogue the switch names
+#define GGL_DL4(BK_, NSTG_, ABL_, BM_)                                                                                        \
+    do {                                                                                                                       \
+        if (g_symm_serial) hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, ABL_, BM_, 4, 1>), grid, dim3(256), 0, st, GGL_DL_ARGS); \
+        else hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, ABL_, BM_, 4, 0>), grid, dim3(256), 0, st, GGL_DL_ARGS);               \
+    } while (0)
+#else
+#define GGL_DL4(BK_, NSTG_, ABL_, BM_) hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, ABL_, BM_>), grid, dim3(256), 0, st, GGL_DL_ARGS)
+#endif
+#define GGL_DL3(BK_, NSTG_, ABL_) GGL_DL4(BK_, NSTG_, ABL_, 64)
+#define GGL_DL2(BK_, NSTG_) GGL_DL4(BK_, NSTG_, 0, 64)
+#define GGL_DL_PICK(a1, a2, a3, a4, NAME, ...) NAME
+#define GGL_DL(...) GGL_DL_PICK(__VA_ARGS__, GGL_DL4, GGL_DL3, GGL_DL2, )(__VA_ARGS__)
     if (dl_cfg == 4 || (dl_cfg >= 8 && dl_cfg <= 13) || (dl_cfg >= 18 && dl_cfg <= 21)) {
         const int T32 = (p + 31) / 32;
         const dim3 grid(xcd_grid(T32 * (T32 + 1) / 2, K + K1) + nride);
@@ -1597,9 +1910,13 @@ static void launch_dl(hipStream_t st, const double* A, const double* B, double* 
         // eight waves per workgroup (two per SIMD) for batches that leave one workgroup per CU.  Measured (MI355X, p = 500):
         // K = 4: 27.0 / 26.3 us vs 26.6 us for the 32x32 kernel; K = 8: 43.9 / 49.3 vs 40.4; K = 16: 68.6 / 74.9 vs 63.9 --
         // no gain anywhere, so the shipped library does not carry them
-#define GGL_DL8(...) hipLaunchKernelGGL((k_symm_dl<__VA_ARGS__>), grid, dim3(512), 0, st, A, B, C, C2, E, E2, coef, K, p, A1, B1, C1, K1, maxdev, rowpart, fropart, rider, cps, red)
-        if (dl_cfg == 6) GGL_DL8(16, 4, 0, 64, 8);
-        else GGL_DL8(32, 3, 0, 64, 8);
+#define GGL_DL8(BK_, NSTG_)                                                                                                   \
+    do {                                                                                                                       \
+        if (g_symm_serial) hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, 0, 64, 8, 1>), grid, dim3(512), 0, st, GGL_DL_ARGS);     \
+        else hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, 0, 64, 8, 0>), grid, dim3(512), 0, st, GGL_DL_ARGS);                   \
+    } while (0)
+        if (dl_cfg == 6) GGL_DL8(16, 4);
+        else GGL_DL8(32, 3);
 #undef GGL_DL8
         return;
     }
@@ -1620,6 +1937,11 @@ static void launch_dl(hipStream_t st, const double* A, const double* B, double* 
 #endif
     else GGL_DL(16, 2);
 #undef GGL_DL
+#undef GGL_DL_PICK
+#undef GGL_DL2
+#undef GGL_DL3
+#undef GGL_DL4
+#undef GGL_DL_ARGS
 }
 
 // ---------------------------------------------------------------------------------------------

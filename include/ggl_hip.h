@@ -682,6 +682,16 @@ int ggl_dev_symm_timeline(int K, int p, long long *out, int max_blocks, int *nbl
  * the two chains' results (must be 0), out[4] barrier flag (1 time-out, 2 a workgroup not on XCD blockIdx % 8).  variant: 16, 17
  * (64x64 tiles), 20 (32x32).  two_level: one L2 write-back per XCD and barrier instead of one per workgroup. */
 int ggl_dev_chain_probe(int K, int p, int variant, int nprod, int iters, int two_level, double *out);
+/* Epilogue of the direct-to-LDS product kernels (symm_dl_tile): 0 the batched one (the only one the product library has), 1 the
+ * serial one, kept as its bitwise yardstick and for A/B timing.  Process-wide; returns the previous mode. */
+int ggl_dev_set_symm_epilogue(int serial);
+/* ggl_dev_symm_bench with the epilogue's operands present: ops bit 0 the affine operand E, bit 1 the second one (E2), bit 2 the
+ * second output C2.  Average milliseconds of `iters` launches. */
+int ggl_dev_symm_bench_ops(int K, int p, int variant, int iters, int ops, double *ms_out);
+/* ggl_dev_symm with every operand of the epilogue: E and E2 (either may be NULL), the full coefficient rows coef8K (K x 8:
+ * cI, cAcc, cE, dI, dC, dE, cE2, dE2) and the second output C2 (may be NULL). */
+int ggl_dev_symm_full(int K, int p, const double *A, const double *B, const double *E, const double *E2, const double *coef8K,
+                      double *C, double *C2, int variant);
 #endif
 
 /* ---- stateless operator entry points (host buffers; used for operator-level parity) ---------- */
