@@ -160,6 +160,10 @@ _SIGNATURES = {
     "ggl_kendall_counts": ([_i, _i, _i, _ip, _i, _i, _ip, ctypes.POINTER(ctypes.c_longlong)], _i),
     "ggl_kendall_skeptic": ([_i, _i, _i, _ip, _i, _i, _ip, _dp, ctypes.POINTER(ctypes.c_longlong)], _i),
     "ggl_set_S_from_kendall": ([_vp, _ip, _i, _i, _i, _ip], _i),
+    "ggl_covariance_pairwise": ([_i, _i, _i, _ip, ctypes.POINTER(_dp), _i, _i, _dp, _dp, _ip], _i),
+    "ggl_covariance_pairwise_subsets": ([_i, _i, _i, _dp, _i, _i, _ip, _i, _i, _dp, _dp, _ip], _i),
+    "ggl_set_S_from_data_pairwise": ([_vp, ctypes.POINTER(_dp), _ip, _i, _i], _i),
+    "ggl_set_S_from_subsets_pairwise": ([_vp, _dp, _i, _i, _i, _ip, _i, _i], _i),
 }
 
 # libggl_hip_dev.so only (-DGGL_DEV)

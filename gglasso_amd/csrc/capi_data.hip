@@ -430,3 +430,223 @@ extern "C" int ggl_set_S_from_kendall(ggl_ctx* c, const int* ranks_host, int N, 
     if (rc) return rc;
     return install_subset_S(c, dS.p, B, {});
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Pairwise-complete covariance of data with missing values, NaN (kernels: covariance_missing.hip).  Every route builds S
+// and the pair counts in buffers of its own; the caller's S_out, or the S of a ctx, is written only after the row check, the
+// pair-count check and (GGL_COV_SCALE) the variance check have passed: a refused call leaves both as they were.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+int check_min_pairs(int min_pairs, size_t K, size_t p)
+{
+    if (min_pairs < 1)
+        return fail(GGL_E_ARG, "bad argument: min_pairs = %d, every pair of variables needs at least one shared sample (min_pairs >= 1)",
+                    min_pairs);
+    ARGCHK(K * p * p < ((size_t)1 << 38), "K * p * p too large");
+    return GGL_OK;
+}
+
+// S_dev, cnt_dev (K,p,p) from the arena (layout as covariance_of_arena) on stream st; with GGL_COV_SCALE S is divided by its
+// own diagonal -- the variance of each variable over all its observed entries -- and var_dev (K,p) gets it.  what: "instance"
+// or "subset", for the messages.  Waits for the stream.
+int pairwise_of_arena(hipStream_t st, int K, int p, const double* X_dev, const long long* off_dev, const int* N_dev, int flags,
+                      int min_pairs, double* S_dev, int* cnt_dev, double* var_dev, const char* what)
+{
+    DevArr<double> dShift, dSd;
+    DevArr<int> dRowCnt, dErr;
+    DevArr<unsigned long long> dPairErr;
+    const size_t kp = (size_t)K * p, pp = (size_t)p * p;
+    HIPCHK(dShift.alloc(kp));
+    HIPCHK(dRowCnt.alloc(kp));
+    HIPCHK(dErr.alloc(1));
+    HIPCHK(dPairErr.alloc(1));
+    HIPCHK(hipMemsetAsync(dErr.p, 0x7f, sizeof(int), st));
+    launch_row_stats_masked(st, X_dev, off_dev, N_dev, dShift.p, dRowCnt.p, dErr.p, K, p);
+    HIPCHK(hipGetLastError());
+    int err = GGL_DIAG_OK;
+    HIPCHK(hipMemcpyAsync(&err, dErr.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (err != GGL_DIAG_OK)
+        return fail(GGL_E_ARG, "bad argument: %s %d, variable %d has no observed entry (every sample is NaN)", what, err / p, err % p);
+    const int tile = (flags & GGL_COV_TILE64) ? 64 : ((flags & GGL_COV_TILE32) ? 32 : 0);
+    launch_gram_nt_pairwise(st, X_dev, off_dev, N_dev, (flags & GGL_COV_CENTER) ? dShift.p : nullptr, S_dev, cnt_dev, K, p, tile);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(dPairErr.p, 0xff, sizeof(unsigned long long), st));
+    launch_pair_count_check(st, cnt_dev, min_pairs, dPairErr.p, K, p);
+    HIPCHK(hipGetLastError());
+    unsigned long long perr = ~0ull;
+    HIPCHK(hipMemcpyAsync(&perr, dPairErr.p, sizeof(perr), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (perr != ~0ull) {
+        int n = 0;
+        HIPCHK(hipMemcpy(&n, cnt_dev + perr, sizeof(int), hipMemcpyDeviceToHost));
+        return fail(GGL_E_ARG, "bad argument: %s %d, the pair of variables (%d, %d) shares %d samples, min_pairs = %d", what,
+                    (int)(perr / pp), (int)(perr % pp / p), (int)(perr % p), n, min_pairs);
+    }
+    if (flags & GGL_COV_SCALE) {
+        HIPCHK(dSd.alloc(kp));
+        HIPCHK(hipMemsetAsync(dErr.p, 0x7f, sizeof(int), st));
+        launch_scale_by_diag(st, S_dev, nullptr, S_dev, var_dev, dSd.p, dErr.p, K, p);
+        HIPCHK(hipGetLastError());
+        int rc = diag_error(st, dErr.p, p, nullptr, S_dev, "the variance");
+        if (rc) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return GGL_OK;
+}
+
+// ... from the host data of K instances (the arena of covariance_to_device; NaNs travel as they are)
+int pairwise_to_device(hipStream_t st, int K, int p, const int* N, const double* const* X_host, int flags, int min_pairs,
+                       double* S_dev, int* cnt_dev, double* var_dev)
+{
+    std::vector<long long> off(K);
+    size_t total = 0;
+    for (int k = 0; k < K; ++k) { off[k] = (long long)total; total += (size_t)p * N[k]; }
+    DevArr<double> dX;
+    DevArr<long long> dOff;
+    DevArr<int> dN;
+    HIPCHK(dX.alloc(total));
+    HIPCHK(dOff.alloc(K));
+    HIPCHK(dN.alloc(K));
+    HIPCHK(hipMemcpyAsync(dOff.p, off.data(), K * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dN.p, N, K * sizeof(int), hipMemcpyHostToDevice, st));
+    for (int k = 0; k < K; ++k)
+        HIPCHK(hipMemcpyAsync(dX.p + off[k], X_host[k], (size_t)p * N[k] * sizeof(double), hipMemcpyHostToDevice, st));
+    return pairwise_of_arena(st, K, p, dX.p, dOff.p, dN.p, flags, min_pairs, S_dev, cnt_dev, var_dev, "instance");
+}
+
+// ... of B column subsets of one X, gathered on the device (k_gather_cols moves bytes: NaNs travel)
+int pairwise_subsets_to_device(hipStream_t st, int p, int N, const double* X_host, int B, int b, const int* idx, int flags,
+                               int min_pairs, double* S_dev, int* cnt_dev, double* var_dev)
+{
+    std::vector<long long> off(B);
+    std::vector<int> Nb(B, b);
+    for (int r = 0; r < B; ++r) off[r] = (long long)r * p * b;
+    DevArr<double> dX, dA;
+    DevArr<long long> dOff;
+    DevArr<int> dN, dIdx;
+    HIPCHK(dX.alloc((size_t)p * N));
+    HIPCHK(dA.alloc((size_t)B * p * b));
+    HIPCHK(dOff.alloc(B));
+    HIPCHK(dN.alloc(B));
+    HIPCHK(dIdx.alloc((size_t)B * b));
+    HIPCHK(hipMemcpyAsync(dX.p, X_host, (size_t)p * N * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dIdx.p, idx, (size_t)B * b * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dOff.p, off.data(), B * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dN.p, Nb.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
+    launch_gather_cols(st, dX.p, dIdx.p, dA.p, p, N, B, b);
+    HIPCHK(hipGetLastError());
+    return pairwise_of_arena(st, B, p, dA.p, dOff.p, dN.p, flags, min_pairs, S_dev, cnt_dev, var_dev, "subset");
+}
+
+// the results of a stateless call go down, the last step of a call that was not refused
+int pairwise_download(int K, int p, int flags, const double* dS, const int* dCnt, const double* dVar, double* S_out,
+                      double* scale_out, int* counts_out)
+{
+    const size_t n = (size_t)K * p * p;
+    DOWN(S_out, dS, n);
+    if (flags & GGL_COV_SCALE) DOWN(scale_out, dVar, (size_t)K * p);
+    if (counts_out) HIPCHK(hipMemcpy(counts_out, dCnt, n * sizeof(int), hipMemcpyDeviceToHost));
+    return GGL_OK;
+}
+}  // namespace
+
+extern "C" int ggl_covariance_pairwise(int device, int K, int p, const int* N, const double* const* X_host, int flags,
+                                       int min_pairs, double* S_out, double* scale_out, int* counts_out)
+{
+    int rc = check_data_args(K, p, N, X_host, flags);
+    if (rc) return rc;
+    rc = check_min_pairs(min_pairs, K, p);
+    if (rc) return rc;
+    ARGCHK(S_out, "S_out");
+    ARGCHK(!(flags & GGL_COV_SCALE) || scale_out, "GGL_COV_SCALE needs scale_out");
+    HIPCHK(hipSetDevice(device));
+    const size_t n = (size_t)K * p * p;
+    DevBuf dS, dVar;
+    DevArr<int> dCnt;
+    HIPCHK(dS.alloc(n));
+    HIPCHK(dVar.alloc((size_t)K * p));
+    HIPCHK(dCnt.alloc(n));
+    rc = pairwise_to_device(nullptr, K, p, N, X_host, flags, min_pairs, dS.p, dCnt.p, dVar.p);
+    if (rc) return rc;
+    return pairwise_download(K, p, flags, dS.p, dCnt.p, dVar.p, S_out, scale_out, counts_out);
+}
+
+extern "C" int ggl_covariance_pairwise_subsets(int device, int p, int N, const double* X_host, int B, int b, const int* idx,
+                                               int flags, int min_pairs, double* S_out, double* scale_out, int* counts_out)
+{
+    int rc = check_subset_args(p, N, X_host, B, b, idx, flags);
+    if (rc) return rc;
+    rc = check_min_pairs(min_pairs, B, p);
+    if (rc) return rc;
+    ARGCHK(S_out, "S_out");
+    ARGCHK(!(flags & GGL_COV_SCALE) || scale_out, "GGL_COV_SCALE needs scale_out");
+    HIPCHK(hipSetDevice(device));
+    const size_t n = (size_t)B * p * p;
+    DevBuf dS, dVar;
+    DevArr<int> dCnt;
+    HIPCHK(dS.alloc(n));
+    HIPCHK(dVar.alloc((size_t)B * p));
+    HIPCHK(dCnt.alloc(n));
+    rc = pairwise_subsets_to_device(nullptr, p, N, X_host, B, b, idx, flags, min_pairs, dS.p, dCnt.p, dVar.p);
+    if (rc) return rc;
+    return pairwise_download(B, p, flags, dS.p, dCnt.p, dVar.p, S_out, scale_out, counts_out);
+}
+
+namespace {
+// the common end of the two ctx routes: B matrices built beside the ctx's S are installed (install_subset_S)
+int install_pairwise(ggl_ctx* c, const double* dS, const double* dVar, int B, int flags)
+{
+    std::vector<double> var;
+    if (flags & GGL_COV_SCALE) {
+        var.resize((size_t)B * c->p);
+        HIPCHK(hipMemcpyAsync(var.data(), dVar, var.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return install_subset_S(c, dS, B, var);
+}
+}  // namespace
+
+extern "C" int ggl_set_S_from_data_pairwise(ggl_ctx* c, const double* const* X_host, const int* N, int flags, int min_pairs)
+{
+    ARGCHK(c, "ctx");
+    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) takes its S from ggl_set_S");
+    int rc = check_data_args(c->K, c->p, N, X_host, flags);
+    if (rc) return rc;
+    rc = check_min_pairs(min_pairs, c->K, c->p);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    DROP_PRE(c);
+    // unlike ggl_set_S_from_data the K matrices are built beside the ctx's S: a refused call leaves the ctx as it was
+    DevBuf dS, dVar;
+    DevArr<int> dCnt;
+    HIPCHK(dS.alloc(c->n));
+    HIPCHK(dVar.alloc((size_t)c->K * c->p));
+    HIPCHK(dCnt.alloc(c->n));
+    rc = pairwise_to_device(c->stream, c->K, c->p, N, X_host, flags, min_pairs, dS.p, dCnt.p, dVar.p);
+    if (rc) return rc;
+    return install_pairwise(c, dS.p, dVar.p, c->K, flags);
+}
+
+extern "C" int ggl_set_S_from_subsets_pairwise(ggl_ctx* c, const double* X_host, int N, int B, int b, const int* idx, int flags,
+                                               int min_pairs)
+{
+    ARGCHK(c, "ctx");
+    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) takes its S from ggl_set_S");
+    int rc = check_subset_args(c->p, N, X_host, B, b, idx, flags);
+    if (rc) return rc;
+    rc = check_min_pairs(min_pairs, B, c->p);
+    if (rc) return rc;
+    if (c->K % B != 0) return fail(GGL_E_ARG, "bad argument: B = %d subsets do not divide the K = %d instances of the ctx", B, c->K);
+    HIPCHK(hipSetDevice(c->device));
+    DROP_PRE(c);
+    const size_t n = (size_t)B * c->p * c->p;
+    DevBuf dS, dVar;
+    DevArr<int> dCnt;
+    HIPCHK(dS.alloc(n));
+    HIPCHK(dVar.alloc((size_t)B * c->p));
+    HIPCHK(dCnt.alloc(n));
+    rc = pairwise_subsets_to_device(c->stream, c->p, N, X_host, B, b, idx, flags, min_pairs, dS.p, dCnt.p, dVar.p);
+    if (rc) return rc;
+    return install_pairwise(c, dS.p, dVar.p, B, flags);
+}

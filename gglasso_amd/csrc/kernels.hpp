@@ -521,6 +521,18 @@ static constexpr int GGL_DIAG_OK = 0x7f7f7f7f;
 void launch_scale_by_diag(hipStream_t st, const double* X, const double* d, double* Y, double* d_out, double* sd, int* err,
                           int K, int p);
 
+// Pairwise-complete covariance of data with missing values, NaN (covariance_missing.hip).  X as above, packed.
+// cnt, c (K,p): the observed entries of every row and their mean; *err (GGL_DIAG_OK from the caller) = smallest k * p + i of a
+// row without any
+void launch_row_stats_masked(hipStream_t st, const double* X, const long long* off, const int* N, double* c, int* cnt, int* err,
+                             int K, int p);
+// S (K,p,p) and counts (K,p,p) int32 = n_ij, both exactly symmetric; shift (K,p): the c above, null for the raw second moment
+// over the shared samples.  n_ij = 0 leaves a NaN in S: launch_pair_count_check decides whether S may be used
+void launch_gram_nt_pairwise(hipStream_t st, const double* X, const long long* off, const int* N, const double* shift, double* S,
+                             int* counts, int K, int p, int tile);
+// *err (every byte 0xff from the caller: none) = smallest (k * p + i) * p + j with counts < min_pairs
+void launch_pair_count_check(hipStream_t st, const int* counts, int min_pairs, unsigned long long* err, int K, int p);
+
 // StARS stability selection (stars.hip).  arena[r,i,c] = X[i, idx[r,c]]: X (p,N) row-major, idx (B,b) with every entry in
 // [0,N) (the caller checked), arena the packed stack of B (p,b) instances the covariance kernels above read
 void launch_gather_cols(hipStream_t st, const double* X, const int* idx, double* arena, int p, int N, int B, int b);

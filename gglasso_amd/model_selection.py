@@ -680,6 +680,17 @@ def _host_subset_covariances(X, idx, center, scale):
     return np.stack(out)
 
 
+def _host_pairwise_covariances(X, idx, center, scale, min_pairs):
+    """numpy counterpart of ``utils.sample_covariance_subsets(..., missing='pairwise')`` for engines without the device route."""
+    from . import utils
+    S, cnt = utils.host_pairwise_covariance(X, center, idx)
+    assert int(min_pairs) >= 1 and cnt.min() >= int(min_pairs), f"a pair of variables shares fewer than min_pairs = {min_pairs} samples"
+    if scale:
+        sd = np.sqrt(np.diagonal(S, axis1=1, axis2=2))
+        S = S / (sd[:, :, None] * sd[:, None, :])
+    return S
+
+
 def _host_edge_counts(Theta, t):
     """(L,p,p) int32 counts and (L,) int64 sums of StARS from a (L,B,p,p) stack: numpy counterpart of
     ``HipEngine.edge_stability`` (only the upper triangle of a Theta is read, a NaN is no edge)."""
@@ -691,7 +702,8 @@ def _host_edge_counts(Theta, t):
 
 
 def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.05, seed=0, indices=None, t=1e-8, center=True,
-                 scale=False, tol=1e-7, rtol=1e-7, max_iter=1000, store_all=False, lambdas_per_batch=None, correlation=None):
+                 scale=False, tol=1e-7, rtol=1e-7, max_iter=1000, store_all=False, lambdas_per_batch=None, correlation=None,
+                 missing=None, min_pairs=2):
     """StARS for the Single Graphical Lasso from observations ``X`` (p,N), variables in rows.  Returns ``(sol, stats)``.
 
     * Subsamples: ``stars_subsamples(N, n_subsamples, subsample_size, seed)``, or ``indices`` (B,b) given by the caller
@@ -712,12 +724,21 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     ``correlation='kendall'``: every ``S_r``, and the matrix of the final fit, is the nonparanormal skeptic matrix
     ``sin(pi/2 tau-b)`` of the observations (``utils.skeptic_correlation``; on the device ``ggl_set_S_from_kendall``) instead of
     the Pearson covariance -- invariant under monotone transforms of the variables, robust to outliers and ties.  ``center`` and
-    ``scale`` have no meaning then and must be left at their defaults.  The matrix may be indefinite; it is used as it is."""
+    ``scale`` have no meaning then and must be left at their defaults.  The matrix may be indefinite; it is used as it is.
+
+    ``missing='pairwise'``: a NaN in X is a missing value; every ``S_r`` and the matrix of the final fit are pairwise-complete
+    covariances (``utils.sample_covariance_subsets(..., missing='pairwise')``; on the device
+    ``ggl_set_S_from_subsets_pairwise``).  A subsample in which a pair of variables shares fewer than ``min_pairs`` samples is
+    refused, naming it.  Together with ``correlation='kendall'`` it is a ValueError."""
     import warnings
     from . import solver as _solver, utils
     from .batch import _sgl_batch_impl
     assert correlation in (None, 'kendall'), "correlation must be None (Pearson) or 'kendall'"
+    assert missing in (None, 'pairwise'), "missing must be None (complete data) or 'pairwise'"
     kendall = correlation == 'kendall'
+    pairwise = missing == 'pairwise'
+    if kendall and pairwise:
+        raise ValueError("missing='pairwise' with correlation='kendall': ranks of data with holes are not implemented")
     if kendall:
         assert center is True and scale is False, "correlation='kendall' has no use for center / scale: leave them at their defaults"
     X = np.ascontiguousarray(X, dtype=np.float64)
@@ -745,6 +766,8 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     THETA = np.zeros((L, B, p, p)) if store_all else None
     if on_device:
         S_host = None
+    elif pairwise:
+        S_host = _host_pairwise_covariances(X, idx, center, scale, min_pairs)
     else:
         S_host = utils.host_skeptic_correlation(X, idx) if kendall else _host_subset_covariances(X, idx, center, scale)
     for l0 in range(0, L, per):
@@ -756,6 +779,8 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
         def before(eng):
             if kendall:
                 eng.set_kendall_subsets(X, idx)
+            elif pairwise:
+                eng.set_data_subsets(X, idx, center=center, scale=scale, missing='pairwise', min_pairs=min_pairs)
             else:
                 eng.set_data_subsets(X, idx, center=center, scale=scale)
 
@@ -791,8 +816,10 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     ix, Dbar = stars_select(D, beta)
     if kendall:
         S_full = utils.skeptic_correlation(X) if on_device else utils.host_skeptic_correlation(X)
+    elif pairwise and not on_device:
+        S_full = _host_pairwise_covariances(X, np.arange(N)[None], center, scale, min_pairs)[0]
     elif on_device:
-        S_full = utils.sample_covariance(X, center=center, scale=scale)
+        S_full = utils.sample_covariance(X, center=center, scale=scale, **(dict(missing='pairwise', min_pairs=min_pairs) if pairwise else {}))
         S_full = S_full[0] if scale else S_full
     else:
         S_full = _host_subset_covariances(X, np.arange(N)[None], center, scale)[0]

@@ -144,7 +144,8 @@ class glasso_problem:
             self._to_correlations()
 
     @classmethod
-    def from_data(cls, X, *, reg="GGL", reg_params=None, latent=False, G=None, do_scaling=False, center=True, correlation=None):
+    def from_data(cls, X, *, reg="GGL", reg_params=None, latent=False, G=None, do_scaling=False, center=True, correlation=None,
+                  missing=None, min_pairs=2):
         """The problem of observations ``X``: (p,N), (K,p,N) or a list / dict of (p_k,N_k) arrays, variables in rows.
         ``N`` is read off the data and S is computed on the device (``utils.sample_covariance``).
 
@@ -152,23 +153,52 @@ class glasso_problem:
         (``utils.skeptic_correlation``: Kendall's tau-b on the int8 matrix cores) -- for data that are not Gaussian (counts,
         skewed or heavy-tailed measurements, ties).  It is a correlation matrix (unit diagonal; ``center`` has no meaning and
         must be left at its default) and it can be indefinite: the ADMM's log-det prox does not need a positive semidefinite
-        input, so the matrix is used as it is and no projection is applied."""
+        input, so the matrix is used as it is and no projection is applied.
+
+        ``missing='pairwise'``: a NaN in X is a missing value and S is every instance's pairwise-complete covariance
+        (``utils.sample_covariance(..., missing='pairwise', min_pairs=min_pairs)``); it can be indefinite as well and is used
+        as it is.  ``N`` stays the number of columns of the data, whatever is missing; the numbers of samples every pair
+        shares are kept in ``problem.pair_counts`` (of the kind of S).  Not with ``correlation='kendall'``."""
         assert correlation in (None, 'kendall'), "correlation must be None (Pearson) or 'kendall'"
+        assert missing in (None, 'pairwise'), "missing must be None (complete data) or 'pairwise'"
+        if missing == 'pairwise' and correlation == 'kendall':
+            raise ValueError("missing='pairwise' with correlation='kendall': ranks of data with holes are not implemented")
         _, Xs = utils._data_list(X)
         N = np.array([x.shape[1] for x in Xs])
+        counts = None
         if correlation == 'kendall':
             assert center is True, "correlation='kendall' has no use for center: leave it at its default"
             S = cls._skeptic(X)
+        elif missing == 'pairwise':
+            S, counts = cls._pairwise(X, center, min_pairs)
         else:
             S = utils.sample_covariance(X, center=center)
         if isinstance(S, dict) and G is None and len({s.shape[0] for s in S.values()}) == 1:
             S = np.stack([S[k] for k in range(len(S))])       # a list of instances of ONE dimension is a conforming stack
+            counts = None if counts is None else np.stack([counts[k] for k in range(len(counts))])
         if isinstance(S, np.ndarray) and S.ndim == 2:
             N = int(N[0])
         prob = cls(S, N, reg=reg, reg_params=reg_params, latent=latent, G=G, do_scaling=do_scaling)
         prob._observations, prob._center = Xs, center       # kept for resampling (stability_selection)
         prob._correlation = correlation
+        prob._missing, prob._min_pairs = missing, min_pairs
+        prob.pair_counts = counts
         return prob
+
+    @staticmethod
+    def _pairwise(X, center, min_pairs):
+        """(S, counts) of the pairwise-complete covariance, of the kind ``utils.sample_covariance`` returns; an engine without
+        the device route (``set_data_subsets``) takes the numpy products and refuses what the library refuses."""
+        if hasattr(_solver.ENGINE, "set_data_subsets"):
+            return utils.sample_covariance(X, center=center, missing='pairwise', min_pairs=min_pairs, return_counts=True)
+        kind, Xs = utils._data_list(X)
+        out = [utils.host_pairwise_covariance(x, center) for x in Xs]
+        assert int(min_pairs) >= 1 and all(c.min() >= int(min_pairs) for _, c in out), \
+            f"a pair of variables shares fewer than min_pairs = {min_pairs} samples"
+        S, C = [s for s, _ in out], [c for _, c in out]
+        if kind == "2d":
+            return S[0], C[0]
+        return (np.stack(S), np.stack(C)) if kind == "3d" else (dict(enumerate(S)), dict(enumerate(C)))
 
     @staticmethod
     def _skeptic(X):
@@ -310,7 +340,8 @@ class glasso_problem:
         ``self.reg_params['lambda1']`` is set to the choice, the estimate on all observations goes to ``self.solution`` and
         the instabilities to ``self.modelselect_stats``.  With ``do_scaling`` every subsample is scaled to its own
         correlations and the solution goes back to the covariances' scale, as in ``solve``.  A problem built with
-        ``correlation='kendall'`` resamples the skeptic matrix instead (``do_scaling`` has nothing to scale then)."""
+        ``correlation='kendall'`` resamples the skeptic matrix instead (``do_scaling`` has nothing to scale then); one built
+        with ``missing='pairwise'`` takes every subsample's, and the final fit's, pairwise-complete covariance."""
         assert getattr(self, '_observations', None) is not None, \
             "Stability selection resamples the observations: build the problem with glasso_problem.from_data(X)."
         assert not self.multiple, "Stability selection is implemented for Single Graphical Lasso problems only."
@@ -320,6 +351,8 @@ class glasso_problem:
             "Stability selection is not implemented with a lambda1_mask."
         how = dict(correlation='kendall') if getattr(self, '_correlation', None) == 'kendall' else \
             dict(center=self._center, scale=bool(self.do_scaling))
+        if getattr(self, '_missing', None) == 'pairwise':
+            how.update(missing='pairwise', min_pairs=self._min_pairs)
         sol, stats = _ms.stars_search(self._observations[0], self.modelselect_params['lambda1_range'],
                                       n_subsamples=n_subsamples, subsample_size=subsample_size, beta=beta, seed=seed,
                                       tol=tol, rtol=rtol, store_all=store_all, **how)

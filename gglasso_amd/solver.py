@@ -106,11 +106,15 @@ class HipEngine:
         self._norms_p = ptr(self._norms)
         self._ptr_cache = {}
 
-    def set_data(self, X, N=None, center=True, scale=False):
+    def set_data(self, X, N=None, center=True, scale=False, missing=None, min_pairs=2):
         """The ctx's S computed on the device from observations and left there (``ggl_set_S_from_data``): X a (K,p,N)
         array or a list of K (p,N_k) arrays, variables in rows; N (optional) the K sample counts, checked against the
-        data.  ``scale``: S becomes the correlations, ``get_S`` then also returns the variances."""
+        data.  ``scale``: S becomes the correlations, ``get_S`` then also returns the variances.
+        ``missing='pairwise'``: NaN is a missing value and S the pairwise-complete covariance
+        (``ggl_set_S_from_data_pairwise``, see ``utils.sample_covariance``); a refused call (a variable without observations, a
+        pair sharing fewer than ``min_pairs`` samples) leaves the ctx's S and variances as they were."""
         import ctypes
+        assert missing in (None, 'pairwise'), "missing must be None (complete data) or 'pairwise'"
         Xs = [as_c(x) for x in (X if isinstance(X, (list, tuple)) else np.asarray(X))]
         assert len(Xs) == self.K and all(x.ndim == 2 and x.shape[0] == self.p for x in Xs), \
             f"data must be {self.K} arrays of shape ({self.p}, N_k)"
@@ -118,22 +122,33 @@ class HipEngine:
         if N is not None:
             assert list(np.broadcast_to(np.asarray(N, dtype=int), (self.K,))) == Nk, f"N = {N} does not match the data ({Nk})"
         flags = (_lib.COV_CENTER if center else 0) | (_lib.COV_SCALE if scale else 0)
+        if missing == 'pairwise':
+            check(self.lib.ggl_set_S_from_data_pairwise(self.h, (_lib._dp * self.K)(*[ptr(x) for x in Xs]),
+                                                        (ctypes.c_int * self.K)(*Nk), flags, int(min_pairs)))
+            self._S_scaled = bool(scale)
+            return
         self._S_scaled = False              # the call drops the ctx's variances first, also where it fails
         check(self.lib.ggl_set_S_from_data(self.h, (_lib._dp * self.K)(*[ptr(x) for x in Xs]), (ctypes.c_int * self.K)(*Nk),
                                            flags))
         self._S_scaled = bool(scale)
 
-    def set_data_subsets(self, X, indices, center=True, scale=False):
+    def set_data_subsets(self, X, indices, center=True, scale=False, missing=None, min_pairs=2):
         """The ctx's S from column subsets of ONE data array, computed on the device (``ggl_set_S_from_subsets``): X (p,N),
         variables in rows, ``indices`` (B,b) ints with B a divisor of K; instance k gets ``cov(X[:, indices[k % B]])``.
-        A refused call (an index outside [0,N), say) leaves S as it was."""
+        A refused call (an index outside [0,N), say) leaves S as it was.  ``missing='pairwise'``: every subset's
+        pairwise-complete covariance (``ggl_set_S_from_subsets_pairwise``), as in ``set_data``."""
         from .utils import _subset_indices
+        assert missing in (None, 'pairwise'), "missing must be None (complete data) or 'pairwise'"
         X = as_c(X)
         assert X.ndim == 2 and X.shape[0] == self.p, f"data must be a ({self.p}, N) array"
         idx = _subset_indices(indices)
         flags = (_lib.COV_CENTER if center else 0) | (_lib.COV_SCALE if scale else 0)
-        check(self.lib.ggl_set_S_from_subsets(self.h, ptr(X), X.shape[1], idx.shape[0], idx.shape[1],
-                                              idx.ctypes.data_as(_lib._ip), flags))
+        if missing == 'pairwise':
+            check(self.lib.ggl_set_S_from_subsets_pairwise(self.h, ptr(X), X.shape[1], idx.shape[0], idx.shape[1],
+                                                           idx.ctypes.data_as(_lib._ip), flags, int(min_pairs)))
+        else:
+            check(self.lib.ggl_set_S_from_subsets(self.h, ptr(X), X.shape[1], idx.shape[0], idx.shape[1],
+                                                  idx.ctypes.data_as(_lib._ip), flags))
         self._S_scaled = bool(scale)
 
     def set_kendall_subsets(self, X, indices=None):

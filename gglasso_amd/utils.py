@@ -60,13 +60,25 @@ def _data_list(X):
     return kind, Xs
 
 
-def sample_covariance(X, center=True, scale=False, device=0):
+def sample_covariance(X, center=True, scale=False, device=0, missing=None, min_pairs=2, return_counts=False):
     """``numpy.cov(X_k, bias=True)`` of every instance on the device (FP64 matrix cores; bitwise symmetric and reproducible).
 
     X: (p,N), (K,p,N), or a list / dict (keys 0..K-1) of (p_k,N_k) arrays, variables in rows (the reference's ``sample[k]``).
     Returns S of the matching kind -- (p,p), (K,p,p), or a dict with keys 0..K-1.  ``center=False``: the raw second moment.
     ``scale=True``: the correlations, and as a second return value the variances (same kind, (p,), (K,p) or dict).
-    Instances of different dimension take one library call per distinct p_k."""
+    Instances of different dimension take one library call per distinct p_k.
+
+    ``missing='pairwise'``: a NaN in X is a missing value and S is the pairwise-complete covariance
+    (``ggl_covariance_pairwise``): entry (i,j) is the covariance of x_i and x_j over the ``n_ij`` samples where both are
+    observed, normalised by ``1/n_ij`` -- ``pandas.DataFrame(X.T).cov() * (n - 1) / n``.  S can be indefinite and is returned
+    as it is.  A variable without observations, or a pair with ``n_ij < min_pairs``, is refused, naming it.  ``scale=True``
+    divides by the diagonal of this S (each variable's variance over all its observed entries): unit diagonal, but an
+    off-diagonal entry can exceed 1 in magnitude.  ``return_counts=True``: the int32 ``n_ij`` come back as one more value of the
+    matching kind.  ``missing=None`` (default) is the complete-data path, where a NaN spreads over its row and column."""
+    assert missing in (None, 'pairwise'), "missing must be None (complete data) or 'pairwise'"
+    if missing == 'pairwise':
+        return _sample_covariance_pairwise(X, center, scale, device, min_pairs, return_counts)
+    assert not return_counts, "return_counts needs missing='pairwise' (on complete data every count is N)"
     kind, Xs = _data_list(X)
     flags = (_lib.COV_CENTER if center else 0) | (_lib.COV_SCALE if scale else 0)
     S, var = [None] * len(Xs), [None] * len(Xs)
@@ -107,17 +119,102 @@ def _covariance_subsets_call(X, idx, flags, device=0):
     return S, var
 
 
-def sample_covariance_subsets(X, indices, center=True, scale=False, device=0):
+def sample_covariance_subsets(X, indices, center=True, scale=False, device=0, missing=None, min_pairs=2, return_counts=False):
     """``numpy.cov(X[:, indices[r]], bias=True)`` for every row r of ``indices`` (B, b) on the device: X (p, N), variables in
     rows, goes up once and the columns are gathered there -- the subsamples of ``model_selection.stars_search``.  Duplicate
     indices are allowed (a bootstrap draw).  Returns S (B,p,p), bitwise what ``sample_covariance`` gives for the B gathered
-    arrays as one (B,p,b) stack; ``scale=True``: each subset's own correlations, and as a second value the variances (B,p)."""
+    arrays as one (B,p,b) stack; ``scale=True``: each subset's own correlations, and as a second value the variances (B,p).
+    ``missing='pairwise'``, ``min_pairs``, ``return_counts``: as in ``sample_covariance`` (the counts are (B,p,p) int32)."""
+    assert missing in (None, 'pairwise'), "missing must be None (complete data) or 'pairwise'"
     X = as_c(X)
     assert X.ndim == 2 and X.shape[0] >= 1 and X.shape[1] >= 1, \
         f"data must be a (p,N) array with variables in rows, has shape {X.shape}"
     flags = (_lib.COV_CENTER if center else 0) | (_lib.COV_SCALE if scale else 0)
+    if missing == 'pairwise':
+        S, var, cnt = _covariance_pairwise_subsets_call(X, _subset_indices(indices), flags, min_pairs, return_counts, device)
+        out = (S,) + ((var,) if scale else ()) + ((cnt,) if return_counts else ())
+        return out if len(out) > 1 else S
+    assert not return_counts, "return_counts needs missing='pairwise' (on complete data every count is b)"
     S, var = _covariance_subsets_call(X, _subset_indices(indices), flags, device)
     return (S, var) if scale else S
+
+
+# -----------------------------------------------------------------------------------------------------------------
+# Pairwise-complete covariance of data with missing values (NaN): csrc/covariance_missing.hip behind ggl_covariance_pairwise
+# -----------------------------------------------------------------------------------------------------------------
+def _covariance_pairwise_call(Xs, flags, min_pairs=2, counts=True, device=0):
+    """One ``ggl_covariance_pairwise`` call: ``Xs`` a list of C-contiguous float64 (p, N_k) arrays of one p.  Returns
+    (S (K,p,p), variances (K,p) or None, counts (K,p,p) int32 or None)."""
+    K, p = len(Xs), Xs[0].shape[0]
+    N = (ctypes.c_int * K)(*[x.shape[1] for x in Xs])
+    Xp = (_lib._dp * K)(*[ptr(x) for x in Xs])
+    S = np.empty((K, p, p))
+    var = np.empty((K, p)) if flags & _lib.COV_SCALE else None
+    cnt = np.empty((K, p, p), dtype=np.int32) if counts else None
+    _lib.require_gpu()
+    check(_lib.load().ggl_covariance_pairwise(int(device), K, p, N, Xp, int(flags), int(min_pairs), ptr(S), ptr(var),
+                                              None if cnt is None else cnt.ctypes.data_as(_lib._ip)))
+    return S, var, cnt
+
+
+def _covariance_pairwise_subsets_call(X, idx, flags, min_pairs=2, counts=True, device=0):
+    """One ``ggl_covariance_pairwise_subsets`` call: X C-contiguous float64 (p, N), idx C-contiguous int32 (B, b).  Returns
+    (S (B,p,p), variances (B,p) or None, counts (B,p,p) int32 or None)."""
+    (p, N), (B, b) = X.shape, idx.shape
+    S = np.empty((B, p, p))
+    var = np.empty((B, p)) if flags & _lib.COV_SCALE else None
+    cnt = np.empty((B, p, p), dtype=np.int32) if counts else None
+    _lib.require_gpu()
+    check(_lib.load().ggl_covariance_pairwise_subsets(int(device), p, N, ptr(X), B, b, idx.ctypes.data_as(_lib._ip), int(flags),
+                                                      int(min_pairs), ptr(S), ptr(var),
+                                                      None if cnt is None else cnt.ctypes.data_as(_lib._ip)))
+    return S, var, cnt
+
+
+def _sample_covariance_pairwise(X, center, scale, device, min_pairs, return_counts):
+    """``sample_covariance(..., missing='pairwise')``: one library call per distinct p_k, results of the matching kind."""
+    kind, Xs = _data_list(X)
+    flags = (_lib.COV_CENTER if center else 0) | (_lib.COV_SCALE if scale else 0)
+    S, var, cnt = [None] * len(Xs), [None] * len(Xs), [None] * len(Xs)
+    for p in sorted({x.shape[0] for x in Xs}):
+        idx = [k for k, x in enumerate(Xs) if x.shape[0] == p]
+        Sp, vp, cp = _covariance_pairwise_call([Xs[k] for k in idx], flags, min_pairs, return_counts, device)
+        for j, k in enumerate(idx):
+            S[k] = Sp[j]
+            var[k] = vp[j] if scale else None
+            cnt[k] = cp[j] if return_counts else None
+    out = [S] + ([var] if scale else []) + ([cnt] if return_counts else [])
+    if kind == "2d":
+        out = [a[0] for a in out]
+    elif kind == "3d":
+        out = [np.stack(a) for a in out]
+    else:
+        out = [{k: np.array(a[k]) for k in range(len(Xs))} for a in out]
+    return tuple(out) if len(out) > 1 else out[0]
+
+
+def host_pairwise_covariance(X, center=True, indices=None):
+    """numpy counterpart of ``sample_covariance(..., missing='pairwise', return_counts=True)`` for one (p,N) array (engines
+    without the device route): the four products of the kernel, ``P = Y Y^T, A = Y W^T, B = W Y^T, C = W W^T`` with ``y = x - c``
+    (c: the mean of a row's observed entries) where observed and 0 where missing, ``w`` the mask, and
+    ``S = (P - A B / C) / C`` (``center=False``: ``y = x``, ``S = P / C``).  Returns ``(S, counts)``: (p,p) arrays, or (B,p,p) with
+    ``indices`` (B,b).  A pair without a shared sample gives NaN; nothing is refused here."""
+    X = np.asarray(X, dtype=np.float64)
+    assert X.ndim == 2, f"data must be a (p,N) array with variables in rows, has shape {X.shape}"
+    subsets = [X] if indices is None else [X[:, np.asarray(ix)] for ix in np.asarray(indices)]
+    S, cnt = [], []
+    for Xr in subsets:
+        obs = ~np.isnan(Xr)
+        W = obs.astype(np.float64)
+        n_row = np.maximum(W.sum(axis=1, keepdims=True), 1.0)
+        X0 = np.where(obs, Xr, 0.0)
+        Y = np.where(obs, Xr - X0.sum(axis=1, keepdims=True) / n_row, 0.0) if center else X0
+        C = W @ W.T
+        with np.errstate(invalid='ignore', divide='ignore'):
+            S.append((Y @ Y.T - (Y @ W.T) * (W @ Y.T) / C) / C if center else (Y @ Y.T) / C)
+        cnt.append(np.rint(C).astype(np.int32))
+    S, cnt = np.stack(S), np.stack(cnt)
+    return (S[0], cnt[0]) if indices is None else (S, cnt)
 
 
 # -----------------------------------------------------------------------------------------------------------------

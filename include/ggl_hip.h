@@ -28,7 +28,8 @@ extern "C" {
  * Entry points and selector values that are only ADDED (GGL_REG_FSGL, ggl_set_block_size, ggl_prox_sum_frob,
  * ggl_frob_norm_per_block, ggl_fsgl_stats, ggl_covariance, ggl_scale_by_diagonal, ggl_set_S_from_data, ggl_get_S, ggl_kkt_terms,
  * ggl_diag_stats, ggl_covariance_subsets, ggl_set_S_from_subsets, ggl_edge_stability, ggl_kendall_counts, ggl_kendall_skeptic,
- * ggl_set_S_from_kendall) leave every existing layout alone and the number where it is. */
+ * ggl_set_S_from_kendall, ggl_covariance_pairwise, ggl_covariance_pairwise_subsets, ggl_set_S_from_data_pairwise,
+ * ggl_set_S_from_subsets_pairwise) leave every existing layout alone and the number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -794,6 +795,34 @@ int ggl_kendall_skeptic(int device, int p, int N, const int *ranks_host, int B, 
  * that of the call above (layout and bookkeeping of ggl_set_S_from_subsets; the ctx keeps no variances).  GGL_E_ARG also for
  * a B that does not divide K and for a ctx with instance dimensions; a refused call leaves the ctx's S as it was. */
 int ggl_set_S_from_kendall(ggl_ctx *ctx, const int *ranks_host, int N, int B, int b, const int *idx);
+
+/* ---- Pairwise-complete covariance of data with missing values (covariance_missing.hip).  Entry points that are only ADDED:
+ * GGL_VERSION stays where it is.
+ *
+ * A NaN entry of X is a missing value (+-Inf is a value, as in pandas; a pair that involves it is not finite).  For every pair
+ * (i,j), the diagonal included, over the samples O_ij where both x_i and x_j are observed, n_ij = |O_ij|:
+ *     S_ij = (1/n_ij) sum_{O_ij} (x_in - m_i|j)(x_jn - m_j|i),  m_i|j the mean of x_i over O_ij      (GGL_COV_CENTER)
+ *     S_ij = (1/n_ij) sum_{O_ij} x_in x_jn                                                            (without)
+ * -- R's cov(use = "pairwise.complete.obs") and pandas' DataFrame.cov() up to the factor (n_ij - 1) / n_ij.  S may be
+ * indefinite; it is returned as it is.  Arguments, layouts and flags as ggl_covariance; counts_out (K,p,p) ints or NULL: n_ij.
+ * S and the counts are exactly symmetric, two calls give the same bits, instance k's result does not depend on the others;
+ * on data without NaN the counts all equal N[k].  GGL_COV_SCALE divides by the diagonal of THIS S, the variance of each
+ * variable over all its observed entries, and returns it in scale_out: the diagonal becomes 1, but an off-diagonal entry,
+ * whose covariance comes from other samples than the two variances, can exceed 1 in magnitude.
+ * GGL_E_ARG, the message naming the offender: min_pairs < 1; a variable without any observed entry (instance, variable); a
+ * pair with n_ij < min_pairs (instance, pair).  A refused call writes nothing to S_out, scale_out, counts_out. */
+int ggl_covariance_pairwise(int device, int K, int p, const int *N, const double *const *X_host, int flags, int min_pairs,
+                            double *S_out, double *scale_out, int *counts_out);
+/* ... of B column subsets of ONE data array (arguments of ggl_covariance_subsets): subset r's matrix is bitwise what the call
+ * above returns for the gathered (p,b) array in a call of K = B instances; the messages name the subset. */
+int ggl_covariance_pairwise_subsets(int device, int p, int N, const double *X_host, int B, int b, const int *idx, int flags,
+                                    int min_pairs, double *S_out, double *scale_out, int *counts_out);
+/* ... straight into the S of a ctx (bookkeeping of ggl_set_S_from_subsets: the matrices are built beside the ctx's S and
+ * installed once every check has passed).  Unlike ggl_set_S_from_data, a refused call leaves the ctx's S, its variances and
+ * what was built for them as they were. */
+int ggl_set_S_from_data_pairwise(ggl_ctx *ctx, const double *const *X_host, const int *N, int flags, int min_pairs);
+int ggl_set_S_from_subsets_pairwise(ggl_ctx *ctx, const double *X_host, int N, int B, int b, const int *idx, int flags,
+                                    int min_pairs);
 
 #ifdef __cplusplus
 }
