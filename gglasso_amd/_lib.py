@@ -27,6 +27,7 @@ NS_MIN_P = 8          # GGL_EIG_AUTO: matrix-function Omega- / L-step for p abov
 BUF_S, BUF_OMEGA, BUF_THETA, BUF_L, BUF_X, BUF_GROUPSQ, BUF_NORMS, BUF_OMEGA_PREV = range(8)
 E_ARG, E_HIP, E_SOLVER, E_ALLOC, E_COMM = -1, -2, -3, -4, -5
 COV_CENTER, COV_SCALE, COV_TILE32, COV_TILE64 = 1, 2, 4, 8      # flags of ggl_covariance / ggl_set_S_from_data
+COV_FULL_RANGE = 16                                              # ggl_covariance_weighted only: loop over all N samples
 PHASES = ("form_W", "eig_omega", "recon_omega", "theta", "eig_L", "recon_L", "dual", "reduce", "eig_omega2", "bound",
           "allreduce_groupsq", "allreduce_norms")
 
@@ -164,6 +165,8 @@ _SIGNATURES = {
     "ggl_covariance_pairwise_subsets": ([_i, _i, _i, _dp, _i, _i, _ip, _i, _i, _dp, _dp, _ip], _i),
     "ggl_set_S_from_data_pairwise": ([_vp, ctypes.POINTER(_dp), _ip, _i, _i], _i),
     "ggl_set_S_from_subsets_pairwise": ([_vp, _dp, _i, _i, _i, _ip, _i, _i], _i),
+    "ggl_covariance_weighted": ([_i, _i, _i, _dp, _i, _dp, _i, _dp, _dp, _dp], _i),
+    "ggl_set_S_from_weighted": ([_vp, _dp, _i, _dp, _i], _i),
 }
 
 # libggl_hip_dev.so only (-DGGL_DEV)

@@ -650,3 +650,127 @@ extern "C" int ggl_set_S_from_subsets_pairwise(ggl_ctx* c, const double* X_host,
     if (rc) return rc;
     return install_pairwise(c, dS.p, dVar.p, B, flags);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Weighted covariance of ONE data array under K weight rows (kernels: covariance_weighted.hip): X and the weights go up
+// once, every instance reads the same X.  Every route builds S in a buffer of its own; the caller's S_out, or the S of a ctx,
+// is written only after the weight check and (GGL_COV_SCALE) the variance check have passed.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int WCOV_FLAGS = COV_FLAGS | GGL_COV_FULL_RANGE;
+
+int check_weighted_args(int p, int N, const double* X_host, int K, const double* w_host, int flags)
+{
+    ARGCHK(p >= 1 && N >= 1, "p >= 1, N >= 1");
+    if (K < 1 || K > 65535) return fail(GGL_E_ARG, "bad argument: K = %d weight rows, 1 .. 65535 are possible", K);
+    ARGCHK(X_host && w_host, "X, w");
+    ARGCHK((flags & ~WCOV_FLAGS) == 0,
+           "flags: unknown bits (GGL_COV_CENTER | GGL_COV_SCALE | GGL_COV_TILE32 | GGL_COV_TILE64 | GGL_COV_FULL_RANGE)");
+    ARGCHK(!((flags & GGL_COV_TILE32) && (flags & GGL_COV_TILE64)), "flags: GGL_COV_TILE32 and GGL_COV_TILE64 exclude each other");
+    ARGCHK((size_t)K * p < (size_t)GGL_DIAG_OK, "K * p too large");
+    return GGL_OK;
+}
+
+// S_dev (K,p,p), var_dev (K,p) with GGL_COV_SCALE and wsum_dev (K) on stream st; the arguments have been checked.  Waits for
+// the stream: the tables go away behind it.  tc: the ctx whose event timeline (ggl_trace_start) takes the marks 30 / 31 in front
+// of and behind the Gram launch, or null.
+int weighted_to_device(hipStream_t st, int p, int N, const double* X_host, int K, const double* w_host, int flags, double* S_dev,
+                       double* var_dev, double* wsum_dev, ggl_ctx* tc = nullptr)
+{
+    DevArr<double> dX, dW, dR, dMean, dSd;
+    DevArr<int> dRng, dErr;
+    DevArr<unsigned long long> dWErr;
+    const size_t kn = (size_t)K * N;
+    HIPCHK(dX.alloc((size_t)p * N));
+    HIPCHK(dW.alloc(kn));
+    HIPCHK(dR.alloc(kn));
+    HIPCHK(dRng.alloc(2 * (size_t)K));
+    HIPCHK(dWErr.alloc(1));
+    HIPCHK(hipMemcpyAsync(dX.p, X_host, (size_t)p * N * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dW.p, w_host, kn * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(dWErr.p, 0xff, sizeof(unsigned long long), st));
+    launch_weight_prepare(st, dW.p, dR.p, wsum_dev, dRng.p, dWErr.p, K, N, (flags & GGL_COV_FULL_RANGE) != 0);
+    HIPCHK(hipGetLastError());
+    unsigned long long werr = ~0ull;
+    HIPCHK(hipMemcpyAsync(&werr, dWErr.p, sizeof(werr), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (werr != ~0ull) {
+        if (werr < kn)
+            return fail(GGL_E_ARG, "bad argument: instance %d, sample %d holds the weight %g; weights must be non-negative and finite",
+                        (int)(werr / N), (int)(werr % N), w_host[werr]);
+        const int k = (int)(werr - kn);
+        double W = 0.0;
+        HIPCHK(hipMemcpy(&W, wsum_dev + k, sizeof(double), hipMemcpyDeviceToHost));
+        return fail(GGL_E_ARG, "bad argument: the weights of instance %d sum to %g; every weight row needs a positive finite sum", k, W);
+    }
+    const bool center = (flags & GGL_COV_CENTER) != 0;
+    if (center) {
+        HIPCHK(dMean.alloc((size_t)K * p));
+        launch_row_means_weighted(st, dX.p, dW.p, wsum_dev, dRng.p, dMean.p, K, p, N);
+        HIPCHK(hipGetLastError());
+    }
+    const int tile = (flags & GGL_COV_TILE64) ? 64 : ((flags & GGL_COV_TILE32) ? 32 : 0);
+    if (tc) trace_mark(tc, st, 30);
+    launch_gram_nt_weighted(st, dX.p, dR.p, wsum_dev, dRng.p, center ? dMean.p : nullptr, S_dev, K, p, N, tile);
+    HIPCHK(hipGetLastError());
+    if (tc) trace_mark(tc, st, 31);
+    if (flags & GGL_COV_SCALE) {
+        HIPCHK(dSd.alloc((size_t)K * p));
+        HIPCHK(dErr.alloc(1));
+        HIPCHK(hipMemsetAsync(dErr.p, 0x7f, sizeof(int), st));
+        launch_scale_by_diag(st, S_dev, nullptr, S_dev, var_dev, dSd.p, dErr.p, K, p);
+        HIPCHK(hipGetLastError());
+        int rc = diag_error(st, dErr.p, p, nullptr, S_dev, "the weighted variance");
+        if (rc) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return GGL_OK;
+}
+}  // namespace
+
+extern "C" int ggl_covariance_weighted(int device, int p, int N, const double* X_host, int K, const double* w_host, int flags,
+                                       double* S_out, double* scale_out, double* wsum_out)
+{
+    int rc = check_weighted_args(p, N, X_host, K, w_host, flags);
+    if (rc) return rc;
+    ARGCHK(S_out, "S_out");
+    ARGCHK(!(flags & GGL_COV_SCALE) || scale_out, "GGL_COV_SCALE needs scale_out");
+    HIPCHK(hipSetDevice(device));
+    const size_t n = (size_t)K * p * p;
+    DevBuf dS, dVar, dWsum;
+    HIPCHK(dS.alloc(n));
+    HIPCHK(dVar.alloc((size_t)K * p));
+    HIPCHK(dWsum.alloc(K));
+    rc = weighted_to_device(nullptr, p, N, X_host, K, w_host, flags, dS.p, dVar.p, dWsum.p);
+    if (rc) return rc;
+    DOWN(S_out, dS.p, n);
+    if (flags & GGL_COV_SCALE) DOWN(scale_out, dVar.p, (size_t)K * p);
+    if (wsum_out) DOWN(wsum_out, dWsum.p, K);
+    return GGL_OK;
+}
+
+extern "C" int ggl_set_S_from_weighted(ggl_ctx* c, const double* X_host, int N, const double* w_host, int flags)
+{
+    ARGCHK(c, "ctx");
+    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) takes its S from ggl_set_S");
+    int rc = check_weighted_args(c->p, N, X_host, c->K, w_host, flags);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    DROP_PRE(c);
+    // as ggl_set_S_from_subsets: the K matrices are built beside the ctx's S; a refused call (a bad weight, a constant variable
+    // under GGL_COV_SCALE) leaves S, its variances and what was built for them as they were
+    const size_t kp = (size_t)c->K * c->p;
+    DevBuf dS, dVar, dWsum;
+    HIPCHK(dS.alloc(c->n));
+    HIPCHK(dVar.alloc(kp));
+    HIPCHK(dWsum.alloc(c->K));
+    rc = weighted_to_device(c->stream, c->p, N, X_host, c->K, w_host, flags, dS.p, dVar.p, dWsum.p, c);
+    if (rc) return rc;
+    std::vector<double> var;
+    if (flags & GGL_COV_SCALE) {
+        var.resize(kp);
+        HIPCHK(hipMemcpyAsync(var.data(), dVar.p, kp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return install_subset_S(c, dS.p, c->K, var);
+}

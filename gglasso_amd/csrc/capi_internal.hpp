@@ -15,7 +15,7 @@
 //   capi_ext.hip        ext_ADMM_MGL (instances of different dimension)
 //   capi_ops.hip        stateless operator entry points, development probes
 //   capi_data.hip       sample covariance from data and from column subsets of one data array, scaling by a diagonal
-//                       (stateless and into a ctx's S)
+//                       (stateless and into a ctx's S); rank correlation, pairwise-complete and weighted covariance
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>

@@ -533,6 +533,19 @@ void launch_gram_nt_pairwise(hipStream_t st, const double* X, const long long* o
 // *err (every byte 0xff from the caller: none) = smallest (k * p + i) * p + j with counts < min_pairs
 void launch_pair_count_check(hipStream_t st, const int* counts, int min_pairs, unsigned long long* err, int K, int p);
 
+// Weighted covariance of ONE (p,N) array X under K weight rows w (K,N) (covariance_weighted.hip).
+// r (K,N) = sqrt(w), wsum (K) = W_k, rng (K,2) = the support [lo, hi) of every row (full: [0, N)); *err (every byte 0xff from
+// the caller: none) = smallest k * N + n of a negative or non-finite weight, else K * N + k of a row with W_k zero or not finite
+void launch_weight_prepare(hipStream_t st, const double* w, double* r, double* wsum, int* rng, unsigned long long* err, int K,
+                           int N, bool full);
+// mean (K,p) = (1/W_k) sum_n w[k,n] X[i,n] over the range of instance k
+void launch_row_means_weighted(hipStream_t st, const double* X, const double* w, const double* wsum, const int* rng,
+                               double* mean, int K, int p, int N);
+// S (K,p,p) = (1/W_k) sum_n (r (x - m))(r (x - m))^T over the range of instance k, exactly symmetric; mean null: the weighted
+// raw second moment.  tile as launch_gram_nt
+void launch_gram_nt_weighted(hipStream_t st, const double* X, const double* r, const double* wsum, const int* rng,
+                             const double* mean, double* S, int K, int p, int N, int tile);
+
 // StARS stability selection (stars.hip).  arena[r,i,c] = X[i, idx[r,c]]: X (p,N) row-major, idx (B,b) with every entry in
 // [0,N) (the caller checked), arena the packed stack of B (p,b) instances the covariance kernels above read
 void launch_gather_cols(hipStream_t st, const double* X, const int* idx, double* arena, int p, int N, int B, int b);

@@ -10,6 +10,8 @@ implementation is this package's own:
 * ``do_scaling`` (covariances -> correlations, and Theta, L back) goes through the device kernel (``ggl_scale_by_diagonal``).
 * ``glasso_problem.from_data(X, ...)`` starts from observations: S comes from ``utils.sample_covariance``, or with
   ``correlation='kendall'`` from ``utils.skeptic_correlation`` (rank based).
+* ``glasso_problem.from_time_series(X, at, bandwidth, ...)`` starts from ONE series with time stamps: S is the stack of
+  kernel-smoothed covariances (``utils.kernel_covariance``), the input of the Fused Graphical Lasso for time-varying networks.
 """
 import numbers
 import warnings
@@ -183,6 +185,30 @@ class glasso_problem:
         prob._correlation = correlation
         prob._missing, prob._min_pairs = missing, min_pairs
         prob.pair_counts = counts
+        return prob
+
+    @classmethod
+    def from_time_series(cls, X, at, bandwidth, *, times=None, kernel='gaussian', cutoff=2.0 ** -53, reg='FGL', reg_params=None,
+                         latent=False, do_scaling=False, center=True):
+        """The time-varying problem of ONE series ``X`` (p,N), a column per observation with time stamps ``times`` (default
+        ``0..N-1``): S is the stack of kernel-smoothed covariances at the K points ``at`` (an integer K, or an array of times)
+        with bandwidth ``bandwidth`` (``utils.kernel_covariance``, computed on the device from one upload of X), and ``N`` the
+        vector of Kish's effective sample sizes -- kernel smoothing followed by the Fused Graphical Lasso (Zhou, Lafferty,
+        Wasserman 2010; Monti et al. 2014).  ``problem.weights`` (K,N) and ``problem.eval_times`` (K,) are kept.  K = 1 gives a
+        Single Graphical Lasso problem.  The observations are not kept: ``stability_selection`` needs ``from_data``."""
+        Xc = utils.as_c(X)
+        assert Xc.ndim == 2 and Xc.shape[0] >= 1 and Xc.shape[1] >= 1, \
+            f"data must be a (p,N) array with variables in rows, has shape {Xc.shape}"
+        _, eval_times, w = utils._kernel_setup(Xc.shape[1], at, bandwidth, times, kernel, cutoff)
+        if hasattr(_solver.ENGINE, "set_data_weighted"):
+            S = utils.weighted_covariance(Xc, w, center=center)
+        else:
+            S = utils.host_weighted_covariance(Xc, w, center)
+        n_eff = utils.effective_sample_size(w)
+        if S.shape[0] == 1:
+            S, n_eff = S[0], float(n_eff[0])
+        prob = cls(S, n_eff, reg=reg, reg_params=reg_params, latent=latent, do_scaling=do_scaling)
+        prob.weights, prob.eval_times = w, eval_times
         return prob
 
     @staticmethod

@@ -151,6 +151,19 @@ class HipEngine:
                                                   idx.ctypes.data_as(_lib._ip), flags))
         self._S_scaled = bool(scale)
 
+    def set_data_weighted(self, X, weights, center=True, scale=False):
+        """The ctx's S as weighted covariances of ONE data array, computed on the device (``ggl_set_S_from_weighted``): X (p,N),
+        variables in rows, ``weights`` (K,N) non-negative; instance k gets ``numpy.cov(X, aweights=weights[k], bias=True)`` --
+        with ``utils.kernel_weights`` the kernel-smoothed stack of a time series.  X goes up once.  A refused call (a negative
+        weight, a row of zeros, a constant variable under ``scale``) leaves the ctx's S and variances as they were."""
+        X = as_c(X)
+        assert X.ndim == 2 and X.shape[0] == self.p, f"data must be a ({self.p}, N) array"
+        w = as_c(weights)
+        assert w.shape == (self.K, X.shape[1]), f"weights must be ({self.K}, {X.shape[1]}), have shape {w.shape}"
+        flags = (_lib.COV_CENTER if center else 0) | (_lib.COV_SCALE if scale else 0)
+        check(self.lib.ggl_set_S_from_weighted(self.h, ptr(X), X.shape[1], ptr(w), flags))
+        self._S_scaled = bool(scale)
+
     def set_kendall_subsets(self, X, indices=None):
         """The ctx's S as skeptic matrices ``sin(pi/2 tau-b)`` of column subsets of ONE data array, computed on the device
         (``ggl_set_S_from_kendall``): X (p,N), variables in rows, ``indices`` (B,b) ints with B a divisor of K (None: all

@@ -1,5 +1,6 @@
 """Utilities on the device: the block norms of the Functional Graphical Lasso (reference: helper/utils.py:69-107 of
-fabian-sp/GGLasso) and the sample covariance of observations (what helper/data_generation.py:221,234 gets from numpy.cov)."""
+fabian-sp/GGLasso), the sample covariance of observations (what helper/data_generation.py:221,234 gets from numpy.cov), its
+rank-based, pairwise-complete and weighted forms, and the kernel-smoothed covariance stack of a time series."""
 import ctypes
 
 import numpy as np
@@ -334,3 +335,133 @@ def skeptic_correlation(X, indices=None, device=0):
     be positive semidefinite.  A variable that is constant (over a subset) is refused, naming it.  Arguments and the kind of
     the result as ``kendall_counts``."""
     return _kendall_per_instance(X, indices, lambda R, idx: _kendall_call(R, idx, True, device)[1])
+
+
+# -----------------------------------------------------------------------------------------------------------------
+# Weighted covariance of one data array under K weight rows, and the kernel-smoothed covariance stack of a time series
+# (Zhou, Lafferty, Wasserman 2010; Monti et al. 2014 "SINGLE"): csrc/covariance_weighted.hip behind ggl_covariance_weighted.
+#     W_k = sum_n w_kn,  m_k = (1/W_k) sum_n w_kn x_n,  S_k = (1/W_k) sum_n w_kn (x_n - m_k)(x_n - m_k)^T
+# -----------------------------------------------------------------------------------------------------------------
+def _weights_2d(weights, N):
+    """(the C-contiguous float64 (K,N) array of ``weights``, whether it was given as one (N,) row)."""
+    w = as_c(weights)
+    assert w.ndim in (1, 2) and w.shape[-1] == N and w.size >= 1, \
+        f"weights must be (N,) or (K,N) with N = {N}, have shape {w.shape}"
+    return (w[None], True) if w.ndim == 1 else (w, False)
+
+
+def _covariance_weighted_call(X, w, flags, device=0):
+    """One ``ggl_covariance_weighted`` call: X C-contiguous float64 (p,N), w C-contiguous float64 (K,N).  Returns
+    (S (K,p,p), variances (K,p) or None, W (K,))."""
+    (p, N), K = X.shape, w.shape[0]
+    S = np.empty((K, p, p))
+    var = np.empty((K, p)) if flags & _lib.COV_SCALE else None
+    wsum = np.empty(K)
+    _lib.require_gpu()
+    check(_lib.load().ggl_covariance_weighted(int(device), p, N, ptr(X), K, ptr(w), int(flags), ptr(S), ptr(var), ptr(wsum)))
+    return S, var, wsum
+
+
+def weighted_covariance(X, weights, center=True, scale=False, device=0, return_wsum=False):
+    """``numpy.cov(X, aweights=weights[k], bias=True)`` for every row of ``weights`` on the device (FP64 matrix cores):
+    ``S_k = (1/W_k) sum_n w_kn (x_n - m_k)(x_n - m_k)^T`` with ``W_k = sum_n w_kn`` and the weighted mean ``m_k``.
+
+    X: (p,N), variables in rows; it goes up once and is shared by all rows.  ``weights``: (N,) gives (p,p), (K,N) gives (K,p,p);
+    non-negative and finite, every row with a positive sum (anything else is refused, naming row and sample).  Only the
+    samples between a row's first and last positive weight are visited.  S is exactly symmetric, positive semidefinite up to
+    rounding, and the same bits on every call.  ``center=False``: the weighted raw second moment.  ``scale=True``: the
+    correlations, and as a second value the weighted variances ((p,) or (K,p)).  ``return_wsum=True``: the ``W_k`` the kernels
+    used as one more value."""
+    X = as_c(X)
+    assert X.ndim == 2 and X.shape[0] >= 1 and X.shape[1] >= 1, \
+        f"data must be a (p,N) array with variables in rows, has shape {X.shape}"
+    w, one = _weights_2d(weights, X.shape[1])
+    flags = (_lib.COV_CENTER if center else 0) | (_lib.COV_SCALE if scale else 0)
+    S, var, wsum = _covariance_weighted_call(X, w, flags, device)
+    out = (S,) + ((var,) if scale else ()) + ((wsum,) if return_wsum else ())
+    if one:
+        out = tuple(a[0] for a in out)
+    return out if len(out) > 1 else out[0]
+
+
+def host_weighted_covariance(X, weights, center=True):
+    """numpy counterpart of ``weighted_covariance`` (engines without the device route): the same formula, two passes.
+    Returns (p,p) for (N,) weights, (K,p,p) for (K,N).  Nothing is refused here but a shape."""
+    X = np.asarray(X, dtype=np.float64)
+    assert X.ndim == 2, f"data must be a (p,N) array with variables in rows, has shape {X.shape}"
+    w, one = _weights_2d(weights, X.shape[1])
+    S = []
+    for wk in w:
+        W = wk.sum()
+        Xc = X - (X @ wk / W)[:, None] if center else X
+        S.append((Xc * wk) @ Xc.T / W)
+    return S[0] if one else np.stack(S)
+
+
+def kernel_weights(times, at, bandwidth, kernel='gaussian', cutoff=2.0 ** -53):
+    """The (K,N) weights ``w_kn = kappa((times[n] - at[k]) / h_k)`` of kernel smoothing at the K points ``at``.
+
+    ``kernel``: 'gaussian' ``exp(-u^2/2)``, 'epanechnikov' ``max(0, 1 - u^2)``, 'uniform' ``|u| <= 1``.  ``bandwidth``: one
+    positive number, or one per point of ``at``.  An entry below ``cutoff * max_n w_kn`` becomes exactly 0: that gives the
+    Gaussian a finite support (about 8.6 h wide at the default), which is what ``weighted_covariance`` visits.  ``times`` need
+    not be sorted, but a row's support -- first to last positive weight, as positions in ``times`` -- is only tight when it is:
+    with shuffled times every row spans nearly all samples and the device visits them all."""
+    t = np.asarray(times, dtype=np.float64)
+    a = np.atleast_1d(np.asarray(at, dtype=np.float64))
+    assert t.ndim == 1 and t.size >= 1 and a.ndim == 1 and a.size >= 1, "times must be (N,), at must be (K,)"
+    assert np.isfinite(t).all() and np.isfinite(a).all(), "times and at must be finite"
+    h = np.broadcast_to(np.asarray(bandwidth, dtype=np.float64), a.shape)
+    assert np.all(h > 0) and np.isfinite(h).all(), "bandwidth must be positive and finite"
+    assert kernel in ('gaussian', 'epanechnikov', 'uniform'), "kernel must be 'gaussian', 'epanechnikov' or 'uniform'"
+    assert 0 <= cutoff < 1, "cutoff must lie in [0, 1)"
+    u = (t[None, :] - a[:, None]) / h[:, None]
+    if kernel == 'gaussian':
+        w = np.exp(-0.5 * u * u)
+    elif kernel == 'epanechnikov':
+        w = np.maximum(0.0, 1.0 - u * u)
+    else:
+        w = (np.abs(u) <= 1.0).astype(np.float64)
+    w[w < cutoff * w.max(axis=1, keepdims=True)] = 0.0
+    return w
+
+
+def effective_sample_size(weights):
+    """Kish's effective sample size ``W_k^2 / sum_n w_kn^2`` of every weight row, as floats: (K,) for (K,N) weights, a float for
+    (N,).  N for equal weights, 1 for a single non-zero weight."""
+    w = np.asarray(weights, dtype=np.float64)
+    assert w.ndim in (1, 2), f"weights must be (N,) or (K,N), have shape {w.shape}"
+    n = w.sum(axis=-1) ** 2 / (w * w).sum(axis=-1)
+    return float(n) if w.ndim == 1 else n
+
+
+def _kernel_setup(N, at, bandwidth, times, kernel, cutoff):
+    """(times, evaluation points, weights (K,N)) of ``kernel_covariance``."""
+    assert bandwidth is not None, "kernel_covariance needs a bandwidth"
+    assert at is not None, "kernel_covariance needs the evaluation points: at = K, or an array of times"
+    t = np.arange(N, dtype=np.float64) if times is None else np.asarray(times, dtype=np.float64)
+    assert t.shape == (N,), f"times must have one entry per column of X, ({N},), has shape {t.shape}"
+    if isinstance(at, (int, np.integer)) and not isinstance(at, bool):
+        assert at >= 1, "at = K needs K >= 1"
+        a = np.linspace(t.min(), t.max(), int(at)) if at > 1 else np.array([0.5 * (t.min() + t.max())])
+    else:
+        a = np.atleast_1d(np.asarray(at, dtype=np.float64))
+    return t, a, kernel_weights(t, a, bandwidth, kernel, cutoff)
+
+
+def kernel_covariance(X, at=None, bandwidth=None, times=None, kernel='gaussian', cutoff=2.0 ** -53, center=True, scale=False,
+                      device=0):
+    """The kernel-smoothed covariance stack of a time series on the device: ``S_k = weighted_covariance(X, w_k)`` with
+    ``w_k = kernel_weights(times, at, bandwidth, kernel, cutoff)[k]`` -- the input of a Fused Graphical Lasso for time-varying
+    networks (Zhou, Lafferty, Wasserman 2010; Monti et al. 2014).
+
+    X: (p,N), one column per observation; ``times`` (N,) its time stamps, default ``0..N-1``.  ``at``: an integer K (that many
+    equally spaced points over the range of ``times``) or an array of evaluation times.  ``bandwidth`` is required (one number
+    or one per point); choosing it is left to the caller.  Returns ``(S (K,p,p), n_eff (K,))`` with Kish's effective sample size
+    per point, and with ``scale=True`` ``(S, n_eff, variances (K,p))``."""
+    X = as_c(X)
+    assert X.ndim == 2 and X.shape[0] >= 1 and X.shape[1] >= 1, \
+        f"data must be a (p,N) array with variables in rows, has shape {X.shape}"
+    _, _, w = _kernel_setup(X.shape[1], at, bandwidth, times, kernel, cutoff)
+    out = weighted_covariance(X, w, center=center, scale=scale, device=device)
+    n_eff = effective_sample_size(w)
+    return (out[0], n_eff, out[1]) if scale else (out, n_eff)

@@ -29,7 +29,8 @@ extern "C" {
  * ggl_frob_norm_per_block, ggl_fsgl_stats, ggl_covariance, ggl_scale_by_diagonal, ggl_set_S_from_data, ggl_get_S, ggl_kkt_terms,
  * ggl_diag_stats, ggl_covariance_subsets, ggl_set_S_from_subsets, ggl_edge_stability, ggl_kendall_counts, ggl_kendall_skeptic,
  * ggl_set_S_from_kendall, ggl_covariance_pairwise, ggl_covariance_pairwise_subsets, ggl_set_S_from_data_pairwise,
- * ggl_set_S_from_subsets_pairwise) leave every existing layout alone and the number where it is. */
+ * ggl_set_S_from_subsets_pairwise, ggl_covariance_weighted, ggl_set_S_from_weighted) leave every existing layout alone and the
+ * number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -592,7 +593,8 @@ int ggl_fsgl_stats(ggl_ctx *ctx, long long out[4]);
  * recording and returns rows {kind 0 device / 1 host, lane (0 main stream, 1.. part streams; -1 host), tag, microseconds since the
  * start}.  Device rows give the COMPLETION time of the launch they follow.  Device tags: 1 parameter copy, 2 form_W, 3 bound_rows,
  * 4 cw_final, 10 product, 11 pair of products, 20 Theta-step, 21 norm reduction; host tags: 100 step entered, 101 Theta-step and
- * reduction queued, 102 early first part queued, 103 residuals seen, 104 rest of the next chain queued (the step returns). */
+ * reduction queued, 102 early first part queued, 103 residuals seen, 104 rest of the next chain queued (the step returns).
+ * ggl_set_S_from_weighted adds the device tags 30 (weights prepared, means done) and 31 (its Gram kernel done). */
 int ggl_trace_start(ggl_ctx *ctx, int max_events);
 int ggl_trace_read(ggl_ctx *ctx, double *out, int cap);
 /* per-instance status of the last eigensolver launch a step fetched: sweeps of the LDS Jacobi kernel (-1: not converged) or
@@ -823,6 +825,35 @@ int ggl_covariance_pairwise_subsets(int device, int p, int N, const double *X_ho
 int ggl_set_S_from_data_pairwise(ggl_ctx *ctx, const double *const *X_host, const int *N, int flags, int min_pairs);
 int ggl_set_S_from_subsets_pairwise(ggl_ctx *ctx, const double *X_host, int N, int B, int b, const int *idx, int flags,
                                     int min_pairs);
+
+/* ---- Weighted covariance of ONE data array under K weight rows (covariance_weighted.hip): the kernel-smoothed covariance
+ * stack of a time series (Zhou, Lafferty, Wasserman 2010; Monti et al. 2014), observation weights, EM responsibilities.  Entry
+ * points that are only ADDED: GGL_VERSION stays where it is.
+ *
+ * X_host the row-major (p,N) array, variables in rows; w_host the row-major (K,N) array of non-negative weights.  Per row k:
+ *     W_k = sum_n w_kn,   m_k = (1/W_k) sum_n w_kn x_n,   S_k = (1/W_k) sum_n w_kn (x_n - m_k)(x_n - m_k)^T    (GGL_COV_CENTER)
+ *     S_k = (1/W_k) sum_n w_kn x_n x_n^T                                                                        (without)
+ * -- numpy.cov(X, aweights=w_k, bias=True).  X goes up once and is read by all K instances.  S_k is the Gram matrix of
+ * sqrt(w_kn) (x_n - m_k): exactly symmetric and positive semidefinite up to rounding.  Instance k visits the samples between
+ * the first and the last positive weight of its row only (from the multiple of 64 at or below the first), so the work follows
+ * the support of the weights; on finite data the result is bitwise that of the loop over all N samples, which
+ * GGL_COV_FULL_RANGE (tests, measurements) runs.  Fixed reduction orders: two calls give the same bits, and instance k's
+ * result depends on X and row k alone.  A non-finite entry of X inside a support spreads over its row and column as in
+ * ggl_covariance; outside every support its effect is unspecified (it is dropped by default and spreads with
+ * GGL_COV_FULL_RANGE).
+ * S_out (K,p,p); scale_out (K,p) or NULL (needed with GGL_COV_SCALE): the weighted variances; wsum_out (K) or NULL: the W_k the
+ * kernels used.  flags as ggl_covariance, and GGL_COV_FULL_RANGE.
+ * GGL_E_ARG, the message naming the offender: p, N or K < 1 (K <= 65535), a NULL buffer, an unknown flag bit, both TILE flags; a
+ * negative or non-finite weight (instance, sample); a weight row whose sum is zero or not finite (instance); with GGL_COV_SCALE
+ * a variable of zero or non-finite variance under that row's weights (instance, variable).  A refused call writes nothing to
+ * S_out, scale_out, wsum_out. */
+#define GGL_COV_FULL_RANGE 16 /* every instance loops over all N samples (tests, measurements) */
+int ggl_covariance_weighted(int device, int p, int N, const double *X_host, int K, const double *w_host, int flags,
+                            double *S_out, double *scale_out, double *wsum_out);
+/* ... straight into the S of a ctx, K the ctx's (bookkeeping of ggl_set_S_from_subsets: the matrices are built beside the
+ * ctx's S and installed once every check has passed; the variances are kept with GGL_COV_SCALE).  A refused call leaves the
+ * ctx's S, its variances and what was built for them as they were. */
+int ggl_set_S_from_weighted(ggl_ctx *ctx, const double *X_host, int N, const double *w_host, int flags);
 
 #ifdef __cplusplus
 }
