@@ -167,6 +167,8 @@ _SIGNATURES = {
     "ggl_set_S_from_subsets_pairwise": ([_vp, _dp, _i, _i, _i, _ip, _i, _i], _i),
     "ggl_covariance_weighted": ([_i, _i, _i, _dp, _i, _dp, _i, _dp, _dp, _dp], _i),
     "ggl_set_S_from_weighted": ([_vp, _dp, _i, _dp, _i], _i),
+    "ggl_mixed_correlation": ([_i, _i, _i, _ip, _ip, _i, _i, _ip, _d, _dp, ctypes.POINTER(ctypes.c_longlong), _ip, _ip], _i),
+    "ggl_set_S_from_mixed": ([_vp, _ip, _ip, _i, _i, _i, _ip, _d], _i),
 }
 
 # libggl_hip_dev.so only (-DGGL_DEV)

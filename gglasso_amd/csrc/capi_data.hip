@@ -346,7 +346,7 @@ int check_kendall_args(int p, int N, const int* ranks_host, int B, int b, const 
 // G_dev (B,p,p) int64 on stream st, and with S_dev the skeptic matrices (B,p,p) -- GGL_E_ARG naming subset and variable where
 // a variable is constant over a subset, S_dev is not written then.  The arguments have been checked.  Waits for the stream.
 int kendall_to_device(hipStream_t st, int p, int N, const int* ranks_host, int B, int b, const int* idx, long long* G_dev,
-                      double* S_dev)
+                      double* S_dev, DevArr<int>* keep = nullptr)
 {
     DevArr<int> dR, dA, dIdx, dErr;
     HIPCHK(dR.alloc((size_t)p * N));
@@ -362,6 +362,8 @@ int kendall_to_device(hipStream_t st, int p, int N, const int* ranks_host, int B
     }
     launch_kendall_counts(st, Rg, G_dev, B, p, b);
     HIPCHK(hipGetLastError());
+    // keep: the caller goes on with the B packed (p,b) rank arrays the counts were taken from (the mixed route), and owns them
+    if (keep) std::swap(keep->p, idx ? dA.p : dR.p);
     if (S_dev) {
         HIPCHK(dErr.alloc(1));
         HIPCHK(hipMemsetAsync(dErr.p, 0x7f, sizeof(int), st));
@@ -429,6 +431,113 @@ extern "C" int ggl_set_S_from_kendall(ggl_ctx* c, const int* ranks_host, int N, 
     rc = kendall_to_device(c->stream, c->p, N, ranks_host, B, b, idx, dG.p, dS.p);
     if (rc) return rc;
     return install_subset_S(c, dS.p, B, {});
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Latent correlation of mixed binary / continuous data (kernels: bridge.hip): the counts of the route above, the zero counts
+// of the binary variables from the same gathered ranks, and one root of the bridge function per pair of variables
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+int check_mixed_args(int p, int N, const int* ranks_host, const int* types, int B, int b, const int* idx, double clip)
+{
+    int rc = check_kendall_args(p, N, ranks_host, B, b, idx);
+    if (rc) return rc;
+    ARGCHK(types, "types");
+    if (!(clip > 0.0 && clip < 1.0)) return fail(GGL_E_ARG, "bad argument: clip = %g, outside (0, 1)", clip);
+    for (int i = 0; i < p; ++i) {
+        if (types[i] != 0 && types[i] != 1)
+            return fail(GGL_E_ARG, "bad argument: types[%d] = %d, a variable is continuous (0) or binary (1)", i, types[i]);
+        int top = 0;
+        for (int n = 0; n < N; ++n) top = std::max(top, ranks_host[(size_t)i * N + n]);
+        if (top == 0)
+            return fail(GGL_E_ARG, "bad argument: variable %d is constant (every rank is 0); the rank correlation needs every "
+                        "variable to vary", i);
+        if (types[i] == 1 && top > 1)
+            return fail(GGL_E_ARG, "bad argument: variable %d is marked binary and holds the rank %d; a binary variable has the "
+                        "dense ranks 0 and 1", i, top);
+    }
+    return GGL_OK;
+}
+
+// S_dev (B,p,p), G_dev (B,p,p), n0_dev (B,p), clip_dev (B) on stream st -- GGL_E_ARG naming subset and variable where a variable
+// takes one value over a subset; S_dev is not written then.  The arguments have been checked.  Waits for the stream.
+int mixed_to_device(hipStream_t st, int p, int N, const int* ranks_host, const int* types, int B, int b, const int* idx,
+                    double clip, double* S_dev, long long* G_dev, int* n0_dev, int* clip_dev)
+{
+    DevArr<int> dRg, dT, dErr;
+    HIPCHK(dT.alloc(p));
+    HIPCHK(dErr.alloc(1));
+    HIPCHK(hipMemcpyAsync(dT.p, types, (size_t)p * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(dErr.p, 0x7f, sizeof(int), st));
+    int rc = kendall_to_device(st, p, N, ranks_host, B, b, idx, G_dev, nullptr, &dRg);
+    if (rc) return rc;
+    launch_bridge_zero_counts(st, dRg.p, n0_dev, dErr.p, B, p, b);
+    HIPCHK(hipGetLastError());
+    launch_bridge_invert(st, G_dev, n0_dev, dT.p, S_dev, clip_dev, dErr.p, B, p, b, clip);
+    HIPCHK(hipGetLastError());
+    int err = GGL_DIAG_OK;
+    HIPCHK(hipMemcpyAsync(&err, dErr.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (err != GGL_DIAG_OK)
+        return fail(GGL_E_ARG, "bad argument: variable %d is constant over subset %d (%s); the latent correlation needs every "
+                    "variable to vary", err % p, err / p, types[err % p] ? "a binary variable with one of its two values only"
+                    : "no untied pair of samples");
+    return GGL_OK;
+}
+
+struct MixedBufs {
+    DevBuf S;
+    DevArr<long long> G;
+    DevArr<int> n0, clipped;
+    int alloc(int B, int p)
+    {
+        const size_t n = (size_t)B * p * p;
+        HIPCHK(S.alloc(n));
+        HIPCHK(G.alloc(n));
+        HIPCHK(n0.alloc((size_t)B * p));
+        HIPCHK(clipped.alloc(B));
+        return GGL_OK;
+    }
+};
+}  // namespace
+
+extern "C" int ggl_mixed_correlation(int device, int p, int N, const int* ranks_host, const int* types, int B, int b,
+                                     const int* idx, double clip, double* S_out, long long* G_out, int* n0_out, int* clipped_out)
+{
+    int rc = check_mixed_args(p, N, ranks_host, types, B, b, idx, clip);
+    if (rc) return rc;
+    ARGCHK(S_out, "S_out");
+    HIPCHK(hipSetDevice(device));
+    MixedBufs d;
+    rc = d.alloc(B, p);
+    if (rc) return rc;
+    rc = mixed_to_device(nullptr, p, N, ranks_host, types, B, b, idx, clip, d.S.p, d.G.p, d.n0.p, d.clipped.p);
+    if (rc) return rc;
+    const size_t n = (size_t)B * p * p;
+    DOWN(S_out, d.S.p, n);
+    if (G_out) HIPCHK(hipMemcpy(G_out, d.G.p, n * sizeof(long long), hipMemcpyDeviceToHost));
+    if (n0_out) HIPCHK(hipMemcpy(n0_out, d.n0.p, (size_t)B * p * sizeof(int), hipMemcpyDeviceToHost));
+    if (clipped_out) HIPCHK(hipMemcpy(clipped_out, d.clipped.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+    return GGL_OK;
+}
+
+extern "C" int ggl_set_S_from_mixed(ggl_ctx* c, const int* ranks_host, const int* types, int N, int B, int b, const int* idx,
+                                    double clip)
+{
+    ARGCHK(c, "ctx");
+    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) takes its S from ggl_set_S");
+    int rc = check_mixed_args(c->p, N, ranks_host, types, B, b, idx, clip);
+    if (rc) return rc;
+    if (c->K % B != 0) return fail(GGL_E_ARG, "bad argument: B = %d subsets do not divide the K = %d instances of the ctx", B, c->K);
+    HIPCHK(hipSetDevice(c->device));
+    DROP_PRE(c);
+    // as ggl_set_S_from_kendall: the B matrices are built beside the ctx's S; a refused call leaves S alone
+    MixedBufs d;
+    rc = d.alloc(B, c->p);
+    if (rc) return rc;
+    rc = mixed_to_device(c->stream, c->p, N, ranks_host, types, B, b, idx, clip, d.S.p, d.G.p, d.n0.p, d.clipped.p);
+    if (rc) return rc;
+    return install_subset_S(c, d.S.p, B, {});
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

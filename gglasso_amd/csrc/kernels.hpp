@@ -565,4 +565,14 @@ void launch_kendall_counts(hipStream_t st, const int* Rg, long long* G, int B, i
 // G[r,i,i] = 0 (a variable constant over the subset), then S is not written
 void launch_kendall_skeptic(hipStream_t st, const long long* G, double* S, int* err, int B, int p);
 
+// Latent correlation of mixed binary / continuous data (bridge.hip).  Rg: B packed (p,b) rank arrays; types (p): 1 binary (ranks
+// 0 / 1), 0 continuous.  n0 (B,p) = the samples of rank 0 of every variable over every subset, exact; *err (set to GGL_DIAG_OK
+// by the caller) = smallest r * p + i of a variable that takes one value only over subset r
+void launch_bridge_zero_counts(hipStream_t st, const int* Rg, int* n0, int* err, int B, int p, int b);
+// S[r,i,j] = the root in [-clip, clip] of the bridge function F(.; Delta_i, Delta_j) = G_ij / (b (b - 1) / 2), Delta = the
+// normal quantile of n0 / b (continuous pairs: sin(pi/2 tau-a)); every unordered pair solved once and written twice, diagonal 1.
+// clipped (B ints, zeroed here) = the pairs of every subset that ended on +-clip.  Nothing is written where *err is raised
+void launch_bridge_invert(hipStream_t st, const long long* G, const int* n0, const int* types, double* S, int* clipped,
+                          const int* err, int B, int p, int b, double clip);
+
 }  // namespace ggl

@@ -729,18 +729,24 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     ``missing='pairwise'``: a NaN in X is a missing value; every ``S_r`` and the matrix of the final fit are pairwise-complete
     covariances (``utils.sample_covariance_subsets(..., missing='pairwise')``; on the device
     ``ggl_set_S_from_subsets_pairwise``).  A subsample in which a pair of variables shares fewer than ``min_pairs`` samples is
-    refused, naming it.  Together with ``correlation='kendall'`` it is a ValueError."""
+    refused, naming it.  Together with ``correlation='kendall'`` or ``'mixed'`` it is a ValueError.
+
+    ``correlation='mixed'``: every ``S_r``, and the matrix of the final fit, is the latent correlation matrix of mixed binary /
+    continuous data (``utils.mixed_correlation``; on the device ``ggl_set_S_from_mixed``).  The types are fixed once, from all N
+    observations: a variable with exactly two distinct values is binary.  A subsample over which a variable is constant is
+    refused, naming both.  ``center`` and ``scale`` as with ``'kendall'``."""
     import warnings
     from . import solver as _solver, utils
     from .batch import _sgl_batch_impl
-    assert correlation in (None, 'kendall'), "correlation must be None (Pearson) or 'kendall'"
+    assert correlation in (None, 'kendall', 'mixed'), "correlation must be None (Pearson), 'kendall' or 'mixed'"
     assert missing in (None, 'pairwise'), "missing must be None (complete data) or 'pairwise'"
-    kendall = correlation == 'kendall'
+    kendall, mixed = correlation == 'kendall', correlation == 'mixed'
     pairwise = missing == 'pairwise'
-    if kendall and pairwise:
-        raise ValueError("missing='pairwise' with correlation='kendall': ranks of data with holes are not implemented")
-    if kendall:
-        assert center is True and scale is False, "correlation='kendall' has no use for center / scale: leave them at their defaults"
+    if (kendall or mixed) and pairwise:
+        raise ValueError(f"missing='pairwise' with correlation='{correlation}': ranks of data with holes are not implemented")
+    if kendall or mixed:
+        assert center is True and scale is False, \
+            f"correlation='{correlation}' has no use for center / scale: leave them at their defaults"
     X = np.ascontiguousarray(X, dtype=np.float64)
     assert X.ndim == 2, f"data must be a (p,N) array with variables in rows, has shape {X.shape}"
     p, N = X.shape
@@ -757,15 +763,19 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     B, b = idx.shape
     L = lam.size
     per = L if lambdas_per_batch is None else max(1, int(lambdas_per_batch))
-    on_device = hasattr(_solver.ENGINE, "set_kendall_subsets" if kendall else "set_data_subsets") and \
+    route = "set_kendall_subsets" if kendall else ("set_mixed_subsets" if mixed else "set_data_subsets")
+    on_device = hasattr(_solver.ENGINE, route) and \
         hasattr(_solver.ENGINE, "edge_stability")
     eye = np.eye(p)
     NUM = np.zeros(L, dtype=np.int64)
     failed = np.zeros(L, dtype=bool)
     COUNTS = np.zeros((L, p, p), dtype=np.int32) if store_all else None
     THETA = np.zeros((L, B, p, p)) if store_all else None
+    types = utils.variable_types(X) if mixed else None          # of all observations: a subsample does not change a type
     if on_device:
         S_host = None
+    elif mixed:
+        S_host = utils.host_mixed_correlation(X, types, idx)
     elif pairwise:
         S_host = _host_pairwise_covariances(X, idx, center, scale, min_pairs)
     else:
@@ -779,6 +789,8 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
         def before(eng):
             if kendall:
                 eng.set_kendall_subsets(X, idx)
+            elif mixed:
+                eng.set_mixed_subsets(X, idx, types=types)
             elif pairwise:
                 eng.set_data_subsets(X, idx, center=center, scale=scale, missing='pairwise', min_pairs=min_pairs)
             else:
@@ -816,6 +828,8 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     ix, Dbar = stars_select(D, beta)
     if kendall:
         S_full = utils.skeptic_correlation(X) if on_device else utils.host_skeptic_correlation(X)
+    elif mixed:
+        S_full = utils.mixed_correlation(X, types) if on_device else utils.host_mixed_correlation(X, types)
     elif pairwise and not on_device:
         S_full = _host_pairwise_covariances(X, np.arange(N)[None], center, scale, min_pairs)[0]
     elif on_device:

@@ -9,7 +9,8 @@ implementation is this package's own:
   solved as batches (``ADMM_SGL_batch`` / ``ADMM_MGL_batch`` / ``ext_ADMM_MGL_batch``) instead of a sequential walk.
 * ``do_scaling`` (covariances -> correlations, and Theta, L back) goes through the device kernel (``ggl_scale_by_diagonal``).
 * ``glasso_problem.from_data(X, ...)`` starts from observations: S comes from ``utils.sample_covariance``, or with
-  ``correlation='kendall'`` from ``utils.skeptic_correlation`` (rank based).
+  ``correlation='kendall'`` from ``utils.skeptic_correlation`` (rank based), with ``correlation='mixed'`` from
+  ``utils.mixed_correlation`` (binary beside continuous variables).
 * ``glasso_problem.from_time_series(X, at, bandwidth, ...)`` starts from ONE series with time stamps: S is the stack of
   kernel-smoothed covariances (``utils.kernel_covariance``), the input of the Fused Graphical Lasso for time-varying networks.
 """
@@ -160,17 +161,26 @@ class glasso_problem:
         ``missing='pairwise'``: a NaN in X is a missing value and S is every instance's pairwise-complete covariance
         (``utils.sample_covariance(..., missing='pairwise', min_pairs=min_pairs)``); it can be indefinite as well and is used
         as it is.  ``N`` stays the number of columns of the data, whatever is missing; the numbers of samples every pair
-        shares are kept in ``problem.pair_counts`` (of the kind of S).  Not with ``correlation='kendall'``."""
-        assert correlation in (None, 'kendall'), "correlation must be None (Pearson) or 'kendall'"
+        shares are kept in ``problem.pair_counts`` (of the kind of S).  Not with ``correlation='kendall'`` or ``'mixed'``.
+
+        ``correlation='mixed'``: S is every instance's latent correlation matrix of mixed binary / continuous data
+        (``utils.mixed_correlation``: a variable with exactly two distinct values is binary; Kendall's tau-a inverted through
+        the bridge function of each pair's types) -- for presence / absence or yes / no variables beside continuous ones, where
+        Pearson attenuates and the skeptic bridge is wrong.  ``center`` as with ``'kendall'``; the matrix can be indefinite and
+        is used as it is."""
+        assert correlation in (None, 'kendall', 'mixed'), "correlation must be None (Pearson), 'kendall' or 'mixed'"
         assert missing in (None, 'pairwise'), "missing must be None (complete data) or 'pairwise'"
-        if missing == 'pairwise' and correlation == 'kendall':
-            raise ValueError("missing='pairwise' with correlation='kendall': ranks of data with holes are not implemented")
+        if missing == 'pairwise' and correlation in ('kendall', 'mixed'):
+            raise ValueError(f"missing='pairwise' with correlation='{correlation}': ranks of data with holes are not implemented")
         _, Xs = utils._data_list(X)
         N = np.array([x.shape[1] for x in Xs])
         counts = None
         if correlation == 'kendall':
             assert center is True, "correlation='kendall' has no use for center: leave it at its default"
             S = cls._skeptic(X)
+        elif correlation == 'mixed':
+            assert center is True, "correlation='mixed' has no use for center: leave it at its default"
+            S = cls._mixed(X)
         elif missing == 'pairwise':
             S, counts = cls._pairwise(X, center, min_pairs)
         else:
@@ -234,6 +244,16 @@ class glasso_problem:
             return utils.skeptic_correlation(X)
         kind, Xs = utils._data_list(X)
         S = [utils.host_skeptic_correlation(x) for x in Xs]
+        return S[0] if kind == "2d" else (np.stack(S) if kind == "3d" else dict(enumerate(S)))
+
+    @staticmethod
+    def _mixed(X):
+        """The latent correlation matrices of mixed data, of the kind ``utils.sample_covariance`` returns; an engine without
+        the device route (``set_mixed_subsets``) takes the numpy twin."""
+        if hasattr(_solver.ENGINE, "set_mixed_subsets"):
+            return utils.mixed_correlation(X)
+        kind, Xs = utils._data_list(X)
+        S = [utils.host_mixed_correlation(x) for x in Xs]
         return S[0] if kind == "2d" else (np.stack(S) if kind == "3d" else dict(enumerate(S)))
 
     def __repr__(self):
@@ -366,7 +386,7 @@ class glasso_problem:
         ``self.reg_params['lambda1']`` is set to the choice, the estimate on all observations goes to ``self.solution`` and
         the instabilities to ``self.modelselect_stats``.  With ``do_scaling`` every subsample is scaled to its own
         correlations and the solution goes back to the covariances' scale, as in ``solve``.  A problem built with
-        ``correlation='kendall'`` resamples the skeptic matrix instead (``do_scaling`` has nothing to scale then); one built
+        ``correlation='kendall'`` or ``'mixed'`` resamples that matrix instead (``do_scaling`` has nothing to scale then); one built
         with ``missing='pairwise'`` takes every subsample's, and the final fit's, pairwise-complete covariance."""
         assert getattr(self, '_observations', None) is not None, \
             "Stability selection resamples the observations: build the problem with glasso_problem.from_data(X)."
@@ -375,7 +395,7 @@ class glasso_problem:
         self.set_modelselect_params(modelselect_params)
         assert self.modelselect_params.get('lambda1_mask') is None and self.reg_params.get('lambda1_mask') is None, \
             "Stability selection is not implemented with a lambda1_mask."
-        how = dict(correlation='kendall') if getattr(self, '_correlation', None) == 'kendall' else \
+        how = dict(correlation=self._correlation) if getattr(self, '_correlation', None) in ('kendall', 'mixed') else \
             dict(center=self._center, scale=bool(self.do_scaling))
         if getattr(self, '_missing', None) == 'pairwise':
             how.update(missing='pairwise', min_pairs=self._min_pairs)

@@ -179,6 +179,22 @@ class HipEngine:
                                               None if idx is None else idx.ctypes.data_as(_lib._ip)))
         self._S_scaled = False
 
+    def set_mixed_subsets(self, X, indices=None, types=None, clip=0.999):
+        """The ctx's S as latent correlation matrices of mixed binary / continuous data (``utils.mixed_correlation``) of column
+        subsets of ONE data array, computed on the device (``ggl_set_S_from_mixed``): X, ``indices`` and the layout as
+        ``set_kendall_subsets``; ``types`` (p,) 1 binary / 0 continuous (None: a variable with two distinct values is binary).
+        A refused call (a variable constant over a subset, a bad ``types`` or ``clip``) leaves S as it was."""
+        from .utils import _mixed_types, _subset_indices, dense_ranks
+        X = as_c(X)
+        assert X.ndim == 2 and X.shape[0] == self.p, f"data must be a ({self.p}, N) array"
+        R = dense_ranks(X)
+        t = _mixed_types(R, types)
+        idx = None if indices is None else _subset_indices(indices)
+        B, b = (1, X.shape[1]) if idx is None else idx.shape
+        check(self.lib.ggl_set_S_from_mixed(self.h, R.ctypes.data_as(_lib._ip), t.ctypes.data_as(_lib._ip), X.shape[1], B, b,
+                                            None if idx is None else idx.ctypes.data_as(_lib._ip), float(clip)))
+        self._S_scaled = False
+
     def edge_stability(self, B, t=1e-8, counts=False):
         """StARS over the Theta snapshots of a batch of K = L * B points (instance l * B + r: subsample r at lambda l):
         the (L,) int64 array ``sum_{i<j} c (B - c)`` of the selection counts ``c[l,i,j] = #{r : |Theta| >= t}``, exact; with

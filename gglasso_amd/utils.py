@@ -338,6 +338,222 @@ def skeptic_correlation(X, indices=None, device=0):
 
 
 # -----------------------------------------------------------------------------------------------------------------
+# Latent correlation of mixed binary / continuous data: the Gaussian copula model of Fan, Liu, Ning, Zou (2017), the
+# estimator of R's mixedCCA / latentcor.  A binary variable is 1{Z > Delta} of a latent normal Z, a continuous one an
+# increasing transform of it.  With Kendall's tau-a = G_ij / (n (n - 1) / 2) of the counts above and Delta = the normal
+# quantile of the share of a binary variable's smaller value, the latent correlation r of a pair solves F(r) = tau:
+#     binary, binary:       F(r) = (1/pi) int_0^{asin r}          g(t; Delta_i, Delta_j) dt
+#     binary, continuous:   F(r) = (2/pi) int_0^{asin(r/sqrt 2)}  g(t; Delta, 0) dt
+#     continuous pair:      r = sin(pi/2 tau)
+#     g(t; h, k) = exp(-(h^2 + k^2 - 2 h k sin t) / (2 cos^2 t))
+# The library evaluates the integral by a 64-node Gauss-Legendre rule, one node per lane (csrc/bridge.hip).
+# -----------------------------------------------------------------------------------------------------------------
+# the 64-node Gauss-Legendre rule on [0, 1] (nodes (1 + x) / 2, weights w / 2): the table of csrc/bridge.hip
+_GL64_U = np.array([
+    0.0003474791321139303, 0.0018299416140223604, 0.00449331426162784, 0.008331873057687022,
+    0.013336586105044517, 0.01949560017397314, 0.026794312570798593, 0.035215413934030215,
+    0.044738931460748595, 0.055342277002442944, 0.06700030092295359, 0.07968535187370981,
+    0.09336734243860122, 0.1080138205283293, 0.12359004636973406, 0.1400590749141946,
+    0.15738184347288336, 0.17551726437267132, 0.19442232241380336, 0.21405217689868297,
+    0.23436026799005272, 0.2552984271464735, 0.27681699137326793, 0.2988649210180042,
+    0.32138992083116596, 0.34433856400489454, 0.3676564188956163, 0.39128817812999644,
+    0.41517778978800357, 0.4392685903519397, 0.4635034391061005, 0.48782485366828776,
+    0.5121751463317122, 0.5364965608938995, 0.5607314096480602, 0.5848222102119964,
+    0.6087118218700035, 0.6323435811043837, 0.6556614359951055, 0.6786100791688341,
+    0.7011350789819958, 0.723183008626732, 0.7447015728535265, 0.7656397320099473,
+    0.7859478231013171, 0.8055776775861966, 0.8244827356273287, 0.8426181565271166,
+    0.8599409250858054, 0.876409953630266, 0.8919861794716707, 0.9066326575613988,
+    0.9203146481262902, 0.9329996990770464, 0.944657722997557, 0.9552610685392514,
+    0.9647845860659698, 0.9732056874292014, 0.9805043998260269, 0.9866634138949555,
+    0.991668126942313, 0.9955066857383722, 0.9981700583859776, 0.999652520867886])
+_GL64_V = np.array([
+    0.0008916403608482165, 0.002073516630281234, 0.0032522289844891814, 0.0044233799131819735,
+    0.005584069730065564, 0.006731523948359321, 0.007863015238012359, 0.008975857887848672,
+    0.010067411576765104, 0.011135086904191627, 0.012176351284355437, 0.01318873485752733,
+    0.014169836307129742, 0.015117328536201239, 0.016028964177425775, 0.016902580918570803,
+    0.017736106628441193, 0.018527564270120023, 0.019275076589307813, 0.01997687056636017,
+    0.020631281621311764, 0.021236757561826795, 0.021791862264661725, 0.022295279081878283,
+    0.02274581396370907, 0.023142398290657208, 0.02348409140810501, 0.023770082857415154,
+    0.023999694298229155, 0.024172381117401477, 0.024287733720751714, 0.024345478504569862,
+    0.024345478504569862, 0.024287733720751714, 0.024172381117401477, 0.023999694298229155,
+    0.023770082857415154, 0.02348409140810501, 0.023142398290657208, 0.02274581396370907,
+    0.022295279081878283, 0.021791862264661725, 0.021236757561826795, 0.020631281621311764,
+    0.01997687056636017, 0.019275076589307813, 0.018527564270120023, 0.017736106628441193,
+    0.016902580918570803, 0.016028964177425775, 0.015117328536201239, 0.014169836307129742,
+    0.01318873485752733, 0.012176351284355437, 0.011135086904191627, 0.010067411576765104,
+    0.008975857887848672, 0.007863015238012359, 0.006731523948359321, 0.005584069730065564,
+    0.0044233799131819735, 0.0032522289844891814, 0.002073516630281234, 0.0008916403608482165])
+
+
+def variable_types(X):
+    """The (p,) int32 array of variable types of ``X`` (p,N) for ``mixed_correlation``: 1 (binary) where a row takes exactly
+    two distinct values, whatever their coding, 0 (continuous) elsewhere."""
+    X = np.asarray(X, dtype=np.float64)
+    assert X.ndim == 2, f"data must be a (p,N) array with variables in rows, has shape {X.shape}"
+    return np.array([len(np.unique(x)) == 2 for x in X], dtype=np.int32)
+
+
+def _mixed_types(R, types):
+    """``types`` as the C-contiguous int32 (p,) array the library takes; None: from the dense ranks R (binary: top rank 1)."""
+    if types is None:
+        return (R.max(axis=1) == 1).astype(np.int32)
+    t = np.ascontiguousarray(types, dtype=np.int32)
+    assert t.shape == (R.shape[0],), f"types must have shape ({R.shape[0]},), has {t.shape}"
+    return t
+
+
+def _normal_quantile_lower(q):
+    """The standard normal quantile of 0 < q <= 1/2: Newton on Phi(x) - q from x = 0.  Phi is convex on the negative axis,
+    so the iterates decrease to the root."""
+    import math
+    x = 0.0
+    for _ in range(200):
+        xn = x - (0.5 * math.erfc(-x / math.sqrt(2.0)) - q) * math.sqrt(2.0 * math.pi) * math.exp(0.5 * x * x)
+        if not xn < x:
+            break
+        x = xn
+    return x
+
+
+def _bridge_delta(n0, n):
+    """Delta = the normal quantile of n0 / n, 0 < n0 < n, taken from the lower tail (as the kernel does)."""
+    n0, n = int(n0), int(n)
+    return _normal_quantile_lower(n0 / n) if 2 * n0 <= n else -_normal_quantile_lower((n - n0) / n)
+
+
+def _bridge_H(x, h2k2, hk2, c):
+    """H(x) = c x sum_n v_n g(x u_n) for arrays of pairs: the kernel's br_H."""
+    t = x[:, None] * _GL64_U[None]
+    co = np.cos(t)
+    return c * x * ((_GL64_V[None] * np.exp(-(h2k2[:, None] - hk2[:, None] * np.sin(t)) / (2.0 * co * co))).sum(axis=1))
+
+
+def _bridge_solve(tau, h, k, bb, clip, max_iter=64, ftol=2.0 ** -51):
+    """The roots of the bridge functions for arrays of pairs, by the kernel's safeguarded Newton iteration in the angle.
+    ``bb``: both variables binary (thresholds h, k), else binary / continuous (threshold h, k = 0).  Returns (r, clipped)."""
+    k = np.where(bb, k, 0.0)
+    h2k2, hk2 = h * h + k * k, 2.0 * h * k
+    c = np.where(bb, 1.0 / np.pi, 2.0 / np.pi)
+    amp = np.where(bb, 1.0, np.sqrt(2.0))
+    pos = tau >= 0.0
+    xe = np.where(pos, 1.0, -1.0) * np.arcsin(clip / amp)
+    Fe = _bridge_H(xe, h2k2, hk2, c)
+    clipped = np.where(pos, tau >= Fe, tau <= Fe)
+    lo, hi = np.minimum(0.0, xe), np.maximum(0.0, xe)
+    with np.errstate(all='ignore'):
+        x = tau / (c * np.exp(-0.5 * h2k2))
+        x = np.where((x > lo) & (x < hi), x, 0.5 * (lo + hi))
+        act = np.flatnonzero(~clipped)
+        for _ in range(max_iter):
+            if act.size == 0:
+                break
+            xa = x[act]
+            f = _bridge_H(xa, h2k2[act], hk2[act], c[act]) - tau[act]
+            go = np.abs(f) > ftol
+            act, xa, f = act[go], xa[go], f[go]
+            hi[act] = np.where(f > 0.0, xa, hi[act])
+            lo[act] = np.where(f > 0.0, lo[act], xa)
+            co = np.cos(xa)
+            d = c[act] * np.exp(-(h2k2[act] - hk2[act] * np.sin(xa)) / (2.0 * co * co))
+            xn = xa - f / d
+            xn = np.where((xn > lo[act]) & (xn < hi[act]), xn, 0.5 * (lo[act] + hi[act]))
+            x[act] = xn
+            act = act[xn != xa]
+    r = np.clip(amp * np.sin(x), -clip, clip)
+    return np.where(clipped, np.where(pos, clip, -clip), r), clipped
+
+
+def host_mixed_correlation(X, types=None, indices=None, clip=0.999, return_info=False, counts=None):
+    """numpy counterpart of ``mixed_correlation`` for one (p,N) array (engines without the device route): the counts of
+    ``host_kendall_counts`` (or ``counts``, where the caller has them), the same 64-node rule and the same safeguarded Newton
+    iteration.  Returns (p,p), or (B,p,p) with ``indices`` (B,b); with ``return_info`` also the dict ``mixed_correlation``
+    describes."""
+    X = np.asarray(X, dtype=np.float64)
+    assert X.ndim == 2 and np.isfinite(X).all(), "rank correlation needs a finite (p,N) array"
+    assert 0.0 < clip < 1.0, f"clip = {clip}, outside (0, 1)"
+    p = X.shape[0]
+    R = dense_ranks(X)
+    t = _mixed_types(R, types)
+    assert np.isin(t, (0, 1)).all(), "types: a variable is continuous (0) or binary (1)"
+    top = R.max(axis=1)
+    assert np.all(top > 0), f"variable {int(np.argmin(top > 0))} is constant"
+    assert np.all(top[t == 1] == 1), "a variable marked binary takes more than two values"
+    G = host_kendall_counts(X, indices) if counts is None else np.asarray(counts)
+    G = G[None] if indices is None else G
+    subsets = [R] if indices is None else [R[:, np.asarray(ix)] for ix in np.asarray(indices)]
+    iu, ju = np.triu_indices(p, 1)
+    ti, tj = t[iu] == 1, t[ju] == 1
+    S = np.empty(G.shape)
+    n0 = np.empty((len(subsets), p), dtype=np.int32)
+    clipped = np.zeros(len(subsets), dtype=np.int32)
+    for r, Rr in enumerate(subsets):
+        n = Rr.shape[1]
+        n0[r] = (Rr == 0).sum(axis=1)
+        flat = Rr.min(axis=1) == Rr.max(axis=1)
+        assert not flat.any(), f"variable {int(np.argmax(flat))} is constant over subset {r}"
+        delta = np.array([_bridge_delta(n0[r, i], n) if t[i] else 0.0 for i in range(p)])
+        tau = G[r][iu, ju] / float(n * (n - 1) // 2)
+        val = np.sin(np.pi / 2 * tau)
+        mix = ti | tj
+        if mix.any():
+            h = np.where(ti, delta[iu], delta[ju])[mix]
+            val[mix], cl = _bridge_solve(tau[mix], h, delta[ju][mix], (ti & tj)[mix], clip)
+            clipped[r] = int(cl.sum())
+        S[r] = np.eye(p)
+        S[r][iu, ju] = val
+        S[r][ju, iu] = val
+    info = {'types': t, 'zero_counts': n0, 'clipped': clipped}
+    if indices is None:
+        S, info = S[0], {'types': t, 'zero_counts': n0[0], 'clipped': int(clipped[0])}
+    return (S, info) if return_info else S
+
+
+def _mixed_call(R, types, idx, clip, device=0):
+    """One ``ggl_mixed_correlation`` call: R, idx as ``_kendall_call``, types C-contiguous int32 (p,).  Returns (S (B,p,p), G
+    (B,p,p) int64, zero counts (B,p) int32, clipped (B,) int32)."""
+    p, N = R.shape
+    B, b = (1, N) if idx is None else idx.shape
+    S = np.empty((B, p, p))
+    G = np.empty((B, p, p), dtype=np.int64)
+    n0 = np.empty((B, p), dtype=np.int32)
+    cl = np.empty(B, dtype=np.int32)
+    _lib.require_gpu()
+    check(_lib.load().ggl_mixed_correlation(int(device), p, N, R.ctypes.data_as(_lib._ip), types.ctypes.data_as(_lib._ip), B, b,
+                                            None if idx is None else idx.ctypes.data_as(_lib._ip), float(clip), ptr(S),
+                                            G.ctypes.data_as(_llp), n0.ctypes.data_as(_lib._ip), cl.ctypes.data_as(_lib._ip)))
+    return S, G, n0, cl
+
+
+def mixed_correlation(X, types=None, indices=None, clip=0.999, device=0, return_info=False):
+    """The latent correlation matrix of mixed binary / continuous data on the device (Fan, Liu, Ning, Zou 2017): Kendall's
+    tau-a of every pair from the exact counts of ``kendall_counts``, inverted through the bridge function of the pair's types
+    (one root per pair: ``ggl_mixed_correlation``).  ``types`` (p,): 1 binary, 0 continuous (default ``variable_types(X)``: a
+    variable with exactly two distinct values is binary, whatever their coding; the same ``types`` serve every instance).
+    The roots are sought in ``[-clip, clip]``; a pair of continuous variables gets ``sin(pi/2 tau-a)``, unclipped -- on data
+    without ties the entry of ``skeptic_correlation``.
+
+    Diagonal exactly 1, exactly symmetric, the same bits on every call, invariant under increasing transforms of any variable
+    (a recoding of a binary one included); it need not be positive semidefinite.  A variable that is constant (over a subset)
+    is refused, naming it.  X, ``indices`` and the kind of the result as ``kendall_counts``.
+
+    ``return_info``: also a dict (one per instance for several instances) of ``types`` (p,), ``zero_counts`` -- the samples at
+    every variable's smaller value, (p,) or (B,p) int32 -- and ``clipped``, the pairs that ended on ``+-clip`` (int, or (B,))."""
+    infos = []
+
+    def one(R, idx):
+        t = _mixed_types(R, types)
+        S, _, n0, cl = _mixed_call(R, t, idx, clip, device)
+        infos.append({'types': t, 'zero_counts': n0, 'clipped': cl} if indices is not None else
+                     {'types': t, 'zero_counts': n0[0], 'clipped': int(cl[0])})
+        return S
+
+    S = _kendall_per_instance(X, indices, one)
+    if not return_info:
+        return S
+    return S, (infos[0] if isinstance(S, np.ndarray) and S.ndim == (2 if indices is None else 3) else infos)
+
+
+# -----------------------------------------------------------------------------------------------------------------
 # Weighted covariance of one data array under K weight rows, and the kernel-smoothed covariance stack of a time series
 # (Zhou, Lafferty, Wasserman 2010; Monti et al. 2014 "SINGLE"): csrc/covariance_weighted.hip behind ggl_covariance_weighted.
 #     W_k = sum_n w_kn,  m_k = (1/W_k) sum_n w_kn x_n,  S_k = (1/W_k) sum_n w_kn (x_n - m_k)(x_n - m_k)^T

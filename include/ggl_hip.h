@@ -29,8 +29,8 @@ extern "C" {
  * ggl_frob_norm_per_block, ggl_fsgl_stats, ggl_covariance, ggl_scale_by_diagonal, ggl_set_S_from_data, ggl_get_S, ggl_kkt_terms,
  * ggl_diag_stats, ggl_covariance_subsets, ggl_set_S_from_subsets, ggl_edge_stability, ggl_kendall_counts, ggl_kendall_skeptic,
  * ggl_set_S_from_kendall, ggl_covariance_pairwise, ggl_covariance_pairwise_subsets, ggl_set_S_from_data_pairwise,
- * ggl_set_S_from_subsets_pairwise, ggl_covariance_weighted, ggl_set_S_from_weighted) leave every existing layout alone and the
- * number where it is. */
+ * ggl_set_S_from_subsets_pairwise, ggl_covariance_weighted, ggl_set_S_from_weighted, ggl_mixed_correlation,
+ * ggl_set_S_from_mixed) leave every existing layout alone and the number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -854,6 +854,33 @@ int ggl_covariance_weighted(int device, int p, int N, const double *X_host, int 
  * ctx's S and installed once every check has passed; the variances are kept with GGL_COV_SCALE).  A refused call leaves the
  * ctx's S, its variances and what was built for them as they were. */
 int ggl_set_S_from_weighted(ggl_ctx *ctx, const double *X_host, int N, const double *w_host, int flags);
+
+/* ---- Latent correlation of mixed binary / continuous data: the Gaussian copula model of Fan, Liu, Ning, Zou (2017), the
+ * estimator of R's mixedCCA / latentcor (bridge.hip behind the counts of kendall.hip).  Entry points that are only ADDED:
+ * GGL_VERSION stays where it is.
+ *
+ * ranks_host, idx, B, b as ggl_kendall_counts.  types (p): 1 for a binary variable (its dense ranks are 0 and 1), 0 for a
+ * continuous one.  Per subset, with n = b samples, tau = G_ij / (n (n - 1) / 2) (Kendall's tau-a of the exact counts G) and, for
+ * a binary variable with n0 samples of rank 0, Delta = the standard normal quantile of n0 / n:
+ *     continuous, continuous:  S_ij = sin(pi/2 tau)                                                         (not clipped)
+ *     binary, binary:          S_ij = the root r of (1/pi) int_0^{asin r}        g(t; Delta_i, Delta_j) dt = tau
+ *     binary, continuous:      S_ij = the root r of (2/pi) int_0^{asin(r/sqrt 2)} g(t; Delta, 0) dt         = tau
+ *     g(t; h, k) = exp(-(h^2 + k^2 - 2 h k sin t) / (2 cos^2 t)),
+ * sought in [-clip, clip]: tau at or beyond the bridge's value at an end gives that end, and such pairs are counted.  The
+ * integral is a 64-node Gauss-Legendre rule, one node per lane of a wave; the root is a safeguarded Newton iteration.  Every
+ * unordered pair is solved once and written twice: S is exactly symmetric, its diagonal exactly 1, two calls give the same
+ * bits.  It need not be positive semidefinite.
+ * S_out (B,p,p); G_out (B,p,p) the counts, n0_out (B,p) the samples of rank 0 of every variable, clipped_out (B) the clipped
+ * pairs: each may be NULL.
+ * GGL_E_ARG, the message naming the offender: what ggl_kendall_counts refuses; a types entry outside {0, 1}; a variable marked
+ * binary with a rank above 1; a variable that is constant (over all samples: found on the host; over one subset: found on the
+ * device, naming subset and variable); clip outside (0, 1).  A refused call writes nothing. */
+int ggl_mixed_correlation(int device, int p, int N, const int *ranks_host, const int *types, int B, int b, const int *idx,
+                          double clip, double *S_out, long long *G_out, int *n0_out, int *clipped_out);
+/* ... straight into the S of a ctx whose K is a multiple of B (layout and bookkeeping of ggl_set_S_from_kendall), bitwise the
+ * matrices of the call above.  A refused call leaves the ctx's S as it was. */
+int ggl_set_S_from_mixed(ggl_ctx *ctx, const int *ranks_host, const int *types, int N, int B, int b, const int *idx,
+                         double clip);
 
 #ifdef __cplusplus
 }

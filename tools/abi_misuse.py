@@ -221,5 +221,43 @@ print("valid ggl_ext_admm_step / ggl_ext_kkt_residual after the probes: rc", rc,
       bool(np.all(np.isfinite(o5))), "kkt finite", bool(np.isfinite(kkt[0])))
 bad += 0 if rc == 0 and rck == 0 and np.all(np.isfinite(o5)) and np.isfinite(kkt[0]) else 1
 lib.ggl_ctx_destroy(h)
+
+# ---- latent correlation of mixed data (ggl_mixed_correlation, ggl_set_S_from_mixed): refused on the host, nothing written ----
+pm, Nm = 4, 12
+Rm = np.ascontiguousarray(np.stack([np.arange(Nm) % 2, np.arange(Nm), (np.arange(Nm) // 6), np.arange(Nm)[::-1]]), dtype=np.int32)
+tm = np.array([1, 0, 1, 0], dtype=np.int32)
+Sm = np.full((1, pm, pm), 7.0)
+mixed = lambda R_=Rm, t_=tm, B=1, b=Nm, idx=None, clip=0.999, out=Sm: lib.ggl_mixed_correlation(
+    0, pm, Nm, None if R_ is None else ints(R_), None if t_ is None else ints(t_), B, b, None if idx is None else ints(idx), d(clip),
+    None if out is None else ptr(out), None, None, None)
+Rflat = Rm.copy()
+Rflat[1] = 0
+for name, kw in (("types=NULL", dict(t_=None)), ("types entry 2", dict(t_=[1, 0, 2, 0])), ("types entry -1", dict(t_=[-1, 0, 1, 0])),
+                 ("a binary variable with rank 11", dict(t_=[1, 1, 1, 0])), ("clip=0", dict(clip=0.0)), ("clip=1", dict(clip=1.0)),
+                 ("clip=nan", dict(clip=float("nan"))), ("a constant variable", dict(R_=Rflat)), ("ranks=NULL", dict(R_=None)),
+                 ("S_out=NULL", dict(out=None)), ("idx=NULL with B=2", dict(B=2)), ("b=1", dict(b=1, idx=[[0]])),
+                 ("an index outside [0,N)", dict(b=3, idx=[[0, 1, Nm]]))):
+    expect_error(f"ggl_mixed_correlation({name})", mixed(**kw))
+bad += 0 if (Sm == 7.0).all() else 1
+rc, h = ctx(2, pm)
+assert rc == 0, last()
+Sm2 = np.stack([np.eye(pm)] * 2)
+assert lib.ggl_set_S(h, ptr(Sm2)) == 0, last()
+set_mixed = lambda hh=h, t_=tm, B=1, b=Nm, idx=None, clip=0.999: lib.ggl_set_S_from_mixed(
+    hh, ints(Rm), None if t_ is None else ints(t_), Nm, B, b, None if idx is None else ints(idx), d(clip))
+expect_error("ggl_set_S_from_mixed(NULL ctx)", set_mixed(hh=None))
+expect_error("ggl_set_S_from_mixed(types=NULL)", set_mixed(t_=None))
+expect_error("ggl_set_S_from_mixed(types entry 3)", set_mixed(t_=[1, 0, 3, 0]))
+expect_error("ggl_set_S_from_mixed(clip=1.5)", set_mixed(clip=1.5))
+expect_error("ggl_set_S_from_mixed(B=3 of K=2)", set_mixed(B=3, b=2, idx=[[0, 1], [2, 3], [4, 5]]))
+got = np.zeros_like(Sm2)
+assert lib.ggl_get_S(h, ptr(got), None) == 0, last()
+bad += 0 if np.array_equal(got, Sm2) else 1
+rc = mixed()
+rc2 = set_mixed()
+print("valid ggl_mixed_correlation / ggl_set_S_from_mixed after the probes: rc", rc, rc2, last() if rc or rc2 else "", "unit diagonal",
+      bool(np.array_equal(np.diagonal(Sm[0]), np.ones(pm))))
+bad += 0 if rc == 0 and rc2 == 0 and np.array_equal(np.diagonal(Sm[0]), np.ones(pm)) else 1
+lib.ggl_ctx_destroy(h)
 print("ok" if bad == 0 else f"{bad} probes misbehaved")
 sys.exit(0 if bad == 0 else 1)
