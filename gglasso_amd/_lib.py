@@ -169,6 +169,8 @@ _SIGNATURES = {
     "ggl_set_S_from_weighted": ([_vp, _dp, _i, _dp, _i], _i),
     "ggl_mixed_correlation": ([_i, _i, _i, _ip, _ip, _i, _i, _ip, _d, _dp, ctypes.POINTER(ctypes.c_longlong), _ip, _ip], _i),
     "ggl_set_S_from_mixed": ([_vp, _ip, _ip, _i, _i, _i, _ip, _d], _i),
+    "ggl_nearest_correlation": ([_i, _i, _dp, _dp, _d, _d, _i, _ip, _dp], _i),
+    "ggl_project_S": ([_vp, _i, _d, _d, _i, _ip, _dp], _i),
 }
 
 # libggl_hip_dev.so only (-DGGL_DEV)

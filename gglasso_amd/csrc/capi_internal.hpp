@@ -16,6 +16,7 @@
 //   capi_ops.hip        stateless operator entry points, development probes
 //   capi_data.hip       sample covariance from data and from column subsets of one data array, scaling by a diagonal
 //                       (stateless and into a ctx's S); rank correlation, pairwise-complete and weighted covariance
+//   capi_nearcorr.hip   nearest-correlation projection of an indefinite S (stateless and in place on a ctx's S)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>

@@ -575,4 +575,22 @@ void launch_bridge_zero_counts(hipStream_t st, const int* Rg, int* n0, int* err,
 void launch_bridge_invert(hipStream_t st, const long long* G, const int* n0, const int* types, double* S, int* clipped,
                           const int* err, int B, int p, int b, double clip);
 
+// Nearest-correlation projection (nearcorr.hip): the kernels around rank_step's (C - mu I)_+.  Stacks are (B,p,p);
+// *err (set to GGL_DIAG_OK by the caller) = smallest b * p + i of a row with a non-finite entry or a non-positive diagonal,
+// every kernel behind launch_nc_begin does nothing once it is raised.  frozen, pass (B ints), nu (B): device-visible.
+int nc_update_blocks(int p);      // per-instance partial rows of launch_nc_update (3 doubles each)
+int nc_finish_blocks(int p);      // ... of launch_nc_finish (1 double each)
+// A0 = Y = R = the symmetrised input scaled to a unit diagonal, dS = 0, dvec (B,p) = diag(A)
+void launch_nc_begin(hipStream_t st, const double* A, double* A0, double* Y, double* dS, double* R, double* dvec, int* err, int B,
+                     int p);
+// with X = L + eps I:  dS' = X - (Y - dS), Y' = X with unit diagonal, R = Y' - dS'; part[b][block][3] = sum (Y' - Y)^2,
+// sum_i (1 - x_ii)^2, sum Y'^2.  A frozen instance keeps Y and dS, its R becomes I
+void launch_nc_update(hipStream_t st, const double* L, double* Y, double* dS, double* R, double* part, const int* frozen,
+                      const int* err, double eps, int B, int p);
+// out[b * 8 + v] = sum of part[b][0..nblk)[v], v < nv <= 3, in a fixed order
+void launch_nc_reduce(hipStream_t st, const double* part, double* out, const int* err, int B, int nblk, int nv);
+// dst = (1 - nu_b) Y off the diagonal times sqrt(d_i d_j), d_i on it; pass[b]: dst = A.  part[b][block] = sum (dst - A)^2
+void launch_nc_finish(hipStream_t st, const double* Y, const double* A, double* dst, const double* dvec, const double* nu,
+                      const int* pass, double* part, const int* err, int B, int p);
+
 }  // namespace ggl

@@ -703,7 +703,7 @@ def _host_edge_counts(Theta, t):
 
 def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.05, seed=0, indices=None, t=1e-8, center=True,
                  scale=False, tol=1e-7, rtol=1e-7, max_iter=1000, store_all=False, lambdas_per_batch=None, correlation=None,
-                 missing=None, min_pairs=2):
+                 missing=None, min_pairs=2, project=False):
     """StARS for the Single Graphical Lasso from observations ``X`` (p,N), variables in rows.  Returns ``(sol, stats)``.
 
     * Subsamples: ``stars_subsamples(N, n_subsamples, subsample_size, seed)``, or ``indices`` (B,b) given by the caller
@@ -724,7 +724,8 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     ``correlation='kendall'``: every ``S_r``, and the matrix of the final fit, is the nonparanormal skeptic matrix
     ``sin(pi/2 tau-b)`` of the observations (``utils.skeptic_correlation``; on the device ``ggl_set_S_from_kendall``) instead of
     the Pearson covariance -- invariant under monotone transforms of the variables, robust to outliers and ties.  ``center`` and
-    ``scale`` have no meaning then and must be left at their defaults.  The matrix may be indefinite; it is used as it is.
+    ``scale`` have no meaning then and must be left at their defaults.  The matrix may be indefinite; it is used as it is
+    unless ``project=True``.
 
     ``missing='pairwise'``: a NaN in X is a missing value; every ``S_r`` and the matrix of the final fit are pairwise-complete
     covariances (``utils.sample_covariance_subsets(..., missing='pairwise')``; on the device
@@ -734,7 +735,13 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     ``correlation='mixed'``: every ``S_r``, and the matrix of the final fit, is the latent correlation matrix of mixed binary /
     continuous data (``utils.mixed_correlation``; on the device ``ggl_set_S_from_mixed``).  The types are fixed once, from all N
     observations: a variable with exactly two distinct values is binary.  A subsample over which a variable is constant is
-    refused, naming both.  ``center`` and ``scale`` as with ``'kendall'``."""
+    refused, naming both.  ``center`` and ``scale`` as with ``'kendall'``.
+
+    ``project=True``: every ``S_r`` and the matrix of the final fit are replaced by their nearest-correlation projections
+    (``utils.nearest_correlation`` with its defaults), after any ``correlation=`` and ``missing=`` choice.  On the device one
+    ``engine.project_S(period=B)`` projects the B subset matrices where they lie, before they are used; an engine without
+    ``project_S`` gets the numpy twin's matrices (``utils.host_nearest_correlation``).  ``stats['PROJECTION']`` is the info of
+    the final fit's matrix."""
     import warnings
     from . import solver as _solver, utils
     from .batch import _sgl_batch_impl
@@ -765,7 +772,7 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     per = L if lambdas_per_batch is None else max(1, int(lambdas_per_batch))
     route = "set_kendall_subsets" if kendall else ("set_mixed_subsets" if mixed else "set_data_subsets")
     on_device = hasattr(_solver.ENGINE, route) and \
-        hasattr(_solver.ENGINE, "edge_stability")
+        hasattr(_solver.ENGINE, "edge_stability") and (not project or hasattr(_solver.ENGINE, "project_S"))
     eye = np.eye(p)
     NUM = np.zeros(L, dtype=np.int64)
     failed = np.zeros(L, dtype=bool)
@@ -780,6 +787,8 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
         S_host = _host_pairwise_covariances(X, idx, center, scale, min_pairs)
     else:
         S_host = utils.host_skeptic_correlation(X, idx) if kendall else _host_subset_covariances(X, idx, center, scale)
+    if project and S_host is not None:
+        S_host = utils.host_nearest_correlation(S_host)
     for l0 in range(0, L, per):
         sl = slice(l0, min(L, l0 + per))
         nl = sl.stop - sl.start
@@ -795,6 +804,8 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
                 eng.set_data_subsets(X, idx, center=center, scale=scale, missing='pairwise', min_pairs=min_pairs)
             else:
                 eng.set_data_subsets(X, idx, center=center, scale=scale)
+            if project:
+                eng.project_S(period=B)
 
         def after(eng, results):
             got['edges'] = eng.edge_stability(B, t, counts=store_all)
@@ -837,10 +848,15 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
         S_full = S_full[0] if scale else S_full
     else:
         S_full = _host_subset_covariances(X, np.arange(N)[None], center, scale)[0]
+    projection = None
+    if project:
+        S_full, projection = (utils.nearest_correlation if on_device else utils.host_nearest_correlation)(S_full, return_info=True)
     sol, _ = _solver.ADMM_SGL(S_full, lam[ix], eye, X_0=eye, tol=tol, rtol=rtol, max_iter=max_iter, verbose=False)
     stats = {'LAMBDA': lam, 'INSTABILITY': D, 'INSTABILITY_MONOTONE': Dbar, 'NUM': [int(n) for n in NUM], 'IX': ix,
              'BEST': {'lambda1': lam[ix]}, 'INDICES': idx, 'subsample_size': b, 'n_subsamples': B,
              'FAILED': [int(l) for l in np.flatnonzero(failed)]}
+    if project:
+        stats['PROJECTION'] = projection
     if store_all:
         stats['COUNTS'], stats['THETA'] = COUNTS, THETA
     return sol, stats

@@ -148,7 +148,7 @@ class glasso_problem:
 
     @classmethod
     def from_data(cls, X, *, reg="GGL", reg_params=None, latent=False, G=None, do_scaling=False, center=True, correlation=None,
-                  missing=None, min_pairs=2):
+                  missing=None, min_pairs=2, project=False):
         """The problem of observations ``X``: (p,N), (K,p,N) or a list / dict of (p_k,N_k) arrays, variables in rows.
         ``N`` is read off the data and S is computed on the device (``utils.sample_covariance``).
 
@@ -156,7 +156,7 @@ class glasso_problem:
         (``utils.skeptic_correlation``: Kendall's tau-b on the int8 matrix cores) -- for data that are not Gaussian (counts,
         skewed or heavy-tailed measurements, ties).  It is a correlation matrix (unit diagonal; ``center`` has no meaning and
         must be left at its default) and it can be indefinite: the ADMM's log-det prox does not need a positive semidefinite
-        input, so the matrix is used as it is and no projection is applied.
+        input, so the matrix is used as it is and no projection is applied.  ``project=True`` (below) projects it.
 
         ``missing='pairwise'``: a NaN in X is a missing value and S is every instance's pairwise-complete covariance
         (``utils.sample_covariance(..., missing='pairwise', min_pairs=min_pairs)``); it can be indefinite as well and is used
@@ -167,7 +167,14 @@ class glasso_problem:
         (``utils.mixed_correlation``: a variable with exactly two distinct values is binary; Kendall's tau-a inverted through
         the bridge function of each pair's types) -- for presence / absence or yes / no variables beside continuous ones, where
         Pearson attenuates and the skeptic bridge is wrong.  ``center`` as with ``'kendall'``; the matrix can be indefinite and
-        is used as it is."""
+        is used as it is.
+
+        ``project=True``: S (every instance of a stack) is replaced by its nearest-correlation projection
+        (``utils.nearest_correlation`` with its defaults: same diagonal, no eigenvalue of its correlation matrix below 1e-8),
+        after any ``correlation=`` and ``missing=`` choice, Pearson included.  With an indefinite S the objective is unbounded
+        below once lambda1 is small, which is where a regularisation path starts.  What the projection did is kept as
+        ``problem.projection`` (the info dict; per instance for a list / dict of different dimensions), and
+        ``stability_selection`` projects every subsample's matrix as well."""
         assert correlation in (None, 'kendall', 'mixed'), "correlation must be None (Pearson), 'kendall' or 'mixed'"
         assert missing in (None, 'pairwise'), "missing must be None (complete data) or 'pairwise'"
         if missing == 'pairwise' and correlation in ('kendall', 'mixed'):
@@ -188,6 +195,9 @@ class glasso_problem:
         if isinstance(S, dict) and G is None and len({s.shape[0] for s in S.values()}) == 1:
             S = np.stack([S[k] for k in range(len(S))])       # a list of instances of ONE dimension is a conforming stack
             counts = None if counts is None else np.stack([counts[k] for k in range(len(counts))])
+        projection = None
+        if project:
+            S, projection = cls._project(S)
         if isinstance(S, np.ndarray) and S.ndim == 2:
             N = int(N[0])
         prob = cls(S, N, reg=reg, reg_params=reg_params, latent=latent, G=G, do_scaling=do_scaling)
@@ -195,6 +205,7 @@ class glasso_problem:
         prob._correlation = correlation
         prob._missing, prob._min_pairs = missing, min_pairs
         prob.pair_counts = counts
+        prob._project_S, prob.projection = bool(project), projection
         return prob
 
     @classmethod
@@ -220,6 +231,16 @@ class glasso_problem:
         prob = cls(S, n_eff, reg=reg, reg_params=reg_params, latent=latent, do_scaling=do_scaling)
         prob.weights, prob.eval_times = w, eval_times
         return prob
+
+    @staticmethod
+    def _project(S):
+        """(projected S, info) of a matrix, a stack or a dict of matrices; an engine without the device route (``project_S``)
+        takes the numpy twin."""
+        fn = utils.nearest_correlation if hasattr(_solver.ENGINE, "project_S") else utils.host_nearest_correlation
+        if isinstance(S, dict):
+            out = {k: fn(S[k], return_info=True) for k in range(len(S))}
+            return {k: o for k, (o, _) in out.items()}, {k: i for k, (_, i) in out.items()}
+        return fn(S, return_info=True)
 
     @staticmethod
     def _pairwise(X, center, min_pairs):
@@ -387,7 +408,8 @@ class glasso_problem:
         the instabilities to ``self.modelselect_stats``.  With ``do_scaling`` every subsample is scaled to its own
         correlations and the solution goes back to the covariances' scale, as in ``solve``.  A problem built with
         ``correlation='kendall'`` or ``'mixed'`` resamples that matrix instead (``do_scaling`` has nothing to scale then); one built
-        with ``missing='pairwise'`` takes every subsample's, and the final fit's, pairwise-complete covariance."""
+        with ``missing='pairwise'`` takes every subsample's, and the final fit's, pairwise-complete covariance; one built with
+        ``project=True`` projects each of them (``stars_search(..., project=True)``)."""
         assert getattr(self, '_observations', None) is not None, \
             "Stability selection resamples the observations: build the problem with glasso_problem.from_data(X)."
         assert not self.multiple, "Stability selection is implemented for Single Graphical Lasso problems only."
@@ -399,6 +421,8 @@ class glasso_problem:
             dict(center=self._center, scale=bool(self.do_scaling))
         if getattr(self, '_missing', None) == 'pairwise':
             how.update(missing='pairwise', min_pairs=self._min_pairs)
+        if getattr(self, '_project_S', False):
+            how.update(project=True)
         sol, stats = _ms.stars_search(self._observations[0], self.modelselect_params['lambda1_range'],
                                       n_subsamples=n_subsamples, subsample_size=subsample_size, beta=beta, seed=seed,
                                       tol=tol, rtol=rtol, store_all=store_all, **how)

@@ -195,6 +195,28 @@ class HipEngine:
                                             None if idx is None else idx.ctypes.data_as(_lib._ip), float(clip)))
         self._S_scaled = False
 
+    def project_S(self, period=None, eps=1e-8, tol=1e-10, max_iter=500):
+        """The ctx's S replaced, where it lies, by its nearest-correlation projection (``ggl_project_S``, see
+        ``utils.nearest_correlation``): every matrix keeps its diagonal and ends with ``lambda_min >= eps min(diagonal)``.
+        ``period=B``, a divisor of K: S holds B distinct matrices, instance k carrying matrix ``k % B`` (what the
+        ``set_*_subsets`` calls install); the B are projected once and replicated on the device.  None: all K.  Returns the
+        info dict of ``utils.nearest_correlation`` (arrays over the matrices projected); a ``RuntimeWarning`` names those that
+        did not converge.  A refused call (a non-finite entry, a non-positive diagonal) leaves S as it was."""
+        from .utils import _nc_result
+        B = self.K if period is None else int(period)
+        assert 0.0 <= eps <= 0.5, f"eps = {eps}, the eigenvalue floor lies in [0, 0.5]"
+        assert 1e-14 <= tol <= 1e-2, f"tol = {tol}, the tolerance lies in [1e-14, 1e-2]"
+        assert int(max_iter) >= 1, f"max_iter = {max_iter}, at least one iteration is needed"
+        assert 1 <= B <= self.K and self.K % B == 0, f"period = {period} must be a divisor of K = {self.K}"
+        iters = np.zeros(B, dtype=np.int32)
+        info = np.zeros((B, 4))
+        check(self.lib.ggl_project_S(self.h, 0 if period is None else B, float(eps), float(tol), int(max_iter),
+                                     iters.ctypes.data_as(_lib._ip), ptr(info)))
+        _, out = _nc_result(None, False, iters.astype(np.int64), info[:, 0].copy(), info[:, 1].copy(), info[:, 2].copy(),
+                            int(max_iter), True, "project_S")
+        out["fallbacks"] = int(info[0, 3])
+        return out
+
     def edge_stability(self, B, t=1e-8, counts=False):
         """StARS over the Theta snapshots of a batch of K = L * B points (instance l * B + r: subsample r at lambda l):
         the (L,) int64 array ``sum_{i<j} c (B - c)`` of the selection counts ``c[l,i,j] = #{r : |Theta| >= t}``, exact; with

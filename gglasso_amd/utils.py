@@ -681,3 +681,125 @@ def kernel_covariance(X, at=None, bandwidth=None, times=None, kernel='gaussian',
     out = weighted_covariance(X, w, center=center, scale=scale, device=device)
     n_eff = effective_sample_size(w)
     return (out[0], n_eff, out[1]) if scale else (out, n_eff)
+
+
+# -----------------------------------------------------------------------------------------------------------------
+# Nearest-correlation projection of an indefinite S (Higham 2002, with Dykstra's correction; what R's Matrix::nearPD does
+# behind latentcor / mixedCCA).  The skeptic, pairwise-complete and latent matrices above need not be positive semidefinite,
+# and the graphical lasso objective is unbounded below for small lambda1 when S is not.  Per matrix, on D^-1/2 S D^-1/2 with
+# the diagonal set to exactly 1, starting from Y = S, dS = 0:
+#     R = Y - dS;   X = V max(lambda, eps) V^T of R = V lambda V^T;   dS = X - R;   Y' = X with the diagonal set to 1
+#     r1 = |Y' - Y|_F / |Y'|_F,   delta = |Y' - X|_F,   r2 = delta / |Y'|_F;   stop when max(r1, r2) <= tol
+# and then always nu = delta / (1 - eps + delta), result (1 - nu) Y' off the diagonal and 1 on it, scaled back by sqrt(d_i d_j):
+# lambda_min(Y') >= eps - delta, so the smallest eigenvalue of the result is at least eps min_i d_i, converged or not.
+# -----------------------------------------------------------------------------------------------------------------
+_NC_KEYS = ("iterations", "converged", "residual", "distance", "shrink")
+
+
+def _nc_args(S, eps, tol, max_iter):
+    """(A (B,p,p) C-contiguous float64, single) of what ``nearest_correlation`` accepts; the scalar arguments checked."""
+    A = np.asarray(S, dtype=np.float64)
+    assert A.ndim in (2, 3) and A.shape[-1] == A.shape[-2] and A.shape[-1] >= 1, \
+        f"nearest correlation needs a square (p,p) matrix or a (B,p,p) stack of them, S has shape {A.shape}"
+    single = A.ndim == 2
+    A = as_c(A[None] if single else A)
+    assert A.shape[0] >= 1, "nearest correlation: the stack is empty"
+    assert 0.0 <= eps <= 0.5, f"eps = {eps}, the eigenvalue floor lies in [0, 0.5]"
+    assert 1e-14 <= tol <= 1e-2, f"tol = {tol}, the tolerance lies in [1e-14, 1e-2]"
+    assert int(max_iter) >= 1, f"max_iter = {max_iter}, at least one iteration is needed"
+    return A, single
+
+
+def _nc_result(out, single, iters, res, dist, nu, max_iter, return_info, what):
+    import warnings
+    conv = iters > 0
+    if not conv.all():
+        bad = np.flatnonzero(~conv)
+        warnings.warn(f"{what}: no convergence within {max_iter} iterations for the matrices {bad.tolist()} (residuals "
+                      f"{[float(r) for r in res[bad]]}); their results are positive definite but not the nearest",
+                      RuntimeWarning, stacklevel=3)
+    if not return_info:
+        return out[0] if single else out
+    vals = (np.abs(iters), conv, res, dist, nu)
+    info = {k: (v[0].item() if single else v) for k, v in zip(_NC_KEYS, vals)}
+    return (out[0] if single else out), info
+
+
+def host_nearest_correlation(S, eps=1e-8, tol=1e-10, max_iter=500, return_info=False):
+    """numpy counterpart of ``nearest_correlation`` (engines without the device route): the same recursion, stopping test,
+    pass-through rule and final shrink, with ``numpy.linalg.eigh`` as the eigen route."""
+    A, single = _nc_args(S, eps, tol, max_iter)
+    B, p = A.shape[0], A.shape[1]
+    out = np.empty_like(A)
+    iters = np.zeros(B, dtype=np.int64)
+    res, dist, nus = np.zeros(B), np.zeros(B), np.zeros(B)
+    di = np.arange(p)
+    for b in range(B):
+        Ab = A[b]
+        bad = ~np.isfinite(Ab).all(axis=1)
+        assert not bad.any(), \
+            f"nearest correlation: the row of variable {int(np.flatnonzero(bad)[0])} of matrix {b} holds a non-finite entry (NaN or inf)"
+        d = np.diagonal(Ab).copy()
+        assert (d > 0).all(), (f"nearest correlation: the diagonal entry of variable {int(np.flatnonzero(~(d > 0))[0])} of matrix {b} "
+                               f"is {d[~(d > 0)][0]}, not positive")
+        sc = np.sqrt(d[:, None] * d[None, :])
+        Y = (Ab + Ab.T) * 0.5 / sc
+        Y[di, di] = 1.0
+        dS = np.zeros_like(Y)
+        delta, r, it, done = 0.0, np.inf, 0, False
+        while it < int(max_iter) and not done:
+            it += 1
+            R = Y - dS
+            w, V = np.linalg.eigh(R)
+            X = (V * np.maximum(w, eps)) @ V.T
+            X = np.triu(X) + np.triu(X, 1).T          # one value for (i,j) and (j,i)
+            dS = X - R
+            Yn = X.copy()
+            Yn[di, di] = 1.0
+            ny = np.sqrt(np.sum(Yn * Yn))
+            delta = np.sqrt(np.sum((1.0 - X[di, di]) ** 2))
+            r = max(np.sqrt(np.sum((Yn - Y) ** 2)) / ny, delta / ny)
+            Y = Yn
+            done = r <= tol
+        if done and it == 1:
+            out[b] = Ab                                # the input needed no projection: bit for bit
+        else:
+            nus[b] = delta / (1.0 - eps + delta)
+            O = Y * (1.0 - nus[b]) * sc
+            O[di, di] = d
+            out[b] = O
+        iters[b] = it if done else -int(max_iter)
+        res[b] = r
+        dist[b] = np.sqrt(np.sum((out[b] - Ab) ** 2))
+    return _nc_result(out, single, iters, res, dist, nus, int(max_iter), return_info, "host_nearest_correlation")
+
+
+def nearest_correlation(S, eps=1e-8, tol=1e-10, max_iter=500, device=0, return_info=False):
+    """The nearest (Frobenius norm) matrix to ``S`` with the same diagonal whose correlation matrix has no eigenvalue below
+    ``eps``, on the device: Higham's alternating projections with Dykstra's correction, the projection onto the cone running
+    as the L-step's ``(C - mu I)_+`` on the FP64 matrix cores, a (B,p,p) stack in lock-step.
+
+    S: (p,p) or (B,p,p), symmetric with a positive diagonal ``d`` (``(S + S^T) / 2`` is used); with ``d != 1`` the iteration
+    runs on ``D^-1/2 S D^-1/2`` and the result is scaled back, so variances are kept.  The result is exactly symmetric, has
+    the diagonal of ``S`` and ``lambda_min >= eps min(d)`` -- also when ``max_iter`` ended the iteration (a ``RuntimeWarning``
+    names those matrices; their result is feasible, only not nearest).  A matrix that already meets the stopping test in the
+    first iteration is returned bit for bit (then ``lambda_min >= eps - tol |S|_F``).  The same bits on every call.
+
+    ``return_info=True``: also a dict with, per matrix, ``iterations``, ``converged``, ``residual`` (max(r1, r2) of the last
+    iteration), ``distance`` (``|out - S|_F``) and ``shrink`` (the final nu); and ``fallbacks``, the eigendecomposition
+    fallbacks of the L-step over the call.  NaN / inf entries and non-positive diagonal entries are refused, naming matrix and
+    variable.  ``device`` must be 0 (a ctx on another device projects its own ``S``: ``HipEngine.project_S``)."""
+    A, single = _nc_args(S, eps, tol, max_iter)
+    assert int(device) == 0, "nearest_correlation runs on device 0; use HipEngine.project_S for a ctx on another device"
+    B, p = A.shape[0], A.shape[1]
+    out = np.empty_like(A)
+    iters = np.zeros(B, dtype=np.int32)
+    info = np.zeros((B, 4))
+    _lib.require_gpu()
+    check(_lib.load().ggl_nearest_correlation(B, p, ptr(A), ptr(out), float(eps), float(tol), int(max_iter),
+                                              iters.ctypes.data_as(_lib._ip), ptr(info)))
+    r = _nc_result(out, single, iters.astype(np.int64), info[:, 0].copy(), info[:, 1].copy(), info[:, 2].copy(), int(max_iter),
+                   return_info, "nearest_correlation")
+    if return_info:
+        r[1]["fallbacks"] = int(info[0, 3])
+    return r

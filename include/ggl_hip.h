@@ -30,7 +30,7 @@ extern "C" {
  * ggl_diag_stats, ggl_covariance_subsets, ggl_set_S_from_subsets, ggl_edge_stability, ggl_kendall_counts, ggl_kendall_skeptic,
  * ggl_set_S_from_kendall, ggl_covariance_pairwise, ggl_covariance_pairwise_subsets, ggl_set_S_from_data_pairwise,
  * ggl_set_S_from_subsets_pairwise, ggl_covariance_weighted, ggl_set_S_from_weighted, ggl_mixed_correlation,
- * ggl_set_S_from_mixed) leave every existing layout alone and the number where it is. */
+ * ggl_set_S_from_mixed, ggl_nearest_correlation, ggl_project_S) leave every existing layout alone and the number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -881,6 +881,33 @@ int ggl_mixed_correlation(int device, int p, int N, const int *ranks_host, const
  * matrices of the call above.  A refused call leaves the ctx's S as it was. */
 int ggl_set_S_from_mixed(ggl_ctx *ctx, const int *ranks_host, const int *types, int N, int B, int b, const int *idx,
                          double clip);
+
+/* ---- Nearest-correlation projection of an indefinite S (nearcorr.hip around the L-step's (C - mu I)_+): Higham's (2002)
+ * alternating projections with Dykstra's correction, what R's Matrix::nearPD does behind latentcor / mixedCCA.  The skeptic,
+ * pairwise-complete and latent matrices above need not be positive semidefinite; this makes them so.  Entry points that are
+ * only ADDED: GGL_VERSION stays where it is.
+ *
+ * A (B,p,p): symmetric matrices with a positive diagonal d (used as (A + A^T) / 2).  Per matrix, on D^-1/2 A D^-1/2 with the
+ * diagonal set to exactly 1, starting from Y = A, dS = 0:
+ *     R = Y - dS;   X = eps I + (R - eps I)_+;   dS = X - R;   Y' = X with the diagonal set to 1
+ *     r1 = |Y' - Y|_F / |Y'|_F,   delta = |Y' - X|_F,   r2 = delta / |Y'|_F;   stop when max(r1, r2) <= tol
+ * The B matrices run in lock-step; one that has stopped is frozen.  Then, always (also after max_iter iterations without
+ * convergence): with nu = delta / (1 - eps + delta) the result is (1 - nu) Y' off the diagonal and 1 on it, scaled back by
+ * sqrt(d_i d_j).  Since lambda_min(Y') >= eps - delta, its smallest eigenvalue is at least eps min_i d_i, and its diagonal is d.
+ * A matrix that meets the stopping test in iteration 1 needed no projection and is returned bit for bit (iters = 1, nu = 0;
+ * lambda_min >= eps - tol |A|_F then).  The result is exactly symmetric; two calls give the same bits.
+ * iters (B): the iterations run, -max_iter where the tolerance was not reached (not an error: the shrunk iterate is feasible,
+ * only not nearest).  info (B,4): max(r1, r2) of the last iteration, |out - A|_F, nu, eigendecomposition fallbacks of the
+ * L-step over the call (the same number in every row).
+ * GGL_E_ARG, the message naming the offender: B or p < 1, B > 65535, a NULL buffer, eps outside [0, 0.5], tol outside [1e-14, 1e-2],
+ * max_iter < 1; a non-finite entry or a non-positive diagonal entry (instance, variable).  A refused call writes nothing. */
+int ggl_nearest_correlation(int B, int p, const double *A, double *out, double eps, double tol, int max_iter, int *iters,
+                            double *info);
+/* ... of the S installed in a ctx, in place.  period = B > 0, a divisor of K: S holds B distinct matrices, instance k carrying
+ * matrix k % B (the layout of ggl_set_S_ex and of the ggl_set_S_from_*subsets calls); the first B are projected and replicated
+ * device to device.  period = 0 projects all K.  iters (B) and info (B,4) as above, B = K for period 0.  The variances kept
+ * beside a correlation S stay as they are.  A refused call (also: a period that does not divide K) leaves S bit for bit. */
+int ggl_project_S(ggl_ctx *ctx, int period, double eps, double tol, int max_iter, int *iters, double *info);
 
 #ifdef __cplusplus
 }
