@@ -158,6 +158,7 @@ _SIGNATURES = {
     "ggl_covariance_subsets": ([_i, _i, _i, _dp, _i, _i, _ip, _i, _dp, _dp], _i),
     "ggl_set_S_from_subsets": ([_vp, _dp, _i, _i, _i, _ip, _i], _i),
     "ggl_edge_stability": ([_vp, _i, _d, _ip, ctypes.POINTER(ctypes.c_longlong)], _i),
+    "ggl_heldout_scores": ([_vp, _dp, _i, _i, _i, _ip, _i, _dp], _i),
     "ggl_kendall_counts": ([_i, _i, _i, _ip, _i, _i, _ip, ctypes.POINTER(ctypes.c_longlong)], _i),
     "ggl_kendall_skeptic": ([_i, _i, _i, _ip, _i, _i, _ip, _dp, ctypes.POINTER(ctypes.c_longlong)], _i),
     "ggl_set_S_from_kendall": ([_vp, _ip, _i, _i, _i, _ip], _i),

@@ -139,15 +139,26 @@ extern "C" int ggl_selection_stats(ggl_ctx* c, double* out)
 {
     ARGCHK(c && out, "ctx, out");
     ARGCHK(c->snapT, "no snapshot taken (ggl_snapshot_k)");
+    return selection_stats_impl(c, out, nullptr, 0);
+}
+
+int selection_stats_impl(ggl_ctx* c, double* out, const double* S_test, int F)
+{
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);
     const int K = c->K, p = c->p;
     const size_t kp = (size_t)K * p;
     const int nblk = elementwise_blocks(p);
     std::vector<double> d(kp), dot(K), nnz(K);
-    // <S_k, Theta_k> and the non-zero count, per instance
-    launch_dot(c->stream, c->snapT, c->S, K, p, c->partials);
-    launch_reduce_partials(c->stream, c->partials, K, nblk, 1, c->norms);
+    // <S_k, Theta_k> (ggl_heldout_scores: <S_test[k % F], Theta_k>) and the non-zero count, per instance
+    if (S_test) {
+        int rcp = ensure_partials(c, (size_t)K * heldout_blocks(p));
+        if (rcp) return rcp;
+        launch_heldout_dot(c->stream, c->snapT, S_test, K, F, p, c->partials, c->norms);
+    } else {
+        launch_dot(c->stream, c->snapT, c->S, K, p, c->partials);
+        launch_reduce_partials(c->stream, c->partials, K, nblk, 1, c->norms);
+    }
     HIPCHK(hipMemcpyAsync(dot.data(), c->norms, K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     launch_count_nonzero(c->stream, c->snapT, K, p, c->partials);
     launch_reduce_partials(c->stream, c->partials, K, nblk, 1, c->norms + K);

@@ -313,6 +313,44 @@ extern "C" int ggl_set_S_from_subsets(ggl_ctx* c, const double* X_host, int N, i
     return install_subset_S(c, dS.p, B, var);
 }
 
+// K-fold cross-validation: the held-out score <S_test[k % F], Theta_k> of every snapshot of a ctx of K = L * F instances
+// (k_heldout_dot, stars.hip) beside the three numbers of ggl_selection_stats, whose route it takes.  The test covariances
+// are built as above, beside the ctx: its S is neither read nor written.
+extern "C" int ggl_heldout_scores(ggl_ctx* c, const double* X_host, int N, int F, int m, const int* idx_test, int flags,
+                                  double* out)
+{
+    ARGCHK(c, "ctx");
+    ARGCHK(X_host, "X");
+    ARGCHK(idx_test, "idx_test");
+    ARGCHK(out, "out");
+    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) has no held-out scores");
+    if ((flags & ~GGL_COV_CENTER) != 0)
+        return fail(GGL_E_ARG, "bad argument: flags = %d, held-out scores take GGL_COV_CENTER or 0 (no GGL_COV_SCALE: the folds share one scale)", flags);
+    if (F < 1 || F > 65535 || c->K % F != 0)
+        return fail(GGL_E_ARG, "bad argument: F = %d folds do not divide the K = %d instances of the ctx", F, c->K);
+    if (m < 1) return fail(GGL_E_ARG, "bad argument: m = %d, every test fold needs at least one observation", m);
+    ARGCHK(N >= 1, "N >= 1");
+    for (int f = 0; f < F; ++f)
+        for (int q = 0; q < m; ++q) {
+            const int n = idx_test[(size_t)f * m + q];
+            if (n < 0 || n >= N)
+                return fail(GGL_E_ARG, "bad argument: fold %d, position %d holds the index %d, outside [0, %d)", f, q, n, N);
+        }
+    ARGCHK(c->snapT, "no snapshot taken (ggl_snapshot_k)");
+    ARGCHK((size_t)c->K * heldout_blocks(c->p) < ((size_t)1 << 31), "K * p * p too large for one launch");
+    int rc = check_subset_args(c->p, N, X_host, F, m, idx_test, flags);      // (the sizes the covariance route takes)
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    DROP_PRE(c);
+    DevBuf dS, dVar;
+    HIPCHK(dS.alloc((size_t)F * c->p * c->p));
+    HIPCHK(dVar.alloc((size_t)F * c->p));
+    rc = subsets_to_device(c->stream, c->p, N, X_host, F, m, idx_test, flags, dS.p, dVar.p);
+    if (rc) return rc;
+    // (waits for the stream before it returns: dS is freed behind it)
+    return selection_stats_impl(c, out, dS.p, F);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Kendall's tau-b and the skeptic matrix sin(pi/2 tau) from dense ranks (kernels: kendall.hip): the ranks go up once, the
 // columns of the B subsets are gathered on the device, the counts G = Z Z^T are exact 64-bit integers

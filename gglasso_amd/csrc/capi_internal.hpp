@@ -15,7 +15,8 @@
 //   capi_ext.hip        ext_ADMM_MGL (instances of different dimension)
 //   capi_ops.hip        stateless operator entry points, development probes
 //   capi_data.hip       sample covariance from data and from column subsets of one data array, scaling by a diagonal
-//                       (stateless and into a ctx's S); rank correlation, pairwise-complete and weighted covariance
+//                       (stateless and into a ctx's S); rank correlation, pairwise-complete and weighted covariance;
+//                       held-out scores of a cross-validation (ggl_heldout_scores)
 //   capi_nearcorr.hip   nearest-correlation projection of an indefinite S (stateless and in place on a ctx's S)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -410,6 +411,9 @@ int probe_part_streams(ggl_ctx* c);
 int rank_step(ggl_ctx* c);
 int rank_step_impl(ggl_ctx* c);
 void sanitize_bounds(ggl_ctx* c, double* b, const double* repl, double repl_scale, double repl_scalar = 1.0);
+// ggl_selection_stats of the ctx's snapshots; S_test (F,p,p, device) not null: column 0 is <S_test[k % F], Theta_k>
+// (ggl_heldout_scores) instead of <S_k, Theta_k>.  Writes out only on success.
+int selection_stats_impl(ggl_ctx* c, double* out, const double* S_test, int F);
 int sgl_batch_step_impl(ggl_ctx* c, const double* rho, const double* lambda1, int latent, const double* mu1,
                                double* out_norms);
 int snapshot_many(ggl_ctx* c, const int* kd, ggl_ctx* src, const int* ks, int n, bool with_state);

@@ -553,6 +553,10 @@ void launch_gather_cols(hipStream_t st, const double* X, const int* idx, double*
 // diagonal; num[l] (zeroed by the caller) += sum_{i<j} c (B - c)
 void launch_edge_stability(hipStream_t st, const double* T, int L, int B, int p, double t, int* counts,
                            unsigned long long* num);
+// Held-out scores of a cross-validation (stars.hip).  T (K,p,p), St (F,p,p): out[k] = <St[k % F], T[k]>, in a fixed order.
+// partials: K * heldout_blocks(p) doubles of scratch
+int heldout_blocks(int p);
+void launch_heldout_dot(hipStream_t st, const double* T, const double* St, int K, int F, int p, double* partials, double* out);
 
 // Kendall's tau-b and the skeptic matrix on the int8 matrix cores (kendall.hip).  out[r,i,c] = R[i, idx[r,c]]: R (p,N) int32
 // dense ranks, idx (B,b) with every entry in [0,N) (the caller checked)

@@ -7,6 +7,9 @@
 // The gather writes the packed arena the covariance kernels read (covariance.hip: instance r is the row-major (p, b) array
 // at r p b), so the B subset covariances are an ordinary K = B call of launch_row_means / launch_gram_nt /
 // launch_scale_by_diag and bitwise those of host-gathered columns.  Both kernels move bytes and do next to no arithmetic.
+//
+// The same layout with folds for subsamples serves K-fold cross-validation, whose output side is at the end of this file:
+//     out[l*F + f] = <S_test[f], Theta[l*F + f]>                              k_heldout_dot, k_heldout_final
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -126,6 +129,107 @@ void launch_edge_stability(hipStream_t st, const double* T, int L, int B, int p,
 {
     const int nT = (p + ES_TILE - 1) / ES_TILE;
     hipLaunchKernelGGL(k_edge_stability, dim3(nT * (nT + 1) / 2, L), dim3(256), 0, st, T, B, p, t, counts, num);
+}
+
+// Held-out scores of a K-fold cross-validation: out[k] = <St[k % F], T[k]> for the K = L F snapshots T and the F test
+// covariances St (ggl_heldout_scores).  Workgroup g of instance k takes the elements [g, g + 1) HO_CHUNK of the row-major
+// matrix, i.e. whole consecutive rows and pieces of them, read once: a lane loads 16 bytes, a wave 1 KiB of one stack per
+// instruction, and 4 + 4 such loads of a thread are issued before the first product (8 KiB per wave in flight).
+//
+// Order of the sum, fixed by p alone: a thread adds its elements, 256 apart, into four accumulators by turns and combines
+// them as (a0 + a1) + (a2 + a3); wave_sum; the four wave sums as (w0 + w1) + (w2 + w3) into partials[k][g]; k_heldout_final
+// adds the partials of an instance in index order g = 0, 1, ...  No atomics: the same inputs give the same bits, and
+// instance k reads T[k] and St[k % F] and nothing else, whichever instances share the launch.
+//
+// What bounds it: memory traffic, 2 flops per 16 bytes.  The bytes of T come from HBM, each read once (400 MB at p = 500,
+// K = 200); St is F matrices that L instances each re-read (10 MB there), so a workgroup moves as many bytes of St as of T,
+// from whichever cache holds them.  Measured (profiles/cross_validation.txt): 32.9 us for the 100 MB of T at K = 50 and
+// 117 us for 400 MB at K = 200, 0.38 and 0.43 of the 8 TB/s HBM peak counting T alone.  Not measured: where the St bytes
+// come from, and how much of the gap to a streaming copy (0.79 of the peak) they explain.  The chunk size and the loads in
+// flight were chosen from published figures for streaming reads on this chip, not tuned.  An odd p * p leaves every second matrix at
+// an address that is no multiple of 16, in T and St independently: such p take 8-byte loads (HO_VEC false), still 512
+// contiguous bytes per wave instruction.
+static constexpr int HO_THREADS = 256, HO_CHUNK = 8192, HO_UNROLL = 4;
+
+int heldout_blocks(int p) { return (int)(((size_t)p * p + HO_CHUNK - 1) / HO_CHUNK); }
+
+template <bool HO_VEC>
+__global__ __launch_bounds__(HO_THREADS) void k_heldout_dot(const double* __restrict__ T, const double* __restrict__ St, int F,
+                                                            int G, size_t pp, double* __restrict__ partials)
+{
+    __shared__ double wsum[HO_THREADS / 64];
+    const int k = blockIdx.x / G, g = blockIdx.x % G;
+    const size_t e0 = (size_t)g * HO_CHUNK, e1 = min(pp, e0 + (size_t)HO_CHUNK);      // e0 < pp: G = ceil(pp / HO_CHUNK)
+    const double* t = T + (size_t)k * pp + e0;
+    const double* s = St + (size_t)(k % F) * pp + e0;
+    double a[HO_UNROLL] = {0.0, 0.0, 0.0, 0.0};
+    if (HO_VEC) {
+        // pp and HO_CHUNK even: e0, e1 even, and the launcher checked that both stacks start at a multiple of 16 bytes
+        const int n = (int)((e1 - e0) / 2);
+        const double2* t2 = reinterpret_cast<const double2*>(t);
+        const double2* s2 = reinterpret_cast<const double2*>(s);
+        int i = threadIdx.x;
+        for (; i + (HO_UNROLL - 1) * HO_THREADS < n; i += HO_UNROLL * HO_THREADS) {
+            double2 x[HO_UNROLL], y[HO_UNROLL];
+#pragma unroll
+            for (int u = 0; u < HO_UNROLL; ++u) x[u] = t2[i + u * HO_THREADS];
+#pragma unroll
+            for (int u = 0; u < HO_UNROLL; ++u) y[u] = s2[i + u * HO_THREADS];
+#pragma unroll
+            for (int u = 0; u < HO_UNROLL; ++u) a[u] += x[u].x * y[u].x + x[u].y * y[u].y;
+        }
+        for (int u = 0; i < n; i += HO_THREADS, ++u) {
+            const double2 x = t2[i], y = s2[i];
+            a[u] += x.x * y.x + x.y * y.y;                                            // (at most HO_UNROLL - 1 turns)
+        }
+    } else {
+        const int n = (int)(e1 - e0);
+        int i = threadIdx.x;
+        for (; i + (HO_UNROLL - 1) * HO_THREADS < n; i += HO_UNROLL * HO_THREADS) {
+            double x[HO_UNROLL], y[HO_UNROLL];
+#pragma unroll
+            for (int u = 0; u < HO_UNROLL; ++u) x[u] = t[i + u * HO_THREADS];
+#pragma unroll
+            for (int u = 0; u < HO_UNROLL; ++u) y[u] = s[i + u * HO_THREADS];
+#pragma unroll
+            for (int u = 0; u < HO_UNROLL; ++u) a[u] += x[u] * y[u];
+        }
+        for (int u = 0; i < n; i += HO_THREADS, ++u) a[u] += t[i] * s[i];
+    }
+    const double w = wave_sum((a[0] + a[1]) + (a[2] + a[3]));
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+__global__ __launch_bounds__(256) void k_heldout_final(const double* __restrict__ partials, int K, int G, double* __restrict__ out)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= K) return;
+    const double* row = partials + (size_t)k * G;
+    double s = 0.0;
+    for (int g0 = 0; g0 < G; g0 += 8) {                                 // eight loads in flight, added in index order
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = row[min(g0 + u, G - 1)];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (g0 + u < G) s += v[u];
+    }
+    out[k] = s;
+}
+
+// (the caller checked K * heldout_blocks(p) < 2^31)
+void launch_heldout_dot(hipStream_t st, const double* T, const double* St, int K, int F, int p, double* partials, double* out)
+{
+    const size_t pp = (size_t)p * p;
+    const int G = heldout_blocks(p);
+    const bool vec = pp % 2 == 0 && (reinterpret_cast<uintptr_t>(T) | reinterpret_cast<uintptr_t>(St)) % 16 == 0;
+    if (vec)
+        hipLaunchKernelGGL(k_heldout_dot<true>, dim3(K * G), dim3(HO_THREADS), 0, st, T, St, F, G, pp, partials);
+    else
+        hipLaunchKernelGGL(k_heldout_dot<false>, dim3(K * G), dim3(HO_THREADS), 0, st, T, St, F, G, pp, partials);
+    hipLaunchKernelGGL(k_heldout_final, dim3((K + 255) / 256), dim3(256), 0, st, partials, K, G, out);
 }
 
 }  // namespace ggl

@@ -860,3 +860,192 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     if store_all:
         stats['COUNTS'], stats['THETA'] = COUNTS, THETA
     return sol, stats
+
+
+# -----------------------------------------------------------------------------------------------------------------
+# K-fold cross-validation of lambda1 from data: held-out Gaussian likelihood (the default of scikit-learn's
+# GraphicalLassoCV and of R's CVglasso).  F folds x L lambdas are F * L independent single problems of one dimension: ONE
+# batch, instance l * F + f = fold f at lambda l (the layout of StARS with B = F).  The data go to the device once for the
+# train covariances and once for the test covariances; what comes back is four numbers per point.
+# -----------------------------------------------------------------------------------------------------------------
+def cv_folds(N, n_folds=5, seed=0):
+    """``(train (F, N - m), test (F, m))`` int32 with sorted rows, ``m = N // F``: ONE permutation of range(N) from
+    ``numpy.random.default_rng([seed, F])``; test fold f is the permuted positions ``f m .. (f + 1) m - 1``, train set f every
+    other index (the ``N - F m`` left-over observations included: they are never tested).  Both arrays are rectangular."""
+    N, F = int(N), int(n_folds)
+    if F < 2:
+        raise ValueError(f"n_folds = {F}: cross-validation needs at least 2 folds")
+    if F > N:
+        raise ValueError(f"n_folds = {F} is more than the N = {N} observations")
+    m = N // F
+    if m < 2:
+        raise ValueError(f"n_folds = {F} leaves m = N // n_folds = {m} observations per test fold: a covariance needs at least 2")
+    perm = np.random.default_rng([int(seed), F]).permutation(N)
+    test = np.stack([np.sort(perm[f * m:(f + 1) * m]) for f in range(F)]).astype(np.int32)
+    train = np.stack([np.setdiff1d(np.arange(N), test[f]) for f in range(F)]).astype(np.int32)
+    return train, test
+
+
+def cv_select(CV, SE, rule='min'):
+    """The choice of a cross-validation on the scores ``CV`` (and their standard errors ``SE``) of a grid in descending
+    order: the index of the smallest usable CV, a tie going to the larger lambda (the smaller index) -- ``rule='min'`` -- or
+    the largest lambda with ``CV[l] <= CV[min] + SE[min]`` -- ``rule='one_se'``.  NaN (a failed point) and +inf (a Theta that
+    is not positive definite) are never chosen.  If no lambda is usable: index 0 and a RuntimeWarning."""
+    import warnings
+    if rule not in ('min', 'one_se'):
+        raise ValueError(f"rule = {rule!r}: 'min' or 'one_se'")
+    CV = np.asarray(CV, dtype=np.float64).reshape(-1)
+    SE = np.asarray(SE, dtype=np.float64).reshape(-1)
+    assert CV.size >= 1 and SE.shape == CV.shape
+    ok = np.flatnonzero(np.isfinite(CV))
+    if ok.size == 0:
+        warnings.warn("cross-validation: no lambda1 of the grid has a finite held-out score; the sparsest point of the grid is "
+                      "returned. Extend the grid to larger lambda1.", RuntimeWarning, stacklevel=2)
+        return 0
+    best = int(ok[np.argmin(CV[ok])])                         # (argmin: the first of equal values, i.e. the larger lambda)
+    if rule == 'min':
+        return best
+    band = CV[best] + (SE[best] if np.isfinite(SE[best]) else 0.0)
+    return int(ok[CV[ok] <= band][0])
+
+
+def _host_heldout_scores(Theta, S_test):
+    """numpy twin of ``HipEngine.heldout_scores``: Theta (K,p,p), S_test (F,p,p), instance k = fold k % F."""
+    import math
+    F = S_test.shape[0]
+    out = np.zeros((Theta.shape[0], 4))
+    for k, T in enumerate(Theta):
+        if not np.all(np.isfinite(T)):
+            out[k] = np.nan
+            continue
+        out[k] = (math.fsum((S_test[k % F] * T).ravel()), robust_logdet(T), np.count_nonzero(T), np.linalg.eigvalsh(T).min())
+    return out
+
+
+def cv_search(X, lambda_range, n_folds=5, seed=0, folds=None, rule='min', center=True, scale=False, tol=1e-7, rtol=1e-7,
+              max_iter=1000, store_all=False, lambdas_per_batch=None, correlation=None, missing=None, project=False,
+              latent=False, lambda1_mask=None):
+    """K-fold cross-validation of lambda1 for the Single Graphical Lasso from observations ``X`` (p,N), variables in rows.
+    Returns ``(sol, stats)``.
+
+    * Folds: ``cv_folds(N, n_folds, seed)``, or ``folds = (train (F,a), test (F,m))`` given by the caller.  The grid is used in
+      descending order, ``stats['LAMBDA']``.
+    * ``Theta[l,f]`` solves ``ADMM_SGL(S_train_f, lambda[l])`` from ``Omega_0 = X_0 = identity``, ``S_train_f =
+      numpy.cov(X[:, train[f]], bias=True)`` (without ``center`` the raw second moment); all F * L points run as one batch.
+    * ``NLL[l,f] = <S_test_f, Theta[l,f]> - log det Theta[l,f]``: twice the negative log-likelihood per held-out observation,
+      up to a constant.  Theta is scored, not Omega: the sparse iterate is the estimate the package returns and the one its
+      information criteria (``ebic_single``) score.  A Theta that is not positive definite (``robust_logdet`` = -inf) scores
+      +inf and is listed in ``NOT_PD``; a lambda with a point that ended as 'solver error' gets NaN and is listed in ``FAILED``.
+    * ``CV[l]`` = mean over the folds, ``SE[l] = std(NLL[l], ddof=1) / sqrt(F)``, ``IX = cv_select(CV, SE, rule)``.
+    * ``scale=True``: every variable is divided by its standard deviation over all N observations, once, before the split (the
+      folds share one scale); the solution is that of the scaled data and ``stats['scale']`` holds the variances.
+    * ``sol``: ``ADMM_SGL`` on the covariance of all N observations at the chosen lambda1 (``stats['BEST']``).
+
+    With the device engine the data are uploaded, the covariances never exist on the host and four numbers per point come
+    back (``HipEngine.heldout_scores``); ``store_all`` also returns ``THETA`` (L,F,p,p).  ``lambdas_per_batch`` as in
+    ``stars_search``.  An engine without ``set_data_subsets`` / ``heldout_scores`` takes the same batch call on numpy
+    covariances and scores on the host (``math.fsum``, ``robust_logdet``).
+
+    Not implemented, each a ValueError: ``correlation=``, ``missing=``, ``project=`` (a held-out Gaussian likelihood against a
+    rank matrix is a different estimator), latent variables, a ``lambda1_mask``, multiple-instance data."""
+    import warnings
+    from . import solver as _solver, utils
+    from .batch import _late_failures, _sgl_batch_impl
+    for name, val in (('correlation', correlation), ('missing', missing)):
+        if val is not None:
+            raise ValueError(f"cv_search: {name}={val!r} is not implemented: a held-out Gaussian likelihood against such a matrix "
+                             f"is a different estimator")
+    if project:
+        raise ValueError("cv_search: project=True is not implemented: a held-out Gaussian likelihood against a projected matrix "
+                         "is a different estimator")
+    if latent:
+        raise ValueError("cv_search: latent variables are not implemented")
+    if lambda1_mask is not None:
+        raise ValueError("cv_search: a lambda1_mask is not implemented")
+    if isinstance(X, (list, tuple, dict)) or np.ndim(X) != 2:
+        raise ValueError("cv_search: data must be ONE (p,N) array with variables in rows; multiple-instance (GGL/FGL) problems "
+                         "are not implemented")
+    if rule not in ('min', 'one_se'):
+        raise ValueError(f"rule = {rule!r}: 'min' or 'one_se'")
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    p, N = X.shape
+    lam = np.sort(np.atleast_1d(np.asarray(lambda_range, dtype=np.float64)).reshape(-1))[::-1].copy()
+    assert lam.size >= 1 and np.all(lam > 0), "lambda1 should be positive"
+    if folds is None:
+        train, test = cv_folds(N, n_folds, seed)
+    else:
+        train, test = (utils._subset_indices(a) for a in folds)
+        assert train.shape[0] == test.shape[0] >= 1, "folds = (train, test) must hold the same number of rows"
+        assert train.shape[1] >= 1 and test.shape[1] >= 1, "every fold needs at least one train and one test observation"
+        # (the library checks the range on the device route; the host route indexes numpy arrays, which would wrap)
+        assert min(train.min(), test.min()) >= 0 and max(train.max(), test.max()) < N, f"folds must lie in [0, {N})"
+    F, L = test.shape[0], lam.size
+    var = None
+    if scale:
+        var = X.var(axis=1) if center else (X * X).mean(axis=1)
+        for i in np.flatnonzero(~(var > 0)):
+            raise ValueError(f"cv_search: variable {int(i)} is constant over the N = {N} observations (variance {var[i]}): "
+                             f"it cannot be scaled")
+        X = np.ascontiguousarray(X / np.sqrt(var)[:, None])
+    per = L if lambdas_per_batch is None else max(1, int(lambdas_per_batch))
+    on_device = hasattr(_solver.ENGINE, "set_data_subsets") and hasattr(_solver.ENGINE, "heldout_scores")
+    eye = np.eye(p)
+    OUT = np.zeros((L, F, 4))
+    failed = np.zeros(L, dtype=bool)
+    THETA = np.zeros((L, F, p, p)) if store_all else None
+    if not on_device:
+        S_train = _host_subset_covariances(X, train, center, False)
+        S_test = _host_subset_covariances(X, test, center, False)
+    for l0 in range(0, L, per):
+        sl = slice(l0, min(L, l0 + per))
+        nl = sl.stop - sl.start
+        lam_k = np.repeat(lam[sl], F)                                   # instance (l - l0) * F + f
+        got = {}
+
+        def before(eng):
+            eng.set_data_subsets(X, train, center=center)
+
+        def after(eng, results):
+            got['scores'] = eng.heldout_scores(X, test, center=center)
+            _late_failures(eng, results, 1)        # (the eigenvalues of the statistics may mark a point)
+
+        if on_device:
+            # (the S argument only shapes the ctx, as in stars_search: `before` writes the real S on the device)
+            res = _sgl_batch_impl(eye, lam_k, eye, None, eye, 1., max_iter, tol, rtol, True,
+                                  False, False, None, None, False, None, None, True, ('Theta',) if store_all else (), None,
+                                  None, _on_device=(before, after))
+            OUT[sl] = got['scores'].reshape(nl, F, 4)
+        else:
+            res = _sgl_batch_impl(np.tile(S_train, (nl, 1, 1)), lam_k, eye, None, eye, 1., max_iter, tol, rtol, True, False,
+                                  False, None, None, False, None, None, True, None, None, None)
+            OUT[sl] = _host_heldout_scores(np.stack([sol['Theta'] for sol, _ in res]), S_test).reshape(nl, F, 4)
+        if store_all:
+            THETA[sl] = np.stack([sol['Theta'] for sol, _ in res]).reshape(nl, F, p, p)
+        failed[sl] = np.array([info['status'] == 'solver error' for _, info in res]).reshape(nl, F).any(axis=1)
+    with np.errstate(invalid='ignore'):
+        NLL = OUT[:, :, 0] - OUT[:, :, 1]                               # (log det = -inf: +inf)
+    not_pd = np.isneginf(OUT[:, :, 1]) & ~failed[:, None]
+    NLL[not_pd] = np.inf
+    NLL[failed] = np.nan
+    with np.errstate(invalid='ignore'):
+        CV = NLL.mean(axis=1)
+        SE = NLL.std(axis=1, ddof=1) / np.sqrt(F) if F > 1 else np.full(L, np.nan)
+    if failed.any():
+        warnings.warn(f"cross-validation: a fold failed at lambda1 = {[float(v) for v in lam[failed]]}; these grid points have no "
+                      f"score and are not chosen", RuntimeWarning, stacklevel=2)
+    ix = cv_select(CV, SE, rule)
+    if on_device:
+        S_full = utils.sample_covariance(X, center=center)
+    else:
+        S_full = _host_subset_covariances(X, np.arange(N)[None], center, False)[0]
+    sol, _ = _solver.ADMM_SGL(S_full, lam[ix], eye, X_0=eye, tol=tol, rtol=rtol, max_iter=max_iter, verbose=False)
+    NNZ = OUT[:, :, 2].copy()
+    NNZ[failed] = np.nan
+    stats = {'LAMBDA': lam, 'NLL': NLL, 'CV': CV, 'SE': SE, 'IX': ix, 'BEST': {'lambda1': lam[ix]}, 'TRAIN': train,
+             'TEST': test, 'n_folds': F, 'rule': rule, 'NNZ': NNZ, 'FAILED': [int(l) for l in np.flatnonzero(failed)],
+             'NOT_PD': [(int(l), int(f)) for l, f in zip(*np.nonzero(not_pd))]}
+    if scale:
+        stats['scale'] = var
+    if store_all:
+        stats['THETA'] = THETA
+    return sol, stats

@@ -430,6 +430,34 @@ class glasso_problem:
         self._keep(sol)
         self.modelselect_stats = dict(stats)
 
+    def cross_validation(self, modelselect_params=None, n_folds=5, seed=0, rule='min', tol=1e-7, rtol=1e-7, store_all=False):
+        """Pick ``lambda1`` of a Single Graphical Lasso problem built by ``from_data`` by K-fold cross-validation of the
+        held-out Gaussian likelihood (``model_selection.cv_search``) over ``modelselect_params['lambda1_range']``;
+        ``rule``: 'min' or 'one_se'.  ``self.reg_params['lambda1']`` is set to the choice, the estimate on all observations goes
+        to ``self.solution`` and the scores to ``self.modelselect_stats``.  With ``do_scaling`` every variable is scaled once, by
+        its standard deviation over all observations, and the solution goes back to the covariances' scale, as in ``solve``.
+        A problem built with ``correlation=``, ``missing=`` or ``project=True`` is refused: a held-out Gaussian likelihood
+        against such a matrix is a different estimator."""
+        assert getattr(self, '_observations', None) is not None, \
+            "Cross-validation splits the observations: build the problem with glasso_problem.from_data(X)."
+        assert not self.multiple, "Cross-validation is implemented for Single Graphical Lasso problems only."
+        assert not self.latent, "Cross-validation is not implemented for problems with latent variables."
+        self.set_modelselect_params(modelselect_params)
+        assert self.modelselect_params.get('lambda1_mask') is None and self.reg_params.get('lambda1_mask') is None, \
+            "Cross-validation is not implemented with a lambda1_mask."
+        if getattr(self, '_correlation', None) is not None:
+            raise ValueError(f"Cross-validation is not implemented for a problem built with correlation={self._correlation!r}.")
+        if getattr(self, '_missing', None) is not None:
+            raise ValueError(f"Cross-validation is not implemented for a problem built with missing={self._missing!r}.")
+        if getattr(self, '_project_S', False):
+            raise ValueError("Cross-validation is not implemented for a problem built with project=True.")
+        sol, stats = _ms.cv_search(self._observations[0], self.modelselect_params['lambda1_range'], n_folds=n_folds, seed=seed,
+                                   rule=rule, center=self._center, scale=bool(self.do_scaling), tol=tol, rtol=rtol,
+                                   store_all=store_all)
+        self.set_reg_params(stats['BEST'])
+        self._keep(sol)
+        self.modelselect_stats = dict(stats)
+
     def _select_single(self, criterion, store_all):
         grid = self.modelselect_params
         sol, Thetas, Ls, stats = _ms.single_grid_search(

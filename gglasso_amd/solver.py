@@ -229,6 +229,23 @@ class HipEngine:
                                           num.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
         return (num, tab) if counts else num
 
+    def heldout_scores(self, X, test_idx, center=True, out=None):
+        """K-fold cross-validation over the Theta snapshots of a batch of K = L * F points (instance l * F + f: fold f at
+        lambda l): (K,4) = ``<S_test[k % F], Theta_k>``, log det Theta_k, count_nonzero(Theta_k), lambda_min(Theta_k), with
+        ``S_test[f]`` the covariance of ``X[:, test_idx[f]]`` (``test_idx`` (F,m) ints) built on the device beside the ctx's S
+        (``ggl_heldout_scores``).  The last three columns are the bits of ``selection_stats``.  ``out``: a (K,4) array to
+        write into; a refused call leaves it alone."""
+        from .utils import _subset_indices
+        X = as_c(X)
+        assert X.ndim == 2 and X.shape[0] == self.p, f"data must be a ({self.p}, N) array"
+        idx = _subset_indices(test_idx)
+        if out is None:
+            out = np.zeros((self.K, 4))
+        assert out.shape == (self.K, 4) and out.dtype == np.float64 and out.flags.c_contiguous
+        check(self.lib.ggl_heldout_scores(self.h, ptr(X), X.shape[1], idx.shape[0], idx.shape[1],
+                                          idx.ctypes.data_as(_lib._ip), _lib.COV_CENTER if center else 0, ptr(out)))
+        return out
+
     def get_S(self):
         """S (K,p,p) as it lies on the device; after ``set_data(..., scale=True)`` the pair (S, variances (K,p))."""
         S = np.empty((self.K, self.p, self.p))

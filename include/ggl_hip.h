@@ -30,7 +30,7 @@ extern "C" {
  * ggl_diag_stats, ggl_covariance_subsets, ggl_set_S_from_subsets, ggl_edge_stability, ggl_kendall_counts, ggl_kendall_skeptic,
  * ggl_set_S_from_kendall, ggl_covariance_pairwise, ggl_covariance_pairwise_subsets, ggl_set_S_from_data_pairwise,
  * ggl_set_S_from_subsets_pairwise, ggl_covariance_weighted, ggl_set_S_from_weighted, ggl_mixed_correlation,
- * ggl_set_S_from_mixed, ggl_nearest_correlation, ggl_project_S) leave every existing layout alone and the number where it is. */
+ * ggl_set_S_from_mixed, ggl_nearest_correlation, ggl_project_S, ggl_heldout_scores) leave every existing layout alone and the number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -774,6 +774,22 @@ int ggl_set_S_from_subsets(ggl_ctx *ctx, const double *X_host, int N, int B, int
  * num_out[l] = sum_{i<j} c (B - c), an exact integer (L values); counts_out (L,p,p) int32 or NULL: c mirrored, zero diagonal.
  * Integer sums: two calls return the same bits.  GGL_E_ARG: B < 1 or not dividing K, t negative or not finite, no snapshot. */
 int ggl_edge_stability(ggl_ctx *ctx, int B, double t, int *counts_out, long long *num_out);
+
+/* ---- K-fold cross-validation of lambda1 from data: the held-out score of every solution, on the device (k_heldout_dot,
+ * stars.hip).  An entry point that is only ADDED: GGL_VERSION stays where it is.
+ *
+ * For a ctx of K = L * F instances that holds Theta snapshots, instance k = fold k % F at lambda k / F (the layout of
+ * ggl_set_S_from_subsets with B = F).  idx_test (F,m): the observations fold f was NOT fitted on.  The F test covariances are
+ * bitwise what ggl_covariance_subsets returns for (X_host, idx_test, flags); they live in a temporary device stack, the
+ * ctx's S is neither read nor written.
+ *   out[k*4..] = { <S_test[k % F], Theta_k>, log det Theta_k, count_nonzero(Theta_k), lambda_min(Theta_k) }
+ * the last three the bits of ggl_selection_stats.  The inner product is summed in a fixed order without floating-point
+ * atomics: two calls return the same bits, and instance k's value depends on Theta_k and S_test[k % F] alone.
+ * flags: GGL_COV_CENTER or 0.  GGL_E_ARG, found before any device work (nothing is written to out, the ctx stays as it
+ * was): any other flag bit, F < 1 or not dividing K, m < 1, an index outside [0,N) (the message names fold and position),
+ * a NULL buffer, a ctx without snapshots, a ctx with instance dimensions. */
+int ggl_heldout_scores(ggl_ctx *ctx, const double *X_host, int N, int F, int m, const int *idx_test, int flags,
+                       double *out);
 
 /* ---- Rank correlation from data: Kendall's tau-b between every pair of variables and the nonparanormal skeptic matrix
  * sin(pi/2 tau) (Liu, Han, Yuan, Lafferty, Wasserman 2012) on the int8 matrix cores (kendall.hip).  Entry points that are only
