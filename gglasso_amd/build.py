@@ -19,7 +19,7 @@ SOURCES = ["elementwise.hip", "theta_pair.hip", "theta_fsgl.hip", "ext_group.hip
            # the C ABI, by subject (csrc/capi_internal.hpp has the map)
            "capi_ctx.hip", "capi_omega.hip", "capi_lstep.hip", "capi_batch.hip", "capi_snapshots.hip", "capi_checks.hip",
            "capi_stats.hip", "capi_comm.hip", "capi_ext.hip", "capi_ops.hip", "capi_data.hip", "capi_nearcorr.hip"]
-HEADERS = ["common.hpp", "kernels.hpp", "sym_tile.hpp", "ggl_comm.hpp", "capi_internal.hpp", os.path.join("..", "..", "include", "ggl_hip.h")]
+HEADERS = ["common.hpp", "kernels.hpp", "sym_tile.hpp", "gram_nt_tile.hpp", "ggl_comm.hpp", "capi_internal.hpp", os.path.join("..", "..", "include", "ggl_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs; without it hipcc 7.2 shuttles the f64
 # accumulators VGPR<->AGPR around every k-slab (64 extra moves + a full matrix-pipe drain per slab)

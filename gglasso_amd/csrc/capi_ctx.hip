@@ -707,10 +707,36 @@ static int upload_stack(ggl_ctx* c, double* dst, const double* src, int period)
     }
     ARGCHK(c->K % period == 0, "the period of a shared array must divide K");
     HIPCHK(hipMemcpyAsync(dst, src, (size_t)period * pp * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    for (size_t have = (size_t)period; have < (size_t)c->K; have *= 2) {
+    return replicate_instances(c, dst, period);
+}
+
+int replicate_instances(ggl_ctx* c, double* stack, int have_)
+{
+    const size_t pp = (size_t)c->p * c->p;
+    for (size_t have = (size_t)have_; have < (size_t)c->K; have *= 2) {
         const size_t take = std::min(have, (size_t)c->K - have);
-        HIPCHK(hipMemcpyAsync(dst + have * pp, dst, take * pp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(stack + have * pp, stack, take * pp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     }
+    return GGL_OK;
+}
+
+void s_replaced_begin(ggl_ctx* c)
+{
+    c->spec_have = false;
+    c->cw_have = false;
+    c->cwL_have = false;
+    c->wf_ready = false;
+    c->S_symmetric = false;
+}
+
+int s_replaced_end(ggl_ctx* c)
+{
+    launch_asym_max(c->stream, c->S, c->K, c->p, c->norms);
+    HIPCHK(hipGetLastError());
+    double asym = 1.0;
+    int rc = host_reduce(c, c->K, 1, &asym, true);
+    if (rc) return rc;
+    c->S_symmetric = (asym == 0.0);
     return GGL_OK;
 }
 
@@ -718,23 +744,13 @@ extern "C" int ggl_set_S_ex(ggl_ctx* c, const double* S, int period)
 {
     ARGCHK(c && S, "ctx, S");
     c->cov_scale.clear();
-    c->spec_have = false;
-    c->cw_have = false;
-    c->cwL_have = false;
+    s_replaced_begin(c);
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);
     int rc = upload_stack(c, c->S, S, period);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
-    // exact symmetry of S decides whether a Theta kernel may form the next W per element (GGL_OPT_FUSED_W)
-    launch_asym_max(c->stream, c->S, c->K, c->p, c->norms);
-    HIPCHK(hipGetLastError());
-    double asym = 1.0;
-    rc = host_reduce(c, c->K, 1, &asym, true);
-    if (rc) return rc;
-    c->S_symmetric = (asym == 0.0);
-    c->wf_ready = false;
-    return GGL_OK;
+    return s_replaced_end(c);
 }
 
 extern "C" int ggl_set_S(ggl_ctx* c, const double* S) { return ggl_set_S_ex(c, S, 0); }

@@ -1,5 +1,8 @@
-// C ABI: the input side -- sample covariance from observations and scaling by a diagonal (kernels: covariance.hip), as
-// stateless operators (host buffers in, host buffers out) and straight into the S of a ctx.
+// C ABI: the input side -- everything that makes an S from data, as stateless operators (host buffers in, host buffers out)
+// and straight into the S of a ctx: sample covariance of K instances or of column subsets of one array and scaling by a
+// diagonal (kernels: covariance.hip), pairwise-complete covariance of data with NaN (covariance_missing.hip), weighted
+// covariance (covariance_weighted.hip), Kendall's tau and the latent correlation of mixed data (kendall.hip, bridge.hip), and
+// the held-out scores of a cross-validation (stars.hip).  The idioms the routes share stand once, in the namespace below.
 #include "capi_internal.hpp"
 
 namespace {
@@ -10,13 +13,70 @@ template <class T> struct DevArr {
 };
 
 constexpr int COV_FLAGS = GGL_COV_CENTER | GGL_COV_SCALE | GGL_COV_TILE32 | GGL_COV_TILE64;
+constexpr int WCOV_FLAGS = COV_FLAGS | GGL_COV_FULL_RANGE;
+
+int check_cov_flags(int flags, int allowed)
+{
+    ARGCHK((flags & ~allowed) == 0,
+           (allowed & GGL_COV_FULL_RANGE)
+               ? "flags: unknown bits (GGL_COV_CENTER | GGL_COV_SCALE | GGL_COV_TILE32 | GGL_COV_TILE64 | GGL_COV_FULL_RANGE)"
+               : "flags: unknown bits (GGL_COV_CENTER | GGL_COV_SCALE | GGL_COV_TILE32 | GGL_COV_TILE64)");
+    ARGCHK(!((flags & GGL_COV_TILE32) && (flags & GGL_COV_TILE64)), "flags: GGL_COV_TILE32 and GGL_COV_TILE64 exclude each other");
+    return GGL_OK;
+}
+
+// the tile argument of the Gram launchers: 0 by size, 32, 64
+int cov_tile(int flags) { return (flags & GGL_COV_TILE64) ? 64 : ((flags & GGL_COV_TILE32) ? 32 : 0); }
+
+// idx (rows, cols): every entry in [0, N).  what: "subset" or "fold", for the message
+int check_index_table(const int* idx, int rows, int cols, int N, const char* what)
+{
+    for (int r = 0; r < rows; ++r)
+        for (int q = 0; q < cols; ++q) {
+            const int n = idx[(size_t)r * cols + q];
+            if (n < 0 || n >= N)
+                return fail(GGL_E_ARG, "bad argument: %s %d, position %d holds the index %d, outside [0, %d)", what, r, q, n, N);
+        }
+    return GGL_OK;
+}
+
+// what every route into a ctx's S asks of the ctx first, and of a period B
+int check_ctx_takes_S(const ggl_ctx* c)
+{
+    ARGCHK(c, "ctx");
+    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) takes its S from ggl_set_S");
+    return GGL_OK;
+}
+
+int check_divides_K(const ggl_ctx* c, int B)
+{
+    if (c->K % B != 0) return fail(GGL_E_ARG, "bad argument: B = %d subsets do not divide the K = %d instances of the ctx", B, c->K);
+    return GGL_OK;
+}
+
+// an error word a kernel left on the device, once the stream has run dry: the 32-bit word (GGL_DIAG_OK: none) and the 64-bit
+// word (every bit set: none)
+int read_err_word(hipStream_t st, const int* err_d, int* err)
+{
+    *err = GGL_DIAG_OK;
+    HIPCHK(hipMemcpyAsync(err, err_d, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return GGL_OK;
+}
+
+int read_err_word64(hipStream_t st, const unsigned long long* err_d, unsigned long long* err)
+{
+    *err = ~0ull;
+    HIPCHK(hipMemcpyAsync(err, err_d, sizeof(*err), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return GGL_OK;
+}
 
 int check_data_args(int K, int p, const int* N, const double* const* X_host, int flags)
 {
     ARGCHK(K >= 1 && p >= 1, "K >= 1, p >= 1");
     ARGCHK(N && X_host, "N, X");
-    ARGCHK((flags & ~COV_FLAGS) == 0, "flags: unknown bits (GGL_COV_CENTER | GGL_COV_SCALE | GGL_COV_TILE32 | GGL_COV_TILE64)");
-    ARGCHK(!((flags & GGL_COV_TILE32) && (flags & GGL_COV_TILE64)), "flags: GGL_COV_TILE32 and GGL_COV_TILE64 exclude each other");
+    RCCHK(check_cov_flags(flags, COV_FLAGS));
     ARGCHK((size_t)K * p < (size_t)GGL_DIAG_OK, "K * p too large");
     for (int k = 0; k < K; ++k) {
         if (!X_host[k]) return fail(GGL_E_ARG, "bad argument: X[%d] is NULL", k);
@@ -29,9 +89,8 @@ int check_data_args(int K, int p, const int* N, const double* const* X_host, int
 // as far as it was written (null: d_host holds the caller's), Xdiag: the stack the diagonal was taken from
 int diag_error(hipStream_t st, const int* err_d, int p, const double* d_host, const double* Xdiag, const char* what)
 {
-    int err = GGL_DIAG_OK;
-    HIPCHK(hipMemcpyAsync(&err, err_d, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    int err;
+    RCCHK(read_err_word(st, err_d, &err));
     if (err == GGL_DIAG_OK) return GGL_OK;
     const int k = err / p, i = err % p;
     double v = 0.0;
@@ -41,75 +100,134 @@ int diag_error(hipStream_t st, const int* err_d, int p, const double* d_host, co
                 what, k, i, v);
 }
 
-// S_dev (K,p,p) from the arena X_dev (instance k the packed row-major (p, N[k]) array at off[k]; off_dev, N_dev: the tables
-// on the device) on stream st; with GGL_COV_SCALE the correlations, and the variances in var_dev (K,p).  Waits for the
-// stream: the caller may free the arena on return.
-int covariance_of_arena(hipStream_t st, int K, int p, const double* X_dev, const long long* off_dev, const int* N_dev, int flags,
-                        double* S_dev, double* var_dev)
+// GGL_COV_SCALE: S_dev (K,p,p) is divided by its own diagonal in place, var_dev (K,p) gets the diagonal; a variance that is not
+// positive and finite is refused naming `what`
+int scale_in_place(hipStream_t st, int K, int p, double* S_dev, double* var_dev, const char* what)
 {
-    DevArr<double> dMean, dSd;
+    DevArr<double> dSd;
     DevArr<int> dErr;
+    HIPCHK(dSd.alloc((size_t)K * p));
+    HIPCHK(dErr.alloc(1));
+    HIPCHK(hipMemsetAsync(dErr.p, 0x7f, sizeof(int), st));
+    launch_scale_by_diag(st, S_dev, nullptr, S_dev, var_dev, dSd.p, dErr.p, K, p);
+    HIPCHK(hipGetLastError());
+    return diag_error(st, dErr.p, p, nullptr, S_dev, what);
+}
+
+// The data on the device as the Gram kernels read them: one arena of sum_k p N_k doubles, instance k the packed row-major
+// (p, N_k) array at off[k], and the two tables.  Filled on a stream; the host tables live as long as the arena, which a
+// caller frees only behind a wait for that stream (the *_of_arena functions end with one).
+struct Arena {
+    int K = 0;
+    DevArr<double> X, src;
+    DevArr<long long> off;
+    DevArr<int> N, idx;
+    std::vector<long long> off_h;
+    std::vector<int> N_h;
+
+    int tables(hipStream_t st, int K_, int p, const int* Nk)
+    {
+        K = K_;
+        off_h.resize(K);
+        N_h.assign(Nk, Nk + K);
+        size_t total = 0;
+        for (int k = 0; k < K; ++k) { off_h[k] = (long long)total; total += (size_t)p * N_h[k]; }
+        HIPCHK(X.alloc(total));
+        HIPCHK(off.alloc(K));
+        HIPCHK(N.alloc(K));
+        HIPCHK(hipMemcpyAsync(off.p, off_h.data(), K * sizeof(long long), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(N.p, N_h.data(), K * sizeof(int), hipMemcpyHostToDevice, st));
+        return GGL_OK;
+    }
+    // K instances from the host, each going up once (NaNs travel as they are)
+    int from_instances(hipStream_t st, int K_, int p, const int* Nk, const double* const* X_host)
+    {
+        RCCHK(tables(st, K_, p, Nk));
+        for (int k = 0; k < K; ++k)
+            HIPCHK(hipMemcpyAsync(X.p + off_h[k], X_host[k], (size_t)p * N_h[k] * sizeof(double), hipMemcpyHostToDevice, st));
+        return GGL_OK;
+    }
+    // B column subsets idx (B,b) of one (p,N) array: X goes up once, the columns are gathered on the device (k_gather_cols,
+    // stars.hip, moves bytes: NaNs travel)
+    int from_subsets(hipStream_t st, int p, int Ncols, const double* X_host, int B, int b, const int* idx_host)
+    {
+        const std::vector<int> Nb(B, b);
+        RCCHK(tables(st, B, p, Nb.data()));
+        HIPCHK(src.alloc((size_t)p * Ncols));
+        HIPCHK(idx.alloc((size_t)B * b));
+        HIPCHK(hipMemcpyAsync(src.p, X_host, (size_t)p * Ncols * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(idx.p, idx_host, (size_t)B * b * sizeof(int), hipMemcpyHostToDevice, st));
+        launch_gather_cols(st, src.p, idx.p, X.p, p, Ncols, B, b);
+        HIPCHK(hipGetLastError());
+        return GGL_OK;
+    }
+};
+
+// S_dev (K,p,p) from the arena on stream st; with GGL_COV_SCALE the correlations, and the variances in var_dev (K,p).  Waits
+// for the stream: the caller may free the arena on return.
+int covariance_of_arena(hipStream_t st, const Arena& a, int p, int flags, double* S_dev, double* var_dev)
+{
+    DevArr<double> dMean;
     const bool center = (flags & GGL_COV_CENTER) != 0;
     if (center) {
-        HIPCHK(dMean.alloc((size_t)K * p));
-        launch_row_means(st, X_dev, off_dev, N_dev, 0, dMean.p, K, p);
+        HIPCHK(dMean.alloc((size_t)a.K * p));
+        launch_row_means(st, a.X.p, a.off.p, a.N.p, dMean.p, a.K, p);
         HIPCHK(hipGetLastError());
     }
-    const int tile = (flags & GGL_COV_TILE64) ? 64 : ((flags & GGL_COV_TILE32) ? 32 : 0);
-    launch_gram_nt(st, X_dev, off_dev, N_dev, 0, center ? dMean.p : nullptr, S_dev, K, p, tile);
+    launch_gram_nt(st, a.X.p, a.off.p, a.N.p, center ? dMean.p : nullptr, S_dev, a.K, p, cov_tile(flags));
     HIPCHK(hipGetLastError());
-    if (flags & GGL_COV_SCALE) {
-        HIPCHK(dSd.alloc((size_t)K * p));
-        HIPCHK(dErr.alloc(1));
-        HIPCHK(hipMemsetAsync(dErr.p, 0x7f, sizeof(int), st));
-        launch_scale_by_diag(st, S_dev, nullptr, S_dev, var_dev, dSd.p, dErr.p, K, p);
-        HIPCHK(hipGetLastError());
-        int rc = diag_error(st, dErr.p, p, nullptr, S_dev, "the variance");
-        if (rc) return rc;
-    }
+    if (flags & GGL_COV_SCALE) RCCHK(scale_in_place(st, a.K, p, S_dev, var_dev, "the variance"));
     HIPCHK(hipStreamSynchronize(st));
     return GGL_OK;
 }
 
-// ... from the host data
+// ... from the host data of K instances
 int covariance_to_device(hipStream_t st, int K, int p, const int* N, const double* const* X_host, int flags, double* S_dev,
                          double* var_dev)
 {
-    std::vector<long long> off(K);
-    size_t total = 0;
-    for (int k = 0; k < K; ++k) { off[k] = (long long)total; total += (size_t)p * N[k]; }
-    // the data go up once, into one arena of sum_k p N_k doubles (instance k packed at off[k], row length N_k)
-    DevArr<double> dX;
-    DevArr<long long> dOff;
-    DevArr<int> dN;
-    HIPCHK(dX.alloc(total));
-    HIPCHK(dOff.alloc(K));
-    HIPCHK(dN.alloc(K));
-    HIPCHK(hipMemcpyAsync(dOff.p, off.data(), K * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dN.p, N, K * sizeof(int), hipMemcpyHostToDevice, st));
-    for (int k = 0; k < K; ++k)
-        HIPCHK(hipMemcpyAsync(dX.p + off[k], X_host[k], (size_t)p * N[k] * sizeof(double), hipMemcpyHostToDevice, st));
-    return covariance_of_arena(st, K, p, dX.p, dOff.p, dN.p, flags, S_dev, var_dev);      // (the arena is freed on return)
+    Arena a;
+    RCCHK(a.from_instances(st, K, p, N, X_host));
+    return covariance_of_arena(st, a, p, flags, S_dev, var_dev);
 }
+
+// The device results of a stateless covariance call and their way to the caller.  begin: the two checks of the output
+// arguments every such call makes behind its own, the device, the buffers; down: the last step of a call that was not refused.
+struct CovOut {
+    DevBuf S, var, wsum;
+    DevArr<int> cnt;
+    size_t K = 0, p = 0;
+    int begin(int device, int K_, int p_, int flags, const double* S_out, const double* scale_out, bool counts, bool sums)
+    {
+        ARGCHK(S_out, "S_out");
+        ARGCHK(!(flags & GGL_COV_SCALE) || scale_out, "GGL_COV_SCALE needs scale_out");
+        HIPCHK(hipSetDevice(device));
+        K = K_;
+        p = p_;
+        HIPCHK(S.alloc(K * p * p));
+        HIPCHK(var.alloc(K * p));
+        if (sums) HIPCHK(wsum.alloc(K));
+        if (counts) HIPCHK(cnt.alloc(K * p * p));
+        return GGL_OK;
+    }
+    int down(int flags, double* S_out, double* scale_out, int* counts_out = nullptr, double* wsum_out = nullptr)
+    {
+        DOWN(S_out, S.p, K * p * p);
+        if (flags & GGL_COV_SCALE) DOWN(scale_out, var.p, K * p);
+        if (wsum_out) DOWN(wsum_out, wsum.p, K);
+        if (counts_out) HIPCHK(hipMemcpy(counts_out, cnt.p, K * p * p * sizeof(int), hipMemcpyDeviceToHost));
+        return GGL_OK;
+    }
+};
 }  // namespace
 
 extern "C" int ggl_covariance(int device, int K, int p, const int* N, const double* const* X_host, int flags, double* S_out,
                               double* scale_out)
 {
-    int rc = check_data_args(K, p, N, X_host, flags);
-    if (rc) return rc;
-    ARGCHK(S_out, "S_out");
-    ARGCHK(!(flags & GGL_COV_SCALE) || scale_out, "GGL_COV_SCALE needs scale_out");
-    HIPCHK(hipSetDevice(device));
-    const size_t n = (size_t)K * p * p;
-    DevBuf dS, dVar;
-    HIPCHK(dS.alloc(n));
-    HIPCHK(dVar.alloc((size_t)K * p));
-    rc = covariance_to_device(nullptr, K, p, N, X_host, flags, dS.p, dVar.p);
-    if (rc) return rc;
-    DOWN(S_out, dS.p, n);
-    if (flags & GGL_COV_SCALE) DOWN(scale_out, dVar.p, (size_t)K * p);
-    return GGL_OK;
+    RCCHK(check_data_args(K, p, N, X_host, flags));
+    CovOut d;
+    RCCHK(d.begin(device, K, p, flags, S_out, scale_out, false, false));
+    RCCHK(covariance_to_device(nullptr, K, p, N, X_host, flags, d.S.p, d.var.p));
+    return d.down(flags, S_out, scale_out);
 }
 
 extern "C" int ggl_scale_by_diagonal(int device, int K, int p, const double* X_host, const double* d_in, double* Y_out,
@@ -132,8 +250,7 @@ extern "C" int ggl_scale_by_diagonal(int device, int K, int p, const double* X_h
     HIPCHK(hipMemset(dErr.p, 0x7f, sizeof(int)));
     launch_scale_by_diag(nullptr, dX.p, d_in ? dD.p : nullptr, dY.p, dDo.p, dSd.p, dErr.p, K, p);
     HIPCHK(hipGetLastError());
-    int rc = diag_error(nullptr, dErr.p, p, d_in, dX.p, d_in ? "d" : "the diagonal");
-    if (rc) return rc;
+    RCCHK(diag_error(nullptr, dErr.p, p, d_in, dX.p, d_in ? "d" : "the diagonal"));
     DOWN(Y_out, dY.p, n);
     if (d_out) DOWN(d_out, dDo.p, kp);
     return GGL_OK;
@@ -141,37 +258,23 @@ extern "C" int ggl_scale_by_diagonal(int device, int K, int p, const double* X_h
 
 extern "C" int ggl_set_S_from_data(ggl_ctx* c, const double* const* X_host, const int* N, int flags)
 {
-    ARGCHK(c, "ctx");
-    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) takes its S from ggl_set_S");
-    int rc = check_data_args(c->K, c->p, N, X_host, flags);
-    if (rc) return rc;
-    c->spec_have = false;
-    c->cw_have = false;
-    c->cwL_have = false;
+    RCCHK(check_ctx_takes_S(c));
+    RCCHK(check_data_args(c->K, c->p, N, X_host, flags));
     // S is overwritten from here on, also where a later step fails: nothing built for the old S may survive
-    c->wf_ready = false;
-    c->S_symmetric = false;
+    s_replaced_begin(c);
     c->cov_scale.clear();
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);
     const size_t kp = (size_t)c->K * c->p;
     DevBuf dVar;
     HIPCHK(dVar.alloc(kp));
-    rc = covariance_to_device(c->stream, c->K, c->p, N, X_host, flags, c->S, dVar.p);
-    if (rc) return rc;
+    RCCHK(covariance_to_device(c->stream, c->K, c->p, N, X_host, flags, c->S, dVar.p));
     if (flags & GGL_COV_SCALE) {
         c->cov_scale.resize(kp);
         HIPCHK(hipMemcpyAsync(c->cov_scale.data(), dVar.p, kp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
-    // as ggl_set_S: exact symmetry of S decides whether a Theta kernel may form the next W per element
-    launch_asym_max(c->stream, c->S, c->K, c->p, c->norms);
-    HIPCHK(hipGetLastError());
-    double asym = 1.0;
-    rc = host_reduce(c, c->K, 1, &asym, true);
-    if (rc) return rc;
-    c->S_symmetric = (asym == 0.0);
-    return GGL_OK;
+    return s_replaced_end(c);
 }
 
 extern "C" int ggl_get_S(ggl_ctx* c, double* S_out, double* scale_out)
@@ -180,137 +283,92 @@ extern "C" int ggl_get_S(ggl_ctx* c, double* S_out, double* scale_out)
     ARGCHK(!scale_out || !c->cov_scale.empty(), "scale_out: the S of this ctx was not computed from data with GGL_COV_SCALE");
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);
-    int rc = download_stacks(c, {{S_out, c->S, c->n * sizeof(double)}});
-    if (rc) return rc;
+    RCCHK(download_stacks(c, {{S_out, c->S, c->n * sizeof(double)}}));
     if (scale_out) std::memcpy(scale_out, c->cov_scale.data(), c->cov_scale.size() * sizeof(double));
     return GGL_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// covariances of B column subsets of one X (the subsamples of StARS stability selection): X goes up once, the columns
-// are gathered on the device (k_gather_cols, stars.hip) into the arena the kernels above read as a K = B call
+// covariances of B column subsets of one X (the subsamples of StARS stability selection): the arena of the subsets is what
+// the kernels above read as a K = B call
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
-int check_subset_args(int p, int N, const double* X_host, int B, int b, const int* idx, int flags)
+// everything but the range of the indices
+int check_subset_sizes(int p, int N, const double* X_host, int B, int b, const int* idx, int flags)
 {
     ARGCHK(p >= 1 && N >= 1, "p >= 1, N >= 1");
     ARGCHK(X_host && idx, "X, idx");
-    ARGCHK((flags & ~COV_FLAGS) == 0, "flags: unknown bits (GGL_COV_CENTER | GGL_COV_SCALE | GGL_COV_TILE32 | GGL_COV_TILE64)");
-    ARGCHK(!((flags & GGL_COV_TILE32) && (flags & GGL_COV_TILE64)), "flags: GGL_COV_TILE32 and GGL_COV_TILE64 exclude each other");
+    RCCHK(check_cov_flags(flags, COV_FLAGS));
     if (B < 1 || B > 65535) return fail(GGL_E_ARG, "bad argument: B = %d subsets, 1 .. 65535 are possible", B);
     if (b < 1) return fail(GGL_E_ARG, "bad argument: b = %d, every subset needs at least one sample", b);
     ARGCHK((size_t)B * p < (size_t)GGL_DIAG_OK, "B * p too large");
-    for (int r = 0; r < B; ++r)
-        for (int q = 0; q < b; ++q) {
-            const int n = idx[(size_t)r * b + q];
-            if (n < 0 || n >= N)
-                return fail(GGL_E_ARG, "bad argument: subset %d, position %d holds the index %d, outside [0, %d)", r, q, n, N);
-        }
     return GGL_OK;
+}
+
+int check_subset_args(int p, int N, const double* X_host, int B, int b, const int* idx, int flags)
+{
+    RCCHK(check_subset_sizes(p, N, X_host, B, b, idx, flags));
+    return check_index_table(idx, B, b, N, "subset");
 }
 
 // S_dev (B,p,p) and var_dev (B,p) of the subsets on stream st; the arguments have been checked
 int subsets_to_device(hipStream_t st, int p, int N, const double* X_host, int B, int b, const int* idx, int flags,
                       double* S_dev, double* var_dev)
 {
-    std::vector<long long> off(B);
-    std::vector<int> Nb(B, b);
-    for (int r = 0; r < B; ++r) off[r] = (long long)r * p * b;
-    DevArr<double> dX, dA;
-    DevArr<long long> dOff;
-    DevArr<int> dN, dIdx;
-    HIPCHK(dX.alloc((size_t)p * N));
-    HIPCHK(dA.alloc((size_t)B * p * b));
-    HIPCHK(dOff.alloc(B));
-    HIPCHK(dN.alloc(B));
-    HIPCHK(dIdx.alloc((size_t)B * b));
-    HIPCHK(hipMemcpyAsync(dX.p, X_host, (size_t)p * N * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dIdx.p, idx, (size_t)B * b * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dOff.p, off.data(), B * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dN.p, Nb.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
-    launch_gather_cols(st, dX.p, dIdx.p, dA.p, p, N, B, b);
-    HIPCHK(hipGetLastError());
-    // (waits for the stream before it returns: the host tables and the arenas go away behind it)
-    return covariance_of_arena(st, B, p, dA.p, dOff.p, dN.p, flags, S_dev, var_dev);
+    Arena a;
+    RCCHK(a.from_subsets(st, p, N, X_host, B, b, idx));
+    return covariance_of_arena(st, a, p, flags, S_dev, var_dev);
 }
 
 // The B complete matrices dS (B,p,p) become the S of the ctx, instance k = subset k % B (the layout of ggl_set_S_ex with period
-// B), replicated device to device; var: the (B,p) variances that go with them, or empty.  What earlier iterations carried is
-// forgotten, as in ggl_set_S.
-int install_subset_S(ggl_ctx* c, const double* dS, int B, const std::vector<double>& var)
+// B), replicated device to device; with GGL_COV_SCALE in flags dVar (B,p, device) holds the variances that go with them.  What
+// earlier iterations carried is forgotten, as in ggl_set_S.
+int install_subset_S(ggl_ctx* c, const double* dS, int B, const double* dVar = nullptr, int flags = 0)
 {
-    const size_t pp = (size_t)c->p * c->p;
-    c->spec_have = false;
-    c->cw_have = false;
-    c->cwL_have = false;
-    c->wf_ready = false;
-    c->S_symmetric = false;
-    c->cov_scale.clear();
-    HIPCHK(hipMemcpyAsync(c->S, dS, (size_t)B * pp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    for (size_t have = (size_t)B; have < (size_t)c->K; have *= 2) {
-        const size_t take = std::min(have, (size_t)c->K - have);
-        HIPCHK(hipMemcpyAsync(c->S + have * pp, c->S, take * pp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    std::vector<double> var;
+    if (flags & GGL_COV_SCALE) {
+        var.resize((size_t)B * c->p);
+        HIPCHK(hipMemcpyAsync(var.data(), dVar, var.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
     }
+    s_replaced_begin(c);
+    c->cov_scale.clear();
+    HIPCHK(hipMemcpyAsync(c->S, dS, (size_t)B * c->p * c->p * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    RCCHK(replicate_instances(c, c->S, B));
     if (!var.empty()) {
         c->cov_scale.resize((size_t)c->K * c->p);
         for (int k = 0; k < c->K; ++k)
             std::memcpy(c->cov_scale.data() + (size_t)k * c->p, var.data() + (size_t)(k % B) * c->p, c->p * sizeof(double));
     }
     HIPCHK(hipStreamSynchronize(c->stream));      // (the caller frees dS on return)
-    // as ggl_set_S: exact symmetry of S decides whether a Theta kernel may form the next W per element
-    launch_asym_max(c->stream, c->S, c->K, c->p, c->norms);
-    HIPCHK(hipGetLastError());
-    double asym = 1.0;
-    int rc = host_reduce(c, c->K, 1, &asym, true);
-    if (rc) return rc;
-    c->S_symmetric = (asym == 0.0);
-    return GGL_OK;
+    return s_replaced_end(c);
 }
 }  // namespace
 
 extern "C" int ggl_covariance_subsets(int device, int p, int N, const double* X_host, int B, int b, const int* idx, int flags,
                                       double* S_out, double* scale_out)
 {
-    int rc = check_subset_args(p, N, X_host, B, b, idx, flags);
-    if (rc) return rc;
-    ARGCHK(S_out, "S_out");
-    ARGCHK(!(flags & GGL_COV_SCALE) || scale_out, "GGL_COV_SCALE needs scale_out");
-    HIPCHK(hipSetDevice(device));
-    const size_t n = (size_t)B * p * p;
-    DevBuf dS, dVar;
-    HIPCHK(dS.alloc(n));
-    HIPCHK(dVar.alloc((size_t)B * p));
-    rc = subsets_to_device(nullptr, p, N, X_host, B, b, idx, flags, dS.p, dVar.p);
-    if (rc) return rc;
-    DOWN(S_out, dS.p, n);
-    if (flags & GGL_COV_SCALE) DOWN(scale_out, dVar.p, (size_t)B * p);
-    return GGL_OK;
+    RCCHK(check_subset_args(p, N, X_host, B, b, idx, flags));
+    CovOut d;
+    RCCHK(d.begin(device, B, p, flags, S_out, scale_out, false, false));
+    RCCHK(subsets_to_device(nullptr, p, N, X_host, B, b, idx, flags, d.S.p, d.var.p));
+    return d.down(flags, S_out, scale_out);
 }
 
 extern "C" int ggl_set_S_from_subsets(ggl_ctx* c, const double* X_host, int N, int B, int b, const int* idx, int flags)
 {
-    ARGCHK(c, "ctx");
-    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) takes its S from ggl_set_S");
-    int rc = check_subset_args(c->p, N, X_host, B, b, idx, flags);
-    if (rc) return rc;
-    if (c->K % B != 0) return fail(GGL_E_ARG, "bad argument: B = %d subsets do not divide the K = %d instances of the ctx", B, c->K);
+    RCCHK(check_ctx_takes_S(c));
+    RCCHK(check_subset_args(c->p, N, X_host, B, b, idx, flags));
+    RCCHK(check_divides_K(c, B));
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);
     // The B matrices are built beside the ctx's S, which is overwritten only once they are complete: a call that is refused
     // (here or by the variance check of GGL_COV_SCALE) leaves S, and what was built for it, as it was.
-    const size_t pp = (size_t)c->p * c->p, bp = (size_t)B * c->p;
     DevBuf dS, dVar;
-    HIPCHK(dS.alloc((size_t)B * pp));
-    HIPCHK(dVar.alloc(bp));
-    rc = subsets_to_device(c->stream, c->p, N, X_host, B, b, idx, flags, dS.p, dVar.p);
-    if (rc) return rc;
-    std::vector<double> var;
-    if (flags & GGL_COV_SCALE) {
-        var.resize(bp);
-        HIPCHK(hipMemcpyAsync(var.data(), dVar.p, bp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    return install_subset_S(c, dS.p, B, var);
+    HIPCHK(dS.alloc((size_t)B * c->p * c->p));
+    HIPCHK(dVar.alloc((size_t)B * c->p));
+    RCCHK(subsets_to_device(c->stream, c->p, N, X_host, B, b, idx, flags, dS.p, dVar.p));
+    return install_subset_S(c, dS.p, B, dVar.p, flags);
 }
 
 // K-fold cross-validation: the held-out score <S_test[k % F], Theta_k> of every snapshot of a ctx of K = L * F instances
@@ -330,23 +388,16 @@ extern "C" int ggl_heldout_scores(ggl_ctx* c, const double* X_host, int N, int F
         return fail(GGL_E_ARG, "bad argument: F = %d folds do not divide the K = %d instances of the ctx", F, c->K);
     if (m < 1) return fail(GGL_E_ARG, "bad argument: m = %d, every test fold needs at least one observation", m);
     ARGCHK(N >= 1, "N >= 1");
-    for (int f = 0; f < F; ++f)
-        for (int q = 0; q < m; ++q) {
-            const int n = idx_test[(size_t)f * m + q];
-            if (n < 0 || n >= N)
-                return fail(GGL_E_ARG, "bad argument: fold %d, position %d holds the index %d, outside [0, %d)", f, q, n, N);
-        }
+    RCCHK(check_index_table(idx_test, F, m, N, "fold"));
     ARGCHK(c->snapT, "no snapshot taken (ggl_snapshot_k)");
     ARGCHK((size_t)c->K * heldout_blocks(c->p) < ((size_t)1 << 31), "K * p * p too large for one launch");
-    int rc = check_subset_args(c->p, N, X_host, F, m, idx_test, flags);      // (the sizes the covariance route takes)
-    if (rc) return rc;
+    RCCHK(check_subset_sizes(c->p, N, X_host, F, m, idx_test, flags));      // (the sizes the covariance route takes)
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);
     DevBuf dS, dVar;
     HIPCHK(dS.alloc((size_t)F * c->p * c->p));
     HIPCHK(dVar.alloc((size_t)F * c->p));
-    rc = subsets_to_device(c->stream, c->p, N, X_host, F, m, idx_test, flags, dS.p, dVar.p);
-    if (rc) return rc;
+    RCCHK(subsets_to_device(c->stream, c->p, N, X_host, F, m, idx_test, flags, dS.p, dVar.p));
     // (waits for the stream before it returns: dS is freed behind it)
     return selection_stats_impl(c, out, dS.p, F);
 }
@@ -366,13 +417,9 @@ int check_kendall_args(int p, int N, const int* ranks_host, int B, int b, const 
     if (b < 2) return fail(GGL_E_ARG, "bad argument: b = %d, a subset needs at least two samples to form a pair", b);
     ARGCHK((size_t)B * p < (size_t)GGL_DIAG_OK, "B * p too large");
     ARGCHK(kendall_counts_fit(p, b, B), "p and b are beyond what one launch takes (p * b < 2^31, p <= 23104, b below about one million)");
-    if (idx)
-        for (int r = 0; r < B; ++r)
-            for (int q = 0; q < b; ++q) {
-                const int n = idx[(size_t)r * b + q];
-                if (n < 0 || n >= N)
-                    return fail(GGL_E_ARG, "bad argument: subset %d, position %d holds the index %d, outside [0, %d)", r, q, n, N);
-            }
+    if (idx) {
+        RCCHK(check_index_table(idx, B, b, N, "subset"));
+    }
     // dense ranks lie in [0, N): their differences then fit 32 bits
     for (size_t e = 0; e < (size_t)p * N; ++e)
         if (ranks_host[e] < 0 || ranks_host[e] >= N)
@@ -407,9 +454,8 @@ int kendall_to_device(hipStream_t st, int p, int N, const int* ranks_host, int B
         HIPCHK(hipMemsetAsync(dErr.p, 0x7f, sizeof(int), st));
         launch_kendall_skeptic(st, G_dev, S_dev, dErr.p, B, p);
         HIPCHK(hipGetLastError());
-        int err = GGL_DIAG_OK;
-        HIPCHK(hipMemcpyAsync(&err, dErr.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+        int err;
+        RCCHK(read_err_word(st, dErr.p, &err));
         if (err != GGL_DIAG_OK)
             return fail(GGL_E_ARG, "bad argument: variable %d is constant over subset %d (no untied pair of samples); the rank "
                         "correlation needs every variable to vary", err % p, err / p);
@@ -426,8 +472,7 @@ int kendall_call(int device, int p, int N, const int* ranks_host, int B, int b, 
     DevBuf dS;
     HIPCHK(dG.alloc(n));
     if (S_out) HIPCHK(dS.alloc(n));
-    int rc = kendall_to_device(nullptr, p, N, ranks_host, B, b, idx, dG.p, S_out ? dS.p : nullptr);
-    if (rc) return rc;
+    RCCHK(kendall_to_device(nullptr, p, N, ranks_host, B, b, idx, dG.p, S_out ? dS.p : nullptr));
     if (G_out) HIPCHK(hipMemcpy(G_out, dG.p, n * sizeof(long long), hipMemcpyDeviceToHost));
     if (S_out) DOWN(S_out, dS.p, n);
     return GGL_OK;
@@ -436,8 +481,7 @@ int kendall_call(int device, int p, int N, const int* ranks_host, int B, int b, 
 
 extern "C" int ggl_kendall_counts(int device, int p, int N, const int* ranks_host, int B, int b, const int* idx, long long* G_out)
 {
-    int rc = check_kendall_args(p, N, ranks_host, B, b, idx);
-    if (rc) return rc;
+    RCCHK(check_kendall_args(p, N, ranks_host, B, b, idx));
     ARGCHK(G_out, "G_out");
     return kendall_call(device, p, N, ranks_host, B, b, idx, nullptr, G_out);
 }
@@ -445,19 +489,16 @@ extern "C" int ggl_kendall_counts(int device, int p, int N, const int* ranks_hos
 extern "C" int ggl_kendall_skeptic(int device, int p, int N, const int* ranks_host, int B, int b, const int* idx, double* S_out,
                                    long long* G_out)
 {
-    int rc = check_kendall_args(p, N, ranks_host, B, b, idx);
-    if (rc) return rc;
+    RCCHK(check_kendall_args(p, N, ranks_host, B, b, idx));
     ARGCHK(S_out, "S_out");
     return kendall_call(device, p, N, ranks_host, B, b, idx, S_out, G_out);
 }
 
 extern "C" int ggl_set_S_from_kendall(ggl_ctx* c, const int* ranks_host, int N, int B, int b, const int* idx)
 {
-    ARGCHK(c, "ctx");
-    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) takes its S from ggl_set_S");
-    int rc = check_kendall_args(c->p, N, ranks_host, B, b, idx);
-    if (rc) return rc;
-    if (c->K % B != 0) return fail(GGL_E_ARG, "bad argument: B = %d subsets do not divide the K = %d instances of the ctx", B, c->K);
+    RCCHK(check_ctx_takes_S(c));
+    RCCHK(check_kendall_args(c->p, N, ranks_host, B, b, idx));
+    RCCHK(check_divides_K(c, B));
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);
     // as ggl_set_S_from_subsets: the B matrices are built beside the ctx's S; a refused call (a constant variable) leaves S alone
@@ -466,9 +507,8 @@ extern "C" int ggl_set_S_from_kendall(ggl_ctx* c, const int* ranks_host, int N, 
     DevBuf dS;
     HIPCHK(dG.alloc(n));
     HIPCHK(dS.alloc(n));
-    rc = kendall_to_device(c->stream, c->p, N, ranks_host, B, b, idx, dG.p, dS.p);
-    if (rc) return rc;
-    return install_subset_S(c, dS.p, B, {});
+    RCCHK(kendall_to_device(c->stream, c->p, N, ranks_host, B, b, idx, dG.p, dS.p));
+    return install_subset_S(c, dS.p, B);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -478,8 +518,7 @@ extern "C" int ggl_set_S_from_kendall(ggl_ctx* c, const int* ranks_host, int N, 
 namespace {
 int check_mixed_args(int p, int N, const int* ranks_host, const int* types, int B, int b, const int* idx, double clip)
 {
-    int rc = check_kendall_args(p, N, ranks_host, B, b, idx);
-    if (rc) return rc;
+    RCCHK(check_kendall_args(p, N, ranks_host, B, b, idx));
     ARGCHK(types, "types");
     if (!(clip > 0.0 && clip < 1.0)) return fail(GGL_E_ARG, "bad argument: clip = %g, outside (0, 1)", clip);
     for (int i = 0; i < p; ++i) {
@@ -507,15 +546,13 @@ int mixed_to_device(hipStream_t st, int p, int N, const int* ranks_host, const i
     HIPCHK(dErr.alloc(1));
     HIPCHK(hipMemcpyAsync(dT.p, types, (size_t)p * sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(dErr.p, 0x7f, sizeof(int), st));
-    int rc = kendall_to_device(st, p, N, ranks_host, B, b, idx, G_dev, nullptr, &dRg);
-    if (rc) return rc;
+    RCCHK(kendall_to_device(st, p, N, ranks_host, B, b, idx, G_dev, nullptr, &dRg));
     launch_bridge_zero_counts(st, dRg.p, n0_dev, dErr.p, B, p, b);
     HIPCHK(hipGetLastError());
     launch_bridge_invert(st, G_dev, n0_dev, dT.p, S_dev, clip_dev, dErr.p, B, p, b, clip);
     HIPCHK(hipGetLastError());
-    int err = GGL_DIAG_OK;
-    HIPCHK(hipMemcpyAsync(&err, dErr.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    int err;
+    RCCHK(read_err_word(st, dErr.p, &err));
     if (err != GGL_DIAG_OK)
         return fail(GGL_E_ARG, "bad argument: variable %d is constant over subset %d (%s); the latent correlation needs every "
                     "variable to vary", err % p, err / p, types[err % p] ? "a binary variable with one of its two values only"
@@ -542,15 +579,12 @@ struct MixedBufs {
 extern "C" int ggl_mixed_correlation(int device, int p, int N, const int* ranks_host, const int* types, int B, int b,
                                      const int* idx, double clip, double* S_out, long long* G_out, int* n0_out, int* clipped_out)
 {
-    int rc = check_mixed_args(p, N, ranks_host, types, B, b, idx, clip);
-    if (rc) return rc;
+    RCCHK(check_mixed_args(p, N, ranks_host, types, B, b, idx, clip));
     ARGCHK(S_out, "S_out");
     HIPCHK(hipSetDevice(device));
     MixedBufs d;
-    rc = d.alloc(B, p);
-    if (rc) return rc;
-    rc = mixed_to_device(nullptr, p, N, ranks_host, types, B, b, idx, clip, d.S.p, d.G.p, d.n0.p, d.clipped.p);
-    if (rc) return rc;
+    RCCHK(d.alloc(B, p));
+    RCCHK(mixed_to_device(nullptr, p, N, ranks_host, types, B, b, idx, clip, d.S.p, d.G.p, d.n0.p, d.clipped.p));
     const size_t n = (size_t)B * p * p;
     DOWN(S_out, d.S.p, n);
     if (G_out) HIPCHK(hipMemcpy(G_out, d.G.p, n * sizeof(long long), hipMemcpyDeviceToHost));
@@ -562,20 +596,16 @@ extern "C" int ggl_mixed_correlation(int device, int p, int N, const int* ranks_
 extern "C" int ggl_set_S_from_mixed(ggl_ctx* c, const int* ranks_host, const int* types, int N, int B, int b, const int* idx,
                                     double clip)
 {
-    ARGCHK(c, "ctx");
-    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) takes its S from ggl_set_S");
-    int rc = check_mixed_args(c->p, N, ranks_host, types, B, b, idx, clip);
-    if (rc) return rc;
-    if (c->K % B != 0) return fail(GGL_E_ARG, "bad argument: B = %d subsets do not divide the K = %d instances of the ctx", B, c->K);
+    RCCHK(check_ctx_takes_S(c));
+    RCCHK(check_mixed_args(c->p, N, ranks_host, types, B, b, idx, clip));
+    RCCHK(check_divides_K(c, B));
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);
     // as ggl_set_S_from_kendall: the B matrices are built beside the ctx's S; a refused call leaves S alone
     MixedBufs d;
-    rc = d.alloc(B, c->p);
-    if (rc) return rc;
-    rc = mixed_to_device(c->stream, c->p, N, ranks_host, types, B, b, idx, clip, d.S.p, d.G.p, d.n0.p, d.clipped.p);
-    if (rc) return rc;
-    return install_subset_S(c, d.S.p, B, {});
+    RCCHK(d.alloc(B, c->p));
+    RCCHK(mixed_to_device(c->stream, c->p, N, ranks_host, types, B, b, idx, clip, d.S.p, d.G.p, d.n0.p, d.clipped.p));
+    return install_subset_S(c, d.S.p, B);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -593,175 +623,93 @@ int check_min_pairs(int min_pairs, size_t K, size_t p)
     return GGL_OK;
 }
 
-// S_dev, cnt_dev (K,p,p) from the arena (layout as covariance_of_arena) on stream st; with GGL_COV_SCALE S is divided by its
-// own diagonal -- the variance of each variable over all its observed entries -- and var_dev (K,p) gets it.  what: "instance"
-// or "subset", for the messages.  Waits for the stream.
-int pairwise_of_arena(hipStream_t st, int K, int p, const double* X_dev, const long long* off_dev, const int* N_dev, int flags,
-                      int min_pairs, double* S_dev, int* cnt_dev, double* var_dev, const char* what)
+// S_dev, cnt_dev (K,p,p) from the arena on stream st; with GGL_COV_SCALE S is divided by its own diagonal -- the variance of
+// each variable over all its observed entries -- and var_dev (K,p) gets it.  what: "instance" or "subset", for the messages.
+// Waits for the stream.
+int pairwise_of_arena(hipStream_t st, const Arena& a, int p, int flags, int min_pairs, double* S_dev, int* cnt_dev,
+                      double* var_dev, const char* what)
 {
-    DevArr<double> dShift, dSd;
+    DevArr<double> dShift;
     DevArr<int> dRowCnt, dErr;
     DevArr<unsigned long long> dPairErr;
+    const int K = a.K;
     const size_t kp = (size_t)K * p, pp = (size_t)p * p;
     HIPCHK(dShift.alloc(kp));
     HIPCHK(dRowCnt.alloc(kp));
     HIPCHK(dErr.alloc(1));
     HIPCHK(dPairErr.alloc(1));
     HIPCHK(hipMemsetAsync(dErr.p, 0x7f, sizeof(int), st));
-    launch_row_stats_masked(st, X_dev, off_dev, N_dev, dShift.p, dRowCnt.p, dErr.p, K, p);
+    launch_row_stats_masked(st, a.X.p, a.off.p, a.N.p, dShift.p, dRowCnt.p, dErr.p, K, p);
     HIPCHK(hipGetLastError());
-    int err = GGL_DIAG_OK;
-    HIPCHK(hipMemcpyAsync(&err, dErr.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    int err;
+    RCCHK(read_err_word(st, dErr.p, &err));
     if (err != GGL_DIAG_OK)
         return fail(GGL_E_ARG, "bad argument: %s %d, variable %d has no observed entry (every sample is NaN)", what, err / p, err % p);
-    const int tile = (flags & GGL_COV_TILE64) ? 64 : ((flags & GGL_COV_TILE32) ? 32 : 0);
-    launch_gram_nt_pairwise(st, X_dev, off_dev, N_dev, (flags & GGL_COV_CENTER) ? dShift.p : nullptr, S_dev, cnt_dev, K, p, tile);
+    launch_gram_nt_pairwise(st, a.X.p, a.off.p, a.N.p, (flags & GGL_COV_CENTER) ? dShift.p : nullptr, S_dev, cnt_dev, K, p,
+                            cov_tile(flags));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemsetAsync(dPairErr.p, 0xff, sizeof(unsigned long long), st));
     launch_pair_count_check(st, cnt_dev, min_pairs, dPairErr.p, K, p);
     HIPCHK(hipGetLastError());
-    unsigned long long perr = ~0ull;
-    HIPCHK(hipMemcpyAsync(&perr, dPairErr.p, sizeof(perr), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    unsigned long long perr;
+    RCCHK(read_err_word64(st, dPairErr.p, &perr));
     if (perr != ~0ull) {
         int n = 0;
         HIPCHK(hipMemcpy(&n, cnt_dev + perr, sizeof(int), hipMemcpyDeviceToHost));
         return fail(GGL_E_ARG, "bad argument: %s %d, the pair of variables (%d, %d) shares %d samples, min_pairs = %d", what,
                     (int)(perr / pp), (int)(perr % pp / p), (int)(perr % p), n, min_pairs);
     }
-    if (flags & GGL_COV_SCALE) {
-        HIPCHK(dSd.alloc(kp));
-        HIPCHK(hipMemsetAsync(dErr.p, 0x7f, sizeof(int), st));
-        launch_scale_by_diag(st, S_dev, nullptr, S_dev, var_dev, dSd.p, dErr.p, K, p);
-        HIPCHK(hipGetLastError());
-        int rc = diag_error(st, dErr.p, p, nullptr, S_dev, "the variance");
-        if (rc) return rc;
-    }
+    if (flags & GGL_COV_SCALE) RCCHK(scale_in_place(st, K, p, S_dev, var_dev, "the variance"));
     HIPCHK(hipStreamSynchronize(st));
     return GGL_OK;
 }
 
-// ... from the host data of K instances (the arena of covariance_to_device; NaNs travel as they are)
+// ... from the host data of K instances
 int pairwise_to_device(hipStream_t st, int K, int p, const int* N, const double* const* X_host, int flags, int min_pairs,
                        double* S_dev, int* cnt_dev, double* var_dev)
 {
-    std::vector<long long> off(K);
-    size_t total = 0;
-    for (int k = 0; k < K; ++k) { off[k] = (long long)total; total += (size_t)p * N[k]; }
-    DevArr<double> dX;
-    DevArr<long long> dOff;
-    DevArr<int> dN;
-    HIPCHK(dX.alloc(total));
-    HIPCHK(dOff.alloc(K));
-    HIPCHK(dN.alloc(K));
-    HIPCHK(hipMemcpyAsync(dOff.p, off.data(), K * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dN.p, N, K * sizeof(int), hipMemcpyHostToDevice, st));
-    for (int k = 0; k < K; ++k)
-        HIPCHK(hipMemcpyAsync(dX.p + off[k], X_host[k], (size_t)p * N[k] * sizeof(double), hipMemcpyHostToDevice, st));
-    return pairwise_of_arena(st, K, p, dX.p, dOff.p, dN.p, flags, min_pairs, S_dev, cnt_dev, var_dev, "instance");
+    Arena a;
+    RCCHK(a.from_instances(st, K, p, N, X_host));
+    return pairwise_of_arena(st, a, p, flags, min_pairs, S_dev, cnt_dev, var_dev, "instance");
 }
 
-// ... of B column subsets of one X, gathered on the device (k_gather_cols moves bytes: NaNs travel)
+// ... of B column subsets of one X
 int pairwise_subsets_to_device(hipStream_t st, int p, int N, const double* X_host, int B, int b, const int* idx, int flags,
                                int min_pairs, double* S_dev, int* cnt_dev, double* var_dev)
 {
-    std::vector<long long> off(B);
-    std::vector<int> Nb(B, b);
-    for (int r = 0; r < B; ++r) off[r] = (long long)r * p * b;
-    DevArr<double> dX, dA;
-    DevArr<long long> dOff;
-    DevArr<int> dN, dIdx;
-    HIPCHK(dX.alloc((size_t)p * N));
-    HIPCHK(dA.alloc((size_t)B * p * b));
-    HIPCHK(dOff.alloc(B));
-    HIPCHK(dN.alloc(B));
-    HIPCHK(dIdx.alloc((size_t)B * b));
-    HIPCHK(hipMemcpyAsync(dX.p, X_host, (size_t)p * N * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dIdx.p, idx, (size_t)B * b * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dOff.p, off.data(), B * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dN.p, Nb.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
-    launch_gather_cols(st, dX.p, dIdx.p, dA.p, p, N, B, b);
-    HIPCHK(hipGetLastError());
-    return pairwise_of_arena(st, B, p, dA.p, dOff.p, dN.p, flags, min_pairs, S_dev, cnt_dev, var_dev, "subset");
-}
-
-// the results of a stateless call go down, the last step of a call that was not refused
-int pairwise_download(int K, int p, int flags, const double* dS, const int* dCnt, const double* dVar, double* S_out,
-                      double* scale_out, int* counts_out)
-{
-    const size_t n = (size_t)K * p * p;
-    DOWN(S_out, dS, n);
-    if (flags & GGL_COV_SCALE) DOWN(scale_out, dVar, (size_t)K * p);
-    if (counts_out) HIPCHK(hipMemcpy(counts_out, dCnt, n * sizeof(int), hipMemcpyDeviceToHost));
-    return GGL_OK;
+    Arena a;
+    RCCHK(a.from_subsets(st, p, N, X_host, B, b, idx));
+    return pairwise_of_arena(st, a, p, flags, min_pairs, S_dev, cnt_dev, var_dev, "subset");
 }
 }  // namespace
 
 extern "C" int ggl_covariance_pairwise(int device, int K, int p, const int* N, const double* const* X_host, int flags,
                                        int min_pairs, double* S_out, double* scale_out, int* counts_out)
 {
-    int rc = check_data_args(K, p, N, X_host, flags);
-    if (rc) return rc;
-    rc = check_min_pairs(min_pairs, K, p);
-    if (rc) return rc;
-    ARGCHK(S_out, "S_out");
-    ARGCHK(!(flags & GGL_COV_SCALE) || scale_out, "GGL_COV_SCALE needs scale_out");
-    HIPCHK(hipSetDevice(device));
-    const size_t n = (size_t)K * p * p;
-    DevBuf dS, dVar;
-    DevArr<int> dCnt;
-    HIPCHK(dS.alloc(n));
-    HIPCHK(dVar.alloc((size_t)K * p));
-    HIPCHK(dCnt.alloc(n));
-    rc = pairwise_to_device(nullptr, K, p, N, X_host, flags, min_pairs, dS.p, dCnt.p, dVar.p);
-    if (rc) return rc;
-    return pairwise_download(K, p, flags, dS.p, dCnt.p, dVar.p, S_out, scale_out, counts_out);
+    RCCHK(check_data_args(K, p, N, X_host, flags));
+    RCCHK(check_min_pairs(min_pairs, K, p));
+    CovOut d;
+    RCCHK(d.begin(device, K, p, flags, S_out, scale_out, true, false));
+    RCCHK(pairwise_to_device(nullptr, K, p, N, X_host, flags, min_pairs, d.S.p, d.cnt.p, d.var.p));
+    return d.down(flags, S_out, scale_out, counts_out);
 }
 
 extern "C" int ggl_covariance_pairwise_subsets(int device, int p, int N, const double* X_host, int B, int b, const int* idx,
                                                int flags, int min_pairs, double* S_out, double* scale_out, int* counts_out)
 {
-    int rc = check_subset_args(p, N, X_host, B, b, idx, flags);
-    if (rc) return rc;
-    rc = check_min_pairs(min_pairs, B, p);
-    if (rc) return rc;
-    ARGCHK(S_out, "S_out");
-    ARGCHK(!(flags & GGL_COV_SCALE) || scale_out, "GGL_COV_SCALE needs scale_out");
-    HIPCHK(hipSetDevice(device));
-    const size_t n = (size_t)B * p * p;
-    DevBuf dS, dVar;
-    DevArr<int> dCnt;
-    HIPCHK(dS.alloc(n));
-    HIPCHK(dVar.alloc((size_t)B * p));
-    HIPCHK(dCnt.alloc(n));
-    rc = pairwise_subsets_to_device(nullptr, p, N, X_host, B, b, idx, flags, min_pairs, dS.p, dCnt.p, dVar.p);
-    if (rc) return rc;
-    return pairwise_download(B, p, flags, dS.p, dCnt.p, dVar.p, S_out, scale_out, counts_out);
+    RCCHK(check_subset_args(p, N, X_host, B, b, idx, flags));
+    RCCHK(check_min_pairs(min_pairs, B, p));
+    CovOut d;
+    RCCHK(d.begin(device, B, p, flags, S_out, scale_out, true, false));
+    RCCHK(pairwise_subsets_to_device(nullptr, p, N, X_host, B, b, idx, flags, min_pairs, d.S.p, d.cnt.p, d.var.p));
+    return d.down(flags, S_out, scale_out, counts_out);
 }
-
-namespace {
-// the common end of the two ctx routes: B matrices built beside the ctx's S are installed (install_subset_S)
-int install_pairwise(ggl_ctx* c, const double* dS, const double* dVar, int B, int flags)
-{
-    std::vector<double> var;
-    if (flags & GGL_COV_SCALE) {
-        var.resize((size_t)B * c->p);
-        HIPCHK(hipMemcpyAsync(var.data(), dVar, var.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    return install_subset_S(c, dS, B, var);
-}
-}  // namespace
 
 extern "C" int ggl_set_S_from_data_pairwise(ggl_ctx* c, const double* const* X_host, const int* N, int flags, int min_pairs)
 {
-    ARGCHK(c, "ctx");
-    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) takes its S from ggl_set_S");
-    int rc = check_data_args(c->K, c->p, N, X_host, flags);
-    if (rc) return rc;
-    rc = check_min_pairs(min_pairs, c->K, c->p);
-    if (rc) return rc;
+    RCCHK(check_ctx_takes_S(c));
+    RCCHK(check_data_args(c->K, c->p, N, X_host, flags));
+    RCCHK(check_min_pairs(min_pairs, c->K, c->p));
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);
     // unlike ggl_set_S_from_data the K matrices are built beside the ctx's S: a refused call leaves the ctx as it was
@@ -770,21 +718,17 @@ extern "C" int ggl_set_S_from_data_pairwise(ggl_ctx* c, const double* const* X_h
     HIPCHK(dS.alloc(c->n));
     HIPCHK(dVar.alloc((size_t)c->K * c->p));
     HIPCHK(dCnt.alloc(c->n));
-    rc = pairwise_to_device(c->stream, c->K, c->p, N, X_host, flags, min_pairs, dS.p, dCnt.p, dVar.p);
-    if (rc) return rc;
-    return install_pairwise(c, dS.p, dVar.p, c->K, flags);
+    RCCHK(pairwise_to_device(c->stream, c->K, c->p, N, X_host, flags, min_pairs, dS.p, dCnt.p, dVar.p));
+    return install_subset_S(c, dS.p, c->K, dVar.p, flags);
 }
 
 extern "C" int ggl_set_S_from_subsets_pairwise(ggl_ctx* c, const double* X_host, int N, int B, int b, const int* idx, int flags,
                                                int min_pairs)
 {
-    ARGCHK(c, "ctx");
-    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) takes its S from ggl_set_S");
-    int rc = check_subset_args(c->p, N, X_host, B, b, idx, flags);
-    if (rc) return rc;
-    rc = check_min_pairs(min_pairs, B, c->p);
-    if (rc) return rc;
-    if (c->K % B != 0) return fail(GGL_E_ARG, "bad argument: B = %d subsets do not divide the K = %d instances of the ctx", B, c->K);
+    RCCHK(check_ctx_takes_S(c));
+    RCCHK(check_subset_args(c->p, N, X_host, B, b, idx, flags));
+    RCCHK(check_min_pairs(min_pairs, B, c->p));
+    RCCHK(check_divides_K(c, B));
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);
     const size_t n = (size_t)B * c->p * c->p;
@@ -793,9 +737,8 @@ extern "C" int ggl_set_S_from_subsets_pairwise(ggl_ctx* c, const double* X_host,
     HIPCHK(dS.alloc(n));
     HIPCHK(dVar.alloc((size_t)B * c->p));
     HIPCHK(dCnt.alloc(n));
-    rc = pairwise_subsets_to_device(c->stream, c->p, N, X_host, B, b, idx, flags, min_pairs, dS.p, dCnt.p, dVar.p);
-    if (rc) return rc;
-    return install_pairwise(c, dS.p, dVar.p, B, flags);
+    RCCHK(pairwise_subsets_to_device(c->stream, c->p, N, X_host, B, b, idx, flags, min_pairs, dS.p, dCnt.p, dVar.p));
+    return install_subset_S(c, dS.p, B, dVar.p, flags);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -804,16 +747,12 @@ extern "C" int ggl_set_S_from_subsets_pairwise(ggl_ctx* c, const double* X_host,
 // is written only after the weight check and (GGL_COV_SCALE) the variance check have passed.
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
-constexpr int WCOV_FLAGS = COV_FLAGS | GGL_COV_FULL_RANGE;
-
 int check_weighted_args(int p, int N, const double* X_host, int K, const double* w_host, int flags)
 {
     ARGCHK(p >= 1 && N >= 1, "p >= 1, N >= 1");
     if (K < 1 || K > 65535) return fail(GGL_E_ARG, "bad argument: K = %d weight rows, 1 .. 65535 are possible", K);
     ARGCHK(X_host && w_host, "X, w");
-    ARGCHK((flags & ~WCOV_FLAGS) == 0,
-           "flags: unknown bits (GGL_COV_CENTER | GGL_COV_SCALE | GGL_COV_TILE32 | GGL_COV_TILE64 | GGL_COV_FULL_RANGE)");
-    ARGCHK(!((flags & GGL_COV_TILE32) && (flags & GGL_COV_TILE64)), "flags: GGL_COV_TILE32 and GGL_COV_TILE64 exclude each other");
+    RCCHK(check_cov_flags(flags, WCOV_FLAGS));
     ARGCHK((size_t)K * p < (size_t)GGL_DIAG_OK, "K * p too large");
     return GGL_OK;
 }
@@ -824,8 +763,8 @@ int check_weighted_args(int p, int N, const double* X_host, int K, const double*
 int weighted_to_device(hipStream_t st, int p, int N, const double* X_host, int K, const double* w_host, int flags, double* S_dev,
                        double* var_dev, double* wsum_dev, ggl_ctx* tc = nullptr)
 {
-    DevArr<double> dX, dW, dR, dMean, dSd;
-    DevArr<int> dRng, dErr;
+    DevArr<double> dX, dW, dR, dMean;
+    DevArr<int> dRng;
     DevArr<unsigned long long> dWErr;
     const size_t kn = (size_t)K * N;
     HIPCHK(dX.alloc((size_t)p * N));
@@ -838,9 +777,8 @@ int weighted_to_device(hipStream_t st, int p, int N, const double* X_host, int K
     HIPCHK(hipMemsetAsync(dWErr.p, 0xff, sizeof(unsigned long long), st));
     launch_weight_prepare(st, dW.p, dR.p, wsum_dev, dRng.p, dWErr.p, K, N, (flags & GGL_COV_FULL_RANGE) != 0);
     HIPCHK(hipGetLastError());
-    unsigned long long werr = ~0ull;
-    HIPCHK(hipMemcpyAsync(&werr, dWErr.p, sizeof(werr), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    unsigned long long werr;
+    RCCHK(read_err_word64(st, dWErr.p, &werr));
     if (werr != ~0ull) {
         if (werr < kn)
             return fail(GGL_E_ARG, "bad argument: instance %d, sample %d holds the weight %g; weights must be non-negative and finite",
@@ -856,20 +794,11 @@ int weighted_to_device(hipStream_t st, int p, int N, const double* X_host, int K
         launch_row_means_weighted(st, dX.p, dW.p, wsum_dev, dRng.p, dMean.p, K, p, N);
         HIPCHK(hipGetLastError());
     }
-    const int tile = (flags & GGL_COV_TILE64) ? 64 : ((flags & GGL_COV_TILE32) ? 32 : 0);
     if (tc) trace_mark(tc, st, 30);
-    launch_gram_nt_weighted(st, dX.p, dR.p, wsum_dev, dRng.p, center ? dMean.p : nullptr, S_dev, K, p, N, tile);
+    launch_gram_nt_weighted(st, dX.p, dR.p, wsum_dev, dRng.p, center ? dMean.p : nullptr, S_dev, K, p, N, cov_tile(flags));
     HIPCHK(hipGetLastError());
     if (tc) trace_mark(tc, st, 31);
-    if (flags & GGL_COV_SCALE) {
-        HIPCHK(dSd.alloc((size_t)K * p));
-        HIPCHK(dErr.alloc(1));
-        HIPCHK(hipMemsetAsync(dErr.p, 0x7f, sizeof(int), st));
-        launch_scale_by_diag(st, S_dev, nullptr, S_dev, var_dev, dSd.p, dErr.p, K, p);
-        HIPCHK(hipGetLastError());
-        int rc = diag_error(st, dErr.p, p, nullptr, S_dev, "the weighted variance");
-        if (rc) return rc;
-    }
+    if (flags & GGL_COV_SCALE) RCCHK(scale_in_place(st, K, p, S_dev, var_dev, "the weighted variance"));
     HIPCHK(hipStreamSynchronize(st));
     return GGL_OK;
 }
@@ -878,46 +807,25 @@ int weighted_to_device(hipStream_t st, int p, int N, const double* X_host, int K
 extern "C" int ggl_covariance_weighted(int device, int p, int N, const double* X_host, int K, const double* w_host, int flags,
                                        double* S_out, double* scale_out, double* wsum_out)
 {
-    int rc = check_weighted_args(p, N, X_host, K, w_host, flags);
-    if (rc) return rc;
-    ARGCHK(S_out, "S_out");
-    ARGCHK(!(flags & GGL_COV_SCALE) || scale_out, "GGL_COV_SCALE needs scale_out");
-    HIPCHK(hipSetDevice(device));
-    const size_t n = (size_t)K * p * p;
-    DevBuf dS, dVar, dWsum;
-    HIPCHK(dS.alloc(n));
-    HIPCHK(dVar.alloc((size_t)K * p));
-    HIPCHK(dWsum.alloc(K));
-    rc = weighted_to_device(nullptr, p, N, X_host, K, w_host, flags, dS.p, dVar.p, dWsum.p);
-    if (rc) return rc;
-    DOWN(S_out, dS.p, n);
-    if (flags & GGL_COV_SCALE) DOWN(scale_out, dVar.p, (size_t)K * p);
-    if (wsum_out) DOWN(wsum_out, dWsum.p, K);
-    return GGL_OK;
+    RCCHK(check_weighted_args(p, N, X_host, K, w_host, flags));
+    CovOut d;
+    RCCHK(d.begin(device, K, p, flags, S_out, scale_out, false, true));
+    RCCHK(weighted_to_device(nullptr, p, N, X_host, K, w_host, flags, d.S.p, d.var.p, d.wsum.p));
+    return d.down(flags, S_out, scale_out, nullptr, wsum_out);
 }
 
 extern "C" int ggl_set_S_from_weighted(ggl_ctx* c, const double* X_host, int N, const double* w_host, int flags)
 {
-    ARGCHK(c, "ctx");
-    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) takes its S from ggl_set_S");
-    int rc = check_weighted_args(c->p, N, X_host, c->K, w_host, flags);
-    if (rc) return rc;
+    RCCHK(check_ctx_takes_S(c));
+    RCCHK(check_weighted_args(c->p, N, X_host, c->K, w_host, flags));
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);
     // as ggl_set_S_from_subsets: the K matrices are built beside the ctx's S; a refused call (a bad weight, a constant variable
     // under GGL_COV_SCALE) leaves S, its variances and what was built for them as they were
-    const size_t kp = (size_t)c->K * c->p;
     DevBuf dS, dVar, dWsum;
     HIPCHK(dS.alloc(c->n));
-    HIPCHK(dVar.alloc(kp));
+    HIPCHK(dVar.alloc((size_t)c->K * c->p));
     HIPCHK(dWsum.alloc(c->K));
-    rc = weighted_to_device(c->stream, c->p, N, X_host, c->K, w_host, flags, dS.p, dVar.p, dWsum.p, c);
-    if (rc) return rc;
-    std::vector<double> var;
-    if (flags & GGL_COV_SCALE) {
-        var.resize(kp);
-        HIPCHK(hipMemcpyAsync(var.data(), dVar.p, kp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    return install_subset_S(c, dS.p, c->K, var);
+    RCCHK(weighted_to_device(c->stream, c->p, N, X_host, c->K, w_host, flags, dS.p, dVar.p, dWsum.p, c));
+    return install_subset_S(c, dS.p, c->K, dVar.p, flags);
 }

@@ -14,9 +14,10 @@
 //   capi_comm.hip       RCCL behind the C ABI (K-sharded step)
 //   capi_ext.hip        ext_ADMM_MGL (instances of different dimension)
 //   capi_ops.hip        stateless operator entry points, development probes
-//   capi_data.hip       sample covariance from data and from column subsets of one data array, scaling by a diagonal
-//                       (stateless and into a ctx's S); rank correlation, pairwise-complete and weighted covariance;
-//                       held-out scores of a cross-validation (ggl_heldout_scores)
+//   capi_data.hip       every way to an S from data, stateless and into a ctx's S: sample covariance of K instances and of
+//                       column subsets of one array, scaling by a diagonal, pairwise-complete covariance (NaN), weighted
+//                       covariance, Kendall rank correlation, latent correlation of mixed data; ggl_get_S; held-out scores
+//                       of a cross-validation (ggl_heldout_scores)
 //   capi_nearcorr.hip   nearest-correlation projection of an indefinite S (stateless and in place on a ctx's S)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -410,6 +411,15 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending = nullptr, bool allow_s
 int probe_part_streams(ggl_ctx* c);
 int rank_step(ggl_ctx* c);
 int rank_step_impl(ggl_ctx* c);
+// the first `have` (p,p) matrices of a (K,p,p) device stack -> all K, instance k = instance k % have, by doubling
+// device-to-device copies on the ctx stream (have divides K)
+int replicate_instances(ggl_ctx* c, double* stack, int have);
+// The S of the ctx is replaced: _begin, before the first write, forgets what earlier iterations carried and what was built for
+// the old S (spectral bounds, carried weights, the fused W, "S is symmetric") -- nothing of it survives a call that fails half
+// way; _end, behind the last write on the ctx stream, checks the exact symmetry that decides whether a Theta kernel may form
+// the next W per element (GGL_OPT_FUSED_W).  cov_scale is the caller's: a site keeps or clears it.
+void s_replaced_begin(ggl_ctx* c);
+int s_replaced_end(ggl_ctx* c);
 void sanitize_bounds(ggl_ctx* c, double* b, const double* repl, double repl_scale, double repl_scalar = 1.0);
 // ggl_selection_stats of the ctx's snapshots; S_test (F,p,p, device) not null: column 0 is <S_test[k % F], Theta_k>
 // (ggl_heldout_scores) instead of <S_k, Theta_k>.  Writes out only on success.
@@ -425,7 +435,8 @@ void trace_symm_hook(hipStream_t st, int kind, void* arg);
 int upload_par(ggl_ctx* c, int slot, const double* vals, double scalar, double div, CopySegs* pending = nullptr);
 int validate_spec(ggl_ctx* c);
 #pragma GCC visibility pop
-#define DROP_PRE(c) do { int rc_ = drop_prelaunch(c); if (rc_) return rc_; } while (0)
+#define RCCHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)      // a step that failed ends the caller with its code
+#define DROP_PRE(c) RCCHK(drop_prelaunch(c))
 
 // ---------------------------------------------------------------------------------------------
 // stateless operators (host buffers in, host buffers out)

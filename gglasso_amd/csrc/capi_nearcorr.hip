@@ -148,7 +148,6 @@ extern "C" int ggl_project_S(ggl_ctx* c, int period, double eps, double tol, int
     DROP_PRE(c);
     HIPCHK(hipStreamSynchronize(c->stream));
     const int B = period > 0 ? period : c->K;
-    const size_t pp = (size_t)c->p * c->p;
     {
         ScratchCtx s;
         rc = ggl_ctx_create(c->device, B, c->p, GGL_EIG_AUTO, nullptr, &s.c);
@@ -157,21 +156,9 @@ extern "C" int ggl_project_S(ggl_ctx* c, int period, double eps, double tol, int
         if (rc) return rc;          // (a refused call: S as it was)
     }
     // what earlier iterations carried is forgotten, as in ggl_set_S; the variances of a correlation S stay (the diagonal is kept)
-    c->spec_have = false;
-    c->cw_have = false;
-    c->cwL_have = false;
-    c->wf_ready = false;
-    c->S_symmetric = false;
-    for (size_t have = (size_t)B; have < (size_t)c->K; have *= 2) {
-        const size_t take = std::min(have, (size_t)c->K - have);
-        HIPCHK(hipMemcpyAsync(c->S + have * pp, c->S, take * pp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    launch_asym_max(c->stream, c->S, c->K, c->p, c->norms);
-    HIPCHK(hipGetLastError());
-    double asym = 1.0;
-    rc = host_reduce(c, c->K, 1, &asym, true);
+    s_replaced_begin(c);
+    rc = replicate_instances(c, c->S, B);
     if (rc) return rc;
-    c->S_symmetric = (asym == 0.0);
-    return GGL_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return s_replaced_end(c);
 }

@@ -6,10 +6,10 @@
 //     S_k      = (1/W_k) sum_n w[k,n] (x_n - m_k)(x_n - m_k)^T             k_gram_nt_weighted (numpy.cov(X, aweights=w_k, bias=True))
 //
 // X is (p, N) row-major, variables in rows, and is shared by all K instances: there is no per-instance copy of the data and
-// no offset table.  k_gram_nt_weighted is the sibling of k_gram_nt (covariance.hip): same tiles, same LDS image
-// [variable][sample] with row length BK + 2, tile pairs I <= J only with the mirror stored from the same accumulator.  It
-// stages r[k,n] (x_in - m[k,i]) for BOTH operands, so a diagonal tile still has one operand and S_k is a true Gram matrix
-// (positive semidefinite up to rounding, bitwise symmetric).
+// no offset table.  k_gram_nt_weighted is the tile body of k_gram_nt (gram_nt_tile.hpp) under the policy GramWeighted: same
+// tiles, same LDS image [variable][sample] with row length BK + 2, tile pairs I <= J only with the mirror stored from the same
+// accumulator.  It stages r[k,n] (x_in - m[k,i]) for BOTH operands, so a diagonal tile still has one operand and S_k is a true
+// Gram matrix (positive semidefinite up to rounding, bitwise symmetric).
 //
 // Range rule.  Instance k loops over the samples [lo_k & ~63, hi_k) only, [lo_k, hi_k) being the support of its weights:
 // with kernel weights of bandwidth h the work is proportional to the support, not to N.  The start is a multiple of 64, so
@@ -21,7 +21,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
-#include "sym_tile.hpp"
+#include "gram_nt_tile.hpp"
 
 namespace ggl {
 
@@ -94,7 +94,41 @@ __global__ __launch_bounds__(256) void k_row_means_weighted(const double* __rest
     if (lane == 0) mean[(size_t)k * p + row] = s / wsum[k];
 }
 
-// LDS image, fragment reads and tile decoding as k_gram_nt (covariance.hip); X is the one (p, N) array of all instances
+// Op of gram_nt_tile: X is the one (p, N) array of all instances, the samples [lo_k & ~63, hi_k) are looped, one plane
+// r (x - m) with r[k,n] fetched beside the slab, one accumulator set, S = acc / W_k
+struct GramWeighted {
+    static constexpr int PLANES = 1, NACC = 1;
+    static constexpr bool PRELOAD = true;
+    const double* X;
+    const double* r;
+    const double* wsum;
+    const int* rng;
+    const double* mean;
+    double* S;
+    int N;
+    const double* rk;
+    double rw_n, dn;
+    int n_lo, n_hi, n_last;
+    __device__ __forceinline__ void instance(int k, int)
+    {
+        n_lo = rng[2 * k] & ~63;
+        n_hi = rng[2 * k + 1];
+        n_last = N - 1;
+        rk = r + (size_t)k * N;
+        dn = wsum[k];
+    }
+    __device__ __forceinline__ const double* row(int i) const { return X + (size_t)i * N; }
+    __device__ __forceinline__ double shift(int k, int p, int i) const { return mean ? mean[(size_t)k * p + i] : 0.0; }
+    __device__ __forceinline__ void fetch(int n) { rw_n = rk[n]; }
+    __device__ __forceinline__ void stage(bool on, double x, double m, double (&v)[1]) const { v[0] = on ? rw_n * (x - m) : 0.0; }
+    __device__ __forceinline__ void mma(const double (&a)[1], const double (&b)[1], v4d (&acc)[1]) const
+    {
+        acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[0], b[0], acc[0], 0, 0, 0);
+    }
+    __device__ __forceinline__ double value(const v4d (&acc)[1], int q) const { return acc[0][q] / dn; }
+    __device__ __forceinline__ void store(double v, size_t e) const { S[e] = v; }
+};
+
 template <int BM, int BK, int WM, int WN>
 __global__ __launch_bounds__(sym_nt(BM, WM, WN)) void k_gram_nt_weighted(const double* __restrict__ X,
                                                                            const double* __restrict__ r,
@@ -103,120 +137,8 @@ __global__ __launch_bounds__(sym_nt(BM, WM, WN)) void k_gram_nt_weighted(const d
                                                                            const double* __restrict__ mean,
                                                                            double* __restrict__ S, int K, int p, int N)
 {
-    using Cfg = SymCfg<BM, BK, WM, WN, false>;
-    constexpr int XLD = BK + 2, SLAB = BM * XLD;
-    constexpr int RSTEP = Cfg::NT / BK;
-    static_assert(Cfg::NT % BK == 0, "a row of the slab must be covered by whole thread rows");
-    static_assert(64 % BK == 0, "a range that starts at a multiple of 64 must start at a slab of the full loop");
-    __shared__ __attribute__((aligned(16))) double smem[2 * SLAB];
-    const int T = (p + BM - 1) / BM;
-    int k, b;
-    if (!decode_block_xcd(T * (T + 1) / 2, K, k, b)) return;
-    int I = 0;
-    while (b >= T - I) { b -= T - I; ++I; }
-    const int J = I + b;
-    const bool diag = (I == J);
-    const int I0 = I * BM, J0 = J * BM;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = (wave / Cfg::NWC) * WM, wc = (wave % Cfg::NWC) * WN;
-    const int n_lo = rng[2 * k] & ~63, n_hi = rng[2 * k + 1];
-    const double* rk = r + (size_t)k * N;
-    double* As = smem;
-    double* Bs = diag ? smem : smem + SLAB;       // a diagonal tile has one operand
-
-    v4d acc[Cfg::TI][Cfg::TJ];
-#pragma unroll
-    for (int i = 0; i < Cfg::TI; ++i)
-#pragma unroll
-        for (int j = 0; j < Cfg::TJ; ++j) acc[i][j] = (v4d){0.0, 0.0, 0.0, 0.0};
-
-    // slab element (row lrow + q * RSTEP, sample lcol): consecutive lanes read consecutive samples of one row
-    const int lcol = tid % BK, lrow = tid / BK;
-    const double *pa[Cfg::LPT], *pb[Cfg::LPT];
-    double ma[Cfg::LPT], mb[Cfg::LPT];
-    bool oka[Cfg::LPT], okb[Cfg::LPT];
-#pragma unroll
-    for (int q = 0; q < Cfg::LPT; ++q) {
-        const int rw = lrow + q * RSTEP;
-        oka[q] = (I0 + rw) < p;
-        okb[q] = (J0 + rw) < p;
-        const int ia = min(I0 + rw, p - 1), ib = min(J0 + rw, p - 1);    // clamped: always a valid row
-        pa[q] = X + (size_t)ia * N;
-        pb[q] = X + (size_t)ib * N;
-        ma[q] = mean ? mean[(size_t)k * p + ia] : 0.0;
-        mb[q] = mean ? mean[(size_t)k * p + ib] : 0.0;
-    }
-    double ra[Cfg::LPT], rb[Cfg::LPT], rw_n;
-    auto fetch = [&](int n0) {
-        const int n = min(n0 + lcol, N - 1);                             // clamped: past the end is never staged as data
-        rw_n = rk[n];
-#pragma unroll
-        for (int q = 0; q < Cfg::LPT; ++q) {
-            ra[q] = pa[q][n];
-            if (!diag) rb[q] = pb[q][n];
-        }
-    };
-    // Centring and weighting happen here, and the zero padding AFTER them: a sample index >= hi_k or a row >= p contributes
-    // 0 to every product.
-    auto stage = [&](int n0) {
-        const bool in = (n0 + lcol) < n_hi;
-#pragma unroll
-        for (int q = 0; q < Cfg::LPT; ++q) {
-            const int rw = lrow + q * RSTEP;
-            As[rw * XLD + lcol] = (in && oka[q]) ? rw_n * (ra[q] - ma[q]) : 0.0;
-            if (!diag) Bs[rw * XLD + lcol] = (in && okb[q]) ? rw_n * (rb[q] - mb[q]) : 0.0;
-        }
-    };
-    auto compute = [&](int nq) {
-        double af[BK / 4][Cfg::TI], bf[BK / 4][Cfg::TJ];
-#pragma unroll
-        for (int kk = 0; kk < BK / 4; ++kk) {
-            if (kk >= nq) break;
-            const int c = kk * 4 + (lane >> 4);
-#pragma unroll
-            for (int i = 0; i < Cfg::TI; ++i) af[kk][i] = As[(wr + i * 16 + (lane & 15)) * XLD + c];
-#pragma unroll
-            for (int j = 0; j < Cfg::TJ; ++j) bf[kk][j] = Bs[(wc + j * 16 + (lane & 15)) * XLD + c];
-        }
-#pragma unroll
-        for (int kk = 0; kk < BK / 4; ++kk) {
-            if (kk >= nq) break;
-#pragma unroll
-            for (int i = 0; i < Cfg::TI; ++i)
-#pragma unroll
-                for (int j = 0; j < Cfg::TJ; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[kk][i], bf[kk][j], acc[i][j], 0, 0, 0);
-        }
-    };
-
-    // a wave whose sub-tile of a diagonal tile lies below the diagonal produces nothing that is kept
-    const bool dead_wave = diag && (wr >= wc + WN);
-    fetch(n_lo);
-    for (int n0 = n_lo; n0 < n_hi; n0 += BK) {
-        stage(n0);
-        __syncthreads();
-        fetch(n0 + BK);                                                   // past the end: clamped, never staged
-        if (!dead_wave) compute(min(BK / 4, (n_hi - n0 + 3) / 4));
-        __syncthreads();
-    }
-
-    // C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 * reg
-    double* Sk = S + (size_t)k * p * p;
-    const double dn = wsum[k];
-#pragma unroll
-    for (int ti = 0; ti < Cfg::TI; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < Cfg::TJ; ++tj)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int gi = I0 + wr + ti * 16 + (lane >> 4) + 4 * q;
-                const int gj = J0 + wc + tj * 16 + (lane & 15);
-                if (gi < p && gj < p && (!diag || gi <= gj)) {
-                    const double v = acc[ti][tj][q] / dn;
-                    Sk[(size_t)gi * p + gj] = v;
-                    if (gi != gj) Sk[(size_t)gj * p + gi] = v;
-                }
-            }
+    GramWeighted op{X, r, wsum, rng, mean, S, N};
+    gram_nt_tile<BM, BK, WM, WN>(op, K, p);
 }
 
 void launch_weight_prepare(hipStream_t st, const double* w, double* r, double* wsum, int* rng, unsigned long long* err, int K,
@@ -234,15 +156,11 @@ void launch_row_means_weighted(hipStream_t st, const double* X, const double* w,
 void launch_gram_nt_weighted(hipStream_t st, const double* X, const double* r, const double* wsum, const int* rng,
                              const double* mean, double* S, int K, int p, int N, int tile)
 {
-    if (gram_tile(K, p, tile) == 64) {
-        const int T = (p + 63) / 64;
-        hipLaunchKernelGGL((k_gram_nt_weighted<64, 16, 32, 32>), dim3(xcd_grid(T * (T + 1) / 2, K)), dim3(256), 0, st, X, r,
-                           wsum, rng, mean, S, K, p, N);
-    } else {
-        const int T = (p + 31) / 32;
-        hipLaunchKernelGGL((k_gram_nt_weighted<32, 32, 16, 16>), dim3(xcd_grid(T * (T + 1) / 2, K)), dim3(256), 0, st, X, r,
-                           wsum, rng, mean, S, K, p, N);
-    }
+    gram_dispatch(K, p, tile, [&](auto s, dim3 grid, dim3 block) {
+        using Sh = decltype(s);
+        hipLaunchKernelGGL((k_gram_nt_weighted<Sh::BM, Sh::BK, Sh::WM, Sh::WN>), grid, block, 0, st, X, r, wsum, rng, mean, S, K,
+                           p, N);
+    });
 }
 
 }  // namespace ggl

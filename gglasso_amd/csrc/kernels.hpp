@@ -510,11 +510,11 @@ void launch_bound_sqrt_inf_fro(hipStream_t st, const double* infpart, int ninf, 
 void launch_rank_t0(hipStream_t st, double* P, const double* C, const double* coef_d, int K, int p);
 
 // Sample covariance from data and scaling by a diagonal (covariance.hip).  X: instance k is the row-major (p, N[k]) array at
-// X + off[k] with row length ld (0: N[k], packed); mean (K,p), null for the raw second moment.  tile: 0 by size, 32, 64.
+// X + off[k], packed; mean (K,p), null for the raw second moment.  tile: 0 by size, 32, 64.
 int gram_tile(int K, int p, int force);
-void launch_row_means(hipStream_t st, const double* X, const long long* off, const int* N, int ld, double* mean, int K, int p);
-void launch_gram_nt(hipStream_t st, const double* X, const long long* off, const int* N, int ld, const double* mean,
-                    double* S, int K, int p, int tile);
+void launch_row_means(hipStream_t st, const double* X, const long long* off, const int* N, double* mean, int K, int p);
+void launch_gram_nt(hipStream_t st, const double* X, const long long* off, const int* N, const double* mean, double* S, int K,
+                    int p, int tile);
 // Y[k,i,j] = X[k,i,j] / (sqrt(d[k,i]) sqrt(d[k,j])), d null = diag(X); d_out, sd: (K,p) the diagonal used and its square
 // roots; *err (set to GGL_DIAG_OK by the caller: every byte 0x7f, a memset) = smallest k * p + i with a non-positive or non-finite d, then Y is not written
 static constexpr int GGL_DIAG_OK = 0x7f7f7f7f;

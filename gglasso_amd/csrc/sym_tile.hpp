@@ -1,5 +1,6 @@
 // Tile geometry and XCD-aware work decoding shared by the register-staged FP64 matrix-core kernels: the symmetric
-// products of gemm_sym.hip and the Gram product of covariance.hip.
+// products of gemm_sym.hip and the Gram tile body of gram_nt_tile.hpp (covariance.hip, covariance_missing.hip,
+// covariance_weighted.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

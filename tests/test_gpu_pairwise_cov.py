@@ -111,6 +111,20 @@ def test_complete_data_agrees_with_the_complete_route(p, N):
         assert np.all(np.abs(S[0].astype(np.longdouble) - full[0]) <= pr.bound(ref[1], ref[2]) + cov_bound), (p, N, center)
 
 
+@pytest.mark.parametrize("p,N,K", [(33, 70, 3), (65, 17, 1)])
+def test_complete_raw_data_gives_the_bits_of_the_complete_route(p, N, K):
+    """Without a NaN and uncentred the pairwise kernel is the plain one: both run the one tile body (gram_nt_tile.hpp), P
+    accumulates the same products in the same order and C = N is exact, so P / C has the bits of acc / N.  (Centred, the
+    pairwise formula is another expression: test_complete_data_agrees_with_the_complete_route bounds it.)"""
+    from gglasso_amd import utils
+    Xs = [np.ascontiguousarray(pr.make_case(p, N, "none", 20 + k)) for k in range(K)]
+    full, _ = utils._covariance_call(Xs, 0)
+    for tile in TILES:
+        S, _, cnt = pw(Xs, tile)
+        assert np.all(cnt == N), tile
+        assert np.array_equal(S, full), tile
+
+
 def test_missing_none_is_the_complete_data_path_bit_for_bit():
     from gglasso_amd import _lib, utils
     X = np.ascontiguousarray(case(33, 65, "none")[0])

@@ -112,6 +112,21 @@ def test_bitwise_invariants(tile):
             assert np.array_equal(part, full) and np.array_equal(Wp, Wf), (a, b, center)
 
 
+@pytest.mark.parametrize("p,N,K", [(33, 70, 3), (65, 17, 1)])
+def test_unit_weights_give_the_bits_of_the_plain_covariance(p, N, K):
+    """Every weight exactly 1.0: sqrt(1) = 1 and 1 (x - m) is exact, the weighted mean sums in the lane order of k_row_means
+    from sample 0, and W = N is exact -- the weighted kernel is the plain one under the one tile body (gram_nt_tile.hpp)."""
+    from gglasso_amd import utils
+    X = np.ascontiguousarray(wr.make_data(p, N, 3))
+    for center in (CENTER, 0):
+        for tile in TILES:
+            plain, _ = utils._covariance_call([X], center | tile)
+            S, _, W = wcov(X, np.ones((K, N)), center | tile)
+            assert np.array_equal(W, np.full(K, float(N))), (center, tile)
+            for k in range(K):
+                assert np.array_equal(S[k], plain[0]), (center, tile, k)
+
+
 def test_special_weights():
     from gglasso_amd import utils
     from test_gpu_covariance import reference as cov_reference
