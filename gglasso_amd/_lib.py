@@ -28,6 +28,7 @@ BUF_S, BUF_OMEGA, BUF_THETA, BUF_L, BUF_X, BUF_GROUPSQ, BUF_NORMS, BUF_OMEGA_PRE
 E_ARG, E_HIP, E_SOLVER, E_ALLOC, E_COMM = -1, -2, -3, -4, -5
 COV_CENTER, COV_SCALE, COV_TILE32, COV_TILE64 = 1, 2, 4, 8      # flags of ggl_covariance / ggl_set_S_from_data
 COV_FULL_RANGE = 16                                              # ggl_covariance_weighted only: loop over all N samples
+DEBIAS_TILE32, DEBIAS_TILE64 = 4, 8                              # flags of ggl_debias: a forced tile shape
 PHASES = ("form_W", "eig_omega", "recon_omega", "theta", "eig_L", "recon_L", "dual", "reduce", "eig_omega2", "bound",
           "allreduce_groupsq", "allreduce_norms")
 
@@ -172,6 +173,8 @@ _SIGNATURES = {
     "ggl_set_S_from_mixed": ([_vp, _ip, _ip, _i, _i, _i, _ip, _d], _i),
     "ggl_nearest_correlation": ([_i, _i, _dp, _dp, _d, _d, _i, _ip, _dp], _i),
     "ggl_project_S": ([_vp, _i, _d, _d, _i, _ip, _dp], _i),
+    "ggl_debias": ([_i, _i, _i, _dp, _dp, _dp, _i, _dp, _dp], _i),
+    "ggl_dev_debias_bench": ([_i, _i, _i, _i, _dp], _i),
 }
 
 # libggl_hip_dev.so only (-DGGL_DEV)

@@ -19,6 +19,7 @@
 //                       covariance, Kendall rank correlation, latent correlation of mixed data; ggl_get_S; held-out scores
 //                       of a cross-validation (ggl_heldout_scores)
 //   capi_nearcorr.hip   nearest-correlation projection of an indefinite S (stateless and in place on a ctx's S)
+//   capi_inference.hip  the output side: debiased graphical lasso and its standard errors (ggl_debias)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>

@@ -597,4 +597,11 @@ void launch_nc_reduce(hipStream_t st, const double* part, double* out, const int
 void launch_nc_finish(hipStream_t st, const double* Y, const double* A, double* dst, const double* dvec, const double* nu,
                       const int* pass, double* part, const int* err, int B, int p);
 
+// Debiased graphical lasso (debias.hip).  M = Theta S (launch_gemm_right), Theta, T, SE: (K,p,p); nobs (K) > 0.
+// T = 2 Theta - M Theta and SE[ij] = sqrt((Theta_ii Theta_jj + Theta_ij^2) / nobs_k) over the tile pairs I <= J, the mirror
+// stored from the same evaluation: both bitwise symmetric.  The epilogue reads the upper triangle of Theta.  tile as
+// launch_gram_nt
+void launch_debias(hipStream_t st, const double* M, const double* Theta, const double* nobs, double* Tout, double* SEout, int K,
+                   int p, int tile);
+
 }  // namespace ggl

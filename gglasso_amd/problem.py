@@ -13,6 +13,8 @@ implementation is this package's own:
   ``utils.mixed_correlation`` (binary beside continuous variables).
 * ``glasso_problem.from_time_series(X, at, bandwidth, ...)`` starts from ONE series with time stamps: S is the stack of
   kernel-smoothed covariances (``utils.kernel_covariance``), the input of the Fused Graphical Lasso for time-varying networks.
+* ``edge_inference()`` tests the edges of the solution at hand and gives confidence intervals: the debiased graphical lasso
+  (``utils.debiased_precision`` on the device, ``utils.edge_tests`` / ``utils.differential_tests`` on the host).
 """
 import numbers
 import warnings
@@ -458,6 +460,63 @@ class glasso_problem:
         self._keep(sol)
         self.modelselect_stats = dict(stats)
 
+    # -- inference ---------------------------------------------------------------------------------------------------------
+    def edge_inference(self, alpha=0.05, method='bh', differential=None, host=False):
+        """Edge-wise tests and confidence intervals for the solution at hand by the debiased graphical lasso (Jankova & van de
+        Geer 2015): ``utils.debiased_precision`` of ``solution.precision_`` against the covariance it was fitted to with
+        ``self.N`` (on the device; ``host=True``: the numpy twin), then ``utils.edge_tests``.  Stored on ``self.solution``:
+        ``debiased_precision_``, ``standard_error_``, ``zscore_``, ``pvalue_``, ``pvalue_adj_`` (``method``: 'bh', 'bonferroni',
+        'none', over the off-diagonal pairs of every instance), ``confidence_interval_`` (low, high; level ``1 - alpha`` per
+        entry) and ``significant_``, the adjacency of the edges rejected at level ``alpha``.
+
+        Everything is on the scale of ``precision_``.  The z-scores, and with them the p-values and ``significant_``, do not
+        depend on ``do_scaling``: with Theta' = D Theta D and S' = D^-1 S D^-1 the debiased estimate is D T D and the standard
+        error d_i d_j SE_ij.  (For a (K,p,p) stack ``do_scaling`` leaves the solution on the correlations' scale, see the
+        class docstring; the correlations are then what it is debiased against.)
+
+        ``differential``: for multiple problems, also test which entries differ between instances
+        (``utils.differential_tests``; the instances' samples must be independent): 'consecutive' (the pairs (k, k + 1), the
+        change points of an FGL stack), 'all', or a list of pairs.  ``solution.differential_`` gets one dict per pair.
+
+        Refused with a ValueError: ``latent=True`` (Theta is then not the precision matrix of the observed variables),
+        instances of different dimension, and a problem built with ``correlation=``, ``missing=`` or ``project=True`` (the
+        variance is that of the Gaussian sample covariance)."""
+        assert self.solution.precision_ is not None, \
+            "Edge inference needs a solution: call solve(), model_selection(), stability_selection() or cross_validation() first."
+        if self.latent:
+            raise ValueError("Edge inference is not implemented for problems with latent variables: Theta is then not the "
+                             "precision matrix of the observed variables.")
+        if not self.conforming:
+            raise ValueError("Edge inference is not implemented for instances of different dimension (non-conforming problems).")
+        if getattr(self, '_correlation', None) is not None:
+            raise ValueError(f"Edge inference is not implemented for a problem built with correlation={self._correlation!r}: "
+                             "the variance formula is that of the Gaussian sample covariance.")
+        if getattr(self, '_missing', None) is not None:
+            raise ValueError(f"Edge inference is not implemented for a problem built with missing={self._missing!r}: "
+                             "the variance formula is that of the Gaussian sample covariance.")
+        if getattr(self, '_project_S', False):
+            raise ValueError("Edge inference is not implemented for a problem built with project=True: "
+                             "the variance formula is that of the Gaussian sample covariance.")
+        if differential is not None and not self.multiple:
+            raise ValueError("differential tests compare the instances of a multiple problem; this is a single one.")
+        if isinstance(differential, str) and differential not in ('consecutive', 'all'):
+            raise ValueError(f"differential must be None, 'consecutive', 'all' or a list of pairs, is {differential!r}")
+        sol = self.solution
+        S = self.S if (self.do_scaling and self._kind == 'stack') else sol.sample_covariance_
+        debias = utils.host_debiased_precision if host else utils.debiased_precision
+        T, SE = debias(sol.precision_, S, self.N)
+        tests = utils.edge_tests(T, SE, alpha=alpha, method=method)
+        sol.debiased_precision_, sol.standard_error_ = T, SE
+        sol.zscore_, sol.pvalue_, sol.pvalue_adj_ = tests['z'], tests['pvalue'], tests['pvalue_adj']
+        sol.confidence_interval_ = (tests['ci_low'], tests['ci_high'])
+        sol.significant_ = tests['reject'].astype(int)
+        sol.differential_ = None
+        if differential is not None:
+            pairs = differential
+            if isinstance(differential, str):
+                pairs = None if differential == 'consecutive' else [(a, b) for a in range(self.K) for b in range(a + 1, self.K)]
+            sol.differential_ = utils.differential_tests(T, SE, pairs=pairs, alpha=alpha, method=method)
+
     def _select_single(self, criterion, store_all):
         grid = self.modelselect_params
         sol, Thetas, Ls, stats = _ms.single_grid_search(
@@ -492,7 +551,9 @@ class glasso_problem:
 class GGLassoEstimator:
     """The estimates of a ``glasso_problem``, scikit-learn style: ``precision_`` (the sparse component Theta),
     ``lowrank_`` (L, with ``latent=True``), ``sample_covariance_`` (the input S), ``adjacency_``, ``n_samples``,
-    ``n_features``.  For instances of different dimension every attribute is a dict with keys 0..K-1."""
+    ``n_features``.  For instances of different dimension every attribute is a dict with keys 0..K-1.
+    ``glasso_problem.edge_inference()`` adds ``debiased_precision_``, ``standard_error_``, ``zscore_``, ``pvalue_``,
+    ``pvalue_adj_``, ``confidence_interval_``, ``significant_`` and ``differential_``."""
 
     def __init__(self, S, N, p, K, multiple=True, latent=False, conforming=True):
         self.multiple, self.latent, self.conforming, self.K = multiple, latent, conforming, K

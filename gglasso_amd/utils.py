@@ -1,6 +1,7 @@
 """Utilities on the device: the block norms of the Functional Graphical Lasso (reference: helper/utils.py:69-107 of
 fabian-sp/GGLasso), the sample covariance of observations (what helper/data_generation.py:221,234 gets from numpy.cov), its
-rank-based, pairwise-complete and weighted forms, and the kernel-smoothed covariance stack of a time series."""
+rank-based, pairwise-complete and weighted forms, the kernel-smoothed covariance stack of a time series, and -- the output
+side -- the debiased graphical lasso with the edge-wise tests and confidence intervals built on it."""
 import ctypes
 
 import numpy as np
@@ -803,3 +804,183 @@ def nearest_correlation(S, eps=1e-8, tol=1e-10, max_iter=500, device=0, return_i
     if return_info:
         r[1]["fallbacks"] = int(info[0, 3])
     return r
+
+
+# -----------------------------------------------------------------------------------------------------------------
+# Inference on a fitted precision matrix: the debiased graphical lasso (Jankova & van de Geer 2015; D-S_GL of R's
+# SILGGM), edge-wise tests and confidence intervals, differential tests between instances
+# -----------------------------------------------------------------------------------------------------------------
+def _debias_args(Theta, S, N):
+    """(Theta (K,p,p), S (K,p,p), n (K,), single) of what ``debiased_precision`` accepts, C-contiguous float64."""
+    Th, Sm = np.asarray(Theta, dtype=np.float64), np.asarray(S, dtype=np.float64)
+    assert Th.ndim in (2, 3) and Th.shape[-1] == Th.shape[-2] and Th.shape[-1] >= 1, \
+        f"debiased precision needs a square (p,p) matrix or a (K,p,p) stack of them, Theta has shape {Th.shape}"
+    assert Sm.shape == Th.shape, f"Theta has shape {Th.shape}, S has shape {Sm.shape}: they must match"
+    single = Th.ndim == 2
+    Th, Sm = as_c(Th[None] if single else Th), as_c(Sm[None] if single else Sm)
+    K = Th.shape[0]
+    assert K >= 1, "debiased precision: the stack is empty"
+    n = np.asarray(N, dtype=np.float64)
+    assert n.ndim == 0 or n.shape == (K,), f"N must be one number or an array of length K = {K}, has shape {n.shape}"
+    n = as_c(np.broadcast_to(n, (K,)))
+    return Th, Sm, n, single
+
+
+def _debias_call(Theta, S, n, flags=0, device=0):
+    """One ``ggl_debias`` call on C-contiguous float64 (K,p,p) stacks and n (K,).  Returns (T, SE)."""
+    K, p = Theta.shape[0], Theta.shape[1]
+    T, SE = np.empty_like(Theta), np.empty_like(Theta)
+    _lib.require_gpu()
+    check(_lib.load().ggl_debias(int(device), K, p, ptr(Theta), ptr(S), ptr(n), int(flags), ptr(T), ptr(SE)))
+    return T, SE
+
+
+def debiased_precision(Theta, S, N, device=0, return_se=True):
+    """The de-sparsified graphical lasso of an estimate ``Theta`` fitted to the covariance ``S`` of ``N`` observations, on
+    the device (``ggl_debias``: two products per instance on the FP64 matrix cores, the second over the upper tile pairs
+    only with both results fused into its epilogue):
+
+        T  = 2 Theta - Theta S Theta                       (not sparse; the lasso's shrinkage is taken out)
+        SE = sqrt((Theta_ii Theta_jj + Theta_ij^2) / N)    (the asymptotic standard error of T_ij)
+
+    so that ``(T_ij - Theta0_ij) / SE_ij`` is asymptotically standard normal (``edge_tests``).  Theta, S: (p,p) or (K,p,p),
+    symmetric; N: one number or (K,), not necessarily integers (effective sample sizes).  Returns ``T, SE`` of the shape of
+    Theta (``return_se=False``: T alone), both bitwise symmetric, the same bits on every call, instance k's independent of the
+    others.  A non-finite entry of Theta or S, a non-positive diagonal entry of Theta and an N that is not positive and
+    finite are refused (AssertionError), naming the instance and the variable."""
+    Th, Sm, n, single = _debias_args(Theta, S, N)
+    T, SE = _debias_call(Th, Sm, n, 0, device)
+    if single:
+        T, SE = T[0], SE[0]
+    return (T, SE) if return_se else T
+
+
+def host_debiased_precision(Theta, S, N):
+    """numpy counterpart of ``debiased_precision``: the same formula, the same refusals, and the same rule that the upper
+    triangle (of the product, and of Theta in the two epilogues) decides and the lower one mirrors it."""
+    Th, Sm, n, single = _debias_args(Theta, S, N)
+    K, p = Th.shape[0], Th.shape[1]
+    for k in range(K):
+        assert n[k] > 0 and np.isfinite(n[k]), f"debiased precision: N of instance {k} is {n[k]}, not positive and finite"
+        for name, A in (("Theta", Th[k]), ("S", Sm[k])):
+            bad = ~np.isfinite(A).all(axis=1)
+            assert not bad.any(), \
+                f"debiased precision: {name} of instance {k}, variable {int(np.flatnonzero(bad)[0])} holds a non-finite entry"
+        d = np.diagonal(Th[k])
+        assert (d > 0).all(), (f"debiased precision: Theta of instance {k}, variable {int(np.flatnonzero(~(d > 0))[0])}: the "
+                               f"diagonal entry is {d[~(d > 0)][0]}, not positive")
+    T, SE = np.empty_like(Th), np.empty_like(Th)
+    for k in range(K):
+        U = np.triu(Th[k])
+        d = np.diagonal(Th[k])
+        t = np.triu(2.0 * U - (Th[k] @ Sm[k]) @ Th[k].T)
+        se = np.triu(np.sqrt((d[:, None] * d[None, :] + U * U) / n[k]))
+        T[k] = t + np.triu(t, 1).T
+        SE[k] = se + np.triu(se, 1).T
+    return (T[0], SE[0]) if single else (T, SE)
+
+
+def _special():
+    """(erfc, ndtri): scipy's, or torch's where scipy is missing."""
+    try:
+        from scipy.special import erfc, ndtri
+        return erfc, ndtri
+    except ImportError:
+        import torch
+        return (lambda x: torch.special.erfc(torch.as_tensor(np.asarray(x, dtype=np.float64))).numpy(),
+                lambda q: torch.special.ndtri(torch.as_tensor(np.asarray(q, dtype=np.float64))).numpy())
+
+
+_ADJUSTMENTS = ('bh', 'bonferroni', 'none')
+
+
+def adjust_pvalues(pv, alpha=0.05, method='bh'):
+    """(adjusted p-values, rejections at level ``alpha``) of one family of p-values ``pv`` (1-d).  ``'bh'``: the step-up
+    procedure of Benjamini & Hochberg -- with m = len(pv) and p_(1) <= ... <= p_(m), every hypothesis with p <= p_(k) is
+    rejected for the largest k with p_(k) <= k alpha / m; the adjusted value of p_(i) is min_{j >= i} min(1, m p_(j) / j), monotone
+    in p.  ``'bonferroni'``: min(1, m p) <= alpha.  ``'none'``: p <= alpha."""
+    assert method in _ADJUSTMENTS, f"method must be one of {_ADJUSTMENTS}, is {method!r}"
+    assert 0.0 < alpha < 1.0, f"alpha = {alpha}, a level lies in (0, 1)"
+    pv = np.asarray(pv, dtype=np.float64)
+    m = pv.size
+    if m == 0:
+        return pv.copy(), np.zeros(0, dtype=bool)
+    if method == 'none':
+        return pv.copy(), pv <= alpha
+    if method == 'bonferroni':
+        adj = np.minimum(1.0, m * pv)
+        return adj, adj <= alpha
+    order = np.argsort(pv, kind='stable')
+    ps = pv[order]
+    ranks = np.arange(1, m + 1)
+    adj = np.empty(m)
+    adj[order] = np.minimum.accumulate(np.minimum(1.0, m * ps / ranks)[::-1])[::-1]
+    ok = np.flatnonzero(ps <= ranks * alpha / m)
+    reject = pv <= ps[ok[-1]] if ok.size else np.zeros(m, dtype=bool)
+    return adj, reject
+
+
+def _tests_of_z(z, alpha, method):
+    """p-values and their adjustment over the off-diagonal pairs of every (p,p) matrix of the stack ``z`` (K,p,p): (pvalue,
+    pvalue_adj, reject), symmetric; on the diagonal the raw p-value, NaN as the adjusted one (it is in no family) and no
+    rejection."""
+    erfc, _ = _special()
+    K, p = z.shape[0], z.shape[1]
+    pv = np.asarray(erfc(np.abs(z) / np.sqrt(2.0)), dtype=np.float64)
+    adj = np.full(z.shape, np.nan)
+    rej = np.zeros(z.shape, dtype=bool)
+    iu = np.triu_indices(p, 1)
+    for k in range(K):
+        a, r = adjust_pvalues(pv[k][iu], alpha, method)
+        adj[k][iu], rej[k][iu] = a, r
+        adj[k].T[iu], rej[k].T[iu] = a, r
+    return pv, adj, rej
+
+
+def _stat_args(T, SE, what):
+    T, SE = np.asarray(T, dtype=np.float64), np.asarray(SE, dtype=np.float64)
+    assert T.ndim in (2, 3) and T.shape[-1] == T.shape[-2], f"{what} needs (p,p) matrices or (K,p,p) stacks, T has shape {T.shape}"
+    assert SE.shape == T.shape, f"T has shape {T.shape}, SE has shape {SE.shape}: they must match"
+    return T, SE
+
+
+def edge_tests(T, SE, alpha=0.05, method='bh', null=0.0):
+    """Edge-wise two-sided tests of ``Theta0_ij = null`` and confidence intervals from the debiased estimate and its
+    standard errors (``debiased_precision``); host only.  T, SE: (p,p) or (K,p,p).
+
+    ``z = (T - null) / SE``, ``pvalue = erfc(|z| / sqrt 2)``; the adjustment (``method``: 'bh' Benjamini-Hochberg, 'bonferroni',
+    'none') runs over the p (p - 1) / 2 off-diagonal pairs of every instance on its own.  Returns a dict of arrays of the shape
+    of T: ``z``, ``pvalue``, ``pvalue_adj`` (NaN on the diagonal, which is in no family), ``reject`` (bool, symmetric, False on
+    the diagonal: the edges significant at level ``alpha`` after adjustment), ``ci_low``, ``ci_high`` (``T -+ ndtri(1 - alpha / 2)
+    SE``: level ``1 - alpha`` per entry, not adjusted)."""
+    T, SE = _stat_args(T, SE, "edge_tests")
+    single = T.ndim == 2
+    with np.errstate(divide='ignore', invalid='ignore'):
+        z = (T - null) / SE
+    pv, adj, rej = _tests_of_z(z[None] if single else z, alpha, method)
+    _, ndtri = _special()
+    half = float(ndtri(1.0 - alpha / 2.0)) * SE
+    pick = (lambda a: a[0]) if single else (lambda a: a)
+    return dict(z=z, pvalue=pick(pv), pvalue_adj=pick(adj), reject=pick(rej), ci_low=T - half, ci_high=T + half)
+
+
+def differential_tests(T, SE, pairs=None, alpha=0.05, method='bh'):
+    """Which entries differ between two instances fitted on independent samples: for every listed pair (a, b) of instances of
+    the (K,p,p) stacks T, SE, ``z_ab = (T_a - T_b) / sqrt(SE_a^2 + SE_b^2)`` with p-values and their adjustment as in
+    ``edge_tests``, per pair; host only.  ``pairs=None``: the consecutive pairs (k, k + 1) -- where the graph of a Fused
+    Graphical Lasso stack changes in time.  Returns a list with one dict per pair: ``pair``, ``z``, ``pvalue``, ``pvalue_adj``,
+    ``reject``."""
+    T, SE = _stat_args(T, SE, "differential_tests")
+    assert T.ndim == 3 and T.shape[0] >= 2, f"differential tests compare the instances of a (K,p,p) stack, K >= 2; T has shape {T.shape}"
+    K = T.shape[0]
+    pairs = [(k, k + 1) for k in range(K - 1)] if pairs is None else [tuple(int(v) for v in pr) for pr in pairs]
+    out = []
+    for pr in pairs:
+        assert len(pr) == 2 and 0 <= pr[0] < K and 0 <= pr[1] < K and pr[0] != pr[1], \
+            f"a pair names two different instances in [0, {K}), got {pr}"
+        a, b = pr
+        with np.errstate(divide='ignore', invalid='ignore'):
+            z = (T[a] - T[b]) / np.sqrt(SE[a] * SE[a] + SE[b] * SE[b])
+        pv, adj, rej = _tests_of_z(z[None], alpha, method)
+        out.append(dict(pair=(a, b), z=z, pvalue=pv[0], pvalue_adj=adj[0], reject=rej[0]))
+    return out

@@ -925,6 +925,32 @@ int ggl_nearest_correlation(int B, int p, const double *A, double *out, double e
  * beside a correlation S stay as they are.  A refused call (also: a period that does not divide K) leaves S bit for bit. */
 int ggl_project_S(ggl_ctx *ctx, int period, double eps, double tol, int max_iter, int *iters, double *info);
 
+/* ---- Debiased (de-sparsified) graphical lasso: the statistics behind edge-wise tests and confidence intervals (Jankova,
+ * van de Geer 2015; D-S_GL of R's SILGGM) on the FP64 matrix cores (debias.hip).  An entry point that is only ADDED:
+ * GGL_VERSION stays where it is.
+ *
+ * Theta_host (K,p,p): the estimates, symmetric; S_host (K,p,p): the covariances they were fitted to, symmetric; n (K) doubles:
+ * the (effective, not necessarily integer) numbers of observations.  Per instance
+ *     T  = 2 Theta - Theta S Theta                                (the debiased estimate; not sparse)
+ *     SE = sqrt((Theta_ii Theta_jj + Theta_ij^2) / n_k)           (the asymptotic standard error of T_ij)
+ * so that (T_ij - Theta0_ij) / SE_ij is asymptotically N(0,1).  Two launches: M = Theta S as a full product, then M Theta
+ * over the tile pairs I <= J with both epilogues fused; Theta_ij, Theta_ii, Theta_jj are read from the upper triangle.
+ * T_out, SE_out (K,p,p).  Every pair is evaluated once and written twice: both stacks are bitwise symmetric.  Fixed
+ * reduction order, no atomics: two calls give the same bits, and instance k's result does not depend on K or on the other
+ * instances.  Any p >= 1.
+ * flags: 0, or one of the forced tile shapes below (tests, measurements); the default is 64 x 64 where K T (T + 1) / 2
+ * tile pairs fill the chip, else 32 x 32.
+ * GGL_E_ARG, found on the host before any device work, the message naming the offender: K or p < 1, a NULL buffer, any other
+ * flag bit or both tile flags; a non-finite entry of Theta or S (instance, row, column); Theta_ii <= 0 (instance, variable);
+ * n_k <= 0 or not finite (instance).  A refused call writes nothing to T_out, SE_out. */
+#define GGL_DEBIAS_TILE32 4
+#define GGL_DEBIAS_TILE64 8
+int ggl_debias(int device, int K, int p, const double *Theta_host, const double *S_host, const double *n, int flags,
+               double *T_out, double *SE_out);
+/* measurement: average milliseconds of `iters` launches on random device data (HIP events); ms_out[0] the full product
+ * M = A T (launch_gemm_right), ms_out[1] k_debias with its epilogues.  tile: 0 (by size), 32, 64. */
+int ggl_dev_debias_bench(int K, int p, int tile, int iters, double *ms_out);
+
 #ifdef __cplusplus
 }
 #endif
