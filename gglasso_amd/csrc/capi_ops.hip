@@ -180,7 +180,7 @@ extern "C" int ggl_dev_symm_bench(int K, int p, int variant, int iters, double* 
 }
 
 #ifdef GGL_DEV
-extern "C" int ggl_dev_set_symm_epilogue(int serial) { return symm_set_serial_epilogue(serial != 0) ? 1 : 0; }
+extern "C" int ggl_dev_set_symm_epilogue(int mode) { return symm_set_epilogue(mode); }
 
 // ggl_dev_symm_bench with the epilogue's operands: E and E2 symmetric stacks (as in the solvers), coefficients that use them
 extern "C" int ggl_dev_symm_bench_ops(int K, int p, int variant, int iters, int ops, double* ms_out)

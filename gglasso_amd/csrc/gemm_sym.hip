@@ -34,6 +34,25 @@ __device__ __forceinline__ double c2val2(double dC, double v, double dE, double 
     return has2 ? __builtin_fma(dE2, f, w) : w;
 }
 
+// Cross-lane moves of the register epilogue (symm_dl_tile), doubles as two dwords each.
+// lane_xor1: the value of lane ^ 1 (DPP quad_perm [1,0,3,2]: no LDS, no wait)
+__device__ __forceinline__ double lane_xor1(double x)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, 0xB1, 0xf, 0xf, true);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), 0xB1, 0xf, 0xf, true);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+// swap_row16: the odd 16-lane rows of a <-> the even ones of b (v_permlane16_swap), a half exchange: the other rows stay
+// where they are.  (The hazard "VALU write -> permlane read" is the compiler's: it pads the builtin itself.)
+__device__ __forceinline__ void swap_row16(double& a, double& b)
+{
+    const unsigned long long x = (unsigned long long)__double_as_longlong(a), y = (unsigned long long)__double_as_longlong(b);
+    const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)y, false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)(x >> 32), (unsigned)(y >> 32), false, false);
+    a = __longlong_as_double((long long)(((unsigned long long)hi[0] << 32) | lo[0]));
+    b = __longlong_as_double((long long)(((unsigned long long)hi[1] << 32) | lo[1]));
+}
 
 // ABL != 0: timing ablations and the timeline probe, instantiated by GGL_DEV builds only (tools/bench_tail.py)
 template <int BM, int BK, int WM, int WN, bool LM, int ABL = 0>
@@ -293,7 +312,8 @@ template <int N> __device__ __forceinline__ void wait_vmcnt()
 // NW: waves per workgroup (4: 2 x 2 waves of BM/2 x BM/2; 8: 4 x 2 waves of BM/4 x BM/2 -- two waves per SIMD, for batches
 // so small that only one workgroup lands on a CU and a lone wave per SIMD cannot hide its LDS round trips and barriers)
 // symm_dl_tile: one output tile (instance k of the combined batch, tile pair b) -- the whole body of k_symm_dl
-// SER 1: the serial epilogue instead of the batched one (development library only); XREG: VGPRs the caller keeps
+// SER 1: the serial epilogue instead of the batched one, SER 2: the batched one with every off-diagonal tile staged in LDS
+// (0: those of launches without bound partials are written from registers); 1 and 2 development library only; XREG: VGPRs the caller keeps
 // live across the tile (the persistent chain's loop state), taken off the batched epilogue's register budget
 // AUX: cache policy of every global READ of the tile body (operand DMA and the E term): 0 = default; 16 = sc1, i.e. served by
 // the XCD's L2 past this CU's vector L1 -- what a persistent kernel needs to read tiles that ANOTHER CU of the same XCD
@@ -469,7 +489,7 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
         else if (wave == 2) { rbk[0] = 16; rbk[TI - 1] = 0; cbk[0] = WN + 16; cbk[TJ - 1] = WN; nval = 1; }   // X=(1,3)
     }
     const bool dead_wave = !REBAL && (I == J) && (wr >= wc + WN);
-    // Epilogue operands.  The batched epilogue (SER == 0) fetches its coefficients HERE, ahead of the slab loop: eight scalar
+    // Epilogue operands.  The batched epilogue (SER != 1) fetches its coefficients HERE, ahead of the slab loop: eight scalar
     // loads whose latency the loop hides, instead of a scalar round trip between the last MFMA and the first epilogue load.
     double cI = 0.0, cAcc = 0.0, cE = 0.0, dI = 0.0, dC = 0.0, dE = 0.0, cE2 = 0.0, dE2 = 0.0;
     double* Ck = (second ? C1 : C) + (size_t)kk * pp;
@@ -482,7 +502,7 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
         dI = coef[k * NS_NCOEF + 3]; dC = coef[k * NS_NCOEF + 4]; dE = coef[k * NS_NCOEF + 5];
         cE2 = E2k ? coef[k * NS_NCOEF + 6] : 0.0; dE2 = E2k ? coef[k * NS_NCOEF + 7] : 0.0;
     };
-    if constexpr (SER == 0 && ABL != 4) load_coefs();
+    if constexpr (SER != 1 && ABL != 4) load_coefs();
     const int S = (p + BK - 1) / BK;
 #pragma unroll
     for (int q = 0; q < NSTG - 1; ++q)
@@ -575,7 +595,7 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
     }
     // all fragment reads done before the slabs are reused as the mirror tile (the batched epilogue has this barrier behind
     // its first loads, see there)
-    if constexpr (ABL == 4 || SER != 0) __syncthreads();
+    if constexpr (ABL == 4 || SER == 1) __syncthreads();
 #if defined(GGL_EXP_SETPRIO) && GGL_EXP_SETPRIO == 2
     __builtin_amdgcn_s_setprio(2);                                       // experiment: the epilogue outranks the other workgroups' slab loops
 #endif
@@ -590,7 +610,7 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
     }
 
 #ifdef GGL_DEV
-    if constexpr (SER != 0) {
+    if constexpr (SER == 1) {
         // the serial epilogue (development library, ggl_dev_set_symm_epilogue): the bitwise yardstick of
         // the batched one below and the other side of its A/B -- one global round trip per trip of every pass
         load_coefs();
@@ -802,13 +822,129 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
         else { double2 e; e.x = ld_pol<AUX>(q); e.y = ld_pol<AUX>(q + 1); return e; }
     };
     double dev = 0.0;
-    // Off-diagonal tiles: the accumulators go to the (XOR-swizzled) LDS tile first and BOTH copies -- the tile and its
+    // Off-diagonal tiles, staged (launches with bound partials, SER 2, and the instantiations the register path below leaves
+    // out): the accumulators go to the (XOR-swizzled) LDS tile first and BOTH copies -- the tile and its
     // mirror -- are written from there with 16-byte accesses, two consecutive columns per lane (tile columns start on even
     // indices): half the global store / E-load instructions of the layout the MFMA leaves the values in (one column per
     // lane: 8-byte accesses, which run at 0.54-0.70x the 16-byte rate on this chip).  Diagonal tiles keep the direct path
     // (upper triangle only, in-tile mirror).
     const bool wide = (I != J) && ABL != 1;
-    if (wide) {
+    // The register epilogue (SER 0; SER 2 keeps the staged one selectable in the development library): an off-diagonal tile of
+    // a launch without bound partials is written -- tile and mirror -- from the accumulator registers.  No LDS tile, no barrier
+    // behind the slab loop (the slabs are not reused), every wave finishes on its own.
+    // A 16x16 block leaves lane l with column c = l & 15, rows g + 4r (g = l >> 4, r = 0..3).
+    //   * direct tile: lanes c and c ^ 1 exchange two of their four values; the even lane then holds rows g, g + 4 and the odd
+    //     lane rows g + 8, g + 12 of the column PAIR (c & ~1, +1): trip h of a block is row g + 8 (c & 1) + 4h, one 16-byte
+    //     load per operand and one 16-byte store per output, with the edge rules of the staged pass;
+    //   * mirror: a lane's final pairs (x = first column, y = second) of the two trips h = 0, 1 are the rows g + 8 (c & 1) + 4h.
+    //     Swapping the lane bit g & 1 with the register bit h -- v_permlane16_swap on the two trips' x and on their y -- leaves
+    //     the lane with two CONSECUTIVE rows 2 (g >> 1) + 4 (g & 1) + 8 (c & 1) + 0, 1 of each of its two columns: 16 contiguous
+    //     bytes of mirror row c & ~1 and 16 of the next one, and the eight lanes of a column pair cover 128 contiguous bytes
+    //     of each -- per store instruction eight rows of 128 bytes, as in the direct pass.  (The 4 x 4 transpose with
+    //     v_permlane32_swap as well gives a lane 32 contiguous bytes of ONE mirror row, but every one of its two stores then
+    //     scatters 16-byte pieces 32 bytes apart, for twice the swaps.)  The second output is mirrored the same way (E and E2
+    //     are bitwise symmetric -- outputs of this kernel family -- so the mirrored entry of every term IS the upper one, as
+    //     the staged mirror already takes for the first output).
+    // Same operations per element in the same order: same bits.  Blocks per batch as on the diagonal path: 16 VGPRs each.
+    // (Not in the instantiations whose residency leaves one trip per batch, NB = 1 -- five workgroups per CU on 96 VGPRs: with
+    // this path beside the staged one, which the bound partials keep, they need 108-110 and would lose a workgroup per CU.)
+    constexpr bool REGEP = (SER == 0) && NB >= 2;
+    const bool regs = REGEP && wide && !rowpart;
+    if (regs) {
+        constexpr int RB = DB;
+        const int g = lane >> 4, odd = lane & 1, cc = lane & 14;
+        // trip h of block (ti, tj): row I0 + wr + 16 ti + g + 8 odd + 4h -- a row of tile row I < J, inside the matrix whatever p
+        // is -- and the column pair gj, gj + 1; the lane's offsets differ from those of its first trip by wave-uniform amounts
+        const size_t o00 = (size_t)(I0 + wr + g + 8 * odd) * p + (size_t)(J0 + wc + cc);
+        // the mirror of block (ti, tj): rows gj, gj + 1, two columns each from I0 + wr + 16 ti + 2 (g >> 1) + 4 (g & 1) + 8 odd
+        // (rows of tile row I again)
+        const size_t m00 = (size_t)(J0 + wc + cc) * p + (size_t)(I0 + wr + 2 * (g >> 1) + 4 * (g & 1) + 8 * odd);
+        double2 re[RB * 2], rf[RB * 2];
+        auto reg_loads = [&](const int b0) {          // one load instruction per operand and trip, see direct_loads below
+#pragma unroll
+            for (int q = 0; q < RB; ++q) {
+                const int ti = (b0 + q) / TJ, tj = (b0 + q) % TJ;
+                const int gj = J0 + wc + 16 * tj + cc;
+                const bool any = gj < p, half = any && gj + 1 >= p;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const size_t o = o00 + (size_t)(16 * ti + 4 * h) * p + 16 * tj - (half ? 1 : 0);
+                    re[q * 2 + h] = double2{0.0, 0.0};
+                    rf[q * 2 + h] = double2{0.0, 0.0};
+                    if (any) {
+                        if (Ek) re[q * 2 + h] = lde2(Ek + o);
+                        if (E2k) rf[q * 2 + h] = lde2(E2k + o);
+                    }
+                }
+            }
+        };
+        // block blk's accumulators, times cAcc, as the lane's two pairs: the even lane keeps registers 0, 1 and takes its
+        // neighbour's, the odd lane keeps 2, 3
+        auto exchange = [&](const int blk, double2* t) {
+            const int ti = blk / TJ, tj = blk % TJ;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const double lo = cAcc * acc[ti][tj][h], hi = cAcc * acc[ti][tj][2 + h];
+                const double plo = lane_xor1(lo), phi = lane_xor1(hi);
+                t[h].x = odd ? phi : lo;
+                t[h].y = odd ? hi : plo;
+            }
+        };
+        reg_loads(0);
+#pragma unroll
+        for (int b0 = 0; b0 < NBLK; b0 += RB) {
+            if (b0 > 0) reg_loads(b0);
+            // the first block's pair exchange runs under the loads
+            double2 t0[2];
+            exchange(b0, t0);
+#pragma unroll
+            for (int q = 0; q < RB * 2; ++q) { landed2(re[q]); landed2(rf[q]); }
+#pragma unroll
+            for (int q = 0; q < RB; ++q) {
+                const int ti = (b0 + q) / TJ, tj = (b0 + q) % TJ;
+                const int gj = J0 + wc + 16 * tj + cc;
+                const bool any = gj < p, full = gj + 1 < p;
+                double2 t[2], v[2], w[2];
+                if (q == 0) { t[0] = t0[0]; t[1] = t0[1]; }
+                else exchange(b0 + q, t);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const size_t o = o00 + (size_t)(16 * ti + 4 * h) * p + 16 * tj;
+                    double2 e = re[q * 2 + h], f = rf[q * 2 + h];
+                    if (any && !full) { e.x = e.y; f.x = f.y; }      // the odd last column, see direct_loads
+                    // every lane does the arithmetic (what is not stored is not looked at); the guards are on the stores
+                    v[h].x = __builtin_fma(cE, e.x, t[h].x);
+                    v[h].y = __builtin_fma(cE, e.y, t[h].y);
+                    if (E2k) { v[h].x = __builtin_fma(cE2, f.x, v[h].x); v[h].y = __builtin_fma(cE2, f.y, v[h].y); }
+                    w[h] = double2{0.0, 0.0};
+                    if (C2k) {
+                        w[h].x = c2val(dC, v[h].x, dE, e.x);
+                        w[h].y = c2val(dC, v[h].y, dE, e.y);
+                        if (E2k) { w[h].x = __builtin_fma(dE2, f.x, w[h].x); w[h].y = __builtin_fma(dE2, f.y, w[h].y); }
+                    }
+                    dev = fmax(dev, fmax(any ? fabs(v[h].x) : 0.0, full ? fabs(v[h].y) : 0.0));
+                    if (full) {
+                        *reinterpret_cast<double2*>(Ck + o) = v[h];
+                        if (C2k) *reinterpret_cast<double2*>(C2k + o) = w[h];
+                    } else if (any) {
+                        Ck[o] = v[h].x;
+                        if (C2k) C2k[o] = w[h].x;
+                    }
+                }
+                const size_t mo = m00 + (size_t)(16 * tj) * p + 16 * ti;
+                swap_row16(v[0].x, v[1].x);
+                swap_row16(v[0].y, v[1].y);
+                if (any) *reinterpret_cast<double2*>(Ck + mo) = double2{v[0].x, v[1].x};
+                if (full) *reinterpret_cast<double2*>(Ck + mo + p) = double2{v[0].y, v[1].y};
+                if (C2k) {
+                    swap_row16(w[0].x, w[1].x);
+                    swap_row16(w[0].y, w[1].y);
+                    if (any) *reinterpret_cast<double2*>(C2k + mo) = double2{w[0].x, w[1].x};
+                    if (full) *reinterpret_cast<double2*>(C2k + mo + p) = double2{w[0].y, w[1].y};
+                }
+            }
+        }
+    } else if (wide) {
         double2 pe[NB], pf[NB];
         // trip u of the direct pass: lane -> row `row`, columns c2, c2 + 1 of the tile; the edge guards as ONE predicate per
         // trip.  (One load instruction per operand and trip, whatever the lane's case: a second one into the same registers
@@ -969,9 +1105,9 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
         if (lane == 0 && dev > 0.0)
             atomicMax(reinterpret_cast<unsigned long long*>(maxdev + k), (unsigned long long)__double_as_longlong(dev));
     }
-    if ((I != J || rowpart) && ABL != 1) lds_barrier();      // the staged tile holds the final values
+    if ((I != J || rowpart) && ABL != 1 && !regs) lds_barrier();      // the staged tile holds the final values
     if (rowpart && ABL != 1 && tid < 2 * BM) symm_dl_partials<BM>(smem, rowpart, fropart, k, p, T, blockTile, I, J, I0, J0, tid);
-    if (wide) {
+    if (wide && !regs) {
         // the mirror: row a of it is column a of the staged tile, two consecutive columns c2, c2 + 1 per lane -- final values,
         // no arithmetic left but the second output's, whose E / E2 terms are loaded at the mirrored addresses
         // (loaded under the serial epilogue's condition -- without bound partials also where dE or dE2 is zero: fma(0, e, x)
@@ -1180,7 +1316,7 @@ __global__ __launch_bounds__(256) void k_cw_rider(const CwRider rider)
     cw_rider_body(rider, (int)blockIdx.x, sh);
 }
 
-// SER 1: the serial epilogue (development library only, see symm_dl_tile)
+// SER 1: the serial epilogue, SER 2: the staged batched one (development library only, see symm_dl_tile)
 template <int BK, int NSTG, int ABL = 0, int BM = 64, int NW = 4, int SER = 0>
 __global__ __launch_bounds__(NW * 64) void k_symm_dl(const double* __restrict__ A, const double* __restrict__ B,
                                                  double* __restrict__ C, double* __restrict__ C2,
@@ -1565,10 +1701,16 @@ __global__ __launch_bounds__(256) void k_symm_sk(const double* __restrict__ A, c
 #endif   // GGL_DEV (k_symm_sk)
 
 #ifdef GGL_DEV
-// which epilogue the direct-to-LDS launches of the development library run: the batched one (false) or the serial one
-// (ggl_dev_set_symm_epilogue; the product library compiles the batched one only)
-static bool g_symm_serial = false;
-bool symm_set_serial_epilogue(bool on) { const bool was = g_symm_serial; g_symm_serial = on; return was; }
+// which epilogue the direct-to-LDS launches of the development library run (ggl_dev_set_symm_epilogue): 0 the product's --
+// batched, off-diagonal tiles written from registers --, 1 the serial one, 2 the batched one with the staged LDS tile (the
+// product's before the register path); the product library compiles 0 only
+static int g_symm_epilogue = 0;
+int symm_set_epilogue(int mode)
+{
+    const int was = g_symm_epilogue;
+    g_symm_epilogue = (mode == 1 || mode == 2) ? mode : 0;
+    return was;
+}
 #endif
 
 #ifdef GGL_DEV      // (round 6: the persistent chain is an option of the development library only -- measured slower)
@@ -1668,7 +1810,9 @@ __global__ __launch_bounds__(256) void k_omega_chain(const ChainProg P, unsigned
         const SymmOp& o = P.op[js];
         int kk = jk;
         if (o.pair && jb >= P.ntiles) { kk = P.K + jk; jb -= P.ntiles; }
-        symm_dl_tile<BK, NSTG, 0, BM, 4, AUX, SER, 32>(o.A, o.B, o.C, o.C2, o.E, o.E2, o.coef, P.K, P.p, o.A1, o.B1, o.C1, o.pair ? P.K : 0,
+        // (the batched epilogue here is the staged one: with the register path beside it the kernel needs 173 VGPRs, 168 keep
+        // three workgroups per CU)
+        symm_dl_tile<BK, NSTG, 0, BM, 4, AUX, SER == 0 ? 2 : SER, 32>(o.A, o.B, o.C, o.C2, o.E, o.E2, o.coef, P.K, P.p, o.A1, o.B1, o.C1, o.pair ? P.K : 0,
                                                nullptr, o.rowpart, o.fropart, kk, jb, smem);
         // this tile's stores are in the XCD's L2 before the arrival is counted; the barrier also frees the LDS image
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1713,7 +1857,7 @@ int launch_omega_chain(hipStream_t st, const ChainProg& P, unsigned* state, int*
         slots -= slots % NXCD;
     }
     if (aux == 0) hipLaunchKernelGGL((k_omega_chain<16, 3, 64, 0>), dim3(slots), dim3(256), 0, st, P, state);   // measurement only
-    else if (g_symm_serial) hipLaunchKernelGGL((k_omega_chain<16, 3, 64, 16, 1>), dim3(slots), dim3(256), 0, st, P, state);
+    else if (g_symm_epilogue == 1) hipLaunchKernelGGL((k_omega_chain<16, 3, 64, 16, 1>), dim3(slots), dim3(256), 0, st, P, state);
     else
     hipLaunchKernelGGL((k_omega_chain<16, 3, 64, 16>), dim3(slots), dim3(256), 0, st, P, state);
     hipLaunchKernelGGL(k_chain_check, dim3(1), dim3(64), 0, st, state, P.K, (unsigned)P.begin[P.nops], flag, flag_h);
@@ -1870,7 +2014,8 @@ static void launch_dl(hipStream_t st, const double* A, const double* B, double* 
     // GGL_DL(BK, NSTG, ABL, BM): the instance with the epilogue the switch names
 #define GGL_DL4(BK_, NSTG_, ABL_, BM_)                                                                                        \
     do {                                                                                                                       \
-        if (g_symm_serial) hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, ABL_, BM_, 4, 1>), grid, dim3(256), 0, st, GGL_DL_ARGS); \
+        if (g_symm_epilogue == 1) hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, ABL_, BM_, 4, 1>), grid, dim3(256), 0, st, GGL_DL_ARGS); \
+        else if (g_symm_epilogue == 2) hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, ABL_, BM_, 4, 2>), grid, dim3(256), 0, st, GGL_DL_ARGS); \
         else hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, ABL_, BM_, 4, 0>), grid, dim3(256), 0, st, GGL_DL_ARGS);               \
     } while (0)
 #else
@@ -1912,7 +2057,8 @@ static void launch_dl(hipStream_t st, const double* A, const double* B, double* 
         // no gain anywhere, so the shipped library does not carry them
 #define GGL_DL8(BK_, NSTG_)                                                                                                   \
     do {                                                                                                                       \
-        if (g_symm_serial) hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, 0, 64, 8, 1>), grid, dim3(512), 0, st, GGL_DL_ARGS);     \
+        if (g_symm_epilogue == 1) hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, 0, 64, 8, 1>), grid, dim3(512), 0, st, GGL_DL_ARGS); \
+        else if (g_symm_epilogue == 2) hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, 0, 64, 8, 2>), grid, dim3(512), 0, st, GGL_DL_ARGS); \
         else hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, 0, 64, 8, 0>), grid, dim3(512), 0, st, GGL_DL_ARGS);                   \
     } while (0)
         if (dl_cfg == 6) GGL_DL8(16, 4);

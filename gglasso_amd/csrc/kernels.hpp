@@ -310,7 +310,7 @@ int symm_bounds_tile(int K, int p, int variant);
 // frees the split-K scratch (k_symm_sk with a tile's k-range over several workgroups) that launches on this stream allocated
 void symm_release_workspace(hipStream_t st);
 #ifdef GGL_DEV
-bool symm_set_serial_epilogue(bool on);  // process-wide: the serial epilogue of the direct-to-LDS kernels; returns the previous mode
+int symm_set_epilogue(int mode);  // process-wide: the epilogue of the direct-to-LDS kernels (0 register, 1 serial, 2 staged); returns the previous mode
 #endif
 
 // ---- the Omega-step's product chain as one persistent launch (gemm_sym.hip, k_omega_chain) ----

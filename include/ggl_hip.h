@@ -685,9 +685,11 @@ int ggl_dev_symm_timeline(int K, int p, long long *out, int max_blocks, int *nbl
  * the two chains' results (must be 0), out[4] barrier flag (1 time-out, 2 a workgroup not on XCD blockIdx % 8).  variant: 16, 17
  * (64x64 tiles), 20 (32x32).  two_level: one L2 write-back per XCD and barrier instead of one per workgroup. */
 int ggl_dev_chain_probe(int K, int p, int variant, int nprod, int iters, int two_level, double *out);
-/* Epilogue of the direct-to-LDS product kernels (symm_dl_tile): 0 the batched one (the only one the product library has), 1 the
- * serial one, kept as its bitwise yardstick and for A/B timing.  Process-wide; returns the previous mode. */
-int ggl_dev_set_symm_epilogue(int serial);
+/* Epilogue of the direct-to-LDS product kernels (symm_dl_tile): 0 the batched one that writes off-diagonal tiles and their
+ * mirrors from registers (the only one the product library has), 1 the serial one, kept as its bitwise yardstick and for A/B
+ * timing, 2 the batched one with every off-diagonal tile staged in LDS (the product's before the register path).  Any other
+ * value counts as 0.  Process-wide; returns the previous mode. */
+int ggl_dev_set_symm_epilogue(int mode);
 /* ggl_dev_symm_bench with the epilogue's operands present: ops bit 0 the affine operand E, bit 1 the second one (E2), bit 2 the
  * second output C2.  Average milliseconds of `iters` launches. */
 int ggl_dev_symm_bench_ops(int K, int p, int variant, int iters, int ops, double *ms_out);
