@@ -184,10 +184,8 @@ _DEV_SIGNATURES = {
     "ggl_dev_omega_i8": ([_i, _i, _dp, _dp, _dp, ctypes.POINTER(_i), _d, _dp, _i, _dp], _i),
     "ggl_dev_mfma_f64_peak": ([_dp], _i),
     "ggl_dev_symm_timeline": ([_i, _i, ctypes.POINTER(ctypes.c_longlong), _i, ctypes.POINTER(_i)], _i),
-    "ggl_dev_chain_probe": ([_i, _i, _i, _i, _i, _i, _dp], _i),
     "ggl_dev_coissue_probe": ([_dp], _i),
     "ggl_dev_mfma_lds_probe": ([_dp], _i),
-    "ggl_dev_chain_run": ([_i, _i, _i, _i, _dp], _i),
     "ggl_dev_switch_bench": ([_i, _i, _i, _i, _i, _dp], _i),
     "ggl_dev_vendor_bench": ([_i, _i, _i, _i, _dp], _i),
     "ggl_dev_set_symm_epilogue": ([_i], _i),

@@ -592,7 +592,7 @@ extern "C" int ggl_ctx_create_subset(ggl_ctx* src, const int* idx, int m, ggl_ct
     c->S_symmetric = src->S_symmetric;
     c->fused_w = src->fused_w;
 #ifdef GGL_DEV
-    c->parts_bias = src->parts_bias; c->parts_order = src->parts_order; c->chain_mode = src->chain_mode; c->fused_cw = src->fused_cw;
+    c->parts_bias = src->parts_bias; c->parts_order = src->parts_order; c->fused_cw = src->fused_cw;
     c->rank_cw = src->rank_cw; c->bound_side = src->bound_side;
 #endif
     c->lds_pinned = src->lds_pinned;

@@ -404,17 +404,17 @@ static int set_option(ggl_ctx* c, int opt, double v)
 #ifdef GGL_DEV
         case GGL_OPT_PARTS_BIAS: c->parts_bias = (int)v; break;
         case GGL_OPT_PARTS_ORDER: c->parts_order = (int)v; break;
-        case GGL_OPT_CHAIN: c->chain_mode = (v == 2.0) ? 2 : (v != 0.0 ? 1 : 0); break;
         case GGL_OPT_FUSED_CW: c->fused_cw = v != 0.0; break;
         case GGL_OPT_RANK_CW: c->rank_cw = v != 0.0; break;
         case GGL_OPT_BOUND_SIDE: c->bound_side = (int)v; break;
 #else
-        case GGL_OPT_PARTS_BIAS: case GGL_OPT_PARTS_ORDER: case GGL_OPT_CHAIN: case GGL_OPT_FUSED_CW: case GGL_OPT_RANK_CW:
+        case GGL_OPT_PARTS_BIAS: case GGL_OPT_PARTS_ORDER: case GGL_OPT_FUSED_CW: case GGL_OPT_RANK_CW:
         case GGL_OPT_BOUND_SIDE: case GGL_OPT_PART_PRIORITY:
+#endif
+        case GGL_OPT_CHAIN:                      // retired: no library carries the persistent chain any more
             if (v == 0.0) break;                 // (the default, which is what the product library runs)
             return fail(GGL_E_ARG, "bad argument: option %d is a measured-and-rejected alternative that only the development "
                         "library (libggl_hip_dev.so, python -m gglasso_amd.build --dev) carries", opt);
-#endif
         case GGL_OPT_DOWNLOAD_THREADS: c->download_threads = std::min(std::max((int)v, 1), 64); break;
         case GGL_OPT_CW_WARM: c->cw_warm = v != 0.0; break;
         case GGL_OPT_ISOLATE: c->isolate = v != 0.0; break;
@@ -498,7 +498,7 @@ extern "C" int ggl_ctx_get_option(ggl_ctx* c, int opt, double* value)
         case GGL_OPT_DOWNLOAD_THREADS: *value = c->download_threads; break;
         case GGL_OPT_NS_TOL: *value = c->ns_tol; break;
         case GGL_OPT_CW_WARM: *value = c->cw_warm; break;
-        case GGL_OPT_CHAIN: *value = c->chain_mode; break;
+        case GGL_OPT_CHAIN: *value = 0; break;
         case GGL_OPT_RANK_L0_COARSE: *value = c->rank_l0_coarse; break;
         case GGL_OPT_ISOLATE: *value = c->isolate; break;
         case GGL_OPT_FUSED_CW: *value = c->fused_cw; break;
@@ -530,7 +530,7 @@ static void dev_env_options(ggl_ctx* c)
         {"GGL_TWO_STREAM", GGL_OPT_PARTS}, {"GGL_PARTS_MAX_TILES", GGL_OPT_PARTS_MAX_TILES},
         {"GGL_SYMM_VARIANT", GGL_OPT_SYMM_VARIANT}, {"GGL_SPIN_WAIT", GGL_OPT_SPIN_WAIT},
         {"GGL_FUSED_BOUNDS", GGL_OPT_FUSED_BOUNDS}, {"GGL_PIPELINE", GGL_OPT_PIPELINE},
-        {"GGL_FUSED_START", GGL_OPT_FUSED_START}, {"GGL_PARTS_SMALL", GGL_OPT_PARTS_SMALL}, {"GGL_CHAIN", GGL_OPT_CHAIN}};
+        {"GGL_FUSED_START", GGL_OPT_FUSED_START}, {"GGL_PARTS_SMALL", GGL_OPT_PARTS_SMALL}};
     for (const auto& t : tab)
         if (const char* v = getenv(t.name)) (void)set_option(c, t.opt, atof(v));
     if (const char* v = getenv("GGL_ROCSOLVER_SYEVJ")) c->use_syevj = atoi(v) != 0;
@@ -593,7 +593,7 @@ extern "C" int ggl_ctx_destroy(ggl_ctx* c)
     }
     // (the rocBLAS handle is the process-wide one of blas_handle(): never destroyed here)
     // lazily allocated buffers, each its own allocation
-    double* lazy[] = {c->partials_own, c->nsNX, c->lds_tab, c->snapT, c->snapL, c->Lam[0], c->Lam[1], c->X1, c->Ckeep_alloc, c->snapC, c->snapOm, c->snapX, c->cwvecL[0], c->cwvecL[1], c->defl_G,
+    double* lazy[] = {c->partials_own, c->lds_tab, c->snapT, c->snapL, c->Lam[0], c->Lam[1], c->X1, c->Ckeep_alloc, c->snapC, c->snapOm, c->snapX, c->cwvecL[0], c->cwvecL[1], c->defl_G,
                       c->defl_work, c->defl_meta, c->maskK, c->fsgl_sq};
     for (double* b : lazy)
         if (b) (void)hipFree(b);
@@ -609,7 +609,6 @@ extern "C" int ggl_ctx_destroy(ggl_ctx* c)
     if (c->rank_idx_h) (void)hipHostFree(c->rank_idx_h);
     for (double* b : c->snap)
         if (b) (void)hipFree(b);
-    if (c->chain_cnt) (void)hipFree(c->chain_cnt);
     free(c->spec_c);
     free(c->spec_beta);
     free(c->pre_beta);

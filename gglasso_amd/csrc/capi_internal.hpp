@@ -4,7 +4,7 @@
 //   capi_ctx.hip        ctx, arenas / stream pool, options, state upload / download
 //   capi_omega.hip      the Omega-step pipeline (speculation, parts, groups, riders), Theta-step, ggl_admm_step
 //                       omega_step is the dispatcher: omega_split fills an OmegaChainPlan (host only), then one function per
-//                       route -- omega_eig_route, omega_lds_route, omega_dev_chain (development library), omega_plan_spec,
+//                       route -- omega_eig_route, omega_lds_route, omega_plan_spec,
 //                       per part omega_phase_a / omega_bound_pass, omega_finish_spec / omega_finish_validated
 //   capi_lstep.hip      the L-step (sign iteration, deflation, continuation) and ggl_finalize_L
 //   capi_batch.hip      batches of independent problems: steps, the loop in C, isolation, compaction
@@ -120,7 +120,6 @@ struct ggl_ctx {
     bool dvo_valid = false;                    // DvO holds the eigenvalues of the last Omega-step
     int symm_variant = -1;
     double *nsYP[2] = {nullptr, nullptr}, *nsT = nullptr;   // [Y|Z] scratch pairs (2 stacks each), T
-    // the Omega-step's product chain as ONE persistent launch with per-instance dependencies (k_omega_chain, gemm_sym.hip)
     // Measured-and-rejected alternatives (each built, bit-identical or parity-tested, and slower or
     // within noise) are options of the DEVELOPMENT library only (round 6): in the product build the switches are constants,
     // the compiler drops their branches, and ggl_ctx_set_option refuses them.  GGL_DEV_OPT(type, name): a field there, 0 here.
@@ -129,10 +128,6 @@ struct ggl_ctx {
 #else
 #define GGL_DEV_OPT(type, name) static constexpr type name = 0
 #endif
-    GGL_DEV_OPT(int, chain_mode);              // GGL_OPT_CHAIN: 0 never, 1 where chain_tile() says so, 2 wherever it can run
-    double* nsNX = nullptr;                    // third [Y|Z] pair: the chain leaves A', B' intact for the bound kernels (lazy)
-    unsigned* chain_cnt = nullptr;             // per-instance completion / ticket words, one 128-byte line each (lazy)
-    long long chain_calls = 0;
     bool flags_dirty = false;
     int step_latent = 0;                       // latent flag of the last Omega-step (the split entry points that follow it)                  // a validation flag was raised: clear ALL device slots before the next step
     int ns_force = 0;                          // 0 auto, 1 symmetric products, 2 stable products

@@ -277,7 +277,7 @@ static void note_family(ggl_ctx* c, const NsPlan& pl)
 // cb[k] >= lambda_max(A'_k), beta_k = nk/rho.  Returns the number of groups (1: the batch stays whole, Kh / k0h untouched).
 static int omega_groups(const ggl_ctx* c, const double* cb, const double* beta_h, int K, int* Kh, int* k0h, int* gunits)
 {
-    if (!c->group_sched || K < 2 || c->ns_force == 2 || c->chain_mode || c->comm) return 1;
+    if (!c->group_sched || K < 2 || c->ns_force == 2 || c->comm) return 1;
     {
         // the K planner queries below cost ~0.1 us each on the host, in front of the chain's launches: only where a step is
         // long enough not to notice (a step is >= 7 launches of F + K I seconds; same constants as ns_group_partition)
@@ -537,7 +537,7 @@ static int omega_lds_route(ggl_ctx* c, OmegaStep& S, CopySegs* pending, bool all
     const LdsSgl* sgl_req = c->sgl_req;         // (consumed here, whichever route the step takes)
     c->sgl_req = nullptr;
     c->sgl_done = false;
-    if (!(c->lds_omega && c->p <= omega_lds_max_p() && c->ns_force == 0 && c->symm_variant < 0 && !c->chain_mode && !S.want_A && !S.resume))
+    if (!(c->lds_omega && c->p <= omega_lds_max_p() && c->ns_force == 0 && c->symm_variant < 0 && !S.want_A && !S.resume))
         return GGL_OK;
     const bool as_spec = allow_spec && c->spec_enable && !S.latent;
     if (c->lds_cool > 0) {
@@ -585,7 +585,7 @@ static int omega_lds_route(ggl_ctx* c, OmegaStep& S, CopySegs* pending, bool all
     c->sgl_done = sgl_fused;
     HIPCHK(hipGetLastError());
     c->last_parts = 1;
-    c->last_variant = 41;
+    c->last_variant = 41;          // the LDS Omega kernel's report code (ggl_ns_stats), not a product-kernel variant: those end at 39
     c->lds_calls += 1;
     c->ns_calls += 1;
     c->ns_launches_total += 1;
@@ -614,79 +614,6 @@ static int omega_lds_route(ggl_ctx* c, OmegaStep& S, CopySegs* pending, bool all
     *done = false;
     return clear_spec_flags(c);
 }
-
-#ifdef GGL_DEV
-// ---- the whole product chain as ONE persistent launch with per-instance dependencies (k_omega_chain) ----------
-// *done: the step is complete (or failed); otherwise it goes on to the launch chain.
-static int omega_dev_chain(ggl_ctx* c, OmegaStep& S, OmegaChainPlan& plan, bool* done)
-{
-    const int K = c->K, nxt = S.nxt;
-    const size_t pp = S.pp;
-    double *pre = S.pre, *pre_d = S.pre_d;
-    *done = false;
-    if (!(S.spec && !S.want_A && !S.resume && c->chain_mode && c->fused_start && c->fused_bounds && (c->symm_variant < 0 || c->symm_variant == 17) &&
-          chain_tile(K, c->p, c->chain_mode == 2) == 64))
-        return GGL_OK;
-    *done = true;
-    if (!c->nsNX) HIPCHK(malloc_filled(&c->nsNX, 2 * c->n * sizeof(double) + STACK_SLACK, c->stream));
-    if (!c->chain_cnt) HIPCHK(hipMalloc(&c->chain_cnt, (size_t)K * CHAIN_CNT_STRIDE * sizeof(unsigned)));
-    for (int k = 0; k < K; ++k) c->cuse_h[k] = c->spec_c[k] * c->spec_factor;
-    NsPlan& pl = plan.plans[0];
-    SymmOp ops[CHAIN_MAX_OPS];
-    int nops = 0;
-    const int bT = (c->p + 63) / 64;
-    if (ns_plan(c->cuse_h, c->par_h, K, c->coef_h, S.start_base_h, &pl, c->ns_force, c->ns_degrees, c->ns_tol, c->omega_poly) == 0 &&
-        !pl.stable) {
-        double* f0 = nullptr;
-        for (int k = 0; k < K; ++k)
-            f0 = ns_fused_start(pl, S.start_base_h + 5 * (size_t)k, c->nsYP[1], c->nsT, (size_t)K * pp,
-                                pre + NS_SLOT(K) + (size_t)k * NS_NCOEF);
-        if (f0)
-            nops = ns_chain_ops(pl, pre_d, pre_d + NS_SLOT(K), c->coef, c->W, c->nsYP[0], c->nsYP[1], c->nsNX, c->nsT,
-                                c->Om[nxt], K, c->p, 0, f0, c->rowpart, c->fropart, ops, CHAIN_MAX_OPS);
-    }
-    if (nops <= 0) { *done = false; return GGL_OK; }
-    CopySegs sg = S.first;
-    sg.add(pre_d, pre, (size_t)K * NS_NCOEF * sizeof(double));
-    sg.add(pre_d + NS_SLOT(K), pre + NS_SLOT(K), (size_t)K * NS_NCOEF * sizeof(double));
-    // validation flags of this step: slot 0 the bound check, slot 1 the chain's completion check, last slot the
-    // all-reduced flag of K-sharded runs
-    sg.add(c->spec_flag, nullptr, 2 * sizeof(int));
-    sg.add(c->spec_flag + ggl_ctx::MAX_PARTS - 1, nullptr, sizeof(int));
-    c->spec_flag_h[0] = c->spec_flag_h[1] = c->spec_flag_h[ggl_ctx::MAX_PARTS - 1] = 0;
-    const int nb_launch = pl.products - 2;
-    if (nb_launch > 0) sg.add(c->coef, c->coef_h, (size_t)nb_launch * NS_SLOT(K) * sizeof(double));
-    sg.add(c->cuse, c->cuse_h, (size_t)K * sizeof(double));
-    if (c->info_dirty) sg.add(c->info, nullptr, K * sizeof(int));
-    sg.add(c->chain_cnt, nullptr, (size_t)K * CHAIN_CNT_STRIDE * sizeof(unsigned));
-    launch_copy_small(c->stream, sg);
-    PB(c, GGL_PH_FORM_W);
-    launch_form_W_sym(c->stream, c->W, c->Theta, nullptr, c->X, c->S, S.beta, K, c->p);
-    PE(c, GGL_PH_FORM_W);
-    PB(c, GGL_PH_EIG_OMEGA);
-    ChainProg P;
-    P.nops = nops; P.K = K; P.p = c->p; P.ntiles = bT * (bT + 1) / 2;
-    P.begin[0] = 0;
-    for (int i = 0; i < nops; ++i) { P.op[i] = ops[i]; P.begin[i + 1] = P.begin[i] + P.ntiles * (ops[i].pair ? 2 : 1); }
-    if (launch_omega_chain(c->stream, P, c->chain_cnt, c->spec_flag + 1, c->spec_flag_h + 1) < 0)
-        return fail(GGL_E_HIP, "k_omega_chain: launch failed (%s)", hipGetErrorString(hipGetLastError()));
-    // the bound of THIS iteration's A' (validation of the assumed one; next iteration's schedule): B' is intact
-    launch_bound_rows(c->stream, c->rowpart, bT, K, c->p, c->nbrow, c->infpart);
-    launch_cw_final(c->stream, c->nsYP[0] + c->n, c->nbrow, K, c->p, c->infpart, c->fropart, bT * (bT + 1) / 2,
-                    c->cwmax, c->cwcnt, c->bounds_h, c->cuse, c->spec_flag, c->spec_flag_h, 0, cw_prev(c, 0), cw_next(c, 0));
-    PE(c, GGL_PH_EIG_OMEGA);
-    HIPCHK(hipGetLastError());
-    c->last_parts = 1;
-    c->last_variant = 40;
-    c->chain_calls += 1;
-    note_sequence(c, pl, K);
-    c->spec_calls += 1;
-    c->spec_pending = true;
-    c->cw_pending = c->cw_warm;
-    step_epilogue(c, nxt);
-    return GGL_OK;
-}
-#endif   // GGL_DEV (GGL_OPT_CHAIN)
 
 // Speculation: the schedules of the parts from the last validated step's bounds, inflated (cuse_h), and the first step's
 // start as 2nd output of the B' launch.  Clears S.spec where a part has no such schedule.
@@ -726,7 +653,7 @@ static void omega_phase_a(ggl_ctx* c, OmegaStep& S, const OmegaChainPlan& pl, in
     // the iteration is no shorter: the parts are bound by what they share, not by their first launch) -- so: 1 = only
     // where the chain is one sequence.
     bool ride_copy = (c->copy_rider == 2 || (c->copy_rider == 1 && nh == 1)) && S.first.n == 0 && !latent && bt.bT != 0 &&
-                     !c->chain_mode && c->prof_on != 1;
+                     c->prof_on != 1;
     for (int k = k0; ride_copy && k < k0 + Kp; ++k) ride_copy = (c->pre0_beta[k] == c->par_h[k]);
     CopySegs sg = S.first;
     if (!ride_copy) {
@@ -998,7 +925,7 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool 
     omega_split(c, S, pl);
     if (c->flags_dirty) {
         // a step was rejected since the flags were last cleared wholesale: whatever slot carried the 1 (a part that does
-        // not exist in this step's split, the chain's completion check) must not outlive it.  On the main stream BEFORE
+        // not exist in this step's split) must not outlive it.  On the main stream BEFORE
         // the fork, so it is ordered ahead of every part's own zeroing and kernels.
         if ((rc = clear_spec_flags(c))) return rc;
         c->flags_dirty = false;
@@ -1006,10 +933,6 @@ int omega_step(ggl_ctx* c, int latent, CopySegs* pending, bool allow_spec, bool 
     bool done;
     rc = omega_lds_route(c, S, pending, allow_spec, only_spec, &done);
     if (rc || done) return rc;
-#ifdef GGL_DEV
-    rc = omega_dev_chain(c, S, pl, &done);
-    if (rc || done) return rc;
-#endif
     if (S.resume) c->early_used += 1;
     else if (S.spec) omega_plan_spec(c, S, pl);
     if (only_spec && !S.spec) return GGL_NOT_LAUNCHED;
@@ -1372,7 +1295,7 @@ extern "C" int ggl_norms_read(ggl_ctx* c, double out_norms[5])
 bool early_wanted(const ggl_ctx* c)
 {
     if (!c->early_caller || !c->early_part || !c->pipeline || !c->omega_ns || !c->spec_enable || c->prof_on == 1 || c->last_step_hint || !c->ratio_calm ||
-        c->chain_mode || c->pre_valid)
+        c->pre_valid)
         return false;
     if (c->lds_omega && c->p <= omega_lds_max_p()) return false;       // (one kernel writes Omega there: nothing to split)
     return true;

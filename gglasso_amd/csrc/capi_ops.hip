@@ -611,213 +611,6 @@ extern "C" int ggl_dev_omega_lds(int K, int p, const double* Theta, const double
 }
 
 #ifdef GGL_DEV
-// persistent-chain probe (gemm_sym.hip): out = {ms per chain as nprod launches, ms per chain as one cooperative launch,
-// grid of the cooperative launch, max |difference| between the two chains' results (same tile code: 0 unless a workgroup
-// read stale data across a grid barrier), barrier time-out flag}.  The chain is X <- I - 1.5 X^2 on a dense symmetric
-// start of norm <= 1/2 (the quadratic map keeps the spectrum in [-1, 1], so it can run for any number of products).
-extern "C" int ggl_dev_chain_probe(int K, int p, int variant, int nprod, int iters, int two_level, double* out)
-{
-    ARGCHK(K >= 1 && p >= 2 && (p & 1) == 0 && nprod >= 1 && iters >= 1 && out, "arguments (p even)");
-    const size_t n = (size_t)K * p * p;
-    std::vector<double> h(n, 0.0), coef((size_t)K * NS_NCOEF, 0.0);
-    unsigned long long s = 88172645463325252ull;
-    for (int k = 0; k < K; ++k) {
-        double* M = h.data() + (size_t)k * p * p;
-        for (int i = 0; i < p; ++i)
-            for (int j = i; j < p; ++j) {
-                s ^= s << 13; s ^= s >> 7; s ^= s << 17;
-                M[(size_t)i * p + j] = M[(size_t)j * p + i] = ((double)(s >> 11) / 9007199254740992.0 - 0.5) / p;
-            }
-        coef[(size_t)k * NS_NCOEF + 0] = 1.0;
-        coef[(size_t)k * NS_NCOEF + 1] = -1.5;
-    }
-    DevBuf dX0, dX1, dcoef, dbar;
-    HIPCHK(dX0.alloc(n));
-    HIPCHK(dX1.alloc(n));
-    HIPCHK(dcoef.alloc(coef.size()));
-    HIPCHK(dbar.alloc(8));
-    UP(dcoef.p, coef.data(), coef.size());
-    unsigned* bar = reinterpret_cast<unsigned*>(dbar.p);
-    double* last = (nprod & 1) ? dX1.p : dX0.p;
-    auto chain_launches = [&]() {
-        for (int j = 0; j < nprod; ++j)
-            launch_symm(nullptr, (j & 1) ? dX1.p : dX0.p, (j & 1) ? dX1.p : dX0.p, (j & 1) ? dX0.p : dX1.p, nullptr, nullptr,
-                        dcoef.p, K, p, variant);
-    };
-    int grid = 0;
-    auto chain_persistent = [&]() -> int {
-        hipError_t e = hipMemsetAsync(dbar.p, 0, 8 * sizeof(double), nullptr);
-        if (e != hipSuccess) return -1;
-        grid = launch_chain_probe(nullptr, dX0.p, dX1.p, dcoef.p, K, p, nprod, variant, bar, bar + 1, two_level);
-        return grid;
-    };
-    // the two chains from the same start must agree bit for bit
-    std::vector<double> r1(n), r2(n);
-    UP(dX0.p, h.data(), n);
-    chain_launches();
-    DOWN(r1.data(), last, n);
-    UP(dX0.p, h.data(), n);
-    HIPCHK(hipMemset(dX1.p, 0, n * sizeof(double)));
-    int g = chain_persistent();
-    ARGCHK(g != 0, "no probe instance of this variant (16, 17, 20)");
-    if (g < 0) return fail(GGL_E_HIP, "cooperative launch of the chain probe failed: %s", hipGetErrorString(hipGetLastError()));
-    DOWN(r2.data(), last, n);
-    double dev = 0.0;
-    for (size_t i = 0; i < n; ++i) dev = std::max(dev, std::fabs(r1[i] - r2[i]));
-    out[3] = dev;
-    unsigned flags[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpy(flags, dbar.p, sizeof(flags), hipMemcpyDeviceToHost));
-    out[4] = flags[1];
-    out[2] = grid;
-    if (flags[1]) return GGL_OK;          // a barrier timed out: do not time it
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    float ms = 0.f;
-    for (int i = 0; i < 3; ++i) chain_launches();
-    HIPCHK(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters; ++i) chain_launches();
-    HIPCHK(hipEventRecord(e1, nullptr));
-    HIPCHK(hipEventSynchronize(e1));
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    out[0] = ms / iters;
-    for (int i = 0; i < 3 + iters; ++i) {
-        if (i == 3) HIPCHK(hipEventRecord(e0, nullptr));
-        if (chain_persistent() <= 0) return fail(GGL_E_HIP, "cooperative launch of the chain probe failed");
-    }
-    HIPCHK(hipEventRecord(e1, nullptr));
-    HIPCHK(hipEventSynchronize(e1));
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    out[1] = ms / iters;
-    HIPCHK(hipMemcpy(flags, dbar.p, sizeof(flags), hipMemcpyDeviceToHost));
-    out[4] = flags[1];
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    HIPCHK(hipGetLastError());
-    return GGL_OK;
-}
-
-// k_omega_chain on a synthetic program: nprod dependent products X <- I - 1.5 X^2 (ping-pong between two stacks) as nprod
-// launches of the three-stage 64x64 kernel (out[0], ms per chain) and as ONE persistent launch with per-instance
-// dependencies (out[1]); out[2] = persistent workgroups, out[3] = max |difference| of the results (same tile code: 0 unless
-// a hand-off delivered stale data), out[4] = completion flag of k_chain_check, out[5..5+K) = done counters after the run
-extern "C" int ggl_dev_chain_run(int K, int p, int nprod, int iters, double* out)
-{
-    ARGCHK(K >= 1 && p >= 2 && (p & 1) == 0 && nprod >= 1 && nprod <= CHAIN_MAX_OPS && iters >= 1 && out, "arguments (p even)");
-    const size_t n = (size_t)K * p * p;
-    std::vector<double> h(n, 0.0), coef((size_t)K * NS_NCOEF, 0.0);
-    unsigned long long s = 88172645463325252ull;
-    for (int k = 0; k < K; ++k) {
-        double* M = h.data() + (size_t)k * p * p;
-        for (int i = 0; i < p; ++i)
-            for (int j = i; j < p; ++j) {
-                s ^= s << 13; s ^= s >> 7; s ^= s << 17;
-                M[(size_t)i * p + j] = M[(size_t)j * p + i] = ((double)(s >> 11) / 9007199254740992.0 - 0.5) / p;
-            }
-        coef[(size_t)k * NS_NCOEF + 0] = 1.0;
-        coef[(size_t)k * NS_NCOEF + 1] = -1.5;
-    }
-    DevBuf dX0, dX1, dcoef, dcnt;
-    HIPCHK(dX0.alloc(n));
-    HIPCHK(dX1.alloc(n));
-    HIPCHK(dcoef.alloc(coef.size()));
-    const size_t ncw = (size_t)K * CHAIN_CNT_STRIDE;          // 32-bit words
-    HIPCHK(dcnt.alloc(ncw / 2 + 8));
-    UP(dcoef.p, coef.data(), coef.size());
-    unsigned* cnt = reinterpret_cast<unsigned*>(dcnt.p);
-    int* flag = reinterpret_cast<int*>(cnt + ncw);
-    const int aux = getenv("GGL_CHAIN_AUX") ? atoi(getenv("GGL_CHAIN_AUX")) : 16;
-    double* last = (nprod & 1) ? dX1.p : dX0.p;
-    const int T = (p + 63) / 64;
-    ChainProg P;
-    P.nops = nprod; P.K = K; P.p = p; P.ntiles = T * (T + 1) / 2;
-    P.begin[0] = 0;
-    for (int j = 0; j < nprod; ++j) {
-        SymmOp o{};
-        o.A = o.B = (j & 1) ? dX1.p : dX0.p;
-        o.C = (j & 1) ? dX0.p : dX1.p;
-        o.coef = dcoef.p;
-        P.op[j] = o;
-        P.begin[j + 1] = P.begin[j] + P.ntiles;
-    }
-    auto chain_launches = [&]() {
-        for (int j = 0; j < nprod; ++j)
-            launch_symm(nullptr, (j & 1) ? dX1.p : dX0.p, (j & 1) ? dX1.p : dX0.p, (j & 1) ? dX0.p : dX1.p, nullptr, nullptr,
-                        dcoef.p, K, p, 17);
-    };
-    int grid = 0;
-    auto chain_persistent = [&]() -> int {
-        if (hipMemsetAsync(dcnt.p, 0, (ncw / 2 + 8) * sizeof(double), nullptr) != hipSuccess) return -1;
-        grid = launch_omega_chain(nullptr, P, cnt, flag, flag + 1, aux);
-        return grid;
-    };
-    std::vector<double> r1(n), r2(n);
-    UP(dX0.p, h.data(), n);
-    chain_launches();
-    DOWN(r1.data(), last, n);
-    UP(dX0.p, h.data(), n);
-    HIPCHK(hipMemset(dX1.p, 0, n * sizeof(double)));
-    if (chain_persistent() <= 0) return fail(GGL_E_HIP, "k_omega_chain launch failed");
-    DOWN(r2.data(), last, n);
-    if (getenv("GGL_CHAIN_PROF")) {
-        // one more run with the per-workgroup time accounting: claim / idle / tile time (100 MHz ticks) and tiles served
-        DevBuf dprof;
-        HIPCHK(dprof.alloc((size_t)grid * 8));
-        HIPCHK(hipMemset(dprof.p, 0, (size_t)grid * 8 * sizeof(double)));
-        P.prof = reinterpret_cast<long long*>(dprof.p);
-        UP(dX0.p, h.data(), n);
-        if (chain_persistent() <= 0) return fail(GGL_E_HIP, "k_omega_chain launch failed");
-        std::vector<long long> hp((size_t)grid * 8);
-        HIPCHK(hipMemcpy(hp.data(), dprof.p, hp.size() * sizeof(long long), hipMemcpyDeviceToHost));
-        P.prof = nullptr;
-        double cl = 0, id = 0, ti = 0, nt = 0, span = 0, cyc = 0;
-        long long t0 = hp[4], t1 = hp[5];
-        int perx[8] = {};
-        for (int g = 0; g < grid; ++g) {
-            const long long* o = hp.data() + (size_t)g * 8;
-            cl += o[0]; id += o[1]; ti += o[2]; nt += o[3]; span += o[5] - o[4]; cyc += o[7];
-            t0 = std::min(t0, o[4]); t1 = std::max(t1, o[5]);
-            perx[o[6] & 7] += 1;
-        }
-        fprintf(stderr, "chain prof: kernel span %.1f us; per workgroup (avg over %d): claim %.1f us, idle %.1f us, tile %.1f us, "
-                "%.2f tiles, %.1f us per tile, alive %.1f us; workgroups per XCD:", (t1 - t0) * 0.01, grid, cl * 0.01 / grid,
-                id * 0.01 / grid, ti * 0.01 / grid, nt / grid, ti * 0.01 / std::max(nt, 1.0), span * 0.01 / grid);
-        for (int x = 0; x < 8; ++x) fprintf(stderr, " %d", perx[x]);
-        fprintf(stderr, "; clock64 ticks per us of wall_clock64 while alive: %.1f\n", cyc / (span * 0.01));
-    }
-    double dev = 0.0;
-    for (size_t i = 0; i < n; ++i) dev = std::max(dev, std::fabs(r1[i] - r2[i]));
-    out[3] = dev;
-    out[2] = grid;
-    std::vector<unsigned> hc(ncw + 2);
-    HIPCHK(hipMemcpy(hc.data(), dcnt.p, hc.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-    out[4] = (double)hc[ncw];
-    for (int k = 0; k < K; ++k) out[5 + k] = (double)hc[(size_t)k * CHAIN_CNT_STRIDE];
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    float ms = 0.f;
-    for (int i = 0; i < 3; ++i) chain_launches();
-    HIPCHK(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters; ++i) chain_launches();
-    HIPCHK(hipEventRecord(e1, nullptr));
-    HIPCHK(hipEventSynchronize(e1));
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    out[0] = ms / iters;
-    for (int i = 0; i < 3 + iters; ++i) {
-        if (i == 3) HIPCHK(hipEventRecord(e0, nullptr));
-        if (chain_persistent() <= 0) return fail(GGL_E_HIP, "k_omega_chain launch failed");
-    }
-    HIPCHK(hipEventRecord(e1, nullptr));
-    HIPCHK(hipEventSynchronize(e1));
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    out[1] = ms / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    HIPCHK(hipGetLastError());
-    return GGL_OK;
-}
-
 // timeline probe: one launch of variant 10; out = [nblocks][5] long long {start, loop, loop_end, end, xcc}
 extern "C" int ggl_dev_symm_timeline(int K, int p, long long* out, int max_blocks, int* nblocks_out)
 {

@@ -13,9 +13,8 @@
 // current one is consumed from LDS (software prefetch), one barrier pair per slab.
 #include <algorithm>
 #include <initializer_list>
-#include <mutex>
-#include <unordered_map>
 #include <type_traits>
+#include <utility>
 
 #include "common.hpp"
 #include "kernels.hpp"
@@ -266,17 +265,6 @@ __global__ __launch_bounds__(sym_nt(BM, WM, WN)) void k_symm_tn(
 #endif
 }
 
-template <int BM, int BK, int WM, int WN, bool LM>
-static void launch_cfg(hipStream_t st, const double* A, const double* B, double* C, double* C2, const double* E,
-                       const double* coef, int K, int p, const double* A1 = nullptr, const double* B1 = nullptr,
-                       double* C1 = nullptr, int K1 = 0, double* maxdev = nullptr, const double* E2 = nullptr)
-{
-    using Cfg = SymCfg<BM, BK, WM, WN, LM>;
-    const int T = (p + BM - 1) / BM;
-    hipLaunchKernelGGL((k_symm_tn<BM, BK, WM, WN, LM>), dim3(xcd_grid(T * (T + 1) / 2, K + K1)), dim3(Cfg::NT), 0, st, A,
-                       B, C, C2, E, coef, K, p, A1, B1, C1, K1, maxdev, E2);
-}
-
 // ---------------------------------------------------------------------------------------------
 // k_symm_dl: the same symmetric product with the operand slabs DMA'd straight into LDS
 // (global_load_lds, 16 bytes per lane, no VGPR round trip and no ds_write pass) and a double-buffered
@@ -313,16 +301,12 @@ template <int N> __device__ __forceinline__ void wait_vmcnt()
 // so small that only one workgroup lands on a CU and a lone wave per SIMD cannot hide its LDS round trips and barriers)
 // symm_dl_tile: one output tile (instance k of the combined batch, tile pair b) -- the whole body of k_symm_dl
 // SER 1: the serial epilogue instead of the batched one, SER 2: the batched one with every off-diagonal tile staged in LDS
-// (0: those of launches without bound partials are written from registers); 1 and 2 development library only; XREG: VGPRs the caller keeps
-// live across the tile (the persistent chain's loop state), taken off the batched epilogue's register budget
-// AUX: cache policy of every global READ of the tile body (operand DMA and the E term): 0 = default; 16 = sc1, i.e. served by
-// the XCD's L2 past this CU's vector L1 -- what a persistent kernel needs to read tiles that ANOTHER CU of the same XCD
-// wrote earlier in the same launch (a CU's L1 is never refreshed by other CUs' stores; MI355X_MICROARCH.md).
-template <int AUX> __device__ __forceinline__ double ld_pol(const double* p)
-{
-    if constexpr (AUX == 0) return *p;
-    else return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // global_load_dwordx2 ... sc1
-}
+// (0: those of launches without bound partials are written from registers); 1 and 2 development library only
+
+// one scalar load of the serial epilogue (SER 1, development library).  A function on purpose: with the subscript written out
+// the compiler lays that epilogue's branches out differently -- same arithmetic, other machine code in 21 SER 1 instances --
+// and the serial epilogue is the bitwise yardstick, kept exactly as measured
+__device__ __forceinline__ double ld1(const double* p) { return *p; }
 
 // the bound partials of one staged tile (symm_dl_tile: rowpart / fropart), by the first 2 BM threads of the workgroup
 template <int BM>
@@ -368,7 +352,7 @@ __device__ __forceinline__ void symm_dl_partials(const double* smem, double* __r
 
 }
 
-template <int BK, int NSTG, int ABL, int BM, int NW, int AUX = 0, int SER = 0, int XREG = 0>
+template <int BK, int NSTG, int ABL, int BM, int NW, int SER = 0>
 __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const double* __restrict__ B,
                                              double* __restrict__ C, double* __restrict__ C2,
                                              const double* __restrict__ E, const double* __restrict__ E2,
@@ -445,8 +429,8 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
 #pragma unroll
             for (int j = 0; j < IPW; ++j) {
                 double* la = base + j * 128;
-                __builtin_amdgcn_global_load_lds((gptr_t)pa[j], (lptr_t)la, 16, 0, AUX);
-                __builtin_amdgcn_global_load_lds((gptr_t)pb[j], (lptr_t)(la + SLAB), 16, 0, AUX);
+                __builtin_amdgcn_global_load_lds((gptr_t)pa[j], (lptr_t)la, 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((gptr_t)pb[j], (lptr_t)(la + SLAB), 16, 0, 0);
                 pa[j] += slab_step;
                 pb[j] += slab_step;
             }
@@ -457,8 +441,8 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
                 const int i = wave * IPW + j;
                 const unsigned ro = min((unsigned)(m0 + RPI * i + lrow), pm1) * pu;
                 double* la = base + j * 128;
-                __builtin_amdgcn_global_load_lds((gptr_t)(Ak + ro + ca), (lptr_t)la, 16, 0, AUX);
-                __builtin_amdgcn_global_load_lds((gptr_t)(Bk + ro + cb), (lptr_t)(la + SLAB), 16, 0, AUX);
+                __builtin_amdgcn_global_load_lds((gptr_t)(Ak + ro + ca), (lptr_t)la, 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((gptr_t)(Bk + ro + cb), (lptr_t)(la + SLAB), 16, 0, 0);
             }
         }
     };
@@ -546,9 +530,6 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
         asm volatile("" ::: "memory");
         if (s + NSTG - 1 < S) issue(s + NSTG - 1, (buf + NSTG - 1) % NSTG);
         if (!dead_wave) {
-#if defined(GGL_EXP_SETPRIO) && GGL_EXP_SETPRIO == 1
-            __builtin_amdgcn_s_setprio(1);                    // experiment (tools/r6_e.sh): the matrix segment of a wave outranks the epilogues of its SIMD
-#endif
             const int nq = min(BK / 4, (valid + 3) / 4);      // k-quads inside the matrix (last slab: 1 of 4 at p = 500)
             // (The exit check between the k-quads stays even for slabs that lie inside the matrix.  Straight-line code --
             // with the compiler's own order, ds_read2st64 pairs ahead of 8 back-to-back MFMAs, or with a scheduling barrier
@@ -578,9 +559,6 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
                         }
                 }
             }
-#if defined(GGL_EXP_SETPRIO) && GGL_EXP_SETPRIO == 1
-            __builtin_amdgcn_s_setprio(0);
-#endif
         }
     };
     auto stages = [&](const int s0, auto... bufs) {
@@ -596,9 +574,6 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
     // all fragment reads done before the slabs are reused as the mirror tile (the batched epilogue has this barrier behind
     // its first loads, see there)
     if constexpr (ABL == 4 || SER == 1) __syncthreads();
-#if defined(GGL_EXP_SETPRIO) && GGL_EXP_SETPRIO == 2
-    __builtin_amdgcn_s_setprio(2);                                       // experiment: the epilogue outranks the other workgroups' slab loops
-#endif
     if (ABL == 4) {                                                      // timing ablation: no epilogue
         double keepalive = 0.0;
 #pragma unroll
@@ -634,10 +609,7 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
                     }
             __syncthreads();
             auto ld2 = [](const double* q) { return *reinterpret_cast<const double2*>(q); };
-            auto lde2 = [&](const double* q) {
-                if constexpr (AUX == 0) return *reinterpret_cast<const double2*>(q);
-                else { double2 e; e.x = ld_pol<AUX>(q); e.y = ld_pol<AUX>(q + 1); return e; }
-            };
+            auto lde2 = [](const double* q) { return *reinterpret_cast<const double2*>(q); };
             for (int e2 = tid; e2 < BM * BM / 2; e2 += NT) {
                 const int row = e2 / (BM / 2), c2 = (e2 % (BM / 2)) * 2;
                 const int gi = I0 + row, gj = J0 + c2;
@@ -667,8 +639,8 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
                     }
                 } else if (gi < p && gj < p) {
                     // odd p: the last column is the first half of a pair whose second half lies outside the matrix
-                    const double e0 = Ek ? ld_pol<AUX>(Ek + (size_t)gi * p + gj) : 0.0;
-                    const double f0 = E2k ? ld_pol<AUX>(E2k + (size_t)gi * p + gj) : 0.0;
+                    const double e0 = Ek ? ld1(Ek + (size_t)gi * p + gj) : 0.0;
+                    const double f0 = E2k ? ld1(E2k + (size_t)gi * p + gj) : 0.0;
                     double v0 = t.x + cE * e0;
                     if (E2k) v0 += cE2 * f0;
                     dev = fmax(dev, fabs(v0));
@@ -706,9 +678,9 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
                     const bool keep = gi < p && gj < p && (I != J || gi <= gj);
                     if (keep) {
                         if (gi == gj) v += cI;
-                        const double e0 = Ek ? ld_pol<AUX>(Ek + (size_t)gi * p + gj) : 0.0;
+                        const double e0 = Ek ? ld1(Ek + (size_t)gi * p + gj) : 0.0;
                         v += cE * e0;
-                        const double f0 = E2k ? ld_pol<AUX>(E2k + (size_t)gi * p + gj) : 0.0;
+                        const double f0 = E2k ? ld1(E2k + (size_t)gi * p + gj) : 0.0;
                         if (E2k) v += cE2 * f0;
                         dev = fmax(dev, fabs(v - (gi == gj ? 1.0 : 0.0)));
                         Ck[(size_t)gi * p + gj] = v;
@@ -735,10 +707,7 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
             // the mirror: row a of it is column a of the staged tile; two consecutive columns c2, c2 + 1 per lane.  Without bound
             // partials the tile still holds cAcc * acc and the E term is added here as well (E is bitwise symmetric -- an output
             // of this kernel family -- so its mirrored entries ARE the upper ones); with them it holds the final values.
-            auto lde2 = [&](const double* q) {
-                if constexpr (AUX == 0) return *reinterpret_cast<const double2*>(q);
-                else { double2 e; e.x = ld_pol<AUX>(q); e.y = ld_pol<AUX>(q + 1); return e; }
-            };
+            auto lde2 = [](const double* q) { return *reinterpret_cast<const double2*>(q); };
             for (int e2 = tid; e2 < BM * BM / 2; e2 += NT) {
                 const int a = e2 / (BM / 2), c2 = (e2 % (BM / 2)) * 2;      // out[J0+a][I0+c2 .. +1] = tile[c2 .. +1][a]
                 if (J0 + a < p && I0 + c2 + 1 < p) {
@@ -767,9 +736,9 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
                     // odd last column can only belong to tile column J; kept so that the pair test above stands on its own)
                     double v0 = smem[c2 * BM + (a ^ c2)];
                     const bool need_e = Ek && (!rowpart || (C2k && dE != 0.0));
-                    const double e0 = need_e ? ld_pol<AUX>(Ek + (size_t)(J0 + a) * p + I0 + c2) : 0.0;
+                    const double e0 = need_e ? ld1(Ek + (size_t)(J0 + a) * p + I0 + c2) : 0.0;
                     const bool need_f = E2k && (!rowpart || (C2k && dE2 != 0.0));
-                    const double f0 = need_f ? ld_pol<AUX>(E2k + (size_t)(J0 + a) * p + I0 + c2) : 0.0;
+                    const double f0 = need_f ? ld1(E2k + (size_t)(J0 + a) * p + I0 + c2) : 0.0;
                     if (!rowpart) { v0 += cE * e0; if (E2k) v0 += cE2 * f0; }
                     Ck[(size_t)(J0 + a) * p + I0 + c2] = v0;
                     if (C2k) C2k[(size_t)(J0 + a) * p + I0 + c2] = c2val2(dC, v0, dE, e0, E2k != nullptr, dE2, f0);
@@ -798,9 +767,8 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
     constexpr int LDSB = NSTG * 2 * SLAB * 8;
     constexpr int WGCU = (160 * 1024 / LDSB) < (8 / (NW / 4)) ? (160 * 1024 / LDSB) : (8 / (NW / 4));   // workgroups per CU
     constexpr int VBUD = (512 / (WGCU * (NW / 4))) & ~7;          // VGPRs per lane that keep that residency
-    // of them, for loads in flight: what the accumulators, ~48 registers of addresses and values in work and the caller's
-    // own live registers (XREG) leave
-    constexpr int BREG = VBUD - TI * TJ * 8 - 48 - XREG;
+    // of them, for loads in flight: what the accumulators and ~48 registers of addresses and values in work leave
+    constexpr int BREG = VBUD - TI * TJ * 8 - 48;
     constexpr int NTRIP = BM * BM / 2 / NT;                       // trips of a pass over an off-diagonal tile
     constexpr int NB = (BREG / 8 >= NTRIP) ? NTRIP : (BREG / 8 >= NTRIP / 2 && NTRIP >= 2) ? NTRIP / 2 : 1;   // trips per batch (8 VGPRs each)
     constexpr int NBLK = TI * TJ;                                 // 16x16 blocks of a wave
@@ -817,10 +785,7 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
     auto landed = [](const double& x) { asm volatile("" ::"v"(x)); };
     auto landed2 = [&](const double2& x) { landed(x.x); landed(x.y); };
     auto ld2 = [](const double* q) { return *reinterpret_cast<const double2*>(q); };
-    auto lde2 = [&](const double* q) {
-        if constexpr (AUX == 0) return *reinterpret_cast<const double2*>(q);
-        else { double2 e; e.x = ld_pol<AUX>(q); e.y = ld_pol<AUX>(q + 1); return e; }
-    };
+    auto lde2 = [](const double* q) { return *reinterpret_cast<const double2*>(q); };
     double dev = 0.0;
     // Off-diagonal tiles, staged (launches with bound partials, SER 2, and the instantiations the register path below leaves
     // out): the accumulators go to the (XOR-swizzled) LDS tile first and BOTH copies -- the tile and its
@@ -1048,8 +1013,8 @@ __device__ __forceinline__ void symm_dl_tile(const double* __restrict__ A, const
                 for (int r = 0; r < 4; ++r) {
                     const int gi = I0 + rbk[ti] + (lane >> 4) + 4 * r, gj = J0 + cbk[tj] + (lane & 15);
                     if (gi < p && gj < p && (I != J || gi <= gj)) {
-                        if (Ek) de[q * 4 + r] = ld_pol<AUX>(Ek + (size_t)gi * p + gj);
-                        if (E2k) df[q * 4 + r] = ld_pol<AUX>(E2k + (size_t)gi * p + gj);
+                        if (Ek) de[q * 4 + r] = Ek[(size_t)gi * p + gj];
+                        if (E2k) df[q * 4 + r] = E2k[(size_t)gi * p + gj];
                     }
                 }
             }
@@ -1372,333 +1337,8 @@ __global__ __launch_bounds__(NW * 64) void k_symm_dl(const double* __restrict__ 
     }
     int k, b;
     if (!decode_block_xcd(T * (T + 1) / 2, K + K1, k, b, bid)) return;
-    symm_dl_tile<BK, NSTG, ABL, BM, NW, 0, SER>(A, B, C, C2, E, E2, coef, K, p, A1, B1, C1, K1, maxdev, rowpart, fropart, k, b, smem);
+    symm_dl_tile<BK, NSTG, ABL, BM, NW, SER>(A, B, C, C2, E, E2, coef, K, p, A1, B1, C1, K1, maxdev, rowpart, fropart, k, b, smem);
 }
-
-#ifdef GGL_DEV
-// ---------------------------------------------------------------------------------------------
-// k_symm_sk: the product for batches that leave the chip UNDER-FILLED (the K-sharded slabs K = 2..8 at p = 500, (20,200)):
-// 32x32 output tiles, and the four waves of a workgroup split the k-range of ONE tile instead of its area.
-//
-// MEASURED, NOT SHIPPED (dev build only; profiles/r3_small_batch_split_k.txt): as fast as the 32x32 direct-to-LDS kernel,
-// not faster, and slower with the k-range split over workgroups -- the under-filled launches are bound by fixed latencies
-// (launch, first DMA, epilogue: ~6.5 us) plus whole tiles per CU, not by what a wave does per k-quad.
-// The 32x32 direct-to-LDS kernel gives each wave one 16x16 block: per k-quad two fragment reads, an LDS round trip and ONE
-// MFMA, a workgroup barrier per slab.  Here every wave owns the whole tile (2x2 blocks: two + two
-// fragment reads feed FOUR independent MFMAs) over the k-slabs s = wave, wave+4, wave+8, ...; it streams ITS slabs into
-// ITS quarter of the LDS through its own DMA pipeline (NSTG stages) and waits for nobody -- no barrier in the main loop at
-// all.  The four partial tiles meet in LDS at the end (one barrier), are summed in a fixed order (wave 0..3:
-// deterministic), and the epilogue (affine terms, second output, mirror, bound partials) runs on the sums.
-// Diagonal tiles take the upper triangle's sums for both halves: the output is symmetric bit for bit.
-// ---------------------------------------------------------------------------------------------
-//
-// SPLIT > 1: the k-range of a tile is dealt over SPLIT workgroups as well (slab s goes to workgroup (s / 4) % SPLIT, wave
-// s % 4) -- 544 tiles on 256 CUs leave some CUs three tiles and the launch ends when those do; 2176 quarter-tiles pack to
-// within 6 %.  Each workgroup leaves the sum of its four waves in a global scratch tile (write-through stores), then one
-// memory-side atomic per workgroup counts the arrivals; the LAST one adds the SPLIT scratch tiles in part order (so the
-// result does not depend on who was last) and runs the epilogue.  No cache write-back / invalidate fences anywhere
-// (see k_cw_final): stores, loads and the counter are agent-scope atomics.  The counter is left at zero.
-template <int SPLIT> __device__ __forceinline__ bool sk_decode(int ntiles, int K, int L, int& k, int& tile, int& part)
-{
-    // as decode_block_xcd, over ntiles * SPLIT units per instance with the SPLIT parts of a tile in consecutive slots
-    auto small = [&](int Ks, int Ls) {
-        const int g = xcd_share(Ks);
-        if (g) {
-            const int xcd = Ls % NXCD, slot = Ls / NXCD;
-            k = xcd / g;
-            tile = (slot / SPLIT) * g + xcd % g;
-            part = slot % SPLIT;
-            return tile < ntiles;
-        }
-        const int u = Ls % (ntiles * SPLIT);
-        k = Ls / (ntiles * SPLIT);
-        tile = u / SPLIT;
-        part = u % SPLIT;
-        return k < Ks;
-    };
-    if (K < NXCD) return small(K, L);
-    const int nfull = NXCD * (K / NXCD) * ntiles * SPLIT;
-    if (L < nfull) {
-        const int xcd = L % NXCD, slot = L / NXCD, u = slot % (ntiles * SPLIT);
-        k = (slot / (ntiles * SPLIT)) * NXCD + xcd;
-        tile = u / SPLIT;
-        part = u % SPLIT;
-        return true;
-    }
-    const bool ok = small(K % NXCD, L - nfull);
-    k += (K / NXCD) * NXCD;
-    return ok;
-}
-inline int sk_grid_small(int ntiles, int K, int split)
-{
-    const int g = xcd_share(K);
-    return g ? NXCD * ((ntiles + g - 1) / g) * split : NXCD * ((ntiles * split * K + NXCD - 1) / NXCD);
-}
-inline int sk_grid(int ntiles, int K, int split)
-{
-    if (K < NXCD) return sk_grid_small(ntiles, K, split);
-    const int r = K % NXCD;
-    return NXCD * (K / NXCD) * ntiles * split + (r ? sk_grid_small(ntiles, r, split) : 0);
-}
-
-template <int BK, int NSTG, int SPLIT>
-__global__ __launch_bounds__(256) void k_symm_sk(const double* __restrict__ A, const double* __restrict__ B,
-                                                 double* __restrict__ C, double* __restrict__ C2,
-                                                 const double* __restrict__ E, const double* __restrict__ coef, int K,
-                                                 int p, double* __restrict__ maxdev, double* __restrict__ rowpart,
-                                                 double* __restrict__ fropart, double* __restrict__ scratch,
-                                                 unsigned* __restrict__ arrivals)
-{
-    constexpr int BM = 32;
-    constexpr int SLAB = BK * BM;                       // doubles per operand slab
-    constexpr int IPS = BK / 4;                         // DMA instructions per operand and slab: 4 rows x 32 doubles = 1 KiB each
-    constexpr int WREG = NSTG * 2 * SLAB;               // doubles of LDS per wave: [stage][A|B][BK][32]; later its partial tile
-    static_assert(BK % 4 == 0 && IPS >= 1, "slab depth");
-    static_assert(WREG >= BM * BM, "a wave's region takes its partial tile");
-    static_assert(NSTG >= 2 && NSTG <= 4, "stages");
-    __shared__ __attribute__((aligned(16))) double smem[4 * WREG];
-    __shared__ int last_s;
-    const int T = (p + BM - 1) / BM;
-    const int ntiles = T * (T + 1) / 2;
-    int k, b, part = 0;
-    if constexpr (SPLIT > 1) { if (!sk_decode<SPLIT>(ntiles, K, (int)blockIdx.x, k, b, part)) return; }
-    else { if (!decode_block_xcd(ntiles, K, k, b)) return; }
-    const int blockTile = b;
-    int I = 0;
-    while (b >= T - I) { b -= T - I; ++I; }
-    const int J = I + b;
-    const int I0 = I * BM, J0 = J * BM;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const size_t pp = (size_t)p * p;
-    const double* Ak = A + (size_t)k * pp;
-    const double* Bk = B + (size_t)k * pp;
-    double* wbase = smem + (size_t)wave * WREG;
-    const int sfirst = 4 * part + wave, sstep = 4 * SPLIT;          // this wave's slabs: sfirst, sfirst + sstep, ...
-
-    v4d acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (v4d){0.0, 0.0, 0.0, 0.0};
-
-    // DMA geometry (as k_symm_dl at BM = 32): lane l -> slab row 4i + (l >> 4), LDS position (l & 15) * 2, source column
-    // position ^ 16 * (row & 1) -- the XOR keeps the fragment reads of a k-quad (four consecutive rows) off each other's banks
-    const unsigned pu = (unsigned)p, pm1 = (unsigned)(p - 1), pm2 = (unsigned)(p - 2);
-    const int lrow = lane >> 4;
-    const unsigned cpos = (unsigned)((lane & 15) * 2) ^ (unsigned)(16 * (lrow & 1));
-    const unsigned ca = min((unsigned)I0 + cpos, pm2), cb = min((unsigned)J0 + cpos, pm2);
-    const int S = (p + BK - 1) / BK;                    // slabs of the whole k-range
-    const int nw = (S > sfirst) ? (S - sfirst + sstep - 1) / sstep : 0;
-    auto issue = [&](int j, int stage) {
-        const int m0 = (sfirst + sstep * j) * BK;
-        double* base = wbase + (size_t)stage * 2 * SLAB;
-#pragma unroll
-        for (int i = 0; i < IPS; ++i) {
-            const unsigned ro = min((unsigned)(m0 + 4 * i + lrow), pm1) * pu;
-            __builtin_amdgcn_global_load_lds((gptr_t)(Ak + ro + ca), (lptr_t)(base + i * 128), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gptr_t)(Bk + ro + cb), (lptr_t)(base + SLAB + i * 128), 16, 0, 0);
-        }
-    };
-#pragma unroll
-    for (int q = 0; q < NSTG - 1; ++q)
-        if (q < nw) issue(q, q);
-    const int fg = lane >> 4, fsw = 16 * (fg & 1);
-    int fa[2], fb[2];                                   // fragment positions in k-quad 0 of a stage image
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        fa[i] = fg * BM + ((i * 16 + (lane & 15)) ^ fsw);
-        fb[i] = SLAB + fg * BM + ((i * 16 + (lane & 15)) ^ fsw);
-    }
-    int stage = 0;
-    for (int j = 0; j < nw; ++j) {
-        // this wave's DMA of its slab j has landed: at most the slabs issued after it may still be in flight
-        const int ahead = min(NSTG - 2, nw - 1 - j);
-        if (NSTG >= 4 && ahead >= 2) wait_vmcnt<4 * IPS>();
-        else if (NSTG >= 3 && ahead >= 1) wait_vmcnt<2 * IPS>();
-        else wait_vmcnt<0>();
-        const double* st = wbase + (size_t)stage * 2 * SLAB;
-        const int valid = p - (sfirst + sstep * j) * BK;      // k-rows of this slab inside the matrix
-        if (valid < BK) {
-            double* stw = wbase + (size_t)stage * 2 * SLAB;
-            for (int e = lane; e < BK * BM; e += 64)
-                if (e / BM >= valid) { stw[e] = 0.0; stw[SLAB + e] = 0.0; }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
-        // the stage slab j-1 was read from is free: its fragment reads completed before the MFMAs that consumed them issued
-        if (j + NSTG - 1 < nw) issue(j + NSTG - 1, (stage + NSTG - 1) % NSTG);
-        const int nq = min(BK / 4, (valid + 3) / 4);
-#pragma unroll
-        for (int kq = 0; kq < BK / 4; ++kq) {
-            if (kq >= nq) break;
-            const double a0 = st[fa[0] + kq * 4 * BM], a1 = st[fa[1] + kq * 4 * BM];
-            const double b0 = st[fb[0] + kq * 4 * BM], b1 = st[fb[1] + kq * 4 * BM];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        stage = (stage + 1 == NSTG) ? 0 : stage + 1;
-    }
-    // the wave's partial tile over its own slabs, plain [row][col]
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                wbase[(ti * 16 + (lane >> 4) + 4 * r) * BM + tj * 16 + (lane & 15)] = acc[ti][tj][r];
-    __syncthreads();
-
-    const double cI = coef[k * NS_NCOEF + 0], cAcc = coef[k * NS_NCOEF + 1], cE = coef[k * NS_NCOEF + 2];
-    const double dI = coef[k * NS_NCOEF + 3], dC = coef[k * NS_NCOEF + 4], dE = coef[k * NS_NCOEF + 5];
-    double* Ck = C + (size_t)k * pp;
-    double* C2k = C2 ? C2 + (size_t)k * pp : nullptr;
-    const double* Ek = E ? E + (size_t)k * pp : nullptr;
-    // thread -> row (tid >> 3), columns c0 .. c0 + 3 of the tile; the four partials are added in wave order
-    const int row = tid >> 3, c0 = (tid & 7) * 4;
-    const int gi = I0 + row;
-    double sum[4];
-    if constexpr (SPLIT > 1) {
-        // this workgroup's share of the tile -> scratch; the last workgroup of the tile to arrive carries on with the total
-        double* mine = scratch + (((size_t)k * ntiles + blockTile) * SPLIT + part) * (BM * BM);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int o = row * BM + c0 + i;
-            double t = smem[o];
-#pragma unroll
-            for (int w = 1; w < 4; ++w) t += smem[(size_t)w * WREG + o];
-            __hip_atomic_store(mine + o, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) {
-            unsigned* cell = arrivals + (size_t)k * ntiles + blockTile;
-            const unsigned old = __hip_atomic_fetch_add(cell, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            last_s = (old == SPLIT - 1);
-            if (old == SPLIT - 1) __hip_atomic_store(cell, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        if (!last_s) return;
-        const double* all = scratch + ((size_t)k * ntiles + blockTile) * SPLIT * (BM * BM);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int c = c0 + i, o = (I != J || row <= c) ? row * BM + c : c * BM + row;
-            double t = __hip_atomic_load(all + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-            for (int g = 1; g < SPLIT; ++g)
-                t += __hip_atomic_load(all + (size_t)g * (BM * BM) + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            sum[i] = t;
-        }
-    } else if (I != J) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            double2 t = *reinterpret_cast<const double2*>(smem + row * BM + c0 + 2 * h);
-#pragma unroll
-            for (int w = 1; w < 4; ++w) {
-                const double2 u = *reinterpret_cast<const double2*>(smem + (size_t)w * WREG + row * BM + c0 + 2 * h);
-                t.x += u.x;
-                t.y += u.y;
-            }
-            sum[2 * h] = t.x;
-            sum[2 * h + 1] = t.y;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int c = c0 + i, o = (row <= c) ? row * BM + c : c * BM + row;       // the upper triangle's sums, both ways
-            double t = smem[o];
-#pragma unroll
-            for (int w = 1; w < 4; ++w) t += smem[(size_t)w * WREG + o];
-            sum[i] = t;
-        }
-    }
-    double dev = 0.0, val[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int gj = J0 + c0 + 2 * h;
-        val[2 * h] = 0.0;
-        val[2 * h + 1] = 0.0;
-        if (gi < p && gj < p) {                         // p is even and gj is: the pair is inside or outside together
-            double2 e = {0.0, 0.0};
-            if (Ek) e = *reinterpret_cast<const double2*>(Ek + (size_t)gi * p + gj);
-            double2 v;
-            v.x = cAcc * sum[2 * h];
-            v.y = cAcc * sum[2 * h + 1];
-            if (gi == gj) v.x += cI;
-            if (gi == gj + 1) v.y += cI;
-            v.x += cE * e.x;
-            v.y += cE * e.y;
-            dev = fmax(dev, fmax(fabs(v.x - (gi == gj ? 1.0 : 0.0)), fabs(v.y - (gi == gj + 1 ? 1.0 : 0.0))));
-            *reinterpret_cast<double2*>(Ck + (size_t)gi * p + gj) = v;
-            if (C2k) {
-                double2 w2;
-                w2.x = c2val(dC, v.x, dE, e.x) + (gi == gj ? dI : 0.0);
-                w2.y = c2val(dC, v.y, dE, e.y) + (gi == gj + 1 ? dI : 0.0);
-                *reinterpret_cast<double2*>(C2k + (size_t)gi * p + gj) = w2;
-            }
-            val[2 * h] = v.x;
-            val[2 * h + 1] = v.y;
-        }
-    }
-    if (maxdev) {
-        dev = wave_max(dev);
-        if (lane == 0 && dev > 0.0)
-            atomicMax(reinterpret_cast<unsigned long long*>(maxdev + k), (unsigned long long)__double_as_longlong(dev));
-    }
-    if (I == J && !rowpart) return;
-    // the final tile (zeros outside the matrix) for the mirror and the bound partials: over wave 0's partial, once everybody
-    // has read the partials
-    __syncthreads();
-    *reinterpret_cast<double2*>(smem + row * BM + c0) = double2{val[0], val[1]};
-    *reinterpret_cast<double2*>(smem + row * BM + c0 + 2) = double2{val[2], val[3]};
-    __syncthreads();
-    if (I != J) {
-        // mirror: row a of it is column a of the tile; E is bitwise symmetric (an output of this kernel family)
-        const int a = row, gm = J0 + a;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int c = c0 + 2 * h, gc = I0 + c;
-            if (gm < p && gc < p) {
-                double2 v;
-                v.x = smem[c * BM + a];
-                v.y = smem[(c + 1) * BM + a];
-                *reinterpret_cast<double2*>(Ck + (size_t)gm * p + gc) = v;
-                if (C2k) {
-                    double2 e = {0.0, 0.0};
-                    if (Ek && dE != 0.0) e = *reinterpret_cast<const double2*>(Ek + (size_t)gm * p + gc);
-                    double2 w2;
-                    w2.x = c2val(dC, v.x, dE, e.x);
-                    w2.y = c2val(dC, v.y, dE, e.y);
-                    *reinterpret_cast<double2*>(C2k + (size_t)gm * p + gc) = w2;
-                }
-            }
-        }
-    }
-    if (rowpart && tid < 2 * BM) {
-        // threads 0..31: row t of the tile; threads 32..63 (off-diagonal tiles): column t, i.e. row J0 + t of the mirror.
-        // A diagonal tile is complete (both triangles) here.
-        const int t = tid & (BM - 1);
-        const bool second = tid >= BM;
-        double rs = 0.0, sq = 0.0;
-        if (!second) {
-#pragma unroll 8
-            for (int c = 0; c < BM; ++c) { const double x = smem[t * BM + ((c + t) & (BM - 1))]; rs += fabs(x); sq += x * x; }
-        } else if (I != J) {
-#pragma unroll 8
-            for (int r = 0; r < BM; ++r) rs += fabs(smem[((r + t) & (BM - 1)) * BM + t]);
-        }
-        if (I != J) sq *= 2.0;                          // the mirror has the same squares
-        if (I != J || !second) {
-            const int slot = second ? I : J, gr = (second ? J0 : I0) + t;
-            if (gr < p) rowpart[((size_t)k * T + slot) * (size_t)p + gr] = rs;
-        }
-        sq = wave_sum(second ? 0.0 : sq);               // tid < 64: wave 0
-        if (tid == 0) fropart[(size_t)k * (T * (T + 1) / 2) + blockTile] = sq;
-    }
-}
-
-#endif   // GGL_DEV (k_symm_sk)
 
 #ifdef GGL_DEV
 // which epilogue the direct-to-LDS launches of the development library run (ggl_dev_set_symm_epilogue): 0 the product's --
@@ -1710,264 +1350,6 @@ int symm_set_epilogue(int mode)
     const int was = g_symm_epilogue;
     g_symm_epilogue = (mode == 1 || mode == 2) ? mode : 0;
     return was;
-}
-#endif
-
-#ifdef GGL_DEV      // (round 6: the persistent chain is an option of the development library only -- measured slower)
-// ---------------------------------------------------------------------------------------------
-// k_omega_chain: the WHOLE product chain of an Omega-step (A', B', the Newton-Schulz products, Omega) of a batch in ONE
-// persistent launch, with the dependencies kept where they are: per INSTANCE.  Product s+1 of instance k needs product s of
-// instance k and nothing else, yet a launch boundary makes every instance wait for the slowest tile of all of them, 7 times
-// per iteration (a K = 32, p = 500 launch keeps the matrix pipes ~52 % busy, two concurrent half-batch launch sequences
-// ~57 %).  Here the workgroups are persistent (as many as are resident: 3 per CU with 48 KiB of LDS), each serves the
-// instances of the XCD it REALLY runs on (HW_REG_XCC_ID; instance k lives on XCD k % 8, so its operands stay in one L2 and
-// every hand-off is XCD-local), and pulls tiles through two counters per instance:
-//     next[k]  tickets handed out (ticket t = product s, tile t - begin[s])      done[k]  tiles completed
-// A ticket of product s is handed out only when done[k] >= begin[s], i.e. all tiles of the products before it are complete.
-// While one instance drains the last tiles of a product, the workgroups run the other instances of the XCD: fixed priority
-// by instance index, so the instances drift apart instead of marching in lockstep.
-// Visibility (MI355X_MICROARCH.md, inter-workgroup visibility): producer = plain stores (they stay in the XCD's L2) ->
-// every wave s_waitcnt vmcnt(0) -> barrier -> one relaxed agent-scope fetch_add on done[k]; consumer = relaxed agent-scope
-// (sc1) load of done[k] -> every global READ of the tile with sc1 (L2-served, never this CU's L1).  No L2 write-back and no
-// L1 invalidate anywhere: producer and consumer share one L2 by construction (a workgroup only serves its own XCD's list).
-// Should the hardware ever place no workgroup on an XCD, that XCD's instances stay unfinished: k_chain_check raises the
-// step's validation flag and the host repeats the step on the launch-per-product path (correct either way).
-// ---------------------------------------------------------------------------------------------
-// state of instance k: one 128-byte line of CHAIN_CNT_STRIDE words -- [0] tiles completed (all products), [1 + s] tickets
-// handed out of product s.  A claim is ONE fetch_add on the ticket word of the product the workgroup last saw ready for
-// that instance (a ticket beyond the product's tiles is void: nothing is lost, nobody waits); only when a product is
-// exhausted does the workgroup read the completion word to see whether the next one may start.
-template <int BK, int NSTG, int BM, int AUX, int SER = 0>
-__global__ __launch_bounds__(256) void k_omega_chain(const ChainProg P, unsigned* __restrict__ state)
-{
-    __shared__ __attribute__((aligned(16))) double smem[NSTG * 2 * BK * BM];
-    __shared__ int sh_job[3];
-    __shared__ unsigned char sh_step[CHAIN_MAX_INST];         // per instance of this XCD: the product last seen ready
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    const int x = (int)(xcc & 0xfu) % NXCD;
-    const int ninst = min((P.K - x + NXCD - 1) / NXCD, CHAIN_MAX_INST);   // instances x, x + 8, ...
-    const int rot = ninst > 0 ? (int)(blockIdx.x / NXCD) % ninst : 0;     // claims start at different instances
-    unsigned backoff = 4;
-    if (threadIdx.x < CHAIN_MAX_INST) sh_step[threadIdx.x] = 0;           // product 0 has no predecessor: ready
-#ifdef GGL_DEV
-    long long t_claim = 0, t_idle = 0, t_tile = 0, n_tile = 0, t_prev = wall_clock64(), t_first = t_prev;
-    const long long c_first = clock64();
-#endif
-    __syncthreads();
-    for (;;) {
-        if (threadIdx.x == 0) {
-            int jk = -2, js = 0, jb = 0;                      // -2: every product of every instance of this XCD is handed out
-            for (int ii = 0; ii < ninst && jk < 0; ++ii) {
-                const int i = (ii + rot) % ninst;
-                const int k = x + NXCD * i;
-                unsigned* w = state + (size_t)k * CHAIN_CNT_STRIDE;
-                int s = sh_step[i];
-                while (s < P.nops) {
-                    // L2-scope read-modify-write (no sc1): every workgroup that touches this line runs on THIS XCD (it
-                    // serves the XCD it really sits on), so the XCD's L2 is the one place the line lives and its atomic
-                    // unit the one place it changes -- a device-scope (memory-side) atomic cost ~26 us per claim under 96
-                    // claimers per XCD
-                    const unsigned nt = (unsigned)(P.begin[s + 1] - P.begin[s]);
-                    const unsigned t = __hip_atomic_fetch_add(w + 1 + s, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if (t < nt) { jk = k; js = s; jb = (int)t; break; }
-                    // product s is handed out completely: may s + 1 start?  (sc1 load: served by the XCD's L2, never by this
-                    // CU's L1 -- a workgroup-scope load would be an L1-hitting sc0 load)
-                    const unsigned d = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (d < (unsigned)P.begin[s + 1]) { jk = max(jk, -1); break; }      // not yet: something is left, later
-                    ++s;
-                }
-                sh_step[i] = (unsigned char)s;
-            }
-            sh_job[0] = jk; sh_job[1] = js; sh_job[2] = jb;
-        }
-        __syncthreads();
-        const int jk = __builtin_amdgcn_readfirstlane(sh_job[0]);
-        const int js = __builtin_amdgcn_readfirstlane(sh_job[1]);
-        int jb = __builtin_amdgcn_readfirstlane(sh_job[2]);
-        __syncthreads();                                      // everyone has read the slot before it is rewritten
-#ifdef GGL_DEV
-        if (jk == -2 && P.prof && threadIdx.x == 0) {
-            long long* o = P.prof + (size_t)blockIdx.x * 8;
-            o[0] = t_claim; o[1] = t_idle; o[2] = t_tile; o[3] = n_tile; o[4] = t_first; o[5] = wall_clock64(); o[6] = x; o[7] = clock64() - c_first;
-        }
-#endif
-        if (jk == -2) return;
-        if (jk == -1) {
-            // nothing ready on this XCD: back off (0.2 .. 3 us) so that idle workgroups do not crowd the lines the working
-            // ones need
-            for (unsigned q = 0; q < backoff; ++q) __builtin_amdgcn_s_sleep(8);
-            backoff = min(backoff * 2u, 64u);
-#ifdef GGL_DEV
-            { const long long t = wall_clock64(); t_idle += t - t_prev; t_prev = t; }
-#endif
-            continue;
-        }
-        backoff = 4;
-#ifdef GGL_DEV
-        { const long long t = wall_clock64(); t_claim += t - t_prev; t_prev = t; }
-#endif
-        const SymmOp& o = P.op[js];
-        int kk = jk;
-        if (o.pair && jb >= P.ntiles) { kk = P.K + jk; jb -= P.ntiles; }
-        // (the batched epilogue here is the staged one: with the register path beside it the kernel needs 173 VGPRs, 168 keep
-        // three workgroups per CU)
-        symm_dl_tile<BK, NSTG, 0, BM, 4, AUX, SER == 0 ? 2 : SER, 32>(o.A, o.B, o.C, o.C2, o.E, o.E2, o.coef, P.K, P.p, o.A1, o.B1, o.C1, o.pair ? P.K : 0,
-                                               nullptr, o.rowpart, o.fropart, kk, jb, smem);
-        // this tile's stores are in the XCD's L2 before the arrival is counted; the barrier also frees the LDS image
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0)
-            __hip_atomic_fetch_add(state + (size_t)jk * CHAIN_CNT_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifdef GGL_DEV
-        { const long long t = wall_clock64(); t_tile += t - t_prev; t_prev = t; n_tile += 1; }
-#endif
-    }
-}
-
-// flag[0] / flag_h[0] = 1 unless every instance completed all of its tiles
-__global__ __launch_bounds__(64) void k_chain_check(const unsigned* __restrict__ state, int K, unsigned total,
-                                                    int* __restrict__ flag, int* __restrict__ flag_h)
-{
-    bool bad = false;
-    for (int k = threadIdx.x; k < K; k += 64) bad = bad || (state[(size_t)k * CHAIN_CNT_STRIDE] != total);
-    if (__any(bad) && threadIdx.x == 0) { *flag = 1; *flag_h = 1; }
-}
-
-int chain_tile(int K, int p, bool force)
-{
-    // the chain kernel is built on the 64x64 three-stage DMA tile; it needs 16-byte rows (even p), a batch that covers the
-    // XCDs (instance k lives on XCD k % 8) and enough tiles per XCD to keep its 96 workgroup slots busy across the
-    // instances' seams
-    if ((p & 1) != 0 || K < NXCD || K > NXCD * CHAIN_MAX_INST) return 0;
-    const long T = (p + 63) / 64;
-    return (force || T * (T + 1) / 2 * K >= 1100) ? 64 : 0;
-}
-
-int launch_omega_chain(hipStream_t st, const ChainProg& P, unsigned* state, int* flag, int* flag_h, int aux)
-{
-    static int slots = 0;
-    if (!slots) {
-        int dev = 0, per_cu = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_omega_chain<16, 3, 64, 16>, 256, 0) != hipSuccess || per_cu < 1)
-            return -1;
-        slots = std::min(per_cu, 3) * prop.multiProcessorCount;
-        slots -= slots % NXCD;
-    }
-    if (aux == 0) hipLaunchKernelGGL((k_omega_chain<16, 3, 64, 0>), dim3(slots), dim3(256), 0, st, P, state);   // measurement only
-    else if (g_symm_epilogue == 1) hipLaunchKernelGGL((k_omega_chain<16, 3, 64, 16, 1>), dim3(slots), dim3(256), 0, st, P, state);
-    else
-    hipLaunchKernelGGL((k_omega_chain<16, 3, 64, 16>), dim3(slots), dim3(256), 0, st, P, state);
-    hipLaunchKernelGGL(k_chain_check, dim3(1), dim3(64), 0, st, state, P.K, (unsigned)P.begin[P.nops], flag, flag_h);
-    return slots;
-}
-
-// ---- persistent-chain probe: nprod DEPENDENT products X <- X * X of a K-batch inside ONE cooperative
-// launch, a grid-wide barrier between products, against the same chain as nprod launches.  What it prices is exactly the
-// trade a persistent Omega-chain kernel would make: a kernel boundary (drain, launch, L2 write-back/invalidate by the
-// command processor) against agent-scope release -> counter -> acquire by the workgroups themselves.
-__device__ __forceinline__ void grid_barrier(unsigned* counter, unsigned target, unsigned* err)
-{
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");          // this XCD's dirty L2 lines out to memory
-        __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        long spins = 0;
-        while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > (1L << 22)) {                              // ~0.3 s: a lost workgroup must not hang the GPU
-                __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");          // this CU's L1 (and stale L2 lines) dropped
-    }
-    __syncthreads();
-}
-
-// two-level form: the workgroups of an XCD count themselves in on a per-XCD counter (their stores are in that XCD's L2 once
-// the __syncthreads() has drained them); the LAST one writes the L2 back -- one buffer_wbl2 per XCD and barrier instead of one
-// per workgroup -- and arrives at the global counter for the XCD.  bar: [0] global, [1] error, [8..15] per-XCD counters.
-__device__ __forceinline__ void grid_barrier_xcd(unsigned* bar, unsigned phase, unsigned per_xcd, unsigned xcd)
-{
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned old = __hip_atomic_fetch_add(bar + 8 + xcd, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old + 1 == phase * per_xcd) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        long spins = 0;
-        while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < phase * NXCD) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > (1L << 22)) {
-                __hip_atomic_store(bar + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    __syncthreads();
-}
-
-template <int BK, int NSTG, int BM>
-__global__ __launch_bounds__(256) void k_symm_chain_probe(double* X0, double* X1, const double* coef, int K, int p,
-                                                          int nprod, unsigned* bar, unsigned* err, int two_level)
-{
-    __shared__ __attribute__((aligned(16))) double smem[NSTG * 2 * BK * BM];
-    const int T = (p + BM - 1) / BM, ntiles = T * (T + 1) / 2;
-    const int total = xcd_grid(ntiles, K);
-    unsigned xcd = blockIdx.x % NXCD;
-    if (two_level) {
-        // the per-XCD counters need the XCD a workgroup REALLY runs on; the round-robin placement is observed, not promised
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        if ((xcc & 0xf) != xcd && threadIdx.x == 0)
-            __hip_atomic_store(err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    for (int j = 0; j < nprod; ++j) {
-        const double* src = (j & 1) ? X1 : X0;
-        double* dst = (j & 1) ? X0 : X1;
-        for (int L = blockIdx.x; L < total; L += gridDim.x) {       // gridDim.x is a multiple of 8: L % 8 = this XCD
-            int k, b;
-            if (decode_block_xcd(ntiles, K, k, b, L))
-                symm_dl_tile<BK, NSTG, 0, BM, 4, 0, 0, 32>(src, src, dst, nullptr, nullptr, nullptr, coef, K, p, nullptr, nullptr, nullptr, 0,
-                                                 nullptr, nullptr, nullptr, k, b, smem);
-            __syncthreads();                                         // the slab storage is reused by the next tile
-        }
-        if (j + 1 < nprod) {
-            if (two_level) grid_barrier_xcd(bar, (unsigned)(j + 1), gridDim.x / NXCD, xcd);
-            else grid_barrier(bar, (unsigned)(j + 1) * gridDim.x, err);
-        }
-    }
-}
-
-// returns the grid used (0: the variant has no probe instance, < 0: HIP error)
-int launch_chain_probe(hipStream_t st, double* X0, double* X1, const double* coef, int K, int p, int nprod, int variant,
-                       unsigned* bar, unsigned* err, int two_level)
-{
-    const void* fn = nullptr;
-    int BM = 64;
-    if (variant == 16) fn = (const void*)k_symm_chain_probe<16, 2, 64>;
-    else if (variant == 17) fn = (const void*)k_symm_chain_probe<16, 3, 64>;
-    else if (variant == 20) { fn = (const void*)k_symm_chain_probe<32, 2, 32>; BM = 32; }
-    else return 0;
-    int per_cu = 0, dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0) != hipSuccess || per_cu < 1) return -1;
-    const int T = (p + BM - 1) / BM;
-    const int total = xcd_grid(T * (T + 1) / 2, K);
-    if (per_cu > 4) per_cu = 4;     // the occupancy query promised 5 (32 KiB of LDS) but 1088 / 1152 workgroups were not co-resident
-    int grid = per_cu * prop.multiProcessorCount;
-    if (grid > total) grid = total;
-    grid -= grid % NXCD;
-    if (grid < NXCD) return -1;
-    void* args[] = {&X0, &X1, &coef, &K, &p, &nprod, &bar, &err, &two_level};
-    if (hipLaunchCooperativeKernel(fn, dim3(grid), dim3(256), args, 0, st) != hipSuccess) return -1;
-    return grid;
 }
 #endif
 
@@ -1991,103 +1373,6 @@ void symm_flush_rider(hipStream_t st)
     if (g_rider.K <= 0) return;
     hipLaunchKernelGGL(k_cw_rider, dim3(g_rider.K * g_rider.nbx), dim3(256), 0, st, g_rider);
     g_rider = CwRider{};
-}
-
-static void launch_dl(hipStream_t st, const double* A, const double* B, double* C, double* C2, const double* E,
-                      const double* coef, int K, int p, const double* A1, const double* B1, double* C1, int K1,
-                      double* maxdev, int dl_cfg = 0, double* rowpart = nullptr, double* fropart = nullptr,
-                      const double* E2 = nullptr)
-{
-    // (the eight-wave development variants do not carry riders: the rider stays pending)
-    const bool eight = dl_cfg == 6 || dl_cfg == 7;
-    const CwRider rider = (g_rider.K > 0 && !eight) ? g_rider : CwRider{};
-    if (rider.K > 0) g_rider = CwRider{};
-    const CopySegs cps = (g_copy_rider.n > 0 && !eight) ? g_copy_rider : CopySegs{};
-    if (cps.n > 0) g_copy_rider = CopySegs{};
-    const RedRider red = (g_red_rider.nblk > 0 && !eight) ? g_red_rider : RedRider{};
-    if (red.nblk > 0) g_red_rider = RedRider{};
-    int ncopy = red.nblk > 0 ? NXCD : 0;          // (in front of the tiles, see k_symm_dl)
-    for (int i = 0; i < cps.n; ++i) ncopy += (int)((cps.words[i] + 1023u) / 1024u);
-    const int nride = rider.K * rider.nbx + ncopy;
-#define GGL_DL_ARGS A, B, C, C2, E, E2, coef, K, p, A1, B1, C1, K1, maxdev, rowpart, fropart, rider, cps, red
-#ifdef GGL_DEV
-    // GGL_DL(BK, NSTG, ABL, BM): the instance with the epilogue the switch names
-#define GGL_DL4(BK_, NSTG_, ABL_, BM_)                                                                                        \
-    do {                                                                                                                       \
-        if (g_symm_epilogue == 1) hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, ABL_, BM_, 4, 1>), grid, dim3(256), 0, st, GGL_DL_ARGS); \
-        else if (g_symm_epilogue == 2) hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, ABL_, BM_, 4, 2>), grid, dim3(256), 0, st, GGL_DL_ARGS); \
-        else hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, ABL_, BM_, 4, 0>), grid, dim3(256), 0, st, GGL_DL_ARGS);               \
-    } while (0)
-#else
-#define GGL_DL4(BK_, NSTG_, ABL_, BM_) hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, ABL_, BM_>), grid, dim3(256), 0, st, GGL_DL_ARGS)
-#endif
-#define GGL_DL3(BK_, NSTG_, ABL_) GGL_DL4(BK_, NSTG_, ABL_, 64)
-#define GGL_DL2(BK_, NSTG_) GGL_DL4(BK_, NSTG_, 0, 64)
-#define GGL_DL_PICK(a1, a2, a3, a4, NAME, ...) NAME
-#define GGL_DL(...) GGL_DL_PICK(__VA_ARGS__, GGL_DL4, GGL_DL3, GGL_DL2, )(__VA_ARGS__)
-    if (dl_cfg == 4 || (dl_cfg >= 8 && dl_cfg <= 13) || (dl_cfg >= 18 && dl_cfg <= 21)) {
-        const int T32 = (p + 31) / 32;
-        const dim3 grid(xcd_grid(T32 * (T32 + 1) / 2, K + K1) + nride);
-        // 32x32 tiles, k-slab 32, double buffer: 32 KiB of LDS, five workgroups per CU.  Measured (MI355X, p = 500, us per
-        // launch at K = 2 / 4 / 8 / 16): 15.9 / 21.8 / 35.0 / 58.6, against 16.3 / 26.4 / 40.2 / 70.3 with four slabs in
-        // flight (64 KiB, two workgroups per CU: residency, not prefetch depth, is what the small batches lack)
-        if (dl_cfg == 4) GGL_DL(32, 2, 0, 32);
-#ifdef GGL_DEV
-        // other slab / prefetch depths of the 32x32 kernel (LDS per workgroup: 32 / 48 / 48 / 64 / 16 / 24 KiB)
-        else if (dl_cfg == 8) GGL_DL(16, 4, 0, 32);
-        else if (dl_cfg == 9) GGL_DL(32, 3, 0, 32);
-        else if (dl_cfg == 10) GGL_DL(16, 6, 0, 32);
-        else if (dl_cfg == 11) GGL_DL(32, 4, 0, 32);
-        else if (dl_cfg == 12) GGL_DL(16, 2, 0, 32);
-        else if (dl_cfg == 13) GGL_DL(16, 3, 0, 32);
-        // the same four timing ablations of the 32x32 kernel
-        else if (dl_cfg == 18) GGL_DL(32, 2, 2, 32);
-        else if (dl_cfg == 19) GGL_DL(32, 2, 3, 32);
-        else if (dl_cfg == 20) GGL_DL(32, 2, 4, 32);
-        else if (dl_cfg == 21) GGL_DL(32, 2, 5, 32);
-#endif
-        return;
-    }
-    const int T = (p + 63) / 64;
-    const dim3 grid(xcd_grid(T * (T + 1) / 2, K + K1) + nride);
-#ifdef GGL_DEV
-    if (dl_cfg == 6 || dl_cfg == 7) {
-        // eight waves per workgroup (two per SIMD) for batches that leave one workgroup per CU.  Measured (MI355X, p = 500):
-        // K = 4: 27.0 / 26.3 us vs 26.6 us for the 32x32 kernel; K = 8: 43.9 / 49.3 vs 40.4; K = 16: 68.6 / 74.9 vs 63.9 --
-        // no gain anywhere, so the shipped library does not carry them
-#define GGL_DL8(BK_, NSTG_)                                                                                                   \
-    do {                                                                                                                       \
-        if (g_symm_epilogue == 1) hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, 0, 64, 8, 1>), grid, dim3(512), 0, st, GGL_DL_ARGS); \
-        else if (g_symm_epilogue == 2) hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, 0, 64, 8, 2>), grid, dim3(512), 0, st, GGL_DL_ARGS); \
-        else hipLaunchKernelGGL((k_symm_dl<BK_, NSTG_, 0, 64, 8, 0>), grid, dim3(512), 0, st, GGL_DL_ARGS);                   \
-    } while (0)
-        if (dl_cfg == 6) GGL_DL8(16, 4);
-        else GGL_DL8(32, 3);
-#undef GGL_DL8
-        return;
-    }
-#endif
-    if (dl_cfg == 1) GGL_DL(16, 3);
-#ifdef GGL_DEV
-    else if (dl_cfg == 2) GGL_DL(16, 4);
-    else if (dl_cfg == 3) GGL_DL(32, 2);
-    else if (dl_cfg == 5) GGL_DL(16, 2, 1);      // no mirror write: timing ablation, wrong results
-    // timing ablations of the three-stage 64x64 kernel (wrong results): no operand loads / no MFMA / no epilogue / no barrier
-    else if (dl_cfg == 14) GGL_DL(16, 3, 2);
-    else if (dl_cfg == 15) GGL_DL(16, 3, 3);
-    else if (dl_cfg == 16) GGL_DL(16, 3, 4);
-    else if (dl_cfg == 17) GGL_DL(16, 3, 5);
-    // shallower slabs, more of them in flight: 32 KiB (4 x 8 KiB) / 48 KiB (6 x 8 KiB) of LDS
-    else if (dl_cfg == 22) GGL_DL(8, 4);
-    else if (dl_cfg == 23) GGL_DL(8, 6);
-#endif
-    else GGL_DL(16, 2);
-#undef GGL_DL
-#undef GGL_DL_PICK
-#undef GGL_DL2
-#undef GGL_DL3
-#undef GGL_DL4
-#undef GGL_DL_ARGS
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2197,199 +1482,125 @@ void launch_gemm_right(hipStream_t st, const double* A, const double* T, double*
     }
 }
 
-#ifdef GGL_DEV
-// FP64 matrix-core ceiling probe: every wave issues `iters` x NACC MFMAs on NACC independent accumulators.
-template <int NACC>
-__global__ __launch_bounds__(256) void k_mfma_f64_peak(double* __restrict__ out, int iters)
-{
-    v4d acc[NACC];
-#pragma unroll
-    for (int i = 0; i < NACC; ++i) acc[i] = (v4d){0.0, 0.0, 0.0, 0.0};
-    double a = 1.0 + threadIdx.x * 1e-9, b = 1.0 - threadIdx.x * 1e-9;
-    for (int it = 0; it < iters; ++it) {
-#pragma unroll
-        for (int i = 0; i < NACC; ++i) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[i], 0, 0, 0);
-    }
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < NACC; ++i) s += acc[i][0] + acc[i][1] + acc[i][2] + acc[i][3];
-    out[(size_t)blockIdx.x * 256 + threadIdx.x] = s;
-}
-
-// same probe with NV dependent 64-bit integer VALU ops (address arithmetic stand-ins) per MFMA
-template <int NV>
-__global__ __launch_bounds__(256) void k_mfma_valu_mix(double* __restrict__ out, int iters, unsigned long long seed)
-{
-    v4d acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i] = (v4d){0.0, 0.0, 0.0, 0.0};
-    double a = 1.0 + threadIdx.x * 1e-9, b = 1.0 - threadIdx.x * 1e-9;
-    unsigned long long x = seed + threadIdx.x;
-    double d = a;
-    for (int it = 0; it < iters; ++it) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[i], 0, 0, 0);
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                if (v & 1) x = (x << 3) + seed;           // v_lshl_add_u64
-                else d = (x & 1) ? d : b;                 // v_cndmask pair
-            }
-        }
-    }
-    double s = d + (double)x;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) s += acc[i][0] + acc[i][1] + acc[i][2] + acc[i][3];
-    out[(size_t)blockIdx.x * 256 + threadIdx.x] = s;
-}
-
-template <int NV>
-static double mix_probe(hipStream_t st, double* scratch, int blocks, int iters)
-{
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    hipLaunchKernelGGL(k_mfma_valu_mix<NV>, dim3(blocks), dim3(256), 0, st, scratch, 16, 12345ull);
-    (void)hipEventRecord(e0, st);
-    hipLaunchKernelGGL(k_mfma_valu_mix<NV>, dim3(blocks), dim3(256), 0, st, scratch, iters, 12345ull);
-    (void)hipEventRecord(e1, st);
-    (void)hipEventSynchronize(e1);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return (double)blocks * 4.0 * iters * 4 * 2.0 * 16 * 16 * 4 / (ms * 1e-3) / 1e12;
-}
-
-double mfma_valu_mix_tflops(hipStream_t st, double* scratch, int blocks, int iters, int nv)
-{
-    switch (nv) {
-        case 0: return mix_probe<0>(st, scratch, blocks, iters);
-        case 2: return mix_probe<2>(st, scratch, blocks, iters);
-        case 4: return mix_probe<4>(st, scratch, blocks, iters);
-        case 8: return mix_probe<8>(st, scratch, blocks, iters);
-        default: return mix_probe<16>(st, scratch, blocks, iters);
-    }
-}
-
-template <int NACC>
-static double mfma_probe(hipStream_t st, double* scratch, int blocks, int iters)
-{
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    hipLaunchKernelGGL(k_mfma_f64_peak<NACC>, dim3(blocks), dim3(256), 0, st, scratch, 16);
-    (void)hipEventRecord(e0, st);
-    hipLaunchKernelGGL(k_mfma_f64_peak<NACC>, dim3(blocks), dim3(256), 0, st, scratch, iters);
-    (void)hipEventRecord(e1, st);
-    (void)hipEventSynchronize(e1);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    const double flops = (double)blocks * 4.0 * iters * NACC * 2.0 * 16 * 16 * 4;
-    return flops / (ms * 1e-3) / 1e12;
-}
-
-// nacc in {1,2,4,8}; blocks = workgroups of 4 waves (256 per "one wave per SIMD" layer)
-double mfma_f64_peak_tflops(hipStream_t st, double* scratch, int blocks, int iters, int nacc)
-{
-    switch (nacc) {
-        case 1: return mfma_probe<1>(st, scratch, blocks, iters);
-        case 2: return mfma_probe<2>(st, scratch, blocks, iters);
-        case 4: return mfma_probe<4>(st, scratch, blocks, iters);
-        default: return mfma_probe<8>(st, scratch, blocks, iters);
-    }
-}
-#endif   // GGL_DEV
-
 static constexpr int SMALL_DL_MIN_P = 16;         // (round 4: measured ahead of the register-staged 32x32 kernel at every even p from 16 up, tools/bench_symm_small.py)
 static constexpr long SMALL_BATCH_TILES = 800;   // up to here the 32x32-tile kernel, above the 64x64 direct-to-LDS one
 
-// Product-kernel variants.  The shipped library holds the instances the solvers dispatch to:
-//    0  k_symm_tn 64x64 tile, k-slab 16 (register-staged; odd p, where the DMA kernel's 16-byte rows do not exist)
-//    9  k_symm_tn 32x32 tile, k-slab 32 (register-staged; small batches of odd p)
-//   16  k_symm_dl 64x64, double-buffered DMA      17  k_symm_dl 64x64, three DMA stages (concurrent parts)
-//   20  k_symm_dl 32x32, k-slab 32, double-buffered DMA (small batches)
-// A GGL_DEV build (libggl_hip_dev.so) adds the measured alternatives 1-5, 8, 11-13, 18, 19, 22 / 23 (64x64 with EIGHT
-// waves per workgroup), 24-29 (other slab / prefetch depths of the 32x32 kernel, see launch_dl) and the ablations 6, 7, 10,
-// 14, 15, 21 (tools/bench_*.py).
-// 41-45: k_symm_sk, the split-K kernel of the under-filled batches: <BK, stages> = <8,3> <8,4> <16,2> <8,2> <4,4>
-// (48 / 64 / 64 / 32 / 32 KiB of LDS per workgroup); 46-50: the same with the k-range of a tile dealt over 2 / 4 workgroups.  40 is not a launch variant: ggl_ns_stats reports it for k_omega_chain.
-int symm_variants() { return 50; }
-bool symm_variant_built(int v)
+// ---------------------------------------------------------------------------------------------
+// Product-kernel variants: ONE table.  What a variant number means -- kernel family, tile edge, template instance, ablation
+// or not, in the product library or in the development library (GGL_DEV, libggl_hip_dev.so) only -- is written here and
+// nowhere else: symm_variant_built, symm_effective_variant, symm_bounds_tile and the launches all read this table.
+//   TN  k_symm_tn, register-staged: <BM, BK, WM, WN, LM, ABL>         DL  k_symm_dl, direct-to-LDS: <BK, NSTG, ABL, BM, NW>
+// The tile edge of a row is its BM.  ABL != 0: a timing ablation (wrong results on purpose; tools/bench_tail.py and others).
+// A DL row at a dimension the DMA kernel does not take (symm_dl_serves) runs the product's TN row of the same tile edge.
+// (40 and 41 are not product-kernel variants: ggl_ns_stats reports 41 for the LDS Omega kernel, capi_omega.hip.)
+// ---------------------------------------------------------------------------------------------
+enum class Fam { TN, DL };
+struct Variant {
+    Fam fam;
+    bool product;               // the product library carries it (the solvers dispatch to it)
+    int bm, bk, abl;
+    int wm, wn;                 // TN: wave tile
+    bool lm;                    // TN: off-diagonal tiles mirrored through LDS
+    int nstg, nw;               // DL: slabs resident in LDS, waves per workgroup
+    const char* what;
+};
+constexpr bool PRODUCT = true, DEV = false;
+constexpr Variant tn(bool product, int bm, int bk, int wm, int wn, bool lm, int abl, const char* what)
+{
+    return Variant{Fam::TN, product, bm, bk, abl, wm, wn, lm, 0, 0, what};
+}
+constexpr Variant dl(bool product, int bk, int nstg, int abl, int bm, int nw, const char* what)
+{
+    return Variant{Fam::DL, product, bm, bk, abl, 0, 0, false, nstg, nw, what};
+}
+constexpr Variant VARIANTS[] = {
+    /*  0 */ tn(PRODUCT, 64, 16, 32, 32, true, 0, "64x64, k-slab 16: large batches at a p the DMA kernel does not take"),
+    /*  1 */ tn(DEV, 64, 32, 32, 32, true, 0, "64x64, k-slab 32"),
+    /*  2 */ tn(DEV, 128, 16, 64, 64, false, 0, "128x128, 64x64 wave tiles, direct mirror stores"),
+    /*  3 */ tn(DEV, 128, 16, 32, 64, false, 0, "128x128, 32x64 wave tiles, direct mirror stores"),
+    /*  4 */ tn(DEV, 64, 16, 32, 32, false, 0, "64x64, direct mirror stores"),
+    /*  5 */ tn(DEV, 128, 32, 64, 64, false, 0, "128x128, k-slab 32, direct mirror stores"),
+    /*  6 */ tn(DEV, 64, 16, 32, 32, true, 1, "ablation of 0: no global loads"),
+    /*  7 */ tn(DEV, 64, 16, 32, 32, true, 2, "ablation of 0: no MFMA"),
+    /*  8 */ tn(DEV, 32, 16, 16, 16, true, 0, "32x32, k-slab 16"),
+    /*  9 */ tn(PRODUCT, 32, 32, 16, 16, true, 0, "32x32, k-slab 32: small batches at a p the DMA kernel does not take"),
+    /* 10 */ tn(DEV, 64, 16, 32, 32, true, 3, "timeline probe of 0 (maxdev is a [grid][5] long long buffer)"),
+    /* 11 */ tn(DEV, 64, 16, 16, 32, true, 0, "64x64, 16x32 wave tiles"),
+    /* 12 */ tn(DEV, 64, 32, 16, 32, true, 0, "64x64, k-slab 32, 16x32 wave tiles"),
+    /* 13 */ tn(DEV, 64, 16, 32, 16, true, 0, "64x64, 32x16 wave tiles"),
+    /* 14 */ tn(DEV, 64, 16, 32, 32, true, 4, "ablation of 0: ds_read + MFMA only"),
+    /* 15 */ tn(DEV, 64, 16, 32, 32, true, 5, "ablation of 0: ds_read + MFMA + ds_write"),
+    /* 16 */ dl(PRODUCT, 16, 2, 0, 64, 4, "64x64, double-buffered DMA: large batches"),
+    /* 17 */ dl(PRODUCT, 16, 3, 0, 64, 4, "64x64, three DMA stages: concurrent parts"),
+    /* 18 */ dl(DEV, 16, 4, 0, 64, 4, "64x64, four DMA stages"),
+    /* 19 */ dl(DEV, 32, 2, 0, 64, 4, "64x64, k-slab 32"),
+    // 32x32 tiles, k-slab 32, double buffer: 32 KiB of LDS, five workgroups per CU.  Measured (MI355X, p = 500, us per launch
+    // at K = 2 / 4 / 8 / 16): 15.9 / 21.8 / 35.0 / 58.6, against 16.3 / 26.4 / 40.2 / 70.3 with four slabs in flight (27: 64 KiB,
+    // two workgroups per CU: residency, not prefetch depth, is what the small batches lack)
+    /* 20 */ dl(PRODUCT, 32, 2, 0, 32, 4, "32x32, k-slab 32, double-buffered DMA: small batches"),
+    /* 21 */ dl(DEV, 16, 2, 1, 64, 4, "ablation of 16: no mirror write (and no bound partials)"),
+    // eight waves per workgroup (two per SIMD) for batches that leave one workgroup per CU.  Measured (MI355X, p = 500):
+    // K = 4: 27.0 / 26.3 us vs 26.6 us for the 32x32 kernel; K = 8: 43.9 / 49.3 vs 40.4; K = 16: 68.6 / 74.9 vs 63.9 -- no gain
+    // anywhere, so the product library does not carry them
+    /* 22 */ dl(DEV, 16, 4, 0, 64, 8, "64x64, eight waves, four DMA stages"),
+    /* 23 */ dl(DEV, 32, 3, 0, 64, 8, "64x64, eight waves, k-slab 32, three DMA stages"),
+    // other slab / prefetch depths of the 32x32 kernel (LDS per workgroup: 32 / 48 / 48 / 64 / 16 / 24 KiB)
+    /* 24 */ dl(DEV, 16, 4, 0, 32, 4, "32x32, k-slab 16, four DMA stages"),
+    /* 25 */ dl(DEV, 32, 3, 0, 32, 4, "32x32, k-slab 32, three DMA stages"),
+    /* 26 */ dl(DEV, 16, 6, 0, 32, 4, "32x32, k-slab 16, six DMA stages"),
+    /* 27 */ dl(DEV, 32, 4, 0, 32, 4, "32x32, k-slab 32, four DMA stages"),
+    /* 28 */ dl(DEV, 16, 2, 0, 32, 4, "32x32, k-slab 16, double-buffered DMA"),
+    /* 29 */ dl(DEV, 16, 3, 0, 32, 4, "32x32, k-slab 16, three DMA stages"),
+    /* 30 */ dl(DEV, 16, 3, 2, 64, 4, "ablation of 17: no operand loads"),
+    /* 31 */ dl(DEV, 16, 3, 3, 64, 4, "ablation of 17: no MFMA"),
+    /* 32 */ dl(DEV, 16, 3, 4, 64, 4, "ablation of 17: no epilogue"),
+    /* 33 */ dl(DEV, 16, 3, 5, 64, 4, "ablation of 17: no slab barrier"),
+    /* 34 */ dl(DEV, 32, 2, 2, 32, 4, "ablation of 20: no operand loads"),
+    /* 35 */ dl(DEV, 32, 2, 3, 32, 4, "ablation of 20: no MFMA"),
+    /* 36 */ dl(DEV, 32, 2, 4, 32, 4, "ablation of 20: no epilogue"),
+    /* 37 */ dl(DEV, 32, 2, 5, 32, 4, "ablation of 20: no slab barrier"),
+    // shallower slabs, more of them in flight: 32 KiB (4 x 8 KiB) / 48 KiB (6 x 8 KiB) of LDS
+    /* 38 */ dl(DEV, 8, 4, 0, 64, 4, "64x64, k-slab 8, four DMA stages"),
+    /* 39 */ dl(DEV, 8, 6, 0, 64, 4, "64x64, k-slab 8, six DMA stages"),
+};
+constexpr int NVARIANT = (int)(sizeof(VARIANTS) / sizeof(VARIANTS[0]));
+
+constexpr bool variant_in_build(int v)
 {
 #ifdef GGL_DEV
-    return v >= 0 && v <= 50 && v != 40;
+    return v >= 0 && v < NVARIANT;
 #else
-    return v == 0 || v == 9 || v == 16 || v == 17 || v == 20;
+    return v >= 0 && v < NVARIANT && VARIANTS[v].product;
 #endif
 }
-
-#ifdef GGL_DEV
-// scratch tiles and arrival counters of the SPLIT > 1 launches, one set per stream (launches on a stream are ordered, so a
-// set is never shared by two launches in flight); grown on demand, released by symm_release_workspace()
-namespace {
-struct SkWork { double* scratch = nullptr; unsigned* arrivals = nullptr; size_t tiles = 0, units = 0; };
-std::mutex sk_mutex;
-std::unordered_map<hipStream_t, SkWork> sk_work;
-}
-static bool sk_workspace(hipStream_t st, size_t tiles, size_t units, double** scratch, unsigned** arrivals)
+// the product library's register-staged kernel of a tile edge: where a DL row goes at a dimension the DMA kernel does not take
+constexpr int tn_fallback(int bm)
 {
-    std::lock_guard<std::mutex> lock(sk_mutex);
-    SkWork& w = sk_work[st];
-    if (w.tiles < tiles || w.units < units) {
-        if (w.scratch) { (void)hipStreamSynchronize(st); (void)hipFree(w.scratch); (void)hipFree(w.arrivals); w = SkWork(); }
-        if (hipMalloc(&w.scratch, units * 1024 * sizeof(double)) != hipSuccess) return false;
-        if (hipMalloc(&w.arrivals, tiles * sizeof(unsigned)) != hipSuccess) return false;
-        if (hipMemset(w.arrivals, 0, tiles * sizeof(unsigned)) != hipSuccess) return false;
-        w.tiles = tiles;
-        w.units = units;
+    for (int v = 0; v < NVARIANT; ++v)
+        if (VARIANTS[v].fam == Fam::TN && VARIANTS[v].product && VARIANTS[v].bm == bm) return v;
+    return -1;
+}
+constexpr int DEFAULT_VARIANT = tn_fallback(64);      // what a number outside the table or the build runs
+constexpr bool variant_table_ok()
+{
+    int nproduct = 0;
+    for (int v = 0; v < NVARIANT; ++v) {
+        const Variant& r = VARIANTS[v];
+        nproduct += r.product;
+        if (r.product && r.abl != 0) return false;                                     // no ablation in the product library
+        if (r.fam == Fam::DL && (tn_fallback(r.bm) < 0 || (r.nw != 4 && r.nw != 8))) return false;
+        if (r.fam == Fam::TN && r.abl != 0 && tn_fallback(r.bm) < 0) return false;      // (pair launches, launch_variant)
     }
-    *scratch = w.scratch;
-    *arrivals = w.arrivals;
-    return true;
+    return nproduct == 5;
 }
-void symm_release_workspace(hipStream_t st)
-{
-    std::lock_guard<std::mutex> lock(sk_mutex);
-    auto it = sk_work.find(st);
-    if (it == sk_work.end()) return;
-    (void)hipFree(it->second.scratch);
-    (void)hipFree(it->second.arrivals);
-    sk_work.erase(it);
-}
+static_assert(NVARIANT == 40, "variant numbers 0 .. 39");
+static_assert(variant_table_ok(), "variant table");
+static_assert(VARIANTS[0].product && VARIANTS[9].product && VARIANTS[16].product && VARIANTS[17].product && VARIANTS[20].product,
+              "the product library carries exactly 0, 9, 16, 17 and 20");
+static_assert(tn_fallback(64) == 0 && tn_fallback(32) == 9, "what ggl_ns_stats reports for the register-staged kernels");
 
-static void launch_sk(hipStream_t st, const double* A, const double* B, double* C, double* C2, const double* E,
-                      const double* coef, int K, int p, double* maxdev, double* rowpart, double* fropart, int variant)
-{
-    const int T32 = (p + 31) / 32;
-    const int ntiles = T32 * (T32 + 1) / 2;
-    double* scratch = nullptr;
-    unsigned* arrivals = nullptr;
-#define GGL_SK(BK_, ST_, SP_)                                                                                          \
-    do {                                                                                                               \
-        if (SP_ > 1 && !sk_workspace(st, (size_t)K * ntiles, (size_t)K * ntiles * SP_, &scratch, &arrivals)) return;   \
-        hipLaunchKernelGGL((k_symm_sk<BK_, ST_, SP_>), dim3(SP_ > 1 ? sk_grid(ntiles, K, SP_) : xcd_grid(ntiles, K)),  \
-                           dim3(256), 0, st, A, B, C, C2, E, coef, K, p, maxdev, rowpart, fropart, scratch, arrivals); \
-    } while (0)
-    switch (variant) {
-        case 41: GGL_SK(8, 3, 1); break;
-        case 42: GGL_SK(8, 4, 1); break;
-        case 43: GGL_SK(16, 2, 1); break;
-        case 44: GGL_SK(8, 2, 1); break;
-        case 45: GGL_SK(4, 4, 1); break;
-        case 46: GGL_SK(8, 3, 2); break;
-        case 47: GGL_SK(8, 3, 4); break;
-        case 48: GGL_SK(8, 2, 2); break;
-        case 49: GGL_SK(8, 2, 4); break;
-        default: GGL_SK(4, 4, 4); break;
-    }
-#undef GGL_SK
-}
-#else
-void symm_release_workspace(hipStream_t) {}
-#endif
+int symm_variants() { return NVARIANT - 1; }
+bool symm_variant_built(int v) { return variant_in_build(v); }
 
 // Measured on MI355X (tools/bench_small_batches.py, profiles/r2_small_batches_product_kernel.txt), us per launch,
 // 32x32 (20) against 64x64 (16) direct-to-LDS tiles: p = 500: K = 2: 16.1 / 28.3, K = 4: 21.6 / 29.7, K = 8: 34.7 / 44.7,
@@ -2411,7 +1622,8 @@ bool symm_dl_serves(int p) { return p >= 2 && ((p & 1) == 0 || g_odd_dl); }
 // register-staged kernel of the same tile (what ggl_ns_stats reports: the dispatch tests assert the kernel, not the request)
 int symm_effective_variant(int variant, int p)
 {
-    if (variant >= 16 && variant <= 39 && !symm_dl_serves(p)) return (variant == 20 || variant >= 24) ? 9 : 0;
+    if (variant >= 0 && variant < NVARIANT && VARIANTS[variant].fam == Fam::DL && !symm_dl_serves(p))
+        return tn_fallback(VARIANTS[variant].bm);
     return variant;
 }
 
@@ -2421,7 +1633,88 @@ int symm_auto_variant(int nprod, int p)
     return (T64 * (T64 + 1) / 2 * nprod <= SMALL_BATCH_TILES) ? (p >= SMALL_DL_MIN_P ? 20 : 9) : 16;
 }
 
-// Two independent products in one launch: C = coef[k]-affine(A*B) for k < K and C1 = coef[K+k]-scaled(A1*B1).
+// tile edge of the direct-to-LDS kernel a variant resolves to, or 0 if the variant (or an odd p) runs the register-staged
+// kernel, which does not produce bound partials (nor does the DL ablation without the mirror write, ABL 1: no staged tile)
+int symm_bounds_tile(int K, int p, int variant)
+{
+    if (variant < 0) variant = symm_auto_variant(K, p);
+    if (variant >= NVARIANT || !symm_dl_serves(p)) return 0;
+    const Variant& r = VARIANTS[variant];
+    return (r.fam == Fam::DL && r.abl != 1) ? r.bm : 0;
+}
+
+// everything a product launch takes; a pair launch (two independent products in one launch: C = coef[k]-affine(A*B) for k < K
+// and C1 = coef[K + k]-scaled(A1*B1)) fills the second operand set, K1 = K
+struct SymmArgs {
+    hipStream_t st;
+    const double *A, *B;
+    double *C, *C2;
+    const double *E, *E2, *coef;
+    int K, p;
+    const double *A1, *B1;
+    double* C1;
+    int K1;
+    double *maxdev, *rowpart, *fropart;
+};
+
+template <int BM, int BK, int WM, int WN, bool LM, int ABL> static void launch_tn(const SymmArgs& a)
+{
+    using Cfg = SymCfg<BM, BK, WM, WN, LM>;
+    const int T = (a.p + BM - 1) / BM;
+    double* md = (ABL == 0 || ABL == 3) ? a.maxdev : nullptr;      // (ABL 3: the timeline buffer)
+    hipLaunchKernelGGL((k_symm_tn<BM, BK, WM, WN, LM, ABL>), dim3(xcd_grid(T * (T + 1) / 2, a.K + a.K1)), dim3(Cfg::NT), 0, a.st,
+                       a.A, a.B, a.C, a.C2, a.E, a.coef, a.K, a.p, a.A1, a.B1, a.C1, a.K1, md, a.E2);
+}
+
+template <int BK, int NSTG, int ABL, int BM, int NW> static void launch_dl(const SymmArgs& a)
+{
+    // (the eight-wave development variants do not carry riders: the rider stays pending)
+    constexpr bool rides = NW == 4;
+    const CwRider rider = (g_rider.K > 0 && rides) ? g_rider : CwRider{};
+    if (rider.K > 0) g_rider = CwRider{};
+    const CopySegs cps = (g_copy_rider.n > 0 && rides) ? g_copy_rider : CopySegs{};
+    if (cps.n > 0) g_copy_rider = CopySegs{};
+    const RedRider red = (g_red_rider.nblk > 0 && rides) ? g_red_rider : RedRider{};
+    if (red.nblk > 0) g_red_rider = RedRider{};
+    int ncopy = red.nblk > 0 ? NXCD : 0;          // (in front of the tiles, see k_symm_dl)
+    for (int i = 0; i < cps.n; ++i) ncopy += (int)((cps.words[i] + 1023u) / 1024u);
+    const int nride = rider.K * rider.nbx + ncopy;
+    const int T = (a.p + BM - 1) / BM;
+    const dim3 grid(xcd_grid(T * (T + 1) / 2, a.K + a.K1) + nride), block(NW * 64);
+#define GGL_DL_LAUNCH(SER)                                                                                                      \
+    hipLaunchKernelGGL((k_symm_dl<BK, NSTG, ABL, BM, NW, SER>), grid, block, 0, a.st, a.A, a.B, a.C, a.C2, a.E, a.E2, a.coef, a.K, \
+                       a.p, a.A1, a.B1, a.C1, a.K1, a.maxdev, a.rowpart, a.fropart, rider, cps, red)
+#ifdef GGL_DEV
+    if (g_symm_epilogue == 1) GGL_DL_LAUNCH(1);       // the epilogue ggl_dev_set_symm_epilogue names
+    else if (g_symm_epilogue == 2) GGL_DL_LAUNCH(2);
+    else
+#endif
+        GGL_DL_LAUNCH(0);
+#undef GGL_DL_LAUNCH
+}
+
+// row V of the table: the one place a template instance is chosen
+template <int V> static void launch_variant(const SymmArgs& a)
+{
+    constexpr Variant r = VARIANTS[V];
+    if constexpr (!variant_in_build(V)) {
+        launch_variant<DEFAULT_VARIANT>(a);
+    } else if constexpr (r.fam == Fam::DL) {
+        if (!symm_dl_serves(a.p)) return launch_variant<tn_fallback(r.bm)>(a);
+        launch_dl<r.bk, r.nstg, r.abl, r.bm, r.nw>(a);
+    } else if constexpr (r.abl != 0) {
+        // the ablations and the timeline probe (which needs the maxdev buffer) are single products: a pair runs the plain kernel
+        if (a.K1 > 0) return launch_variant<tn_fallback(r.bm)>(a);
+        launch_tn<r.bm, r.bk, r.wm, r.wn, r.lm, r.abl>(a);
+    } else {
+        launch_tn<r.bm, r.bk, r.wm, r.wn, r.lm, 0>(a);
+    }
+}
+template <int... V> static void launch_row(int variant, const SymmArgs& a, std::integer_sequence<int, V...>)
+{
+    if (!((variant == V && (launch_variant<V>(a), true)) || ...)) launch_variant<DEFAULT_VARIANT>(a);
+}
+
 // Launch hook of the event timeline (ggl_trace_*, capi_stats.hip): called after every product launch with its stream.
 static void (*g_symm_hook)(hipStream_t, int, void*) = nullptr;
 static void* g_symm_hook_arg = nullptr;
@@ -2436,36 +1729,8 @@ void launch_symm_pair(hipStream_t st, const double* A, const double* B, double* 
 {
     SymmHookAtExit hook{st, 1};
     if (variant < 0) variant = symm_auto_variant(2 * K, p);
-    if (variant >= 41 && variant <= 50) variant = 20;       // k_symm_sk takes single products only
-    switch (variant) {
-        case 16: case 17: case 18: case 19: case 20: case 22: case 23: case 24: case 25: case 26: case 27: case 28: case 29: case 30: case 31: case 32: case 33: case 34: case 35: case 36: case 37: case 38: case 39:
-            if (symm_dl_serves(p)) {
-                launch_dl(st, A, B, C, nullptr, nullptr, coef2K, K, p, A1, B1, C1, K, nullptr, variant - 16);
-                break;
-            }
-            if (variant == 20 || variant >= 24) launch_cfg<32, 32, 16, 16, true>(st, A, B, C, nullptr, nullptr, coef2K, K, p, A1, B1, C1, K);
-            else launch_cfg<64, 16, 32, 32, true>(st, A, B, C, nullptr, nullptr, coef2K, K, p, A1, B1, C1, K);
-            break;
-        case 9: launch_cfg<32, 32, 16, 16, true>(st, A, B, C, nullptr, nullptr, coef2K, K, p, A1, B1, C1, K); break;
-#ifdef GGL_DEV
-        case 1: launch_cfg<64, 32, 32, 32, true>(st, A, B, C, nullptr, nullptr, coef2K, K, p, A1, B1, C1, K); break;
-        case 3: launch_cfg<128, 16, 32, 64, false>(st, A, B, C, nullptr, nullptr, coef2K, K, p, A1, B1, C1, K); break;
-        case 4: launch_cfg<64, 16, 32, 32, false>(st, A, B, C, nullptr, nullptr, coef2K, K, p, A1, B1, C1, K); break;
-        case 8: launch_cfg<32, 16, 16, 16, true>(st, A, B, C, nullptr, nullptr, coef2K, K, p, A1, B1, C1, K); break;
-#endif
-        default: launch_cfg<64, 16, 32, 32, true>(st, A, B, C, nullptr, nullptr, coef2K, K, p, A1, B1, C1, K); break;
-    }
-}
-
-// tile edge of the direct-to-LDS kernel a variant resolves to, or 0 if the variant (or an odd p) runs the register-staged
-// kernel, which does not produce bound partials
-int symm_bounds_tile(int K, int p, int variant)
-{
-    if (variant < 0) variant = symm_auto_variant(K, p);
-    if (!symm_dl_serves(p)) return 0;
-    if (variant == 20 || (variant >= 24 && variant <= 29) || (variant >= 34 && variant <= 37) || (variant >= 41 && variant <= 50)) return 32;
-    if ((variant >= 16 && variant <= 19) || variant == 22 || variant == 23 || (variant >= 30 && variant <= 33) || variant == 38 || variant == 39) return 64;
-    return 0;
+    launch_row(variant, SymmArgs{st, A, B, C, nullptr, nullptr, nullptr, coef2K, K, p, A1, B1, C1, K, nullptr, nullptr, nullptr},
+               std::make_integer_sequence<int, NVARIANT>{});
 }
 
 void launch_symm(hipStream_t st, const double* A, const double* B, double* C, double* C2, const double* E,
@@ -2474,51 +1739,9 @@ void launch_symm(hipStream_t st, const double* A, const double* B, double* C, do
 {
     SymmHookAtExit hook{st, 0};
     if (variant < 0) variant = symm_auto_variant(K, p);
-#define GGL_TN(BM, BK, WM, WN, LM) \
-    launch_cfg<BM, BK, WM, WN, LM>(st, A, B, C, C2, E, coef, K, p, nullptr, nullptr, nullptr, 0, maxdev, E2)
-#ifdef GGL_DEV
-    if (E2 && variant >= 41 && variant <= 50) variant = 20;    // k_symm_sk carries one affine operand only
-    if (variant >= 41 && variant <= 50) {
-        if ((p & 1) == 0 && p >= 2) { launch_sk(st, A, B, C, C2, E, coef, K, p, maxdev, rowpart, fropart, variant); return; }
-        variant = 9;                                     // odd p: the register-staged 32x32 kernel
-    }
-#endif
-    switch (variant) {
-        case 16: case 17: case 18: case 19: case 20: case 21: case 22: case 23: case 24: case 25: case 26: case 27: case 28: case 29: case 30: case 31: case 32: case 33: case 34: case 35: case 36: case 37: case 38: case 39:
-            if (symm_dl_serves(p)) {
-                launch_dl(st, A, B, C, C2, E, coef, K, p, nullptr, nullptr, nullptr, 0, maxdev, variant - 16, rowpart, fropart, E2);
-                break;
-            }
-            if (variant == 20 || variant >= 24) GGL_TN(32, 32, 16, 16, true);
-            else GGL_TN(64, 16, 32, 32, true);
-            break;
-        case 9: GGL_TN(32, 32, 16, 16, true); break;
-#ifdef GGL_DEV
-        case 1: GGL_TN(64, 32, 32, 32, true); break;
-        case 2: GGL_TN(128, 16, 64, 64, false); break;
-        case 3: GGL_TN(128, 16, 32, 64, false); break;
-        case 4: GGL_TN(64, 16, 32, 32, false); break;
-        case 5: GGL_TN(128, 32, 64, 64, false); break;
-        case 8: GGL_TN(32, 16, 16, 16, true); break;
-        case 11: GGL_TN(64, 16, 16, 32, true); break;
-        case 12: GGL_TN(64, 32, 16, 32, true); break;
-        case 13: GGL_TN(64, 16, 32, 16, true); break;
-        case 6: case 7: case 10: case 14: case 15: {
-            // ablations of variant 0: 6 no global loads, 7 no MFMA, 14 ds_read + MFMA only, 15 + ds_write; 10 = timeline
-            // probe (maxdev is a [grid][5] long long buffer)
-            const int T = (p + 63) / 64;
-            const dim3 grid(xcd_grid(T * (T + 1) / 2, K));
-            double* md = (variant == 10) ? maxdev : nullptr;
-#define GGL_ABL(N) hipLaunchKernelGGL((k_symm_tn<64, 16, 32, 32, true, N>), grid, dim3(256), 0, st, A, B, C, C2, E, coef, K, p, nullptr, nullptr, nullptr, 0, md, E2)
-            if (variant == 6) GGL_ABL(1); else if (variant == 7) GGL_ABL(2); else if (variant == 10) GGL_ABL(3);
-            else if (variant == 14) GGL_ABL(4); else GGL_ABL(5);
-#undef GGL_ABL
-            break;
-        }
-#endif
-        default: GGL_TN(64, 16, 32, 32, true); break;
-    }
-#undef GGL_TN
+    launch_row(variant, SymmArgs{st, A, B, C, C2, E, E2, coef, K, p, nullptr, nullptr, nullptr, 0, maxdev, rowpart, fropart},
+               std::make_integer_sequence<int, NVARIANT>{});
 }
 
 }  // namespace ggl
+

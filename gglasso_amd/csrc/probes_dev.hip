@@ -185,5 +185,110 @@ void mfma_lds_probe(hipStream_t st, double* scratch, double* out)
     out[5] = mfma_lds_tf<1, 1, 32768>(st, scratch, 256 * 5, it);
 }
 
+// ---- FP64 matrix-core ceiling (ggl_dev_mfma_f64_peak, tools/probe_mfma_mix.py) ---------------------------------------
+// FP64 matrix-core ceiling probe: every wave issues `iters` x NACC MFMAs on NACC independent accumulators.
+template <int NACC>
+__global__ __launch_bounds__(256) void k_mfma_f64_peak(double* __restrict__ out, int iters)
+{
+    v4d acc[NACC];
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) acc[i] = (v4d){0.0, 0.0, 0.0, 0.0};
+    double a = 1.0 + threadIdx.x * 1e-9, b = 1.0 - threadIdx.x * 1e-9;
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+        for (int i = 0; i < NACC; ++i) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[i], 0, 0, 0);
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) s += acc[i][0] + acc[i][1] + acc[i][2] + acc[i][3];
+    out[(size_t)blockIdx.x * 256 + threadIdx.x] = s;
+}
+
+// same probe with NV dependent 64-bit integer VALU ops (address arithmetic stand-ins) per MFMA
+template <int NV>
+__global__ __launch_bounds__(256) void k_mfma_valu_mix(double* __restrict__ out, int iters, unsigned long long seed)
+{
+    v4d acc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = (v4d){0.0, 0.0, 0.0, 0.0};
+    double a = 1.0 + threadIdx.x * 1e-9, b = 1.0 - threadIdx.x * 1e-9;
+    unsigned long long x = seed + threadIdx.x;
+    double d = a;
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[i], 0, 0, 0);
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                if (v & 1) x = (x << 3) + seed;           // v_lshl_add_u64
+                else d = (x & 1) ? d : b;                 // v_cndmask pair
+            }
+        }
+    }
+    double s = d + (double)x;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s += acc[i][0] + acc[i][1] + acc[i][2] + acc[i][3];
+    out[(size_t)blockIdx.x * 256 + threadIdx.x] = s;
+}
+
+template <int NV>
+static double mix_probe(hipStream_t st, double* scratch, int blocks, int iters)
+{
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    hipLaunchKernelGGL(k_mfma_valu_mix<NV>, dim3(blocks), dim3(256), 0, st, scratch, 16, 12345ull);
+    (void)hipEventRecord(e0, st);
+    hipLaunchKernelGGL(k_mfma_valu_mix<NV>, dim3(blocks), dim3(256), 0, st, scratch, iters, 12345ull);
+    (void)hipEventRecord(e1, st);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return (double)blocks * 4.0 * iters * 4 * 2.0 * 16 * 16 * 4 / (ms * 1e-3) / 1e12;
+}
+
+double mfma_valu_mix_tflops(hipStream_t st, double* scratch, int blocks, int iters, int nv)
+{
+    switch (nv) {
+        case 0: return mix_probe<0>(st, scratch, blocks, iters);
+        case 2: return mix_probe<2>(st, scratch, blocks, iters);
+        case 4: return mix_probe<4>(st, scratch, blocks, iters);
+        case 8: return mix_probe<8>(st, scratch, blocks, iters);
+        default: return mix_probe<16>(st, scratch, blocks, iters);
+    }
+}
+
+template <int NACC>
+static double mfma_probe(hipStream_t st, double* scratch, int blocks, int iters)
+{
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    hipLaunchKernelGGL(k_mfma_f64_peak<NACC>, dim3(blocks), dim3(256), 0, st, scratch, 16);
+    (void)hipEventRecord(e0, st);
+    hipLaunchKernelGGL(k_mfma_f64_peak<NACC>, dim3(blocks), dim3(256), 0, st, scratch, iters);
+    (void)hipEventRecord(e1, st);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    const double flops = (double)blocks * 4.0 * iters * NACC * 2.0 * 16 * 16 * 4;
+    return flops / (ms * 1e-3) / 1e12;
+}
+
+// nacc in {1,2,4,8}; blocks = workgroups of 4 waves (256 per "one wave per SIMD" layer)
+double mfma_f64_peak_tflops(hipStream_t st, double* scratch, int blocks, int iters, int nacc)
+{
+    switch (nacc) {
+        case 1: return mfma_probe<1>(st, scratch, blocks, iters);
+        case 2: return mfma_probe<2>(st, scratch, blocks, iters);
+        case 4: return mfma_probe<4>(st, scratch, blocks, iters);
+        default: return mfma_probe<8>(st, scratch, blocks, iters);
+    }
+}
+
 }  // namespace ggl
 #endif   // GGL_DEV

@@ -129,11 +129,12 @@ void *ggl_device_ptr(ggl_ctx *ctx, int which);
 #define GGL_OPT_CW_WARM 16         /* [1] the Collatz-Wielandt weight vector of the spectral bound is carried from one iteration to
                                     * the next (a power iteration at no extra pass; the bound stays rigorous and tightens
                                     * towards the Perron root of |B'|); 0: the row sums of |B'| every time                  */
-#define GGL_OPT_CHAIN 17           /* DEV [0] 1: speculative Omega-steps of batches that cover the XCDs (K >= 8, even p, >= 1100 64x64 tile
+#define GGL_OPT_CHAIN 17           /* RETIRED [0]: the persistent chain was removed; both libraries take 0, refuse
+                                    * anything else and report 0.  What it was -- 1: speculative Omega-steps of batches that cover the XCDs (K >= 8, even p, >= 1100 64x64 tile
                                     * pairs) run their whole product chain as ONE persistent launch with per-instance
                                     * dependencies (k_omega_chain, csrc/gemm_sym.hip) instead of one launch per product in
                                     * concurrent parts; 2: wherever it can run (any K >= 8, even p).  Same products, same bits
-                                    * (tests/test_gpu_chain.py).  Off by default: measured SLOWER on MI355X (headline Omega
+                                    * (tests/test_gpu_chain.py, removed with it).  Measured SLOWER on MI355X (headline Omega
                                     * phase 0.89 vs 0.72 ms; DESIGN.md section 8.1, profiles/r3_omega_chain_*.txt)           */
 #define GGL_OPT_RANK_DEFLATE 20    /* [1] L-step (sign iteration): after a first pass at GGL_OPT_RANK_L0_DEFLATE the eigenvalues next to the
                                       threshold are deflated (range of I - X^2, exact small problem) instead of iterated down */
@@ -664,9 +665,6 @@ int ggl_dev_mfma_f64_peak(double *tflops_out);
 int ggl_dev_coissue_probe(double *out12);
 /* MFMA fed from LDS (the product kernel's inner loop alone), TF/s for wave tiles {2x2 @3 WG/CU, 2x2 @5, 2x4 @3, 4x4 @2, 4x4 @3, 1x1 @5} */
 int ggl_dev_mfma_lds_probe(double *out6);
-/* k_omega_chain on a synthetic chain of nprod dependent products X <- I - 1.5 X^2: out = {ms as nprod launches, ms as one
- * persistent launch, persistent workgroups, max |difference| of the results, completion flag, done counters [K]} */
-int ggl_dev_chain_run(int K, int p, int nprod, int iters, double *out);
 /* What a change of kernel between dependent launches costs (tools/kernel_switch_cost.py): mode 0 `iters` product launches, 1 each
  * followed by a one-thread kernel, 2 the one-thread kernel alone, 3 each followed by an elementwise kernel over its output;
  * ms per repetition. */
@@ -680,11 +678,6 @@ int ggl_dev_vendor_bench(int K, int p, int mode, int iters, double *ms_out);
  * that came out zero }. */
 int ggl_dev_fill_copy_probe(int reps, int K, int p, int slices, int gap_us, long long out[2]);
 int ggl_dev_symm_timeline(int K, int p, long long *out, int max_blocks, int *nblocks_out);
-/* persistent-chain probe: nprod dependent products X <- X X of a K-batch as nprod launches (out[0], ms) and as ONE cooperative
- * launch with grid-wide barriers between the products (out[1], ms); out[2] grid of the latter, out[3] max |difference| of
- * the two chains' results (must be 0), out[4] barrier flag (1 time-out, 2 a workgroup not on XCD blockIdx % 8).  variant: 16, 17
- * (64x64 tiles), 20 (32x32).  two_level: one L2 write-back per XCD and barrier instead of one per workgroup. */
-int ggl_dev_chain_probe(int K, int p, int variant, int nprod, int iters, int two_level, double *out);
 /* Epilogue of the direct-to-LDS product kernels (symm_dl_tile): 0 the batched one that writes off-diagonal tiles and their
  * mirrors from registers (the only one the product library has), 1 the serial one, kept as its bitwise yardstick and for A/B
  * timing, 2 the batched one with every off-diagonal tile staged in LDS (the product's before the register path).  Any other

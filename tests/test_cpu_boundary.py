@@ -119,6 +119,19 @@ def test_argument_asserts_happen_before_any_device_work(lib):
         solver.ADMM_SGL(np.eye(4), 0.1, np.eye(4), latent=True)
 
 
+def test_split_k_variant_numbers_are_in_no_build(lib):
+    """41-50 were the split-K kernel's variant numbers (removed): both libraries refuse them as "not in this build".
+    Through ggl_dev_symm, whose variant check comes before any device call: refusals only, nothing here reaches the device."""
+    from gglasso_amd._lib import ptr
+    x = np.eye(2)[None].copy()
+    coef, C = np.zeros((1, 5)), np.empty((1, 2, 2))
+    for so in (lib.load(), lib.load_dev()):
+        for v in range(41, 51):
+            rc = so.ggl_dev_symm(1, 2, ptr(x), ptr(x), None, ptr(coef), ptr(C), None, v)
+            assert rc == lib.E_ARG, (v, rc)
+            assert "not in this build" in so.ggl_last_error().decode(), v
+
+
 @pytest.fixture()
 def oracle_engine(monkeypatch):
     from gglasso_amd import solver

@@ -8,11 +8,7 @@ omega_poly = 0 (the Newton-Schulz schedule everywhere) -- and checks
   3. the last Omega-step against phi^+ of the Newton-Schulz run's W by eigh.
 Routes: the headline's two concurrent speculative parts with early parts (fused start G in the B' launch, E2 = W), an odd p
 on the direct-to-LDS and on the register-staged kernel, every speculation missed (spec_factor 0.9: the repeated step plans
-after the bound, G from k_ns_start), a grouped batch with the early part on, and the persistent chain (development library)
-bit for bit against the launch path."""
-import contextlib
-import io
-
+after the bound, G from k_ns_start) and a grouped batch with the early part on."""
 import numpy as np
 import pytest
 
@@ -129,40 +125,3 @@ def test_grouped_with_early_part():
     assert gs["steps"] > 0 and ps["early_used"] > 0, (gs, ps)
     assert poly["seqs"] > 0, poly
 
-
-@pytest.mark.gpu
-@pytest.mark.usefixtures("dev_library")
-def test_persistent_chain_bitwise():
-    """k_omega_chain (development library) runs the direct family's launches as ONE launch: the same bits as the launch path"""
-    from gglasso_amd import solver
-    S = _problem(32, 500, 1239)
-    K, p = S.shape[0], S.shape[-1]
-    Om0 = np.repeat(np.eye(p)[None], K, axis=0)
-    kw = dict(max_iter=14, tol=1e-20, rtol=1e-20, update_rho=False, rho=2.0)
-    res = []
-    for chain in (2, 0):
-        stats = []
-        real_close = solver.HipEngine.close
-
-        def closing(self):
-            if getattr(self, "h", None):
-                stats.append((self.ns_stats(), self.poly_stats()))
-            real_close(self)
-
-        solver.HipEngine.close = closing
-        old = dict(solver.ENGINE_OPTIONS)
-        solver.ENGINE_OPTIONS.clear()
-        solver.ENGINE_OPTIONS.update({"chain": chain, "parts": 1, "symm_variant": 17, "early_part": 0})
-        try:
-            with contextlib.redirect_stdout(io.StringIO()):
-                out, _ = solver.ADMM_MGL(S, LAM1, LAM2, "GGL", Om0, **kw)
-        finally:
-            solver.ENGINE_OPTIONS.clear()
-            solver.ENGINE_OPTIONS.update(old)
-            solver.HipEngine.close = real_close
-        res.append((out, stats[-1]))
-    (a, (na, pa)), (b, (nb, pb)) = res
-    assert na["last_variant"] == 40 and pa["seqs"] > 0, (na, pa)
-    assert pb["seqs"] > 0
-    for nm in ("Omega", "Theta", "X"):
-        assert np.array_equal(a[nm], b[nm]), (nm, float(np.abs(a[nm] - b[nm]).max()))

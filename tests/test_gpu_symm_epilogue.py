@@ -5,7 +5,8 @@ development library keeps behind ggl_dev_set_symm_epilogue(1): the same bits, ev
 Kernel level (ggl_dev_symm, ggl_dev_symm_full, ggl_dev_symm_bounds): the 64x64 kernels (16, 17), the 32x32 kernel (20) and the eight-wave
 instances (22, 23), with E and the second output, with E alone, without E, with E, E2 and every coefficient; shapes, one purpose each: (2, 64) a single diagonal
 tile, (2, 130) diagonal, off-diagonal and a two-column edge tile at BM = 64, (3, 129) odd p (the last column as half a pair),
-(2, 200), (9, 70) the XCD remainder dealing, (1, 500) the headline's tile grid.
+(2, 200), (9, 70) the XCD remainder dealing, (1, 500) the headline's tile grid.  Every variant of the development library that
+is not a timing ablation, at (3, 130) and (2, 97): a symmetric C within rounding of numpy's, bound partials that are C's.
 Step level (ggl_admm_step, where E2 and the fused second output exist): 8 iterations of (8, 301) at ns_tol 1e-9 and of
 (16, 400) with every speculation missed, both epilogues, every iterate and the five norms of every step."""
 import numpy as np
@@ -128,6 +129,46 @@ def test_bound_partials_bitwise(dev_library, variant, K, p):
     assert np.abs(ref[0][:, iu[0], iu[1]] - (A @ B)[:, iu[0], iu[1]]).max() <= 1e-12 * np.abs(ref[0]).max() * p
     for nm, x, y in zip(("C", "row sums", "Frobenius", "bound"), got, ref):
         assert np.array_equal(x, y), nm
+
+
+# What a variant number is, restated here on purpose (csrc/gemm_sym.hip keeps it in one table): the timing ablations, whose
+# results are wrong by design, and the direct-to-LDS variants, the only ones that leave bound partials.
+ABLATIONS = {6, 7, 10, 14, 15, 21} | set(range(30, 38))
+DIRECT_TO_LDS = set(range(16, 40))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K,p", [(3, 130), (2, 97)])
+@pytest.mark.parametrize("variant", [v for v in range(40) if v not in ABLATIONS])
+def test_every_variant_computes_the_product(dev_library, variant, K, p):
+    """Every row of the variant table that is not an ablation: a bitwise symmetric C = cI I + cAcc A B + cE E, and -- where the
+    variant leaves bound partials -- row sums and Frobenius norm that are those of the C it returned.  (3, 130): even p, two
+    64-tiles and a remainder, an off-diagonal tile with its mirror even at tile edge 128, K outside the XCD-sharing cases;
+    (2, 97): odd p, the last-column pair rule and a partial tile at every edge."""
+    from gglasso_amd import _lib
+    from gglasso_amd._lib import ptr
+    rng = np.random.default_rng(500 * variant + p)
+    A, B, E = _sym(rng, K, p), _sym(rng, K, p), _sym(rng, K, p)
+    coef = np.ascontiguousarray(rng.uniform(0.5, 1.5, (K, 5)))
+    C = np.full_like(A, np.nan)
+    _lib.check(dev_library.ggl_dev_symm(K, p, ptr(A), ptr(B), ptr(E), ptr(coef), ptr(C), None, variant))
+    assert np.isfinite(C).all()
+    assert np.array_equal(C, C.transpose(0, 2, 1))
+    iu = np.triu_indices(p)
+    ref = coef[:, 0, None, None] * np.eye(p)[None] + coef[:, 1, None, None] * (A @ B) + coef[:, 2, None, None] * E
+    err = np.abs(C[:, iu[0], iu[1]] - ref[:, iu[0], iu[1]]).max()
+    print("variant", variant, "K", K, "p", p, "max error", err, "bound", 1e-12 * np.abs(ref).max() * p)
+    assert err <= 1e-12 * np.abs(ref).max() * p
+    Cb, rows, fro2, bound = np.full_like(A, np.nan), np.empty((K, p)), np.empty(K), np.empty(K)
+    rc = dev_library.ggl_dev_symm_bounds(K, p, ptr(A), ptr(B), variant, ptr(Cb), ptr(rows), ptr(fro2), ptr(bound))
+    if variant not in DIRECT_TO_LDS:
+        assert rc == _lib.E_ARG and "no bound partials" in dev_library.ggl_last_error().decode()
+        return
+    _lib.check(rc)
+    assert np.array_equal(Cb, Cb.transpose(0, 2, 1))
+    # (the tolerances of test_product_epilogue_bound_partials, tests/test_gpu_ops.py)
+    assert np.allclose(rows, np.abs(Cb).sum(axis=2), rtol=1e-13, atol=0)
+    assert np.allclose(fro2, (Cb ** 2).sum(axis=(1, 2)), rtol=1e-13)
 
 
 def _steps(S, options, iters=8):

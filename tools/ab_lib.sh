@@ -3,7 +3,7 @@
 #   tools/ab_lib.sh <tag> <rounds> <libA.so> <libB.so> ["<bench args>" ...]
 # The libraries are copied over gglasso_amd/lib/libggl_hip.so in turn; the library that was installed before the run is
 # restored on exit (whatever the exit path), so later pytest / bench runs in the same tree measure what build.py built.
-set -u
+set -u -o pipefail
 TAG=$1; ROUNDS=$2; LA=$3; LB=$4; shift 4
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/$TAG
@@ -18,7 +18,8 @@ for r in $(seq 1 $ROUNDS); do
     if [ $side = A ]; then cp $LA gglasso_amd/lib/libggl_hip.so; else cp $LB gglasso_amd/lib/libggl_hip.so; fi
     i=0
     for cfg in "$@"; do
-      python bench.py --full --no-cpu-baseline --steps 60 --warmup 10 $cfg 2>/dev/null | grep "^{" >> $O/$side$i.jsonl
+      # a run that fails or overruns ends the comparison: nothing more is started on the device behind it
+      timeout -k 10 ${AB_STEP_TIMEOUT:-300} python bench.py --full --no-cpu-baseline --steps 60 --warmup 10 $cfg 2>/dev/null | grep "^{" >> $O/$side$i.jsonl || exit 1
       i=$((i+1))
     done
   done

@@ -50,7 +50,7 @@ for sub in ("fetch", "write", "sq", "tcc"):
 # the instance copies, the persistent chain and the int8 product kernel.  (r3_pmc_summary.json reported 224 MB per launch for
 # flat4v against 320 MB algorithmic: FETCH 188 MB was half of the truth; 2 x 94 + 125 = 313 MB.)
 FETCH_FACTOR = {"k_symm_dl": 2.0, "k_theta_ggl_flat4v<16": 1.0, "k_theta_ggl_flat4": 2.0, "k_copy_instances": 2.0,
-                "k_omega_chain": 2.0, "k_symm_i8": 2.0}
+                "k_symm_i8": 2.0}
 for kname, c in out.items():
     f = c.get("FETCH_SIZE", {}).get("mean_per_launch")
     w = c.get("WRITE_SIZE", {}).get("mean_per_launch")
