@@ -175,6 +175,9 @@ _SIGNATURES = {
     "ggl_project_S": ([_vp, _i, _d, _d, _i, _ip, _dp], _i),
     "ggl_debias": ([_i, _i, _i, _dp, _dp, _dp, _i, _dp, _dp], _i),
     "ggl_dev_debias_bench": ([_i, _i, _i, _i, _dp], _i),
+    "ggl_cholesky_predict": ([_i, _i, _i, _dp, _dp, _d, _dp], _i),
+    "ggl_weighted_predictive_scores": ([_i, _i, _i, _dp, _i, _dp, _ip, _d, _i, _i, _dp], _i),
+    "ggl_dev_chol_bench": ([_i, _i, _i, _dp], _i),
 }
 
 # libggl_hip_dev.so only (-DGGL_DEV)

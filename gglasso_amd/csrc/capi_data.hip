@@ -829,3 +829,87 @@ extern "C" int ggl_set_S_from_weighted(ggl_ctx* c, const double* X_host, int N, 
     RCCHK(weighted_to_device(c->stream, c->p, N, X_host, c->K, w_host, flags, dS.p, dVar.p, dWsum.p, c));
     return install_subset_S(c, dS.p, c->K, dVar.p, flags);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Gaussian predictive scores under weighted means and covariances: row r of w scores column target[r] of X.  The
+// covariances are those of ggl_covariance_weighted -- the same three launches per chunk of rows -- and never leave the device:
+// k_predict_rhs forms d = x_target - m_r from the means, k_chol_predict (cholesky.hip) factors S_r in place and leaves
+// { log det, d^T S^-1 d, smallest pivot, status }.  X goes up once.  Here beside the weighted covariance because it shares its
+// argument checks and its launch sequence.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr size_t PREDICT_CHUNK_BYTES = (size_t)256 << 20;   // chunk = 0: the covariance stack of a chunk takes at most this
+}
+
+extern "C" int ggl_weighted_predictive_scores(int device, int p, int N, const double* X_host, int M, const double* w_host,
+                                              const int* target, double ridge, int flags, int chunk, double* out)
+{
+    ARGCHK(M >= 1, "M >= 1");
+    RCCHK(check_weighted_args(p, N, X_host, std::min(M, 65535), w_host, flags));
+    ARGCHK(!(flags & GGL_COV_SCALE), "flags: GGL_COV_SCALE has no meaning for a predictive score");
+    ARGCHK(target && out, "target and out must not be NULL");
+    ARGCHK(ridge >= 0.0 && std::isfinite(ridge), "ridge must be non-negative and finite");
+    ARGCHK(chunk >= 0, "chunk >= 0 (0: sized from the memory budget)");
+    for (int r = 0; r < M; ++r)
+        if (target[r] < 0 || target[r] >= N)
+            return fail(GGL_E_ARG, "bad argument: row %d scores the sample %d, outside [0, %d)", r, target[r], N);
+    // what k_weight_prepare would find, found here: a refused call does no device work
+    for (int r = 0; r < M; ++r) {
+        const double* wr = w_host + (size_t)r * N;
+        bool any = false;
+        for (int n = 0; n < N; ++n) {
+            if (!(wr[n] >= 0.0) || !std::isfinite(wr[n]))
+                return fail(GGL_E_ARG, "bad argument: instance %d, sample %d holds the weight %g; weights must be non-negative and finite",
+                            r, n, wr[n]);
+            any = any || wr[n] > 0.0;
+        }
+        if (!any)
+            return fail(GGL_E_ARG, "bad argument: the weights of instance %d sum to %g; every weight row needs a positive finite sum",
+                        r, 0.0);
+    }
+    const size_t pp = (size_t)p * p;
+    int C = chunk;
+    if (C == 0) C = (int)std::max<size_t>(1, std::min<size_t>(PREDICT_CHUNK_BYTES / (pp * sizeof(double)), 65535));
+    C = std::min(std::min(C, M), 65535);
+    ARGCHK((size_t)C * p < (size_t)GGL_DIAG_OK, "chunk * p too large");
+
+    HIPCHK(hipSetDevice(device));
+    hipStream_t st = nullptr;
+    DevArr<double> dX, dW, dR, dWsum, dMean, dD, dS, dOut;
+    DevArr<int> dRng, dTarget;
+    DevArr<unsigned long long> dWErr;
+    HIPCHK(dX.alloc((size_t)p * N));
+    HIPCHK(dW.alloc((size_t)C * N));
+    HIPCHK(dR.alloc((size_t)C * N));
+    HIPCHK(dWsum.alloc(C));
+    HIPCHK(dMean.alloc((size_t)C * p));
+    HIPCHK(dD.alloc((size_t)C * p));
+    HIPCHK(dS.alloc((size_t)C * pp));
+    HIPCHK(dOut.alloc((size_t)M * 4));
+    HIPCHK(dRng.alloc(2 * (size_t)C));
+    HIPCHK(dTarget.alloc(M));
+    HIPCHK(dWErr.alloc(1));
+    HIPCHK(hipMemcpyAsync(dX.p, X_host, (size_t)p * N * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dTarget.p, target, (size_t)M * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(dWErr.p, 0xff, sizeof(unsigned long long), st));
+    const bool center = (flags & GGL_COV_CENTER) != 0;
+    // the tile shape of ONE call on all M rows, whatever the chunk: out does not depend on chunk by construction
+    const int tile = gram_tile(std::min(M, 65535), p, cov_tile(flags));
+    for (int r0 = 0; r0 < M; r0 += C) {
+        const int c = std::min(C, M - r0);
+        HIPCHK(hipMemcpyAsync(dW.p, w_host + (size_t)r0 * N, (size_t)c * N * sizeof(double), hipMemcpyHostToDevice, st));
+        launch_weight_prepare(st, dW.p, dR.p, dWsum.p, dRng.p, dWErr.p, c, N, (flags & GGL_COV_FULL_RANGE) != 0);
+        if (center) launch_row_means_weighted(st, dX.p, dW.p, dWsum.p, dRng.p, dMean.p, c, p, N);
+        launch_gram_nt_weighted(st, dX.p, dR.p, dWsum.p, dRng.p, center ? dMean.p : nullptr, dS.p, c, p, N, tile);
+        launch_predict_rhs(st, dX.p, center ? dMean.p : nullptr, dTarget.p + r0, dD.p, c, p, N);
+        launch_chol_predict(st, dS.p, dD.p, ridge, dOut.p + (size_t)r0 * 4, c, p);
+        HIPCHK(hipGetLastError());
+    }
+    // a weight sum that overflowed is all the host check above leaves to the device's error word
+    unsigned long long werr;
+    RCCHK(read_err_word64(st, dWErr.p, &werr));
+    if (werr != ~0ull)
+        return fail(GGL_E_ARG, "bad argument: the weights of a row do not have a positive finite sum; every weight row needs one");
+    DOWN(out, dOut.p, (size_t)M * 4);
+    return GGL_OK;
+}

@@ -1,7 +1,7 @@
 // C ABI: the output side -- inference on a fitted precision matrix.  The debiased graphical lasso and its standard errors
 // (kernels: launch_gemm_right of gemm_sym.hip, then debias.hip) as a stateless operator, host buffers in, host
 // buffers out.  The tests built on T and SE (z-scores, p-values, multiplicity adjustment) are O(p^2) host work on what comes
-// back anyway (gglasso_amd/utils.py).
+// back anyway (gglasso_amd/utils.py).  And the batched Cholesky behind Gaussian predictive scores (cholesky.hip).
 #include "capi_internal.hpp"
 
 namespace {
@@ -114,6 +114,88 @@ extern "C" int ggl_dev_debias_bench(int K, int p, int tile, int iters, double* m
         HIPCHK(hipEventElapsedTime(&ms, e0, e1));
         ms_out[route] = ms / iters;
     }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    HIPCHK(hipGetLastError());
+    return GGL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Batched Cholesky with the outputs of a Gaussian predictive score (cholesky.hip) as a stateless operator.  The
+// bandwidth search itself (ggl_weighted_predictive_scores) stands beside the weighted covariance in capi_data.hip.
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int ggl_cholesky_predict(int device, int K, int p, const double* S_host, const double* d_host, double ridge,
+                                    double* out)
+{
+    ARGCHK(K >= 1 && p >= 1, "K >= 1, p >= 1");
+    ARGCHK(S_host && out, "S and out must not be NULL");
+    ARGCHK(ridge >= 0.0 && std::isfinite(ridge), "ridge must be non-negative and finite");
+    HIPCHK(hipSetDevice(device));
+    const size_t np = (size_t)K * p * p;
+    DevBuf dS, dD, dOut;
+    HIPCHK(dS.alloc(np));
+    HIPCHK(dOut.alloc((size_t)K * 4));
+    UP(dS.p, S_host, np);
+    if (d_host) {
+        HIPCHK(dD.alloc((size_t)K * p));
+        UP(dD.p, d_host, (size_t)K * p);
+    }
+    launch_chol_predict(nullptr, dS.p, d_host ? dD.p : nullptr, ridge, dOut.p, K, p);
+    HIPCHK(hipGetLastError());
+    DOWN(out, dOut.p, (size_t)K * 4);
+    return GGL_OK;
+}
+
+// K copies of one random SPD matrix (unit diagonal plus p, off-diagonal entries in (-0.5, 0.5): diagonally dominant) with a
+// right-hand side; every timed launch is preceded by the device copy that restores the stack the kernel overwrites, and
+// ms_out[2] is that copy alone
+extern "C" int ggl_dev_chol_bench(int K, int p, int iters, double* ms_out)
+{
+    ARGCHK(K >= 1 && p >= 1 && iters >= 1 && ms_out, "arguments");
+    const size_t pp = (size_t)p * p, np = (size_t)K * pp;
+    std::vector<double> h(pp), hd(p);
+    unsigned long long s = 88172645463325252ull;
+    for (int i = 0; i < p; ++i) {
+        for (int j = i; j < p; ++j) {
+            s ^= s << 13; s ^= s >> 7; s ^= s << 17;
+            const double v = i == j ? 1.0 + p : (double)(s >> 11) / 9007199254740992.0 - 0.5;
+            h[(size_t)i * p + j] = h[(size_t)j * p + i] = v;
+        }
+        hd[i] = (double)((s >> 20) & 1023) / 1024.0 - 0.5;
+    }
+    DevBuf dS0, dD0, dS, dD, dOut;
+    HIPCHK(dS0.alloc(np));
+    HIPCHK(dD0.alloc((size_t)K * p));
+    HIPCHK(dS.alloc(np));
+    HIPCHK(dD.alloc((size_t)K * p));
+    HIPCHK(dOut.alloc((size_t)K * 4));
+    for (int k = 0; k < K; ++k) {
+        UP(dS0.p + (size_t)k * pp, h.data(), pp);
+        UP(dD0.p + (size_t)k * p, hd.data(), p);
+    }
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    for (int route = 0; route < 3; ++route) {
+        auto launch = [&]() -> hipError_t {
+            hipError_t e = hipMemcpyAsync(dS.p, dS0.p, np * sizeof(double), hipMemcpyDeviceToDevice, nullptr);
+            if (e != hipSuccess) return e;
+            e = hipMemcpyAsync(dD.p, dD0.p, (size_t)K * p * sizeof(double), hipMemcpyDeviceToDevice, nullptr);
+            if (e != hipSuccess) return e;
+            if (route < 2) launch_chol_predict(nullptr, dS.p, dD.p, 0.0, dOut.p, K, p, route == 0);
+            return hipSuccess;
+        };
+        for (int i = 0; i < 3; ++i) HIPCHK(launch());
+        HIPCHK(hipEventRecord(e0, nullptr));
+        for (int i = 0; i < iters; ++i) HIPCHK(launch());
+        HIPCHK(hipEventRecord(e1, nullptr));
+        HIPCHK(hipEventSynchronize(e1));
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+        ms_out[route] = ms / iters;
+    }
+    ms_out[0] -= ms_out[2];
+    ms_out[1] -= ms_out[2];
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     HIPCHK(hipGetLastError());

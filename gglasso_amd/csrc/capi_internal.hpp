@@ -17,9 +17,11 @@
 //   capi_data.hip       every way to an S from data, stateless and into a ctx's S: sample covariance of K instances and of
 //                       column subsets of one array, scaling by a diagonal, pairwise-complete covariance (NaN), weighted
 //                       covariance, Kendall rank correlation, latent correlation of mixed data; ggl_get_S; held-out scores
-//                       of a cross-validation (ggl_heldout_scores)
+//                       of a cross-validation (ggl_heldout_scores); predictive scores under weighted covariances, the
+//                       leave-one-out bandwidth search (ggl_weighted_predictive_scores)
 //   capi_nearcorr.hip   nearest-correlation projection of an indefinite S (stateless and in place on a ctx's S)
-//   capi_inference.hip  the output side: debiased graphical lasso and its standard errors (ggl_debias)
+//   capi_inference.hip  the output side: debiased graphical lasso and its standard errors (ggl_debias); batched Cholesky with
+//                       log det and quadratic form (ggl_cholesky_predict)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>

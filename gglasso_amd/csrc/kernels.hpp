@@ -566,4 +566,13 @@ void launch_nc_finish(hipStream_t st, const double* Y, const double* A, double* 
 void launch_debias(hipStream_t st, const double* M, const double* Theta, const double* nobs, double* Tout, double* SEout, int K,
                    int p, int tile);
 
+// Batched Cholesky with the outputs of a Gaussian predictive score (cholesky.hip).  S (K,p,p) symmetric, lower
+// triangle read, OVERWRITTEN by L; d (K,p) or null, OVERWRITTEN by L^-1 d; ridge >= 0 goes on the diagonal.
+// out[4k..] = { 2 sum log l_jj, d^T (S + ridge I)^-1 d (0 without d), smallest pivot l_jj^2, status }: status -1, or the first
+// column whose pivot is not positive and finite (then -inf, NaN, the smallest pivot up to that one).  One workgroup per
+// matrix, any p >= 1.  mfma false: the block update on the VALU (measurements).
+void launch_chol_predict(hipStream_t st, double* S, double* d, double ridge, double* out, int K, int p, bool mfma = true);
+// d (K,p) = X[:, target[r]] - mean[r,:] for X (p,N); mean null: X[:, target[r]]
+void launch_predict_rhs(hipStream_t st, const double* X, const double* mean, const int* target, double* d, int K, int p, int N);
+
 }  // namespace ggl

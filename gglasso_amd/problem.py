@@ -12,7 +12,8 @@ implementation is this package's own:
   ``correlation='kendall'`` from ``utils.skeptic_correlation`` (rank based), with ``correlation='mixed'`` from
   ``utils.mixed_correlation`` (binary beside continuous variables).
 * ``glasso_problem.from_time_series(X, at, bandwidth, ...)`` starts from ONE series with time stamps: S is the stack of
-  kernel-smoothed covariances (``utils.kernel_covariance``), the input of the Fused Graphical Lasso for time-varying networks.
+  kernel-smoothed covariances (``utils.kernel_covariance``), the input of the Fused Graphical Lasso for time-varying networks;
+  ``from_time_series_cv(X, at, bandwidths, ...)`` chooses the bandwidth from the series first (``bandwidth_search``).
 * ``edge_inference()`` tests the edges of the solution at hand and gives confidence intervals: the debiased graphical lasso
   (``utils.debiased_precision`` on the device, ``utils.edge_tests`` / ``utils.differential_tests`` on the host).
 """
@@ -232,6 +233,21 @@ class glasso_problem:
             S, n_eff = S[0], float(n_eff[0])
         prob = cls(S, n_eff, reg=reg, reg_params=reg_params, latent=latent, do_scaling=do_scaling)
         prob.weights, prob.eval_times = w, eval_times
+        return prob
+
+    @classmethod
+    def from_time_series_cv(cls, X, at, bandwidths, *, rule='min', ridge=0.0, eval_index=None, times=None, kernel='gaussian',
+                            cutoff=2.0 ** -53, reg='FGL', reg_params=None, latent=False, do_scaling=False, center=True):
+        """``from_time_series`` with the bandwidth chosen from the series: ``model_selection.bandwidth_search(X, bandwidths,
+        rule, ...)`` scores the grid by the leave-one-out Gaussian predictive likelihood (``rule``: ``'min'`` or ``'one_se'``;
+        ``ridge``, ``eval_index`` as there; ``times``, ``kernel``, ``cutoff``, ``center`` are shared by the search and the
+        stack), then the problem is built with the chosen bandwidth.  ``problem.bandwidth_`` is that bandwidth and
+        ``problem.bandwidth_stats`` the statistics of the search."""
+        h, stats = _ms.bandwidth_search(X, bandwidths, rule=rule, times=times, kernel=kernel, cutoff=cutoff, center=center,
+                                        ridge=ridge, eval_index=eval_index)
+        prob = cls.from_time_series(X, at, h, times=times, kernel=kernel, cutoff=cutoff, reg=reg, reg_params=reg_params,
+                                    latent=latent, do_scaling=do_scaling, center=center)
+        prob.bandwidth_, prob.bandwidth_stats = h, stats
         return prob
 
     @staticmethod

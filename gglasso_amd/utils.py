@@ -685,6 +685,173 @@ def kernel_covariance(X, at=None, bandwidth=None, times=None, kernel='gaussian',
 
 
 # -----------------------------------------------------------------------------------------------------------------
+# Leave-one-out choice of the bandwidth by the Gaussian predictive likelihood (Yin, Geng, Li, Wang 2010; Monti et al. 2014;
+# DESIGN 25).  For a bandwidth h and the observation i at time tau_i
+#     w_n = kappa((tau_n - tau_i) / h) for n != i,  w_i = 0;    m, S = the weighted mean and covariance of X under w
+#     score_i(h) = log det S + (x_i - m)^T S^-1 (x_i - m)        (-2 log-density of x_i, up to p log 2 pi)
+# On the device: the launches of the weighted covariance, then csrc/cholesky.hip (a batched Cholesky that returns the log
+# det and the quadratic form), behind ggl_weighted_predictive_scores; the covariances never leave the device.
+# -----------------------------------------------------------------------------------------------------------------
+def _chol_args(S, d, ridge):
+    """(S (K,p,p), d (K,p) or None, single) of what ``cholesky_predict`` accepts, C-contiguous float64."""
+    Sm = np.asarray(S, dtype=np.float64)
+    assert Sm.ndim in (2, 3) and Sm.shape[-1] == Sm.shape[-2] and Sm.shape[-1] >= 1 and Sm.shape[0] >= 1, \
+        f"cholesky_predict needs a square (p,p) matrix or a (K,p,p) stack of them, S has shape {Sm.shape}"
+    single = Sm.ndim == 2
+    Sm = as_c(Sm[None] if single else Sm)
+    if d is not None:
+        d = np.asarray(d, dtype=np.float64)
+        d = as_c(d[None] if single and d.ndim == 1 else d)
+        assert d.shape == Sm.shape[:2], f"d must have shape {Sm.shape[1:2] if single else Sm.shape[:2]}, has {d.shape}"
+    assert ridge >= 0 and np.isfinite(ridge), f"ridge = {ridge}: it must be non-negative and finite"
+    return Sm, d, single
+
+
+def _chol_result(out, single):
+    res = (out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy(), out[:, 3].astype(np.int64))
+    return tuple(a[0] for a in res) if single else res
+
+
+def cholesky_predict(S, d=None, ridge=0.0, device=0):
+    """Batched Cholesky factorisation ``S + ridge I = L L^T`` on the device (``ggl_cholesky_predict``, one workgroup per
+    matrix, the block updates on the FP64 matrix cores).  S: (p,p) or (K,p,p), symmetric, only the lower triangle is read;
+    d: (p,) / (K,p) or None.  Returns ``(logdet, quad, min_pivot, status)``, floats for one matrix and (K,) arrays for a stack:
+    ``logdet = 2 sum_j log l_jj``, ``quad = d^T (S + ridge I)^-1 d`` (0 without d), ``min_pivot`` the smallest ``l_jj^2``, and
+    ``status`` -1, or the first column whose pivot was not positive and finite -- then ``logdet = -inf``, ``quad = nan`` and
+    ``min_pivot`` the smallest pivot up to and including that one.  A matrix that is not positive definite is not an error.
+    The same bits on every call, instance k's independent of the others."""
+    Sm, dm, single = _chol_args(S, d, ridge)
+    K, p = Sm.shape[0], Sm.shape[1]
+    out = np.empty((K, 4))
+    _lib.require_gpu()
+    check(_lib.load().ggl_cholesky_predict(int(device), K, p, ptr(Sm), ptr(dm), float(ridge), ptr(out)))
+    return _chol_result(out, single)
+
+
+def host_cholesky_predict(S, d=None, ridge=0.0):
+    """numpy counterpart of ``cholesky_predict``: the plain column Cholesky with d as a border row and the same failure
+    rule, so the first failing column is the same."""
+    Sm, dm, single = _chol_args(S, d, ridge)
+    K, p = Sm.shape[0], Sm.shape[1]
+    out = np.empty((K, 4))
+    for k in range(K):
+        A = np.tril(Sm[k])
+        A[np.arange(p), np.arange(p)] += ridge
+        L, y = np.zeros_like(A), np.zeros(p)
+        lsum, minpiv, status = 0.0, np.inf, -1
+        with np.errstate(all='ignore'):
+            for j in range(p):
+                piv = A[j, j] - L[j, :j] @ L[j, :j]
+                minpiv = piv if (piv < minpiv or piv != piv) else minpiv
+                if not (piv > 0 and np.isfinite(piv)):
+                    status = j
+                    break
+                L[j, j] = np.sqrt(piv)
+                lsum += np.log(L[j, j])
+                L[j + 1:, j] = (A[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+                if dm is not None:                               # the border row: y = L^-1 d, one entry per column
+                    y[j] = (dm[k, j] - y[:j] @ L[j, :j]) / L[j, j]
+        if status >= 0:
+            out[k] = (-np.inf, np.nan, minpiv, status)
+        else:
+            out[k] = (2.0 * lsum, float(y @ y), minpiv, -1)
+    return _chol_result(out, single)
+
+
+def _loo_setup(X, bandwidths, times, eval_index):
+    """(X (p,N), bandwidths (H,) as given, times (N,), evaluation samples (M,) int32) of the bandwidth search."""
+    X = as_c(X)
+    assert X.ndim == 2 and X.shape[0] >= 1 and X.shape[1] >= 2, \
+        f"data must be a (p,N) array with variables in rows and N >= 2, has shape {X.shape}"
+    N = X.shape[1]
+    h = np.atleast_1d(np.asarray(bandwidths, dtype=np.float64)).reshape(-1)
+    assert h.size >= 1 and np.all(h > 0) and np.isfinite(h).all(), "bandwidths must be positive and finite"
+    t = np.arange(N, dtype=np.float64) if times is None else np.asarray(times, dtype=np.float64)
+    assert t.shape == (N,), f"times must have one entry per column of X, ({N},), has shape {t.shape}"
+    if eval_index is None:
+        ev = np.arange(N)
+    elif isinstance(eval_index, (int, np.integer)) and not isinstance(eval_index, bool):
+        assert 1 <= eval_index <= N, f"eval_index = {eval_index}: between 1 and N = {N} samples can be evaluated"
+        ev = np.unique(np.round(np.linspace(0, N - 1, int(eval_index))).astype(np.int64))
+    else:
+        ev = np.asarray(eval_index)
+        assert ev.ndim == 1 and ev.size >= 1 and np.issubdtype(ev.dtype, np.integer), "eval_index must be a 1-d integer array"
+        assert ev.min() >= 0 and ev.max() < N, f"eval_index must lie in [0, {N})"
+    return X, h, t, np.ascontiguousarray(ev, dtype=np.int32)
+
+
+def loo_weights(times, eval_index, bandwidth, kernel='gaussian', cutoff=2.0 ** -53):
+    """The (M,N) leave-one-out weights of one bandwidth: ``kernel_weights(times, times[eval_index], bandwidth, kernel,
+    cutoff)`` with the own column of every row set to exactly 0.  A row left without a positive weight is a ValueError naming
+    the bandwidth and the sample."""
+    ev = np.asarray(eval_index)
+    w = kernel_weights(times, np.asarray(times, dtype=np.float64)[ev], float(bandwidth), kernel, cutoff)
+    w[np.arange(ev.size), ev] = 0.0
+    alone = ~(w > 0).any(axis=1)
+    if alone.any():
+        raise ValueError(f"bandwidth {float(bandwidth):g}: the evaluation sample {int(ev[np.flatnonzero(alone)[0]])} has no "
+                         f"neighbour with a positive weight ({kernel} kernel); the bandwidth is too narrow for these times")
+    return w
+
+
+def _loo_scores(X, bandwidths, times, kernel, cutoff, center, ridge, eval_index, device, chunk, host):
+    """(SCORE (H,M), STATUS (H,M), N_EFF (H,), evaluation samples) in the order of ``bandwidths``."""
+    X, h, t, ev = _loo_setup(X, bandwidths, times, eval_index)
+    assert ridge >= 0 and np.isfinite(ridge), f"ridge = {ridge}: it must be non-negative and finite"
+    assert isinstance(chunk, (int, np.integer)) and chunk >= 0, f"chunk = {chunk}: a non-negative integer (0: by memory budget)"
+    (p, N), M = X.shape, ev.size
+    keep = h.size * M * N <= 1 << 26                             # the weights of the grid, kept where they take <= 512 MiB
+    Ws = [loo_weights(t, ev, hb, kernel, cutoff) for hb in h] if keep else None
+    if not keep:
+        for hb in h:                                             # every refusal before anything is uploaded
+            loo_weights(t, ev, hb, kernel, cutoff)
+    SCORE, STATUS, N_EFF = np.empty((h.size, M)), np.empty((h.size, M), dtype=np.int64), np.empty(h.size)
+    flags = _lib.COV_CENTER if center else 0
+    if not host:
+        _lib.require_gpu()
+    for b, hb in enumerate(h):
+        w = Ws[b] if keep else loo_weights(t, ev, hb, kernel, cutoff)
+        N_EFF[b] = effective_sample_size(w).min()
+        out = np.empty((M, 4))
+        if host:
+            for r in range(M):
+                n = np.flatnonzero(w[r])
+                S = host_weighted_covariance(X[:, n], w[r, n], center)
+                d = X[:, ev[r]] - (X[:, n] @ w[r, n] / w[r, n].sum() if center else 0.0)
+                out[r] = host_cholesky_predict(S, d, ridge)
+        else:
+            check(_lib.load().ggl_weighted_predictive_scores(int(device), p, N, ptr(X), M, ptr(w), ev.ctypes.data_as(_lib._ip),
+                                                             float(ridge), flags, int(chunk), ptr(out)))
+        STATUS[b] = out[:, 3].astype(np.int64)
+        SCORE[b] = np.where(STATUS[b] < 0, out[:, 0] + out[:, 1], np.inf)
+    return SCORE, STATUS, N_EFF, ev
+
+
+def loo_bandwidth_scores(X, bandwidths, times=None, kernel='gaussian', cutoff=2.0 ** -53, center=True, ridge=0.0,
+                         eval_index=None, device=0, chunk=0):
+    """Leave-one-out Gaussian predictive scores of a time series under kernel smoothing, on the device:
+    ``SCORE[b,r] = log det S + (x_i - m)^T S^-1 (x_i - m)`` for ``i = eval_index[r]``, with ``m, S`` the weighted mean and
+    covariance of X (p,N) under ``loo_weights(times, eval_index, bandwidths[b], kernel, cutoff)[r]`` -- minus twice the log
+    density of ``x_i`` under the estimate that never saw it, up to ``p log 2 pi``.  The smaller, the better the bandwidth predicts.
+
+    ``times`` (N,) default ``0..N-1``; ``kernel`` and ``cutoff`` as ``kernel_covariance``.  ``eval_index``: None (all N
+    samples), an integer m (m equally spaced samples) or an index array.  ``center=False``: ``m = 0`` and the weighted raw second
+    moment.  ``ridge >= 0`` is added to every diagonal before the factorisation.  ``chunk``: weight rows per device pass, 0
+    sizing it from a memory budget; the result does not depend on it.  A bandwidth that leaves an evaluation sample without a
+    neighbour is refused (ValueError) before anything is uploaded.  Returns ``SCORE (H,M)`` and ``STATUS (H,M)`` in the order
+    of ``bandwidths``: status -1, or the first column at which the covariance was found not positive definite -- its score is
+    +inf.  The same bits on every call."""
+    return _loo_scores(X, bandwidths, times, kernel, cutoff, center, ridge, eval_index, device, chunk, False)[:2]
+
+
+def host_loo_bandwidth_scores(X, bandwidths, times=None, kernel='gaussian', cutoff=2.0 ** -53, center=True, ridge=0.0,
+                              eval_index=None):
+    """numpy counterpart of ``loo_bandwidth_scores`` (engines without the device route): the same weights, the same formula
+    through ``host_weighted_covariance`` and ``host_cholesky_predict``, the same refusals."""
+    return _loo_scores(X, bandwidths, times, kernel, cutoff, center, ridge, eval_index, 0, 0, True)[:2]
+
+
+# -----------------------------------------------------------------------------------------------------------------
 # Nearest-correlation projection of an indefinite S (Higham 2002, with Dykstra's correction; what R's Matrix::nearPD does
 # behind latentcor / mixedCCA).  The skeptic, pairwise-complete and latent matrices above need not be positive semidefinite,
 # and the graphical lasso objective is unbounded below for small lambda1 when S is not.  Per matrix, on D^-1/2 S D^-1/2 with

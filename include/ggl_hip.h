@@ -30,7 +30,8 @@ extern "C" {
  * ggl_diag_stats, ggl_covariance_subsets, ggl_set_S_from_subsets, ggl_edge_stability, ggl_kendall_counts, ggl_kendall_skeptic,
  * ggl_set_S_from_kendall, ggl_covariance_pairwise, ggl_covariance_pairwise_subsets, ggl_set_S_from_data_pairwise,
  * ggl_set_S_from_subsets_pairwise, ggl_covariance_weighted, ggl_set_S_from_weighted, ggl_mixed_correlation,
- * ggl_set_S_from_mixed, ggl_nearest_correlation, ggl_project_S, ggl_heldout_scores) leave every existing layout alone and the number where it is. */
+ * ggl_set_S_from_mixed, ggl_nearest_correlation, ggl_project_S, ggl_heldout_scores, ggl_debias, ggl_cholesky_predict,
+ * ggl_weighted_predictive_scores) leave every existing layout alone and the number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -945,6 +946,38 @@ int ggl_debias(int device, int K, int p, const double *Theta_host, const double 
 /* measurement: average milliseconds of `iters` launches on random device data (HIP events); ms_out[0] the full product
  * M = A T (launch_gemm_right), ms_out[1] k_debias with its epilogues.  tile: 0 (by size), 32, 64. */
 int ggl_dev_debias_bench(int K, int p, int tile, int iters, double *ms_out);
+
+/* ---- Gaussian predictive scores by a batched FP64 Cholesky factorisation (cholesky.hip): the log det and the
+ * quadratic form behind the leave-one-out choice of a kernel bandwidth (Yin et al. 2010; Monti et al. 2014).  Entry points
+ * that are only ADDED: GGL_VERSION stays where it is.
+ *
+ * ggl_cholesky_predict: S_host (K,p,p) symmetric (only the lower triangle is read), d_host (K,p) or NULL, ridge >= 0 added
+ * to every diagonal.  out (K,4) per instance:
+ *     out[0] = log det (S + ridge I) = 2 sum_j log l_jj        out[1] = d^T (S + ridge I)^-1 d   (0 with d_host NULL)
+ *     out[2] = the smallest pivot l_jj^2                        out[3] = status
+ * status is -1 if every pivot a_jj - sum_m l_jm^2 was positive and finite, else the first column whose pivot was not; then
+ * out[0] = -inf, out[1] = NaN and out[2] is the smallest pivot up to and including the failing one (NaN if that one is NaN).
+ * A matrix that is not positive definite, or holds a NaN, is a status and not an error.  One workgroup per matrix, any
+ * p >= 1, fixed summation orders and no atomics: two calls give the same bits and instance k's bits do not depend on K.
+ * GGL_E_ARG before any device work, nothing written to out: K or p < 1, S_host or out NULL, ridge negative or not finite.
+ *
+ * ggl_weighted_predictive_scores: row r of w_host (M,N) weights the columns of X_host (p,N) as in ggl_covariance_weighted
+ * (same kernels, S_r bit for bit); the call scores column target[r] of X under the Gaussian with that mean and covariance:
+ * d = x_target - m_r, formed on the device from the weighted means (without GGL_COV_CENTER: d = x_target, S_r the weighted
+ * raw second moment), out (M,4) as above for (S_r, d).  w[r,target[r]] need not be 0; a leave-one-out caller sets it.
+ * X goes up once; the rows are processed `chunk` at a time, chunk = 0 sizing the chunk so that its covariance stack takes
+ * at most 256 MiB (and at most 65535 rows).  out does not depend on chunk, bit for bit.
+ * flags: 0 or GGL_COV_CENTER, | GGL_COV_FULL_RANGE, | one of GGL_COV_TILE32 / GGL_COV_TILE64.
+ * GGL_E_ARG before any device work, nothing written to out: what ggl_covariance_weighted refuses, with its messages (also a
+ * negative or non-finite weight and a weight row without a positive weight, found on the host here); GGL_COV_SCALE; ridge
+ * negative or not finite; a target outside [0,N) (the row is named); chunk < 0; a NULL buffer; M or p < 1. */
+int ggl_cholesky_predict(int device, int K, int p, const double *S_host, const double *d_host, double ridge, double *out);
+int ggl_weighted_predictive_scores(int device, int p, int N, const double *X_host, int M, const double *w_host,
+                                   const int *target, double ridge, int flags, int chunk, double *out);
+/* measurement: average milliseconds of `iters` launches of k_chol_predict on K random SPD (p,p) matrices with right-hand
+ * sides (HIP events, the stack restored by a device copy in front of every launch; ms_out[2] is that copy alone):
+ * ms_out[0] the update on the matrix cores, ms_out[1] the same kernel with the update on the VALU. */
+int ggl_dev_chol_bench(int K, int p, int iters, double *ms_out);
 
 #ifdef __cplusplus
 }
