@@ -178,6 +178,8 @@ _SIGNATURES = {
     "ggl_cholesky_predict": ([_i, _i, _i, _dp, _dp, _d, _dp], _i),
     "ggl_weighted_predictive_scores": ([_i, _i, _i, _dp, _i, _dp, _ip, _d, _i, _i, _dp], _i),
     "ggl_dev_chol_bench": ([_i, _i, _i, _dp], _i),
+    "ggl_neighborhood_path": ([_i, _i, _i, _dp, _i, _dp, _i, _d, _i, _dp, _dp, _ip], _i),
+    "ggl_neighborhood_stability": ([_vp, _i, _dp, _i, _d, _i, _d, ctypes.POINTER(ctypes.c_longlong), _ip, _dp, _ip], _i),
 }
 
 # libggl_hip_dev.so only (-DGGL_DEV)

@@ -22,6 +22,8 @@
 //   capi_nearcorr.hip   nearest-correlation projection of an indefinite S (stateless and in place on a ctx's S)
 //   capi_inference.hip  the output side: debiased graphical lasso and its standard errors (ggl_debias); batched Cholesky with
 //                       log det and quadratic form (ggl_cholesky_predict)
+//   capi_neighborhood.hip  Meinshausen-Buhlmann neighbourhood selection: the lasso path of every node (ggl_neighborhood_path)
+//                       and the same on a ctx's S with the edge stability of the result (ggl_neighborhood_stability)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>

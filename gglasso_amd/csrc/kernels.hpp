@@ -575,4 +575,15 @@ void launch_chol_predict(hipStream_t st, double* S, double* d, double ridge, dou
 // d (K,p) = X[:, target[r]] - mean[r,:] for X (p,N); mean null: X[:, target[r]]
 void launch_predict_rhs(hipStream_t st, const double* X, const double* mean, const int* target, double* d, int K, int p, int N);
 
+// Meinshausen-Buhlmann neighbourhood selection (neighborhood.hip).  S (M,p,p) symmetric, lam (L) on the device,
+// positive and descending.  The result of (matrix m, lambda l) is slot m * strideM + l * strideL of coef (slots of (p,p):
+// ROW j = beta^(j), diagonal 0), resvar (slots of p, may be null) and info (slots of (p,2): sweeps, status 0 converged / 1 a
+// cap was reached / 2 non-finite, then the row is NaN from that lambda on).  1 <= p <= MB_MAX_P.
+static constexpr int MB_MAX_P = 2048;
+void launch_mb_path(hipStream_t st, const double* S, int M, int p, const double* lam, int L, double tol, int max_sweeps,
+                    double* coef, double* resvar, int* info, size_t strideM, size_t strideL);
+// nmat (p,p) matrices as launch_mb_path left them, in place: rule 0 the transpose (column j = beta^(j)), 1 / 2 the 'and' /
+// 'or' matrix -- of beta^(j)_i and beta^(i)_j the one of smaller / larger magnitude to (i,j) and (j,i), the former on a tie
+void launch_mb_symmetrize(hipStream_t st, double* C, size_t nmat, int p, int rule);
+
 }  // namespace ggl

@@ -703,7 +703,7 @@ def _host_edge_counts(Theta, t):
 
 def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.05, seed=0, indices=None, t=1e-8, center=True,
                  scale=False, tol=1e-7, rtol=1e-7, max_iter=1000, store_all=False, lambdas_per_batch=None, correlation=None,
-                 missing=None, min_pairs=2, project=False):
+                 missing=None, min_pairs=2, project=False, method='glasso', rule='and'):
     """StARS for the Single Graphical Lasso from observations ``X`` (p,N), variables in rows.  Returns ``(sol, stats)``.
 
     * Subsamples: ``stars_subsamples(N, n_subsamples, subsample_size, seed)``, or ``indices`` (B,b) given by the caller
@@ -741,10 +741,28 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     (``utils.nearest_correlation`` with its defaults), after any ``correlation=`` and ``missing=`` choice.  On the device one
     ``engine.project_S(period=B)`` projects the B subset matrices where they lie, before they are used; an engine without
     ``project_S`` gets the numpy twin's matrices (``utils.host_nearest_correlation``).  ``stats['PROJECTION']`` is the info of
-    the final fit's matrix."""
+    the final fit's matrix.
+
+    ``method='mb'``: the estimator at every point is Meinshausen-Buhlmann neighbourhood selection instead of the graphical
+    lasso (``utils.neighborhood_selection``; ``method = "mb"`` of R's huge): one lasso per variable on ``S_r``, the grid walked
+    in descending order with warm starts, and ``Theta[l,r]`` -- ``THETA`` with ``store_all`` -- is the coefficient matrix
+    symmetrised by ``rule`` (``'and'`` / ``'or'``, ``utils.neighborhood_graph``), to which the same ``|.| >= t`` applies.
+    Subsamples, ``correlation=``, ``missing=``, ``project=``, ``lambdas_per_batch`` (every batch starts its path anew),
+    ``store_all``, the keys of ``stats`` and ``stars_select`` are those of the graphical lasso; ``tol`` is the path's tolerance,
+    ``rtol`` and ``max_iter`` are not used.  On the device one ctx of B instances holds the subsample matrices and
+    ``HipEngine.neighborhood_stability`` returns the integers; an engine without it gets ``utils.host_neighborhood_selection``
+    on numpy matrices.  ``FAILED`` lists a lambda at which a node of a subsample met a non-finite value (status 2); nodes that
+    reached a cap (status 1) raise a ``RuntimeWarning`` with their number and fail nothing.  ``sol`` is the path's result at the
+    chosen lambda on the matrix of all N observations: ``{'adjacency', 'coef', 'resvar', 'lambda1'}`` -- the boolean graph under
+    ``rule`` and ``t``, the raw coefficients (column j: node j's) and the residual variances.  The lasso is not invariant
+    under rescaling a variable: ``mb`` works on whatever scale ``center`` / ``scale`` produce, and ``scale=True`` (correlations)
+    is what huge does.  With ``method='glasso'`` nothing of this applies."""
     import warnings
     from . import solver as _solver, utils
     from .batch import _sgl_batch_impl
+    assert method in ('glasso', 'mb'), "method must be 'glasso' or 'mb'"
+    mb = method == 'mb'
+    assert not mb or rule in ('and', 'or'), "rule must be 'and' or 'or'"
     assert correlation in (None, 'kendall', 'mixed'), "correlation must be None (Pearson), 'kendall' or 'mixed'"
     assert missing in (None, 'pairwise'), "missing must be None (complete data) or 'pairwise'"
     kendall, mixed = correlation == 'kendall', correlation == 'mixed'
@@ -772,7 +790,9 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     per = L if lambdas_per_batch is None else max(1, int(lambdas_per_batch))
     route = "set_kendall_subsets" if kendall else ("set_mixed_subsets" if mixed else "set_data_subsets")
     on_device = hasattr(_solver.ENGINE, route) and \
-        hasattr(_solver.ENGINE, "edge_stability") and (not project or hasattr(_solver.ENGINE, "project_S"))
+        hasattr(_solver.ENGINE, "neighborhood_stability" if mb else "edge_stability") and \
+        (not project or hasattr(_solver.ENGINE, "project_S"))
+    capped = 0
     eye = np.eye(p)
     NUM = np.zeros(L, dtype=np.int64)
     failed = np.zeros(L, dtype=bool)
@@ -810,6 +830,29 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
         def after(eng, results):
             got['edges'] = eng.edge_stability(B, t, counts=store_all)
 
+        if mb:
+            if on_device:
+                # a ctx of B instances, shaped by ONE placeholder matrix; `before` writes the subsample matrices into its S
+                ph = np.broadcast_to(eye, (B, p, p))
+                eng = _solver.ENGINE(ph, ph, ph, np.broadcast_to(np.zeros((p, p)), (B, p, p)))
+                try:
+                    before(eng)
+                    out = eng.neighborhood_stability(lam[sl], rule, tol=tol, t=t, counts=store_all, stack=store_all)
+                finally:
+                    eng.close()
+                NUM[sl], status = out['num'], out['status']
+                if store_all:
+                    COUNTS[sl], THETA[sl] = out['counts'], out['stack']
+            else:
+                W, inf = utils.host_neighborhood_selection(S_host, lam[sl], rule, tol=tol, return_info=True)
+                Th = np.ascontiguousarray(np.swapaxes(W, 0, 1))              # (B,nl,p,p) -> (nl,B,p,p)
+                cnt, NUM[sl] = _host_edge_counts(Th, t)
+                status = np.swapaxes(inf['STATUS'], 0, 1)
+                if store_all:
+                    COUNTS[sl], THETA[sl] = cnt, Th
+            failed[sl] = (status == 2).any(axis=(1, 2))
+            capped += int((status == 1).sum())
+            continue
         if on_device:
             # the S argument only shapes the ctx: ONE (p,p) matrix, which the batch hands to the engine as a broadcast view
             # (uploaded once, replicated on the device); `before` then writes the real S there
@@ -836,6 +879,9 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     if failed.any():
         warnings.warn(f"StARS: a subsample failed at lambda1 = {[float(v) for v in lam[failed]]}; these grid points have no instability "
                       f"and are not chosen", RuntimeWarning, stacklevel=2)
+    if capped:
+        warnings.warn(f"StARS, method='mb': {capped} (subsample, lambda1, node) units reached a cap of the coordinate descent "
+                      f"before tol = {tol}; their coefficients are used as they are", RuntimeWarning, stacklevel=2)
     ix, Dbar = stars_select(D, beta)
     if kendall:
         S_full = utils.skeptic_correlation(X) if on_device else utils.host_skeptic_correlation(X)
@@ -851,7 +897,20 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     projection = None
     if project:
         S_full, projection = (utils.nearest_correlation if on_device else utils.host_nearest_correlation)(S_full, return_info=True)
-    sol, _ = _solver.ADMM_SGL(S_full, lam[ix], eye, X_0=eye, tol=tol, rtol=rtol, max_iter=max_iter, verbose=False)
+    if mb and not np.all(np.isfinite(S_full)):
+        # (the stateless call refuses such a matrix; the subsamples that draw the observation behind it are in FAILED)
+        warnings.warn("StARS, method='mb': the matrix of all N observations holds a non-finite value; there is no final fit and "
+                      "sol holds NaN", RuntimeWarning, stacklevel=2)
+        sol = {'adjacency': np.zeros((p, p), dtype=bool), 'coef': np.full((p, p), np.nan), 'resvar': np.full(p, np.nan),
+               'lambda1': lam[ix]}
+    elif mb:
+        path = utils.neighborhood_selection if on_device else utils.host_neighborhood_selection
+        W, inf = path(S_full, lam[:ix + 1], rule, tol=tol, return_info=True)
+        with np.errstate(invalid='ignore'):
+            sol = {'adjacency': (np.abs(W[ix]) >= t) & (W[ix] != 0), 'coef': inf['COEF'][ix],
+                   'resvar': inf['RESVAR'][ix], 'lambda1': lam[ix]}
+    else:
+        sol, _ = _solver.ADMM_SGL(S_full, lam[ix], eye, X_0=eye, tol=tol, rtol=rtol, max_iter=max_iter, verbose=False)
     stats = {'LAMBDA': lam, 'INSTABILITY': D, 'INSTABILITY_MONOTONE': Dbar, 'NUM': [int(n) for n in NUM], 'IX': ix,
              'BEST': {'lambda1': lam[ix]}, 'INDICES': idx, 'subsample_size': b, 'n_subsamples': B,
              'FAILED': [int(l) for l in np.flatnonzero(failed)]}

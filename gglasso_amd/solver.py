@@ -229,6 +229,32 @@ class HipEngine:
                                           num.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
         return (num, tab) if counts else num
 
+    def neighborhood_stability(self, lambda_range, rule='and', tol=1e-7, max_sweeps=10000, t=1e-8, counts=False, stack=False):
+        """Meinshausen-Buhlmann neighbourhood selection on the K matrices the ctx's S holds -- the B = K subsample matrices
+        a ``set_*_subsets`` call wrote -- along the descending grid ``lambda_range`` (``ggl_neighborhood_stability``, see
+        ``utils.neighborhood_selection``), and the edge stability of the result: the symmetrised (L,K,p,p) stack stays on the
+        device and is reduced as in ``edge_stability``.  Returns a dict: ``num`` (L,) int64, ``sweeps`` and ``status``
+        (L,K,p), with ``counts`` the (L,p,p) int32 tables, with ``stack`` the stack itself."""
+        import ctypes
+        from .utils import _MB_RULES
+        lam = as_c(np.asarray(lambda_range, dtype=np.float64).reshape(-1))
+        assert rule in ('and', 'or'), f"rule = {rule!r}: 'and' or 'or'"
+        L = lam.size
+        num = np.zeros(L, dtype=np.int64)
+        info = np.empty((L, self.K, self.p, 2), dtype=np.int32)
+        tab = np.empty((L, self.p, self.p), dtype=np.int32) if counts else None
+        W = np.empty((L, self.K, self.p, self.p)) if stack else None
+        check(self.lib.ggl_neighborhood_stability(self.h, L, ptr(lam), _MB_RULES[rule], float(tol), int(max_sweeps), float(t),
+                                                  num.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)),
+                                                  None if tab is None else tab.ctypes.data_as(_lib._ip), ptr(W),
+                                                  info.ctypes.data_as(_lib._ip)))
+        out = {'num': num, 'sweeps': info[..., 0].astype(np.int64), 'status': info[..., 1].astype(np.int64)}
+        if counts:
+            out['counts'] = tab
+        if stack:
+            out['stack'] = W
+        return out
+
     def heldout_scores(self, X, test_idx, center=True, out=None):
         """K-fold cross-validation over the Theta snapshots of a batch of K = L * F points (instance l * F + f: fold f at
         lambda l): (K,4) = ``<S_test[k % F], Theta_k>``, log det Theta_k, count_nonzero(Theta_k), lambda_min(Theta_k), with

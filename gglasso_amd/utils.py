@@ -1151,3 +1151,181 @@ def differential_tests(T, SE, pairs=None, alpha=0.05, method='bh'):
         pv, adj, rej = _tests_of_z(z[None], alpha, method)
         out.append(dict(pair=(a, b), z=z, pvalue=pv[0], pvalue_adj=adj[0], reject=rej[0]))
     return out
+
+
+# -----------------------------------------------------------------------------------------------------------------
+# Meinshausen-Buhlmann neighbourhood selection (2006; ``method = "mb"`` of R's huge, the default of SpiecEasi): one lasso per
+# node on a shared matrix, the graph from the supports.  For a symmetric S with positive diagonal, node j and lambda > 0
+#     beta^(j) = argmin over beta with beta_j = 0 of  1/2 beta' S beta - s_j' beta + lambda sum_{k != j} |beta_k|
+# (with S = X X' / n the lasso of variable j on the others, lambda = glmnet's / scikit-learn's alpha).  On the device:
+# csrc/neighborhood.hip, one wave per (matrix, node), the whole descending grid in one launch; DESIGN 26.
+# -----------------------------------------------------------------------------------------------------------------
+_MB_RULES = {'raw': 0, 'and': 1, 'or': 2}
+
+
+def _mb_args(S, lambda_range, rule, tol, max_sweeps):
+    """(S (M,p,p) C-contiguous, the grid in descending order, single) of what ``neighborhood_selection`` accepts."""
+    Sm = np.asarray(S, dtype=np.float64)
+    assert Sm.ndim in (2, 3) and Sm.shape[-1] == Sm.shape[-2] and Sm.shape[-1] >= 1 and Sm.shape[0] >= 1, \
+        f"neighborhood_selection needs a square (p,p) matrix or a (M,p,p) stack of them, S has shape {Sm.shape}"
+    single = Sm.ndim == 2
+    lam = np.sort(np.atleast_1d(np.asarray(lambda_range, dtype=np.float64)).reshape(-1))[::-1].copy()
+    assert lam.size >= 1 and np.all(lam > 0) and np.all(np.isfinite(lam)), "every lambda must be positive and finite"
+    assert np.all(np.diff(lam) < 0), "the lambdas of a grid must differ"
+    assert rule in _MB_RULES, f"rule = {rule!r}: 'and', 'or' or 'raw'"
+    assert tol >= 0 and np.isfinite(tol), f"tol = {tol}: it must be non-negative and finite"
+    assert int(max_sweeps) >= 1, f"max_sweeps = {max_sweeps}: at least one sweep is needed"
+    return as_c(Sm[None] if single else Sm), lam, single
+
+
+def neighborhood_graph(coef, rule='and'):
+    """The symmetric matrix of a (...,p,p) stack of raw coefficients (column j holds ``beta^(j)``): for i < j, of
+    ``a = beta^(j)_i`` and ``b = beta^(i)_j`` the one of smaller (``'and'``) or larger (``'or'``) magnitude, ``a`` on a tie,
+    at (i,j) and (j,i).  Bitwise symmetric, zero diagonal; its non-zero pattern is the AND / OR graph.  Host only: a
+    selection, no arithmetic, so it is bit for bit what ``k_mb_symmetrize`` writes."""
+    assert rule in ('and', 'or'), f"rule = {rule!r}: 'and' or 'or'"
+    a = np.asarray(coef, dtype=np.float64)
+    b = np.swapaxes(a, -1, -2)
+    with np.errstate(invalid='ignore'):
+        take_b = (np.abs(b) < np.abs(a)) if rule == 'and' else (np.abs(b) > np.abs(a))
+    up = np.triu(np.where(take_b, b, a), 1)
+    return up + np.swapaxes(up, -1, -2)
+
+
+def _mb_result(W, raw, resvar, info, lam, single, return_info):
+    pick = (lambda a: a[0]) if single else (lambda a: a)
+    if not return_info:
+        return pick(W)
+    return pick(W), {'LAMBDA': lam, 'COEF': pick(raw), 'RESVAR': pick(resvar), 'SWEEPS': pick(info[..., 0].astype(np.int64)),
+                     'STATUS': pick(info[..., 1].astype(np.int64))}
+
+
+def neighborhood_selection(S, lambda_range, rule='and', tol=1e-7, max_sweeps=10000, device=0, return_info=False):
+    """Meinshausen-Buhlmann neighbourhood selection on the device (``ggl_neighborhood_path``).  S: (p,p) or (M,p,p),
+    symmetric with a positive diagonal, p <= 2048; the grid is used in descending order, every lambda warm-started from the
+    one before.  Returns the (L,p,p) or (M,L,p,p) stack of symmetrised coefficient matrices (``neighborhood_graph``;
+    ``rule='raw'``: the raw columns); its non-zero pattern is the graph.
+
+    The method is cyclic coordinate descent with covariance updates on an active set (glmnet, huge).  ``tol`` bounds a sweep's
+    ``max_k |change of beta_k| S_kk``; a (node, lambda) is finished only once the gradient recomputed from beta, one further
+    sweep and one further screen of all variables change nothing beyond ``tol`` and find no violator.  ``max_sweeps`` caps
+    the sweeps of one (node, lambda).
+
+    ``return_info``: also a dict with ``LAMBDA`` (L,), ``COEF`` ([M,]L,p,p: column j is ``beta^(j)``), ``RESVAR`` ([M,]L,p: the
+    residual variances ``S_jj - 2 s_j' beta + beta' S beta``), ``SWEEPS`` and ``STATUS`` ([M,]L,p: 0 converged, 1 a cap was
+    reached, 2 a non-finite value -- that node's coefficients are NaN from that lambda on).  (The raw columns are a second
+    call of the library; the bits of a call do not change.)  The same bits on every call, matrix m's independent of the
+    others, a lambda's independent of those behind it."""
+    Sm, lam, single = _mb_args(S, lambda_range, rule, tol, max_sweeps)
+    M, p, L = Sm.shape[0], Sm.shape[1], lam.size
+    _lib.require_gpu()
+    lib = _lib.load()
+
+    def call(r, with_resvar):
+        coef, info = np.empty((M, L, p, p)), np.empty((M, L, p, 2), dtype=np.int32)
+        resvar = np.empty((M, L, p)) if with_resvar else None
+        check(lib.ggl_neighborhood_path(int(device), M, p, ptr(Sm), L, ptr(lam), _MB_RULES[r], float(tol), int(max_sweeps),
+                                        ptr(coef), ptr(resvar), info.ctypes.data_as(_lib._ip)))
+        return coef, resvar, info
+
+    if not return_info:
+        return _mb_result(call(rule, False)[0], None, None, None, lam, single, False)
+    raw, resvar, info = call('raw', True)
+    W = raw if rule == 'raw' else call(rule, False)[0]
+    return _mb_result(W, raw, resvar, info, lam, single, True)
+
+
+def _host_mb_node(S, j, lam, tol, max_sweeps, max_rounds=100):
+    """The path of node j: (beta (L,p), resvar (L,), sweeps (L,), status (L,)) -- ``k_mb_path``'s unit of work, step by step."""
+    p, L = S.shape[0], lam.size
+    beta, g = np.zeros(p), S[j].copy()
+    member = np.zeros(p, dtype=bool)
+    act = np.zeros(0, dtype=np.int64)
+    out_b, out_r = np.zeros((L, p)), np.zeros(L)
+    out_s, out_st = np.zeros(L, dtype=np.int64), np.zeros(L, dtype=np.int64)
+    dead = False
+
+    def sweep(lamv):
+        dmax = 0.0
+        for k in act:
+            skk, bk = S[k, k], beta[k]
+            z = g[k] + skk * bk
+            b = np.sign(z) * max(abs(z) - lamv, 0.0) / skk
+            d = b - bk
+            if d != 0.0:
+                g[:] -= d * S[k]
+                beta[k] = b
+            c = abs(d) * skk
+            dmax = c if c > dmax else dmax
+        return dmax
+
+    def screen(lamv):
+        viol = ~member & (np.abs(g) > lamv)
+        viol[j] = False
+        member[viol] = True
+        return int(viol.sum())
+
+    def bad():
+        return not (np.all(np.isfinite(g)) and np.all(np.isfinite(beta[act])))
+
+    for l in range(L):
+        lamv, sweeps, status = lam[l], 0, 1
+        if dead or bad():
+            status = 2
+        else:
+            d1 = 0.0
+            for rnd in range(max_rounds):
+                nviol = screen(lamv)
+                act = np.flatnonzero(member)
+                if nviol == 0 and (not (d1 > tol) if rnd > 0 else act.size == 0):
+                    status = 0
+                    break
+                conv = False
+                while sweeps < max_sweeps:
+                    dm = sweep(lamv)
+                    sweeps += 1
+                    if not (dm > tol):
+                        conv = True
+                        break
+                if not conv:
+                    break
+                g[:] = S[j]
+                for k in act:
+                    if beta[k] != 0.0:
+                        g[:] -= beta[k] * S[k]
+                if sweeps >= max_sweeps:
+                    break
+                d1 = sweep(lamv)
+                sweeps += 1
+                if bad():
+                    status = 2
+                    break
+            if status == 1 and bad():
+                status = 2
+        dead = status == 2
+        if dead:
+            out_b[l], out_r[l] = np.nan, np.nan
+            out_b[l, j] = 0.0
+        else:
+            out_b[l] = beta
+            out_r[l] = S[j, j] - float(np.sum(beta[act] * (S[j, act] + g[act])))
+        out_s[l], out_st[l] = sweeps, status
+    return out_b, out_r, out_s, out_st
+
+
+def host_neighborhood_selection(S, lambda_range, rule='and', tol=1e-7, max_sweeps=10000, return_info=False):
+    """numpy twin of ``neighborhood_selection``: the same algorithm in the same order (screen, sweeps over the ascending
+    active set, the gradient recomputed in ascending order, one further sweep, one further screen; the same caps and the same
+    statuses), in float64 without fused multiply-adds, so its last bits differ from the device's.  For engines without the
+    device route and for tests without a GPU."""
+    Sm, lam, single = _mb_args(S, lambda_range, rule, tol, max_sweeps)
+    M, p, L = Sm.shape[0], Sm.shape[1], lam.size
+    raw, resvar = np.zeros((M, L, p, p)), np.zeros((M, L, p))
+    info = np.zeros((M, L, p, 2), dtype=np.int32)
+    with np.errstate(all='ignore'):
+        for m in range(M):
+            for j in range(p):
+                b, r, s, st = _host_mb_node(Sm[m], j, lam, float(tol), int(max_sweeps))
+                raw[m, :, :, j], resvar[m, :, j], info[m, :, j, 0], info[m, :, j, 1] = b, r, s, st
+    W = raw if rule == 'raw' else neighborhood_graph(raw, rule)
+    return _mb_result(W, raw, resvar, info, lam, single, return_info)

@@ -31,7 +31,7 @@ extern "C" {
  * ggl_set_S_from_kendall, ggl_covariance_pairwise, ggl_covariance_pairwise_subsets, ggl_set_S_from_data_pairwise,
  * ggl_set_S_from_subsets_pairwise, ggl_covariance_weighted, ggl_set_S_from_weighted, ggl_mixed_correlation,
  * ggl_set_S_from_mixed, ggl_nearest_correlation, ggl_project_S, ggl_heldout_scores, ggl_debias, ggl_cholesky_predict,
- * ggl_weighted_predictive_scores) leave every existing layout alone and the number where it is. */
+ * ggl_weighted_predictive_scores, ggl_neighborhood_path, ggl_neighborhood_stability) leave every existing layout alone and the number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -978,6 +978,45 @@ int ggl_weighted_predictive_scores(int device, int p, int N, const double *X_hos
  * sides (HIP events, the stack restored by a device copy in front of every launch; ms_out[2] is that copy alone):
  * ms_out[0] the update on the matrix cores, ms_out[1] the same kernel with the update on the VALU. */
 int ggl_dev_chol_bench(int K, int p, int iters, double *ms_out);
+
+/* ---- Meinshausen-Buhlmann neighbourhood selection (2006; method = "mb" of R's huge): one lasso per node on a shared matrix
+ * (neighborhood.hip).  Entry points that are only ADDED: GGL_VERSION stays where it is.
+ *
+ * For a symmetric S with positive diagonal, node j and lambda > 0:
+ *     beta^(j) = argmin over beta with beta_j = 0 of  1/2 beta' S beta - s_j' beta + lambda sum_{k != j} |beta_k|
+ * by cyclic coordinate descent with covariance updates on an active set, one wave per (matrix, node), the grid walked in
+ * descending order inside the kernel with warm starts.  A (node, lambda) is finished only in a state where the gradient
+ * recomputed from beta, one further sweep and one further screen of all variables move nothing beyond tol and find no
+ * violator.  Largest p: 2048.
+ *
+ * ggl_neighborhood_path: S_host (M,p,p); lam (L) strictly descending, positive, finite; tol bounds a sweep's
+ * max_k |change of beta_k| S_kk; max_sweeps caps the sweeps of one (node, lambda).
+ *   coef_out (M,L,p,p):  rule GGL_MB_RAW: column j holds beta^(j).  GGL_MB_AND / GGL_MB_OR: for i < j, of a = beta^(j)_i and
+ *                        b = beta^(i)_j the one of smaller / larger magnitude, a on a tie, written to (i,j) and (j,i):
+ *                        bitwise symmetric with a zero diagonal
+ *   resvar_out (M,L,p) or NULL:  tau_j^2 = S_jj - 2 s_j' beta + beta' S beta
+ *   info_out (M,L,p,2) int32:  sweeps, status -- 0 converged, 1 a cap was reached (max_sweeps, or 100 screens), 2 a
+ *                        non-finite value: beta^(j) is NaN at this lambda and every later one
+ * No atomics, fixed summation orders: two calls give the same bits, matrix m's do not depend on M, and lambda l's do not
+ * depend on the lambdas behind it.
+ * GGL_E_ARG before any device work, nothing written: M, L or p < 1; p > 2048; a NULL buffer other than resvar_out; a lambda
+ * that is not positive and finite (named); a grid that is not strictly descending; tol negative or not finite;
+ * max_sweeps < 1; an unknown rule; a non-finite entry or a non-positive diagonal entry of S_host (matrix and index named).
+ *
+ * ggl_neighborhood_stability: the same path on the S of a ctx, its K instances taken as B = K matrices (what
+ * ggl_set_S_from_subsets, _kendall, _mixed, _pairwise and ggl_project_S leave there: the data went up once, the matrices never
+ * exist on the host), rule GGL_MB_AND or GGL_MB_OR.  The symmetrised (L,B,p,p) stack stays on the device and is reduced by the
+ * kernel of ggl_edge_stability: num_out (L) and counts_out (L,p,p) int32 or NULL as there, for |W_ij| >= t.  stack_out
+ * (L,B,p,p) or NULL; info_out (L,B,p,2) as above.  S is on the device: a non-finite value there is status 2 of the nodes it
+ * reaches, not an error.  GGL_E_ARG as above (without the checks of S_host), also: GGL_MB_RAW, t negative or not finite, a ctx
+ * with instance dimensions. */
+#define GGL_MB_RAW 0
+#define GGL_MB_AND 1
+#define GGL_MB_OR 2
+int ggl_neighborhood_path(int device, int M, int p, const double *S_host, int L, const double *lam, int rule, double tol,
+                          int max_sweeps, double *coef_out, double *resvar_out, int *info_out);
+int ggl_neighborhood_stability(ggl_ctx *ctx, int L, const double *lam, int rule, double tol, int max_sweeps, double t,
+                               long long *num_out, int *counts_out, double *stack_out, int *info_out);
 
 #ifdef __cplusplus
 }
