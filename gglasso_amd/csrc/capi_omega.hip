@@ -37,10 +37,13 @@ int eig_recon(ggl_ctx* c, double* A, double* out, double* Dv, int map, const dou
     // row-major symmetric == column-major symmetric; the row-major LOWER triangle (what numpy's
     // eigh reads) is the column-major UPPER one.  Eigenvectors come back in column-major columns
     // == row-major ROWS, the layout launch_recon wants.
+    // (c->sweeps, which only the syevj experiment above writes, holds the exponents of the scaling: recon_gemm.hip)
+    launch_eig_prescale(c->stream, A, c->sweeps, c->K, c->p);
     rocblas_status st = rocsolver_dsyevd_strided_batched(c->blas, rocblas_evect_original, rocblas_fill_upper, c->p, A,
                                                          c->p, (rocblas_stride)c->p * c->p, Dv, c->p, c->E, c->p,
                                                          c->info, c->K);
     if (st != rocblas_status_success) return fail(GGL_E_SOLVER, "rocsolver_dsyevd_strided_batched: status %d", (int)st);
+    launch_eig_unscale(c->stream, Dv, c->sweeps, c->K, c->p);
     if (ph_eig >= 0) PE(c, ph_eig);
     if (ph_recon >= 0) PB(c, ph_recon);
     launch_recon(c->stream, out, A, Dv, betaK, map, c->K, c->p, c->scale);
@@ -60,10 +63,12 @@ int eigvals_only(ggl_ctx* c, double* A, double* Dv)
         int rcb = blas_handle(c, &c->blas);
         if (rcb) return rcb;
     }
+    launch_eig_prescale(c->stream, A, c->sweeps, c->K, c->p);
     rocblas_status st = rocsolver_dsyevd_strided_batched(c->blas, rocblas_evect_none, rocblas_fill_upper, c->p, A, c->p,
                                                          (rocblas_stride)c->p * c->p, Dv, c->p, c->E, c->p, c->info,
                                                          c->K);
     if (st != rocblas_status_success) return fail(GGL_E_SOLVER, "rocsolver_dsyevd (values): status %d", (int)st);
+    launch_eig_unscale(c->stream, Dv, c->sweeps, c->K, c->p);
     return GGL_OK;
 }
 

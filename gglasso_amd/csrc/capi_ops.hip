@@ -30,9 +30,14 @@ static int eig_common(int K, int p, const double* A, const double* beta, double*
         rocblas_handle h;
         if (rocblas_create_handle(&h) != rocblas_status_success) return fail(GGL_E_SOLVER, "rocblas_create_handle");
         HIPCHK(dE.alloc(kp));
+        int* dexp = nullptr;
+        HIPCHK(hipMalloc(&dexp, K * sizeof(int)));
+        InfoFree expfree{dexp};
+        launch_eig_prescale(nullptr, dA.p, dexp, K, p);
         rocblas_status st = rocsolver_dsyevd_strided_batched(h, (Q || out) ? rocblas_evect_original : rocblas_evect_none,
                                                              rocblas_fill_upper, p, dA.p, p, (rocblas_stride)p * p,
                                                              dD.p, p, dE.p, p, dinfo, K);
+        if (st == rocblas_status_success) launch_eig_unscale(nullptr, dD.p, dexp, K, p);
         if (st == rocblas_status_success && out) {
             hipError_t e = dS.alloc(2 * kp);
             if (e == hipSuccess) launch_recon(nullptr, dO.p, dA.p, dD.p, beta ? dB.p : nullptr, map, K, p, dS.p);

@@ -10,7 +10,8 @@
 // lanes that keeps both rows in registers, reduces the three inner products with wavefront
 // shuffles, and rotates.  One barrier per step; G never leaves LDS.  Converged when a full sweep
 // applies no rotation (|g_a.g_b| <= tol |g_a||g_b|).  Eigenvalue_i = |g_i| - sigma, eigenvector_i
-// = g_i/|g_i|.
+// = g_i/|g_i|.  G is held as 2^-e G with e = ilogb(sigma), so the result does not depend on the scale of A
+// (tests/eig_ref.py has the NumPy twin and the error bounds).
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -61,7 +62,22 @@ __global__ __launch_bounds__(JT) void k_jacobi(const double* __restrict__ A, dou
     double sigma = 0.0;
     for (int i = 0; i < p; ++i) sigma = fmax(sigma, fv[i]);   // same value in every thread
     sigma = (sigma > 0.0) ? 2.0 * sigma : 1.0;
+    // Work on 2^-e G with e = ilogb(sigma), so that sigma is in [1, 2) and the products of squared row norms in the
+    // rotation test (size sigma^4) neither overflow nor underflow whatever the scale of A.  A power of two commutes with
+    // every operation below, so an in-range result keeps its bits; the eigenvalues are scaled back with ldexp.  A
+    // non-finite sigma (Inf in A, or row sums past the range) is left unscaled: its NaNs reach D and the output as before.
+    const int e = isfinite(sigma) ? ilogb(sigma) : 0;
     __syncthreads();
+    if (e != 0) {
+        // two exact factors: 2^-e alone is out of range for e > 1022
+        const double s1 = ldexp(1.0, -(e / 2)), s2 = ldexp(1.0, -(e - e / 2));
+        for (int idx = tid; idx < p * p; idx += JT) {
+            const int i = idx / p, j = idx - i * p;
+            G[i * ld + j] = (G[i * ld + j] * s1) * s2;
+        }
+        sigma = (sigma * s1) * s2;
+        __syncthreads();
+    }
     if (tid < p) G[tid * ld + tid] += sigma;
     __syncthreads();
 
@@ -133,7 +149,7 @@ __global__ __launch_bounds__(JT) void k_jacobi(const double* __restrict__ A, dou
         const double inv = 1.0 / nu;
         for (int c = li; c < p; c += LG) G[r * ld + c] *= inv;
         if (li == 0) {
-            const double d = nu - sigma;
+            const double d = ldexp(nu - sigma, e);
             dv[r] = d;
             fv[r] = eig_map(map, d, betaK ? betaK[k] : 0.0);
         }

@@ -286,6 +286,9 @@ hipError_t launch_jacobi(hipStream_t st, const double* A, double* D, double* R, 
 // scale_work: 2*K*p doubles of scratch.
 void launch_recon(hipStream_t st, double* out, const double* R, const double* D, const double* betaK,
                   int map, int K, int p, double* scale_work);
+// around rocsolver_dsyevd: A <- 2^-ek A in the triangle it reads (ek[k] = ilogb of the largest entry), then D <- 2^ek D
+void launch_eig_prescale(hipStream_t st, double* A, int* ek, int K, int p);
+void launch_eig_unscale(hipStream_t st, double* D, const int* ek, int K, int p);
 
 // ---- gemm_sym.hip -----------------------------------------------------------------------
 // C[k] = cI*I + cAcc*(A[k]*B[k]) + cE*E[k] [+ cE2*E2[k]]  and optionally  C2[k] = dI*I + dC*C[k] + dE*E[k] [+ dE2*E2[k]]

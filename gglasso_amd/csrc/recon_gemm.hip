@@ -115,6 +115,56 @@ __global__ __launch_bounds__(256) void k_recon(double* __restrict__ out, const d
     }
 }
 
+// rocsolver_dsyevd is not independent of the scale of its input: for a matrix scaled by 2^-100 or less it returns info = 0
+// with eigenvalue errors of 0.1 % to 10 % of |A| (tests/test_gpu_eig_spectra.py has the figures).  So the route hands it
+// 2^-e A, e = ilogb(max |a_ij|) over the triangle it reads, an exact scaling that leaves the eigenvectors alone, and scales
+// the eigenvalues back with ldexp -- what k_jacobi does with its own input.  Entries of order 1 are not touched at all.
+__global__ __launch_bounds__(256) void k_eig_prescale(double* __restrict__ A, int* __restrict__ ek, int p)
+{
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    double* a = A + (size_t)blockIdx.x * p * p;
+    // the row-major lower triangle: what numpy's eigh reads, and the column-major upper one syevd is given
+    double m = 0.0;
+    for (int idx = tid; idx < p * p; idx += 256) {
+        const int i = idx / p, j = idx - i * p;
+        if (j <= i) m = fmax(m, fabs(a[idx]));
+    }
+    red[tid] = m;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) red[tid] = fmax(red[tid], red[tid + off]);
+        __syncthreads();
+    }
+    m = red[0];
+    const int e = (m > 0.0 && isfinite(m)) ? ilogb(m) : 0;     // zero, Inf: as it is (NaN entries do not count in fmax)
+    if (tid == 0) ek[blockIdx.x] = e;
+    if (e == 0) return;
+    const double s1 = ldexp(1.0, -(e / 2)), s2 = ldexp(1.0, -(e - e / 2));   // two factors: 2^-e alone can leave the range
+    for (int idx = tid; idx < p * p; idx += 256) {
+        const int i = idx / p, j = idx - i * p;
+        if (j <= i) a[idx] = (a[idx] * s1) * s2;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_eig_unscale(double* __restrict__ D, const int* __restrict__ ek, int p)
+{
+    const int e = ek[blockIdx.y];
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (e == 0 || m >= p) return;
+    D[(size_t)blockIdx.y * p + m] = ldexp(D[(size_t)blockIdx.y * p + m], e);
+}
+
+void launch_eig_prescale(hipStream_t st, double* A, int* ek, int K, int p)
+{
+    hipLaunchKernelGGL(k_eig_prescale, dim3(K), dim3(256), 0, st, A, ek, p);
+}
+
+void launch_eig_unscale(hipStream_t st, double* D, const int* ek, int K, int p)
+{
+    hipLaunchKernelGGL(k_eig_unscale, dim3((p + 255) / 256, K), dim3(256), 0, st, D, ek, p);
+}
+
 void launch_recon(hipStream_t st, double* out, const double* R, const double* D, const double* betaK, int map,
                   int K, int p, double* scale_work)
 {
