@@ -402,6 +402,28 @@ extern "C" int ggl_heldout_scores(ggl_ctx* c, const double* X_host, int N, int F
     return selection_stats_impl(c, out, dS.p, F);
 }
 
+// The test-fold side of ggl_heldout_scores for a caller in another file (ggl_neighborhood_cv): the same refusals about the
+// folds, then the same route to the F test covariances, so the same bits.  dS (F,p,p) and dVar (F,p) are the caller's.
+int heldout_fold_check(ggl_ctx* c, const double* X_host, int N, int F, int m, const int* idx_test, int flags)
+{
+    ARGCHK(X_host, "X");
+    ARGCHK(idx_test, "idx_test");
+    if ((flags & ~GGL_COV_CENTER) != 0)
+        return fail(GGL_E_ARG, "bad argument: flags = %d, held-out scores take GGL_COV_CENTER or 0 (no GGL_COV_SCALE: the folds share one scale)", flags);
+    if (F < 1 || F > 65535 || c->K % F != 0)
+        return fail(GGL_E_ARG, "bad argument: F = %d folds do not divide the K = %d instances of the ctx", F, c->K);
+    if (m < 1) return fail(GGL_E_ARG, "bad argument: m = %d, every test fold needs at least one observation", m);
+    ARGCHK(N >= 1, "N >= 1");
+    RCCHK(check_index_table(idx_test, F, m, N, "fold"));
+    return check_subset_sizes(c->p, N, X_host, F, m, idx_test, flags);
+}
+
+int heldout_fold_covariances(ggl_ctx* c, const double* X_host, int N, int F, int m, const int* idx_test, int flags, double* dS,
+                             double* dVar)
+{
+    return subsets_to_device(c->stream, c->p, N, X_host, F, m, idx_test, flags, dS, dVar);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Kendall's tau-b and the skeptic matrix sin(pi/2 tau) from dense ranks (kernels: kendall.hip): the ranks go up once, the
 // columns of the B subsets are gathered on the device, the counts G = Z Z^T are exact 64-bit integers

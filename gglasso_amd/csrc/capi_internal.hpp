@@ -23,7 +23,9 @@
 //   capi_inference.hip  the output side: debiased graphical lasso and its standard errors (ggl_debias); batched Cholesky with
 //                       log det and quadratic form (ggl_cholesky_predict)
 //   capi_neighborhood.hip  Meinshausen-Buhlmann neighbourhood selection: the lasso path of every node (ggl_neighborhood_path)
-//                       and the same on a ctx's S with the edge stability of the result (ggl_neighborhood_stability)
+//                       and the same on a ctx's S with the edge stability of the result (ggl_neighborhood_stability); the
+//                       least-squares refit on a graph (ggl_neighborhood_refit) and one cross-validation step of it on a
+//                       ctx (ggl_neighborhood_cv)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
@@ -399,6 +401,11 @@ int fsgl_check(ggl_ctx* c, int reg, double lambda1);
 int finish_norms(ggl_ctx* c, int rows, double* out_norms, int group = 0);
 int ggl_step_finish_impl(ggl_ctx* c, double rho, double lambda1, double lambda2, int reg, int latent,
                                 const double* mu1, int groupsq_ready, double out_norms[5]);
+// what ggl_heldout_scores refuses about its folds, and its route to the F test covariances dS (F,p,p), dVar (F,p) on the
+// ctx stream (capi_data.hip)
+int heldout_fold_check(ggl_ctx* c, const double* X_host, int N, int F, int m, const int* idx_test, int flags);
+int heldout_fold_covariances(ggl_ctx* c, const double* X_host, int N, int F, int m, const int* idx_test, int flags, double* dS,
+                             double* dVar);
 int host_reduce(ggl_ctx* c, int rows, int nv, double* out /*nv*/, bool take_max);
 void lds_missed(ggl_ctx* c);
 int lds_table(ggl_ctx* c);

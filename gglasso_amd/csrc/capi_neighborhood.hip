@@ -1,7 +1,8 @@
 // C ABI: Meinshausen-Buhlmann neighbourhood selection (kernels: neighborhood.hip).  ggl_neighborhood_path is the
 // stateless operator, host buffers in and out; ggl_neighborhood_stability runs the same path on the B matrices a ctx holds
 // (the StARS route: ggl_set_S_from_subsets and its siblings wrote them), keeps the symmetrised (L,B,p,p) stack on the device
-// and reduces it with the kernel behind ggl_edge_stability.
+// and reduces it with the kernel behind ggl_edge_stability.  ggl_neighborhood_refit and ggl_neighborhood_cv (below) refit a
+// graph by least squares and score the regressions on held-out data (kernels: mb_refit.hip).
 #include "capi_internal.hpp"
 
 namespace {
@@ -108,6 +109,153 @@ extern "C" int ggl_neighborhood_stability(ggl_ctx* c, int L, const double* lam, 
     HIPCHK(hipMemcpyAsync(info_out, dInfo.p, nLB * p * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
     if (counts_out) HIPCHK(hipMemcpyAsync(counts_out, dCnt.p, (size_t)L * pp * sizeof(int), hipMemcpyDeviceToHost, st));
     if (stack_out) HIPCHK(hipMemcpyAsync(stack_out, dStack.p, nLB * pp * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return GGL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Refit on the graph (kernels: mb_refit.hip): the relaxed lasso of Meinshausen (2007), the regression-based
+// precision estimator of Yuan (2010, JMLR 11) and Zhou, Ruetimann, Xu, Buehlmann (2011, JMLR 12)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+// The refit of nslot slots on stream st: dCoef zeroed, every unit through the wave kernel, info read back once, the pending
+// units (32 < degree <= MBR_MAX_DEG) listed and served a workgroup each, then the transpose that puts beta^(j) into column j.
+// info_host (nslot,p,2) holds the final info on return; the stream has been waited for.
+int run_refit(hipStream_t st, const double* dS, const double* dT, const double* dW, double t, int p, size_t nslot, int sdiv,
+              int smod, double* dCoef, double* dRes, double* dHeld, int* dInfo, int* info_host)
+{
+    const size_t pp = (size_t)p * p, nunit = nslot * p;
+    HIPCHK(hipMemsetAsync(dCoef, 0, nslot * pp * sizeof(double), st));
+    launch_mb_refit(st, dS, dT, dW, t, p, nslot, sdiv, smod, dCoef, dRes, dHeld, dInfo);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(info_host, dInfo, nunit * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<int> list;
+    for (size_t u = 0; u < nunit; ++u)
+        if (info_host[2 * u + 1] == -1) list.push_back((int)u);
+    IntBuf dList;
+    if (!list.empty()) {
+        HIPCHK(dList.alloc(list.size()));
+        HIPCHK(hipMemcpyAsync(dList.p, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        launch_mb_refit_listed(st, dS, dT, dW, t, p, dList.p, (int)list.size(), sdiv, smod, dCoef, dRes, dHeld, dInfo);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(info_host, dInfo, nunit * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    launch_mb_symmetrize(st, dCoef, nslot, p, GGL_MB_RAW);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return GGL_OK;
+}
+
+int check_threshold(double t)
+{
+    if (!(t >= 0.0) || !(t <= 1.79769313486231570815e308))
+        return fail(GGL_E_ARG, "bad argument: the edge threshold t = %g must be finite and not negative", t);
+    return GGL_OK;
+}
+}  // namespace
+
+extern "C" void ggl_mb_refit_limits(int out[2])
+{
+    if (!out) return;
+    out[0] = MBR_MAX_DEG;
+    out[1] = MB_MAX_P;
+}
+
+extern "C" int ggl_neighborhood_refit(int device, int M, int p, const double* S_host, int G, const double* W_host, double t,
+                                      const double* T_host, double* coef_out, double* resvar_out, double* heldout_out,
+                                      int* info_out)
+{
+    if (M < 1 || G < 1 || p < 1) return fail(GGL_E_ARG, "bad argument: M = %d, G = %d, p = %d; each must be at least 1", M, G, p);
+    if (p > MB_MAX_P) return fail(GGL_E_ARG, "bad argument: p = %d, k_mb_refit serves p <= %d", p, MB_MAX_P);
+    ARGCHK(S_host, "S must not be NULL");
+    ARGCHK(W_host, "W must not be NULL");
+    ARGCHK(coef_out, "coef_out must not be NULL");
+    ARGCHK(resvar_out, "resvar_out must not be NULL");
+    ARGCHK(info_out, "info_out must not be NULL");
+    ARGCHK(!heldout_out || T_host, "heldout_out needs the second stack T");
+    RCCHK(check_threshold(t));
+    ARGCHK((double)M * G * p < 2147483647.0, "M * G * p must stay below 2^31");
+    const size_t pp = (size_t)p * p;
+    for (int m = 0; m < M; ++m) {
+        const double* a = S_host + (size_t)m * pp;
+        for (size_t e = 0; e < pp; ++e)
+            if (!std::isfinite(a[e]))
+                return fail(GGL_E_ARG, "bad argument: S of matrix %d: the entry (%d, %d) is not finite", m, (int)(e / p), (int)(e % p));
+        for (int i = 0; i < p; ++i)
+            if (!(a[(size_t)i * p + i] > 0.0))
+                return fail(GGL_E_ARG, "bad argument: S of matrix %d, variable %d: the diagonal entry is %g; it must be positive", m,
+                            i, a[(size_t)i * p + i]);
+    }
+    HIPCHK(hipSetDevice(device));
+    const size_t nslot = (size_t)M * G;
+    const bool held = heldout_out != nullptr;
+    DevBuf dS, dT, dW, dCoef, dRes, dHeld;
+    IntBuf dInfo;
+    HIPCHK(dS.alloc((size_t)M * pp));
+    if (held) HIPCHK(dT.alloc((size_t)M * pp));
+    HIPCHK(dW.alloc(nslot * pp));
+    HIPCHK(dCoef.alloc(nslot * pp));
+    HIPCHK(dRes.alloc(nslot * p));
+    if (held) HIPCHK(dHeld.alloc(nslot * p));
+    HIPCHK(dInfo.alloc(nslot * p * 2));
+    UP(dS.p, S_host, (size_t)M * pp);
+    if (held) UP(dT.p, T_host, (size_t)M * pp);
+    UP(dW.p, W_host, nslot * pp);
+    std::vector<int> info(nslot * p * 2);
+    RCCHK(run_refit(nullptr, dS.p, dT.p, dW.p, t, p, nslot, G, M, dCoef.p, dRes.p, dHeld.p, dInfo.p, info.data()));
+    DOWN(coef_out, dCoef.p, nslot * pp);
+    DOWN(resvar_out, dRes.p, nslot * p);
+    if (held) DOWN(heldout_out, dHeld.p, nslot * p);
+    std::memcpy(info_out, info.data(), info.size() * sizeof(int));
+    return GGL_OK;
+}
+
+extern "C" int ggl_neighborhood_cv(ggl_ctx* c, const double* X_host, int N, int F, int m, const int* idx_test, int flags, int L,
+                                   const double* lam, int rule, double tol, int max_sweeps, double t, int refit,
+                                   double* resvar_out, double* heldout_out, int* info_out, double* stack_out)
+{
+    ARGCHK(c && resvar_out && heldout_out && info_out, "ctx, resvar_out, heldout_out and info_out must not be NULL");
+    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) holds no stack of one dimension");
+    RCCHK(check_mb_args(L, lam, rule, GGL_MB_AND, tol, max_sweeps, c->p));
+    RCCHK(check_threshold(t));
+    RCCHK(heldout_fold_check(c, X_host, N, F, m, idx_test, flags));
+    if (c->K != F)
+        return fail(GGL_E_ARG, "bad argument: the ctx holds K = %d matrices, the cross-validation has F = %d folds; instance f must "
+                    "be the train matrix of fold f", c->K, F);
+    const int p = c->p;
+    ARGCHK(L <= 65535, "more than 65535 lambdas in one call");
+    ARGCHK((double)L * F * p < 2147483647.0, "L * F * p must stay below 2^31");
+    HIPCHK(hipSetDevice(c->device));
+    DROP_PRE(c);
+    const size_t pp = (size_t)p * p, nLF = (size_t)L * F;
+    DevBuf dLam, dStack, dCoef, dRes, dHeld, dT, dVar;
+    IntBuf dInfo;
+    HIPCHK(dLam.alloc(L));
+    HIPCHK(dStack.alloc(nLF * pp));
+    if (refit) HIPCHK(dCoef.alloc(nLF * pp));
+    HIPCHK(dRes.alloc(nLF * p));
+    HIPCHK(dHeld.alloc(nLF * p));
+    HIPCHK(dT.alloc((size_t)F * pp));
+    HIPCHK(dVar.alloc((size_t)F * p));
+    HIPCHK(dInfo.alloc(nLF * p * 2));
+    hipStream_t st = c->stream;
+    RCCHK(heldout_fold_covariances(c, X_host, N, F, m, idx_test, flags, dT.p, dVar.p));
+    HIPCHK(hipMemcpyAsync(dLam.p, lam, L * sizeof(double), hipMemcpyHostToDevice, st));
+    // slot (fold f, lambda l) is l * F + f, as in ggl_neighborhood_stability; its matrices are S[f], T[f]
+    launch_mb_path(st, c->S, F, p, dLam.p, L, tol, max_sweeps, dStack.p, refit ? nullptr : dRes.p, dInfo.p, 1, (size_t)F);
+    HIPCHK(hipGetLastError());
+    if (!refit) {
+        launch_mb_heldout(st, dT.p, dStack.p, p, nLF, 1, F, dHeld.p);       // the lasso's own beta, still in rows
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(info_out, dInfo.p, nLF * p * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    launch_mb_symmetrize(st, dStack.p, nLF, p, rule);
+    HIPCHK(hipGetLastError());
+    if (refit) RCCHK(run_refit(st, c->S, dT.p, dStack.p, t, p, nLF, 1, F, dCoef.p, dRes.p, dHeld.p, dInfo.p, info_out));
+    HIPCHK(hipMemcpyAsync(resvar_out, dRes.p, nLF * p * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(heldout_out, dHeld.p, nLF * p * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (stack_out) HIPCHK(hipMemcpyAsync(stack_out, dStack.p, nLF * pp * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return GGL_OK;
 }

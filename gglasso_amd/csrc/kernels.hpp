@@ -589,4 +589,19 @@ void launch_mb_path(hipStream_t st, const double* S, int M, int p, const double*
 // 'or' matrix -- of beta^(j)_i and beta^(i)_j the one of smaller / larger magnitude to (i,j) and (j,i), the former on a tie
 void launch_mb_symmetrize(hipStream_t st, double* C, size_t nmat, int p, int rule);
 
+// Refit of neighbourhood selection on its graph (mb_refit.hip).  W: nslot slots of (p,p); the unit (slot s, node j)
+// takes its neighbours from ROW j of slot s (|.| >= t, a NaN is none) and its data from matrix (s / sdiv) % smod of S and,
+// where heldout is not null, of T.  coef: nslot slots of (p,p), ZEROED by the caller; ROW j receives beta^(j) (as
+// launch_mb_path leaves it: launch_mb_symmetrize rule 0 turns it into column j).  resvar, heldout (may be null): nslot slots
+// of p; info: nslot slots of (p,2) = (degree, status 0 solved / 1 pivot / 2 non-finite / 3 degree > MBR_MAX_DEG; -1 pending).
+// launch_mb_refit serves every unit of degree <= 32 and leaves the others pending; launch_mb_refit_listed serves the units
+// named in list (nlist ints on the device, s * p + j), which must have degree <= MBR_MAX_DEG.  nslot * p < 2^31.
+static constexpr int MBR_MAX_DEG = 128;
+void launch_mb_refit(hipStream_t st, const double* S, const double* T, const double* W, double t, int p, size_t nslot, int sdiv,
+                     int smod, double* coef, double* resvar, double* heldout, int* info);
+void launch_mb_refit_listed(hipStream_t st, const double* S, const double* T, const double* W, double t, int p, const int* list,
+                            int nlist, int sdiv, int smod, double* coef, double* resvar, double* heldout, int* info);
+// heldout[s,j] = q(T; ROW j of slot s of C) over the row's non-zero entries, the sums of launch_mb_refit's q
+void launch_mb_heldout(hipStream_t st, const double* T, const double* C, int p, size_t nslot, int sdiv, int smod, double* heldout);
+
 }  // namespace ggl

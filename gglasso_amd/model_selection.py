@@ -703,7 +703,7 @@ def _host_edge_counts(Theta, t):
 
 def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.05, seed=0, indices=None, t=1e-8, center=True,
                  scale=False, tol=1e-7, rtol=1e-7, max_iter=1000, store_all=False, lambdas_per_batch=None, correlation=None,
-                 missing=None, min_pairs=2, project=False, method='glasso', rule='and'):
+                 missing=None, min_pairs=2, project=False, method='glasso', rule='and', refit=False):
     """StARS for the Single Graphical Lasso from observations ``X`` (p,N), variables in rows.  Returns ``(sol, stats)``.
 
     * Subsamples: ``stars_subsamples(N, n_subsamples, subsample_size, seed)``, or ``indices`` (B,b) given by the caller
@@ -756,13 +756,17 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     chosen lambda on the matrix of all N observations: ``{'adjacency', 'coef', 'resvar', 'lambda1'}`` -- the boolean graph under
     ``rule`` and ``t``, the raw coefficients (column j: node j's) and the residual variances.  The lasso is not invariant
     under rescaling a variable: ``mb`` works on whatever scale ``center`` / ``scale`` produce, and ``scale=True`` (correlations)
-    is what huge does.  With ``method='glasso'`` nothing of this applies."""
+    is what huge does.  ``refit=True`` (``method='mb'`` only): ``sol`` gains ``coef_refit`` and ``resvar_refit``, the
+    least-squares refit of every node on its neighbours in ``sol['adjacency']`` (``utils.neighborhood_refit``), and
+    ``precision``, ``utils.neighborhood_precision`` of the two; with the default the keys and bits of ``sol`` stay.  With
+    ``method='glasso'`` nothing of this applies."""
     import warnings
     from . import solver as _solver, utils
     from .batch import _sgl_batch_impl
     assert method in ('glasso', 'mb'), "method must be 'glasso' or 'mb'"
     mb = method == 'mb'
     assert not mb or rule in ('and', 'or'), "rule must be 'and' or 'or'"
+    assert mb or not refit, "refit=True needs method='mb': the graphical lasso has no node-wise regressions to refit"
     assert correlation in (None, 'kendall', 'mixed'), "correlation must be None (Pearson), 'kendall' or 'mixed'"
     assert missing in (None, 'pairwise'), "missing must be None (complete data) or 'pairwise'"
     kendall, mixed = correlation == 'kendall', correlation == 'mixed'
@@ -909,6 +913,10 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
         with np.errstate(invalid='ignore'):
             sol = {'adjacency': (np.abs(W[ix]) >= t) & (W[ix] != 0), 'coef': inf['COEF'][ix],
                    'resvar': inf['RESVAR'][ix], 'lambda1': lam[ix]}
+        if refit:
+            rf = (utils.neighborhood_refit if on_device else utils.host_neighborhood_refit)(S_full, W[ix], t)
+            sol['coef_refit'], sol['resvar_refit'] = rf['COEF'], rf['RESVAR']
+            sol['precision'] = utils.neighborhood_precision(rf['COEF'], rf['RESVAR'])[0]
     else:
         sol, _ = _solver.ADMM_SGL(S_full, lam[ix], eye, X_0=eye, tol=tol, rtol=rtol, max_iter=max_iter, verbose=False)
     stats = {'LAMBDA': lam, 'INSTABILITY': D, 'INSTABILITY_MONOTONE': Dbar, 'NUM': [int(n) for n in NUM], 'IX': ix,
@@ -983,7 +991,7 @@ def _host_heldout_scores(Theta, S_test):
 
 def cv_search(X, lambda_range, n_folds=5, seed=0, folds=None, rule='min', center=True, scale=False, tol=1e-7, rtol=1e-7,
               max_iter=1000, store_all=False, lambdas_per_batch=None, correlation=None, missing=None, project=False,
-              latent=False, lambda1_mask=None):
+              latent=False, lambda1_mask=None, method='glasso', graph_rule='and', refit=True, score='pseudo', t=1e-8):
     """K-fold cross-validation of lambda1 for the Single Graphical Lasso from observations ``X`` (p,N), variables in rows.
     Returns ``(sol, stats)``.
 
@@ -1006,10 +1014,35 @@ def cv_search(X, lambda_range, n_folds=5, seed=0, folds=None, rule='min', center
     covariances and scores on the host (``math.fsum``, ``robust_logdet``).
 
     Not implemented, each a ValueError: ``correlation=``, ``missing=``, ``project=`` (a held-out Gaussian likelihood against a
-    rank matrix is a different estimator), latent variables, a ``lambda1_mask``, multiple-instance data."""
+    rank matrix is a different estimator), latent variables, a ``lambda1_mask``, multiple-instance data.
+
+    ``method='mb'``: the estimator is Meinshausen-Buhlmann neighbourhood selection and the score the held-out prediction error
+    of its regressions -- a different statistic from the held-out likelihood above; the two are not comparable in value.
+    Per (lambda, fold): the path on ``S_train_f`` symmetrised by ``graph_rule`` (``'and'`` / ``'or'``); with ``refit`` (the
+    default) every node regressed by least squares on its neighbours in that graph (edges: ``|.| >= t``;
+    ``utils.neighborhood_refit``), without it the lasso's own coefficients; ``tau_j^2`` the residual variance on the train
+    matrix and ``r_j`` the same quadratic form on the test matrix.  ``score='pseudo'``: ``sum_j log tau_j^2 + r_j / tau_j^2``,
+    the negative Gaussian pseudo-log-likelihood; ``score='mse'``: ``sum_j r_j``.  Both are summed on the host
+    (``utils.mb_cv_scores``); a (lambda, fold) with a node that was not solved (refit status 1-3, a non-finite path) is +inf
+    under ``'pseudo'`` and listed in ``NOT_SOLVED``.  ``CV``, ``SE`` and ``IX`` as above.  ``stats`` holds ``SCORE`` (L,F) in
+    the place of ``NLL`` and the per-node arrays ``RESVAR``, ``HELDOUT``, ``STATUS`` (L,F,p); ``store_all`` adds ``THETA``, the
+    symmetrised stack.  ``sol``: on all N observations at the chosen lambda ``{'adjacency', 'coef', 'resvar', 'lambda1'}`` of
+    the path as in ``stars_search``, and with ``refit`` also ``coef_refit``, ``resvar_refit``; ``precision`` is
+    ``utils.neighborhood_precision`` of the refit (without ``refit``: of the lasso's own pair).  On the device one ctx of F
+    instances holds the train matrices and ``HipEngine.neighborhood_cv`` does the rest; the matrices never exist on the host.
+    ``rtol``, ``max_iter`` are not used.  With ``method='glasso'`` nothing of this applies."""
     import warnings
     from . import solver as _solver, utils
     from .batch import _late_failures, _sgl_batch_impl
+    if method not in ('glasso', 'mb'):
+        raise ValueError(f"method = {method!r}: 'glasso' or 'mb'")
+    if method == 'mb':
+        if graph_rule not in ('and', 'or'):
+            raise ValueError(f"graph_rule = {graph_rule!r}: 'and' or 'or'")
+        if score not in ('pseudo', 'mse'):
+            raise ValueError(f"score = {score!r}: 'pseudo' or 'mse'")
+        if not (np.isfinite(t) and t >= 0):
+            raise ValueError(f"t = {t}: the edge threshold must be finite and not negative")
     for name, val in (('correlation', correlation), ('missing', missing)):
         if val is not None:
             raise ValueError(f"cv_search: {name}={val!r} is not implemented: a held-out Gaussian likelihood against such a matrix "
@@ -1047,6 +1080,8 @@ def cv_search(X, lambda_range, n_folds=5, seed=0, folds=None, rule='min', center
                              f"it cannot be scaled")
         X = np.ascontiguousarray(X / np.sqrt(var)[:, None])
     per = L if lambdas_per_batch is None else max(1, int(lambdas_per_batch))
+    if method == 'mb':
+        return _cv_search_mb(X, lam, train, test, rule, graph_rule, bool(refit), score, float(t), center, var, tol, store_all, per)
     on_device = hasattr(_solver.ENGINE, "set_data_subsets") and hasattr(_solver.ENGINE, "heldout_scores")
     eye = np.eye(p)
     OUT = np.zeros((L, F, 4))
@@ -1104,6 +1139,88 @@ def cv_search(X, lambda_range, n_folds=5, seed=0, folds=None, rule='min', center
              'TEST': test, 'n_folds': F, 'rule': rule, 'NNZ': NNZ, 'FAILED': [int(l) for l in np.flatnonzero(failed)],
              'NOT_PD': [(int(l), int(f)) for l, f in zip(*np.nonzero(not_pd))]}
     if scale:
+        stats['scale'] = var
+    if store_all:
+        stats['THETA'] = THETA
+    return sol, stats
+
+
+def _cv_search_mb(X, lam, train, test, rule, graph_rule, refit, score, t, center, var, tol, store_all, per):
+    """``cv_search(method='mb')`` behind its argument checks: X scaled already, the grid descending."""
+    import warnings
+    from . import solver as _solver, utils
+    p, N = X.shape
+    F, L = test.shape[0], lam.size
+    on_device = hasattr(_solver.ENGINE, "set_data_subsets") and hasattr(_solver.ENGINE, "neighborhood_cv")
+    TAU, R = np.zeros((L, F, p)), np.zeros((L, F, p))
+    STATUS = np.zeros((L, F, p), dtype=np.int64)
+    THETA = np.zeros((L, F, p, p)) if store_all else None
+    if not on_device:
+        S_train = _host_subset_covariances(X, train, center, False)
+        S_test = _host_subset_covariances(X, test, center, False)
+    eye = np.eye(p)
+    for l0 in range(0, L, per):
+        sl = slice(l0, min(L, l0 + per))
+        if on_device:
+            ph = np.broadcast_to(eye, (F, p, p))                            # (shapes the ctx, as in stars_search)
+            eng = _solver.ENGINE(ph, ph, ph, np.broadcast_to(np.zeros((p, p)), (F, p, p)))
+            try:
+                eng.set_data_subsets(X, train, center=center)
+                out = eng.neighborhood_cv(X, test, lam[sl], graph_rule, tol=tol, t=t, refit=refit, center=center, stack=store_all)
+            finally:
+                eng.close()
+            TAU[sl], R[sl], STATUS[sl] = out['resvar'], out['heldout'], out['status']
+            if store_all:
+                THETA[sl] = out['stack']
+            continue
+        W, inf = utils.host_neighborhood_selection(S_train, lam[sl], graph_rule, tol=tol, return_info=True)     # (F,nl,..)
+        if refit:
+            rf = utils.host_neighborhood_refit(S_train, W, t, S_test)
+            tau, r, st = rf['RESVAR'], rf['HELDOUT'], rf['STATUS']
+        else:
+            tau, st = inf['RESVAR'], inf['STATUS']
+            r = np.full(tau.shape, np.nan)
+            with np.errstate(all='ignore'):
+                for f in range(F):
+                    for l in range(W.shape[1]):
+                        for j in range(p):
+                            b = inf['COEF'][f, l][:, j]
+                            A = np.flatnonzero(b != 0)
+                            r[f, l, j] = utils._host_quad(S_test[f], j, A, b[A])
+        TAU[sl], R[sl], STATUS[sl] = (np.swapaxes(a, 0, 1) for a in (tau, r, st))
+        if store_all:
+            THETA[sl] = np.swapaxes(W, 0, 1)
+    bad = (STATUS != 0) if refit else (STATUS == 2)
+    SC = utils.mb_cv_scores(TAU, R, bad, score)
+    capped = 0 if refit else int((STATUS == 1).sum())
+    if capped:
+        warnings.warn(f"cross-validation, method='mb': {capped} (lambda1, fold, node) units reached a cap of the coordinate "
+                      f"descent before tol = {tol}; their coefficients are used as they are", RuntimeWarning, stacklevel=3)
+    failed = np.isnan(SC).any(axis=1)
+    with np.errstate(invalid='ignore'):
+        CV = SC.mean(axis=1)
+        SE = SC.std(axis=1, ddof=1) / np.sqrt(F) if F > 1 else np.full(L, np.nan)
+    ix = cv_select(CV, SE, rule)
+    if on_device:
+        S_full = utils.sample_covariance(X, center=center)
+    else:
+        S_full = _host_subset_covariances(X, np.arange(N)[None], center, False)[0]
+    path = utils.neighborhood_selection if on_device else utils.host_neighborhood_selection
+    W, inf = path(S_full, lam[:ix + 1], graph_rule, tol=tol, return_info=True)
+    with np.errstate(invalid='ignore'):
+        sol = {'adjacency': (np.abs(W[ix]) >= t) & (W[ix] != 0), 'coef': inf['COEF'][ix], 'resvar': inf['RESVAR'][ix],
+               'lambda1': lam[ix]}
+    if refit:
+        rf = (utils.neighborhood_refit if on_device else utils.host_neighborhood_refit)(S_full, W[ix], t)
+        sol['coef_refit'], sol['resvar_refit'] = rf['COEF'], rf['RESVAR']
+        sol['precision'] = utils.neighborhood_precision(rf['COEF'], rf['RESVAR'])[0]
+    else:
+        sol['precision'] = utils.neighborhood_precision(sol['coef'], sol['resvar'])[0]
+    stats = {'LAMBDA': lam, 'SCORE': SC, 'CV': CV, 'SE': SE, 'IX': ix, 'BEST': {'lambda1': lam[ix]}, 'TRAIN': train,
+             'TEST': test, 'n_folds': F, 'rule': rule, 'method': 'mb', 'graph_rule': graph_rule, 'refit': refit, 'score': score,
+             'RESVAR': TAU, 'HELDOUT': R, 'STATUS': STATUS, 'FAILED': [int(l) for l in np.flatnonzero(failed)],
+             'NOT_SOLVED': [(int(l), int(f)) for l, f in zip(*np.nonzero(bad.any(axis=2)))]}
+    if var is not None:
         stats['scale'] = var
     if store_all:
         stats['THETA'] = THETA

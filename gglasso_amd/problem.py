@@ -476,6 +476,55 @@ class glasso_problem:
         self._keep(sol)
         self.modelselect_stats = dict(stats)
 
+    def neighborhood_selection(self, lambda_range, select='stars', rule='and', refit=True, **kw):
+        """Meinshausen-Buhlmann neighbourhood selection for a Single Graphical Lasso problem built by ``from_data``: the
+        penalty is chosen along ``lambda_range`` by StARS (``select='stars'``, ``model_selection.stars_search(method='mb')``) or
+        by cross-validated prediction error (``select='cv'``, ``model_selection.cv_search(method='mb')``); ``rule`` (``'and'`` /
+        ``'or'``) symmetrises the supports into the graph; ``kw`` goes to the search (``n_subsamples``, ``beta``, ``n_folds``,
+        ``score``, ``seed``, ``tol``, ...; the ``rule`` of ``cv_search``, 'min' / 'one_se', as ``cv_rule``).  With ``refit`` (the
+        default) every node is then regressed on its neighbours by least squares (``utils.neighborhood_refit``), and
+        ``solution.precision_`` is ``utils.neighborhood_precision`` of those regressions; without it, of the lasso's own
+        coefficients.  ``solution.adjacency_`` is the selected graph, ``reg_params['lambda1']`` the chosen penalty,
+        ``modelselect_stats`` the search's tables and ``neighborhood_`` the search's ``sol``.  The precision matrix is not
+        positive definite by construction (``utils.neighborhood_precision``).  ``solve``, ``model_selection`` and the other
+        methods are untouched.  With ``do_scaling`` the method works on correlations and the precision matrix goes back to the
+        covariances' scale, as in ``solve``.  ``select='cv'`` refuses what ``cross_validation`` refuses."""
+        from . import utils as _utils
+        assert select in ('stars', 'cv'), f"select = {select!r}: 'stars' or 'cv'"
+        assert rule in ('and', 'or'), f"rule = {rule!r}: 'and' or 'or'"
+        assert getattr(self, '_observations', None) is not None, \
+            "Neighbourhood selection resamples the observations: build the problem with glasso_problem.from_data(X)."
+        assert not self.multiple, "Neighbourhood selection is implemented for Single Graphical Lasso problems only."
+        assert not self.latent, "Neighbourhood selection is not implemented for problems with latent variables: a lasso per " \
+                                "node has no low-rank component."
+        assert self.reg_params.get('lambda1_mask') is None, "Neighbourhood selection is not implemented with a lambda1_mask."
+        X = self._observations[0]
+        if select == 'stars':
+            how = dict(correlation=self._correlation) if getattr(self, '_correlation', None) in ('kendall', 'mixed') else \
+                dict(center=self._center, scale=bool(self.do_scaling))
+            if getattr(self, '_missing', None) == 'pairwise':
+                how.update(missing='pairwise', min_pairs=self._min_pairs)
+            if getattr(self, '_project_S', False):
+                how.update(project=True)
+            sol, stats = _ms.stars_search(X, lambda_range, method='mb', rule=rule, refit=bool(refit), **how, **kw)
+        else:
+            for name, val in (('correlation', getattr(self, '_correlation', None)), ('missing', getattr(self, '_missing', None))):
+                if val is not None:
+                    raise ValueError(f"Neighbourhood selection by cross-validation is not implemented for a problem built with {name}={val!r}.")
+            if getattr(self, '_project_S', False):
+                raise ValueError("Neighbourhood selection by cross-validation is not implemented for a problem built with project=True.")
+            kw = dict(kw)
+            if 'cv_rule' in kw:
+                kw['rule'] = kw.pop('cv_rule')
+            sol, stats = _ms.cv_search(X, lambda_range, method='mb', graph_rule=rule, refit=bool(refit), center=self._center,
+                                       scale=bool(self.do_scaling), **kw)
+        Theta = sol['precision'] if 'precision' in sol else _utils.neighborhood_precision(sol['coef'], sol['resvar'])[0]
+        self.set_reg_params(stats['BEST'])
+        self._keep({'Theta': Theta})
+        self.solution.adjacency_ = np.asarray(sol['adjacency']).astype(int)
+        self.neighborhood_ = dict(sol)
+        self.modelselect_stats = dict(stats)
+
     # -- inference ---------------------------------------------------------------------------------------------------------
     def edge_inference(self, alpha=0.05, method='bh', differential=None, host=False):
         """Edge-wise tests and confidence intervals for the solution at hand by the debiased graphical lasso (Jankova & van de

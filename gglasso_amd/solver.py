@@ -255,6 +255,35 @@ class HipEngine:
             out['stack'] = W
         return out
 
+    def neighborhood_cv(self, X, test_idx, lambda_range, rule='and', tol=1e-7, max_sweeps=10000, t=1e-8, refit=True,
+                        center=True, stack=False):
+        """One cross-validation step of neighbourhood selection on the K = F train matrices the ctx's S holds (a
+        ``set_*_subsets`` call with the train indices wrote them), ``ggl_neighborhood_cv``: the path along the descending grid,
+        symmetrised by ``rule``; the F test covariances of ``X[:, test_idx[f]]`` built on the device as ``heldout_scores``
+        builds them; then with ``refit`` every node regressed on its neighbours by least squares on the train matrix
+        (``utils.neighborhood_refit``) and scored on the test matrix, without it the lasso's own coefficients scored there.
+        Returns a dict of (L,K,p) arrays: ``resvar`` (tau^2), ``heldout`` (r), ``status``, and ``degree`` (with ``refit``) or
+        ``sweeps`` (without); with ``stack`` the symmetrised (L,K,p,p) stack."""
+        from .utils import _MB_RULES, _subset_indices
+        X = as_c(X)
+        assert X.ndim == 2 and X.shape[0] == self.p, f"data must be a ({self.p}, N) array"
+        idx = _subset_indices(test_idx)
+        lam = as_c(np.asarray(lambda_range, dtype=np.float64).reshape(-1))
+        assert rule in ('and', 'or'), f"rule = {rule!r}: 'and' or 'or'"
+        L = lam.size
+        resvar, heldout = np.empty((L, self.K, self.p)), np.empty((L, self.K, self.p))
+        info = np.empty((L, self.K, self.p, 2), dtype=np.int32)
+        W = np.empty((L, self.K, self.p, self.p)) if stack else None
+        check(self.lib.ggl_neighborhood_cv(self.h, ptr(X), X.shape[1], idx.shape[0], idx.shape[1], idx.ctypes.data_as(_lib._ip),
+                                           _lib.COV_CENTER if center else 0, L, ptr(lam), _MB_RULES[rule], float(tol),
+                                           int(max_sweeps), float(t), 1 if refit else 0, ptr(resvar), ptr(heldout),
+                                           info.ctypes.data_as(_lib._ip), ptr(W)))
+        out = {'resvar': resvar, 'heldout': heldout, 'status': info[..., 1].astype(np.int64),
+               ('degree' if refit else 'sweeps'): info[..., 0].astype(np.int64)}
+        if stack:
+            out['stack'] = W
+        return out
+
     def heldout_scores(self, X, test_idx, center=True, out=None):
         """K-fold cross-validation over the Theta snapshots of a batch of K = L * F points (instance l * F + f: fold f at
         lambda l): (K,4) = ``<S_test[k % F], Theta_k>``, log det Theta_k, count_nonzero(Theta_k), lambda_min(Theta_k), with

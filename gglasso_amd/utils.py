@@ -1329,3 +1329,221 @@ def host_neighborhood_selection(S, lambda_range, rule='and', tol=1e-7, max_sweep
                 raw[m, :, :, j], resvar[m, :, j], info[m, :, j, 0], info[m, :, j, 1] = b, r, s, st
     W = raw if rule == 'raw' else neighborhood_graph(raw, rule)
     return _mb_result(W, raw, resvar, info, lam, single, return_info)
+
+
+# -----------------------------------------------------------------------------------------------------------------
+# Refit of neighbourhood selection on its graph: with the graph held fixed every node is regressed on its neighbours by
+# ordinary least squares -- the relaxed lasso (Meinshausen 2007) and the regression-based precision estimator of Yuan (2010)
+# and Zhou, Ruetimann, Xu, Buehlmann (2011).  It takes the lasso's shrinkage out of the coefficients, gives a precision matrix
+# (``neighborhood_precision``) and, scored on held-out data, the prediction error that tunes lambda (``cv_search(method='mb')``).
+# On the device: csrc/mb_refit.hip; DESIGN 28.
+# -----------------------------------------------------------------------------------------------------------------
+MB_REFIT_MAX_P = 2048
+MB_REFIT_MAX_DEG = 128          # MBR_MAX_DEG of csrc/kernels.hpp; the twin applies the same cap
+
+
+def mb_refit_max_degree():
+    """The largest degree the device refit solves, as the library reports it (``ggl_mb_refit_limits``)."""
+    out = (ctypes.c_int * 2)()
+    _lib.load().ggl_mb_refit_limits(out)
+    return int(out[0])
+
+
+def _refit_args(S, W, t, S_test):
+    Sm = np.asarray(S, dtype=np.float64)
+    assert Sm.ndim in (2, 3) and Sm.shape[-1] == Sm.shape[-2] and Sm.shape[-1] >= 1 and Sm.shape[0] >= 1, \
+        f"neighborhood_refit needs a square (p,p) matrix or a (M,p,p) stack of them, S has shape {Sm.shape}"
+    single = Sm.ndim == 2
+    Sm = as_c(Sm[None] if single else Sm)
+    M, p = Sm.shape[0], Sm.shape[1]
+    assert p <= MB_REFIT_MAX_P, f"p = {p}: the refit serves p <= {MB_REFIT_MAX_P}"
+    Wm = np.asarray(W, dtype=np.float64)
+    assert Wm.ndim >= 2 and Wm.shape[-2:] == (p, p), f"W must end in ({p},{p}), has shape {Wm.shape}"
+    if single:
+        assert Wm.ndim in (2, 3), f"with one matrix S, W is (p,p) or (G,p,p); it has shape {Wm.shape}"
+        one_graph = Wm.ndim == 2
+        Wm = Wm.reshape((1, -1, p, p))
+    else:
+        assert Wm.ndim in (3, 4) and Wm.shape[0] == M, f"with a (M,p,p) stack S, W is (M,p,p) or (M,G,p,p); it has shape {Wm.shape}"
+        one_graph = Wm.ndim == 3
+        Wm = Wm.reshape((M, -1, p, p))
+    assert Wm.shape[1] >= 1, "W holds no graph"
+    assert np.isfinite(t) and t >= 0, f"t = {t}: the edge threshold must be finite and not negative"
+    Tm = None
+    if S_test is not None:
+        Tm = np.asarray(S_test, dtype=np.float64)
+        assert Tm.shape == ((p, p) if single else (M, p, p)), f"S_test must have the shape of S, has {Tm.shape}"
+        Tm = as_c(Tm[None] if single else Tm)
+    if not np.all(np.isfinite(Sm)):
+        m, i, k = np.argwhere(~np.isfinite(Sm))[0]
+        raise ValueError(f"neighborhood_refit: S of matrix {int(m)}: the entry ({int(i)}, {int(k)}) is not finite")
+    dg = np.diagonal(Sm, axis1=1, axis2=2)
+    if not np.all(dg > 0):
+        m, i = np.argwhere(~(dg > 0))[0]
+        raise ValueError(f"neighborhood_refit: S of matrix {int(m)}, variable {int(i)}: the diagonal entry is {dg[m, i]}; it must be positive")
+
+    def pick(a):
+        a = a[:, 0] if one_graph else a
+        return a[0] if single else a
+    return Sm, as_c(Wm), Tm, pick
+
+
+def _refit_result(coef, resvar, heldout, info, pick):
+    return {'COEF': pick(coef), 'RESVAR': pick(resvar), 'HELDOUT': None if heldout is None else pick(heldout),
+            'DEGREE': pick(info[..., 0].astype(np.int64)), 'STATUS': pick(info[..., 1].astype(np.int64))}
+
+
+def neighborhood_refit(S, W, t=1e-8, S_test=None, device=0):
+    """Least-squares refit of every node on its neighbours in a given graph, on the device (``ggl_neighborhood_refit``).
+
+    S: (p,p) or (M,p,p), symmetric, finite, positive diagonal, p <= 2048.  W: ([M,][G,]p,p), the graphs: node j's neighbours
+    are ``A = {i != j : |W[.., j, i]| >= t}``, ROW j (the edge definition of ``stars_search``; a NaN is no edge).  W need not
+    be symmetric: the AND / OR matrices of ``neighborhood_selection`` give graph refits, a raw coefficient matrix transposed
+    (row j = node j's support) the per-node relaxed lasso.  With ``d = |A|``: ``beta = S_AA^-1 s_A`` by Cholesky,
+    ``tau^2 = S_jj - 2 s_A' beta + beta' S_AA beta``, and with ``S_test`` (the shape of S) the same form on it: the held-out
+    residual sum of squares per test sample.
+
+    Returns a dict: ``COEF`` (..,p,p: column j holds node j's coefficients), ``RESVAR``, ``HELDOUT`` (None without ``S_test``),
+    ``DEGREE``, ``STATUS`` (..,p): 0 solved; 1 a pivot was not positive and finite (``S_AA`` is not positive definite: a
+    duplicated variable, more neighbours than observations); 2 a non-finite value in ``S_test``; 3 the degree exceeds
+    ``MB_REFIT_MAX_DEG`` = 128.  For 1-3 that node's coefficients (its diagonal entry aside), ``RESVAR`` and ``HELDOUT``
+    are NaN; no other node is touched and nothing is an error.  The same bits on every call; those of one (matrix, graph) do not
+    depend on the others in the call."""
+    Sm, Wm, Tm, pick = _refit_args(S, W, t, S_test)
+    M, G, p = Wm.shape[0], Wm.shape[1], Wm.shape[2]
+    _lib.require_gpu()
+    lib = _lib.load()
+    coef, resvar = np.empty((M, G, p, p)), np.empty((M, G, p))
+    heldout = None if Tm is None else np.empty((M, G, p))
+    info = np.empty((M, G, p, 2), dtype=np.int32)
+    check(lib.ggl_neighborhood_refit(int(device), M, p, ptr(Sm), G, ptr(Wm), float(t), ptr(Tm), ptr(coef), ptr(resvar),
+                                     ptr(heldout), info.ctypes.data_as(_lib._ip)))
+    return _refit_result(coef, resvar, heldout, info, pick)
+
+
+def _host_quad(Mat, j, A, beta):
+    """``q(M; beta) = M_jj - 2 m_A' beta + beta' M_AA beta`` in the device's arrangement ``M_jj + sum_i beta_i (w_i - 2 m_i)``."""
+    if A.size == 0:
+        return Mat[j, j]
+    x = Mat[np.ix_(A, A)] @ beta - 2.0 * Mat[A, j]
+    return Mat[j, j] + float(beta @ x)
+
+
+def _host_refit_node(S, T, w_row, j, t, cap):
+    """(beta (p,), tau2, r, degree, status) of one node: the device's steps and the order of its tests (3, 2 on S, 1, 2 on T)."""
+    p = S.shape[0]
+    with np.errstate(invalid='ignore'):
+        e = np.abs(w_row) >= t
+    e[j] = False
+    A = np.flatnonzero(e)
+    d = int(A.size)
+    bad = np.full(p, np.nan)
+    bad[j] = 0.0
+    if d > cap:
+        return bad, np.nan, np.nan, d, 3
+    SAA, sA = S[np.ix_(A, A)], S[A, j]
+    if not (np.all(np.isfinite(SAA)) and np.all(np.isfinite(sA)) and np.isfinite(S[j, j])):
+        return bad, np.nan, np.nan, d, 2
+    beta = np.zeros(0)
+    if d:
+        try:
+            Lf = np.linalg.cholesky(SAA)
+        except np.linalg.LinAlgError:
+            return bad, np.nan, np.nan, d, 1
+        if not (np.all(np.isfinite(Lf)) and np.all(np.diagonal(Lf) > 0)):
+            return bad, np.nan, np.nan, d, 1
+        y = np.zeros(d)
+        for k in range(d):
+            y[k] = (sA[k] - Lf[k, :k] @ y[:k]) / Lf[k, k]
+        beta = np.zeros(d)
+        for k in range(d - 1, -1, -1):
+            beta[k] = (y[k] - Lf[k + 1:, k] @ beta[k + 1:]) / Lf[k, k]
+    tau = _host_quad(S, j, A, beta)
+    r = np.nan
+    if T is not None:
+        if not (np.all(np.isfinite(T[np.ix_(A, A)])) and np.all(np.isfinite(T[A, j])) and np.isfinite(T[j, j])):
+            return bad, np.nan, np.nan, d, 2
+        r = _host_quad(T, j, A, beta)
+    out = np.zeros(p)
+    out[A] = beta
+    return out, tau, r, d, 0
+
+
+def host_neighborhood_refit(S, W, t=1e-8, S_test=None):
+    """numpy twin of ``neighborhood_refit``: the same steps in float64 -- the neighbour list from row j,
+    ``numpy.linalg.cholesky`` per node (a failure, or a factor that is not finite with a positive diagonal, is status 1), the
+    two triangular solves by substitution, the quadratic forms -- the same degree cap and the same statuses, in numpy's own
+    summation orders and without fused multiply-adds, so its last bits differ from the device's.  For engines without the
+    device route and tests without a GPU."""
+    Sm, Wm, Tm, pick = _refit_args(S, W, t, S_test)
+    M, G, p = Wm.shape[0], Wm.shape[1], Wm.shape[2]
+    cap = MB_REFIT_MAX_DEG
+    coef, resvar = np.zeros((M, G, p, p)), np.zeros((M, G, p))
+    heldout = None if Tm is None else np.zeros((M, G, p))
+    info = np.zeros((M, G, p, 2), dtype=np.int32)
+    with np.errstate(all='ignore'):
+        for m in range(M):
+            for g in range(G):
+                for j in range(p):
+                    b, tau, r, d, st = _host_refit_node(Sm[m], None if Tm is None else Tm[m], Wm[m, g, j], j, float(t), cap)
+                    coef[m, g, :, j], resvar[m, g, j], info[m, g, j] = b, tau, (d, st)
+                    if heldout is not None:
+                        heldout[m, g, j] = r
+    return _refit_result(coef, resvar, heldout, info, pick)
+
+
+def neighborhood_precision(coef, resvar, rule='min'):
+    """The precision matrix of a set of node-wise regressions (Yuan 2010; Zhou et al. 2011), on the host (O(p^2)):
+    ``Theta_jj = 1 / resvar_j``, column j off the diagonal ``-coef[:, j] / resvar_j``, then symmetrised -- ``rule='min'``: of
+    ``Theta_ij`` and ``Theta_ji`` the one of smaller magnitude (the (i,j) entry with i < j on a tie) goes to both places, so a
+    pair that only one regression selects is zero; ``rule='average'``: their mean.  Bitwise symmetric.  ``coef`` (p,p) with
+    column j node j's coefficients, ``resvar`` (p,): ``COEF`` / ``RESVAR`` of ``neighborhood_refit`` (or of the lasso itself).
+
+    Returns ``(Theta, lambda_min(Theta))``.  The estimator is NOT positive definite by construction -- the node-wise
+    regressions are not tied to one another -- and a ``RuntimeWarning`` says so when the smallest eigenvalue is not positive
+    (or the inputs hold a NaN: a node whose refit failed).  A positive definite estimate on the same graph needs the
+    constrained maximum-likelihood refit, which is not implemented."""
+    import warnings
+    assert rule in ('min', 'average'), f"rule = {rule!r}: 'min' or 'average'"
+    C = np.asarray(coef, dtype=np.float64)
+    tau = np.asarray(resvar, dtype=np.float64).reshape(-1)
+    assert C.ndim == 2 and C.shape[0] == C.shape[1] == tau.size, f"coef (p,p) and resvar (p,) do not fit: {C.shape}, {tau.shape}"
+    p = tau.size
+    with np.errstate(all='ignore'):
+        raw = -C / tau[None, :]
+        a, b = np.triu(raw, 1), np.triu(raw.T, 1)                           # Theta_ij from node j, from node i (i < j)
+        up = np.where(np.abs(b) < np.abs(a), b, a) if rule == 'min' else 0.5 * (a + b)
+        up = np.triu(up, 1)
+        Theta = up + up.T
+        Theta[np.arange(p), np.arange(p)] = 1.0 / tau
+    if not np.all(np.isfinite(Theta)):
+        warnings.warn("neighborhood_precision: the regressions hold a non-finite value (a node whose refit failed, a residual "
+                      "variance of zero); the matrix is returned as it is", RuntimeWarning, stacklevel=2)
+        return Theta, float('nan')
+    lmin = float(np.linalg.eigvalsh(Theta)[0])
+    if not lmin > 0:
+        warnings.warn(f"neighborhood_precision: the smallest eigenvalue is {lmin:.3g}; the regression-based estimator is not "
+                      f"positive definite by construction", RuntimeWarning, stacklevel=2)
+    return Theta, lmin
+
+
+def mb_cv_scores(resvar, heldout, bad, score='pseudo'):
+    """(L,F) scores of a neighbourhood cross-validation from its per-node arrays (L,F,p), summed on the host:
+    ``'pseudo'``: ``sum_j log tau_j^2 + r_j / tau_j^2`` (the negative Gaussian pseudo-log-likelihood per held-out observation, up
+    to a constant), +inf for a (lambda, fold) with a node marked in ``bad`` (L,F,p: a refit status 1-3, a non-finite path) or
+    whose tau^2 is not positive; ``'mse'``:
+    ``sum_j r_j`` (NaN where a node has none)."""
+    import math
+    assert score in ('pseudo', 'mse'), f"score = {score!r}: 'pseudo' or 'mse'"
+    tau, r, bad = np.asarray(resvar, dtype=np.float64), np.asarray(heldout, dtype=np.float64), np.asarray(bad, dtype=bool)
+    L, F = tau.shape[:2]
+    out = np.zeros((L, F))
+    for l in range(L):
+        for f in range(F):
+            if score == 'mse':
+                out[l, f] = math.fsum(r[l, f]) if np.all(np.isfinite(r[l, f])) else np.nan
+            elif np.any(bad[l, f]) or not np.all(tau[l, f] > 0) or not np.all(np.isfinite(r[l, f])):
+                out[l, f] = np.inf
+            else:
+                out[l, f] = math.fsum(np.log(tau[l, f]) + r[l, f] / tau[l, f])
+    return out

@@ -31,7 +31,8 @@ extern "C" {
  * ggl_set_S_from_kendall, ggl_covariance_pairwise, ggl_covariance_pairwise_subsets, ggl_set_S_from_data_pairwise,
  * ggl_set_S_from_subsets_pairwise, ggl_covariance_weighted, ggl_set_S_from_weighted, ggl_mixed_correlation,
  * ggl_set_S_from_mixed, ggl_nearest_correlation, ggl_project_S, ggl_heldout_scores, ggl_debias, ggl_cholesky_predict,
- * ggl_weighted_predictive_scores, ggl_neighborhood_path, ggl_neighborhood_stability) leave every existing layout alone and the number where it is. */
+ * ggl_weighted_predictive_scores, ggl_neighborhood_path, ggl_neighborhood_stability, ggl_neighborhood_refit,
+ * ggl_neighborhood_cv, ggl_mb_refit_limits) leave every existing layout alone and the number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -1017,6 +1018,43 @@ int ggl_neighborhood_path(int device, int M, int p, const double *S_host, int L,
                           int max_sweeps, double *coef_out, double *resvar_out, int *info_out);
 int ggl_neighborhood_stability(ggl_ctx *ctx, int L, const double *lam, int rule, double tol, int max_sweeps, double t,
                                long long *num_out, int *counts_out, double *stack_out, int *info_out);
+
+/* ---- Refit of neighbourhood selection on its graph (mb_refit.hip): with the graph held fixed every node is
+ * regressed on its neighbours by ordinary least squares.  This is the relaxed lasso (Meinshausen 2007, Comput. Statist. Data
+ * Anal. 52) and the regression-based precision estimator of Yuan (2010, JMLR 11) and Zhou, Ruetimann, Xu, Buehlmann (2011,
+ * JMLR 12); held-out prediction error of the regressions is how the 2006 paper tunes lambda.  Entry points that are only
+ * ADDED: GGL_VERSION stays where it is.
+ *
+ * Per (matrix m, graph g, node j), with W_host (M,G,p,p) and S_host (M,p,p):
+ *     A      = { i != j : |W[m,g,j,i]| >= t }     ROW j, ascending; a NaN is no edge; W need not be symmetric
+ *     beta   = S_AA^-1 s_A,  s_A = S[A, j]         Cholesky
+ *     tau^2  = q(S; beta),  r = q(T; beta),        q(M; b) = M_jj - 2 m_A' b + b' M_AA b
+ *   coef_out (M,G,p,p):  column j holds beta^(j), zero off A
+ *   resvar_out (M,G,p);  heldout_out (M,G,p) or NULL: r, needs T_host (M,p,p)
+ *   info_out (M,G,p,2):  the degree |A| and a status: 0 solved / 1 a pivot was not positive and finite (S_AA is not positive
+ *                        definite) / 2 a non-finite value among the gathered entries (of T here: S_host is checked) / 3 the
+ *                        degree exceeds the cap.  For 1, 2, 3 that node's tau^2, r and column of coef are NaN (diagonal 0);
+ *                        nobody else is touched and nothing is an error.
+ * ggl_mb_refit_limits: out[0] the degree cap (128), out[1] the largest p (2048).
+ * Reproducible: fixed summation orders, no atomics; the bits of (m,g) depend neither on M nor on G.
+ * GGL_E_ARG before any device work, nothing written: M, G or p < 1; p > 2048; a NULL S_host, W_host, coef_out, resvar_out or
+ * info_out; heldout_out without T_host; t negative or not finite; a non-finite entry or a non-positive diagonal entry of
+ * S_host (matrix and index named).
+ *
+ * ggl_neighborhood_cv: one whole cross-validation step on a ctx whose K = F instances hold the train matrices of the folds
+ * (ggl_set_S_from_subsets and its siblings, ggl_project_S).  The path runs and is symmetrised as in
+ * ggl_neighborhood_stability (rule GGL_MB_AND or GGL_MB_OR); the F test covariances are built from X_host (p,N) and idx_test
+ * (F,m) exactly as ggl_heldout_scores builds them (flags: GGL_COV_CENTER or 0); then, refit != 0: the refit above with
+ * S = train, T = test, W = the symmetrised stack; refit == 0: the lasso's own beta and tau^2, and r = q(T; beta).
+ *   resvar_out, heldout_out (L,F,p);  info_out (L,F,p,2): (degree, status) of the refit, or with refit == 0 (sweeps, status)
+ *   of the path;  stack_out (L,F,p,p) or NULL: the symmetrised stack.  The matrices never exist on the host.
+ * GGL_E_ARG: what ggl_neighborhood_stability and ggl_heldout_scores refuse; a ctx with K != F. */
+void ggl_mb_refit_limits(int out[2]);
+int ggl_neighborhood_refit(int device, int M, int p, const double *S_host, int G, const double *W_host, double t,
+                           const double *T_host, double *coef_out, double *resvar_out, double *heldout_out, int *info_out);
+int ggl_neighborhood_cv(ggl_ctx *ctx, const double *X_host, int N, int F, int m, const int *idx_test, int flags, int L,
+                        const double *lam, int rule, double tol, int max_sweeps, double t, int refit, double *resvar_out,
+                        double *heldout_out, int *info_out, double *stack_out);
 
 #ifdef __cplusplus
 }
