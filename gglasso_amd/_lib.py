@@ -181,6 +181,11 @@ _SIGNATURES = {
     "ggl_neighborhood_path": ([_i, _i, _i, _dp, _i, _dp, _i, _d, _i, _dp, _dp, _ip], _i),
     "ggl_neighborhood_stability": ([_vp, _i, _dp, _i, _d, _i, _d, ctypes.POINTER(ctypes.c_longlong), _ip, _dp, _ip], _i),
     "ggl_mb_refit_limits": ([_ip], None),
+    "ggl_neighborhood_path_w": ([_i, _i, _i, _dp, _i, _dp, _i, _d, _i, _dp, _i, _i, _d, _i, _dp, _dp, _ip], _i),
+    "ggl_neighborhood_stability_w": ([_vp, _i, _dp, _i, _d, _i, _d, _dp, _i, _i, _d, _i, ctypes.POINTER(ctypes.c_longlong), _ip,
+                                      _dp, _ip], _i),
+    "ggl_neighborhood_cv_w": ([_vp, _dp, _i, _i, _i, _ip, _i, _i, _dp, _i, _d, _i, _d, _i, _dp, _i, _i, _d, _i, _dp, _dp, _ip,
+                               _dp], _i),
     "ggl_neighborhood_refit": ([_i, _i, _i, _dp, _i, _dp, _d, _dp, _dp, _dp, _dp, _ip], _i),
     "ggl_neighborhood_cv": ([_vp, _dp, _i, _i, _i, _ip, _i, _i, _dp, _i, _d, _i, _d, _i, _dp, _dp, _ip, _dp], _i),
 }

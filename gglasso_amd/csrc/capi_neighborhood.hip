@@ -259,3 +259,172 @@ extern "C" int ggl_neighborhood_cv(ggl_ctx* c, const double* X_host, int N, int 
     HIPCHK(hipStreamSynchronize(st));
     return GGL_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Penalty weights and the scaled lasso (kernel: neighborhood_weighted.hip): the adaptive lasso of Zou (2006, JASA
+// 101), the scaled lasso of Sun & Zhang (2012, Biometrika 99; 2013, JMLR 14) / the square-root lasso of Belloni, Chernozhukov,
+// Wang (2011, Biometrika 98), the estimator behind TIGER (Liu & Wang 2017, EJS 11).  Each entry is its sibling above plus
+// (weights, weights_per_matrix, mode, sig_tol, max_outer); everything behind the path is the sibling's code.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+int check_mbw_args(const double* weights, int weights_per_matrix, int M, int p, int mode, double sig_tol, int max_outer)
+{
+    if (mode != GGL_MB_LASSO && mode != GGL_MB_SCALED)
+        return fail(GGL_E_ARG, "bad argument: mode = %d (GGL_MB_LASSO 0, GGL_MB_SCALED 1)", mode);
+    if (!(sig_tol >= 0.0) || !std::isfinite(sig_tol))
+        return fail(GGL_E_ARG, "bad argument: sig_tol = %g must be non-negative and finite", sig_tol);
+    if (max_outer < 1) return fail(GGL_E_ARG, "bad argument: max_outer = %d; max_outer >= 1", max_outer);
+    if (weights) {
+        const size_t pp = (size_t)p * p;
+        const int nW = weights_per_matrix ? M : 1;
+        for (int m = 0; m < nW; ++m)
+            for (size_t e = 0; e < pp; ++e) {
+                const double v = weights[(size_t)m * pp + e];
+                if (!(v >= 0.0))                                            // +inf is legal: the coordinate is excluded
+                    return fail(GGL_E_ARG, "bad argument: weights of matrix %d: the entry (%d, %d) is %g; a penalty weight must "
+                                "lie in [0, +inf]", m, (int)(e / p), (int)(e % p), v);
+            }
+    }
+    return GGL_OK;
+}
+}  // namespace
+
+extern "C" int ggl_neighborhood_path_w(int device, int M, int p, const double* S_host, int L, const double* lam, int rule,
+                                       double tol, int max_sweeps, const double* weights, int weights_per_matrix, int mode,
+                                       double sig_tol, int max_outer, double* coef_out, double* resvar_out, int* info_out)
+{
+    ARGCHK(M >= 1, "M >= 1");
+    RCCHK(check_mb_args(L, lam, rule, GGL_MB_RAW, tol, max_sweeps, p));
+    ARGCHK(S_host && coef_out && info_out, "S, coef_out and info_out must not be NULL");
+    ARGCHK((double)M * p < 2147483647.0, "M * p must stay below 2^31");
+    RCCHK(check_mbw_args(weights, weights_per_matrix, M, p, mode, sig_tol, max_outer));
+    const size_t pp = (size_t)p * p;
+    for (int m = 0; m < M; ++m) {
+        const double* a = S_host + (size_t)m * pp;
+        for (size_t e = 0; e < pp; ++e)
+            if (!std::isfinite(a[e]))
+                return fail(GGL_E_ARG, "bad argument: S of matrix %d: the entry (%d, %d) is not finite", m, (int)(e / p), (int)(e % p));
+        for (int i = 0; i < p; ++i)
+            if (!(a[(size_t)i * p + i] > 0.0))
+                return fail(GGL_E_ARG, "bad argument: S of matrix %d, variable %d: the diagonal entry is %g; it must be positive", m,
+                            i, a[(size_t)i * p + i]);
+    }
+    HIPCHK(hipSetDevice(device));
+    const size_t nML = (size_t)M * L, nW = weights ? (weights_per_matrix ? (size_t)M : 1) * pp : 0;
+    DevBuf dS, dLam, dCoef, dRes, dW;
+    IntBuf dInfo;
+    HIPCHK(dS.alloc((size_t)M * pp));
+    HIPCHK(dLam.alloc(L));
+    HIPCHK(dCoef.alloc(nML * pp));
+    if (resvar_out) HIPCHK(dRes.alloc(nML * p));
+    if (weights) HIPCHK(dW.alloc(nW));
+    HIPCHK(dInfo.alloc(nML * p * 3));
+    UP(dS.p, S_host, (size_t)M * pp);
+    UP(dLam.p, lam, L);
+    if (weights) UP(dW.p, weights, nW);
+    HIPCHK(launch_mb_path_w(nullptr, dS.p, M, p, dW.p, weights_per_matrix ? pp : 0, dLam.p, L, mode, tol, max_sweeps, sig_tol,
+                            max_outer, dCoef.p, dRes.p, dInfo.p, (size_t)L, 1));
+    launch_mb_symmetrize(nullptr, dCoef.p, nML, p, rule);
+    HIPCHK(hipGetLastError());
+    DOWN(coef_out, dCoef.p, nML * pp);
+    if (resvar_out) DOWN(resvar_out, dRes.p, nML * p);
+    HIPCHK(hipMemcpy(info_out, dInfo.p, nML * p * 3 * sizeof(int), hipMemcpyDeviceToHost));
+    return GGL_OK;
+}
+
+extern "C" int ggl_neighborhood_stability_w(ggl_ctx* c, int L, const double* lam, int rule, double tol, int max_sweeps, double t,
+                                            const double* weights, int weights_per_matrix, int mode, double sig_tol,
+                                            int max_outer, long long* num_out, int* counts_out, double* stack_out, int* info_out)
+{
+    ARGCHK(c && num_out && info_out, "ctx, num_out and info_out must not be NULL");
+    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) holds no stack of one dimension");
+    RCCHK(check_mb_args(L, lam, rule, GGL_MB_AND, tol, max_sweeps, c->p));
+    RCCHK(check_threshold(t));
+    const int B = c->K, p = c->p;
+    ARGCHK(L <= 65535, "more than 65535 lambdas in one call");
+    ARGCHK((double)B * p < 2147483647.0, "K * p must stay below 2^31");
+    ARGCHK((double)p * (double)p * (double)B * (double)B < 7e19, "p * B too large for exact 64-bit sums");
+    RCCHK(check_mbw_args(weights, weights_per_matrix, B, p, mode, sig_tol, max_outer));
+    HIPCHK(hipSetDevice(c->device));
+    DROP_PRE(c);
+    const size_t pp = (size_t)p * p, nLB = (size_t)L * B, nW = weights ? (weights_per_matrix ? (size_t)B : 1) * pp : 0;
+    DevBuf dLam, dStack, dNum, dW;
+    IntBuf dInfo, dCnt;
+    HIPCHK(dLam.alloc(L));
+    HIPCHK(dStack.alloc(nLB * pp));
+    HIPCHK(dNum.alloc(L));
+    if (weights) HIPCHK(dW.alloc(nW));
+    HIPCHK(dInfo.alloc(nLB * p * 3));
+    if (counts_out) HIPCHK(dCnt.alloc((size_t)L * pp));
+    hipStream_t st = c->stream;
+    unsigned long long* num = reinterpret_cast<unsigned long long*>(dNum.p);
+    HIPCHK(hipMemcpyAsync(dLam.p, lam, L * sizeof(double), hipMemcpyHostToDevice, st));
+    if (weights) HIPCHK(hipMemcpyAsync(dW.p, weights, nW * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(num, 0, L * sizeof(unsigned long long), st));
+    // slot (subsample r, lambda l) of the stack is l * B + r: the layout k_edge_stability reads
+    HIPCHK(launch_mb_path_w(st, c->S, B, p, dW.p, weights_per_matrix ? pp : 0, dLam.p, L, mode, tol, max_sweeps, sig_tol, max_outer,
+                            dStack.p, nullptr, dInfo.p, 1, (size_t)B));
+    launch_mb_symmetrize(st, dStack.p, nLB, p, rule);
+    HIPCHK(hipGetLastError());
+    launch_edge_stability(st, dStack.p, L, B, p, t, dCnt.p, num);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(num_out, num, L * sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(info_out, dInfo.p, nLB * p * 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (counts_out) HIPCHK(hipMemcpyAsync(counts_out, dCnt.p, (size_t)L * pp * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (stack_out) HIPCHK(hipMemcpyAsync(stack_out, dStack.p, nLB * pp * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return GGL_OK;
+}
+
+extern "C" int ggl_neighborhood_cv_w(ggl_ctx* c, const double* X_host, int N, int F, int m, const int* idx_test, int flags, int L,
+                                     const double* lam, int rule, double tol, int max_sweeps, double t, int refit,
+                                     const double* weights, int weights_per_matrix, int mode, double sig_tol, int max_outer,
+                                     double* resvar_out, double* heldout_out, int* info_out, double* stack_out)
+{
+    ARGCHK(c && resvar_out && heldout_out && info_out, "ctx, resvar_out, heldout_out and info_out must not be NULL");
+    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) holds no stack of one dimension");
+    RCCHK(check_mb_args(L, lam, rule, GGL_MB_AND, tol, max_sweeps, c->p));
+    RCCHK(check_threshold(t));
+    RCCHK(heldout_fold_check(c, X_host, N, F, m, idx_test, flags));
+    if (c->K != F)
+        return fail(GGL_E_ARG, "bad argument: the ctx holds K = %d matrices, the cross-validation has F = %d folds; instance f must "
+                    "be the train matrix of fold f", c->K, F);
+    const int p = c->p;
+    ARGCHK(L <= 65535, "more than 65535 lambdas in one call");
+    ARGCHK((double)L * F * p < 2147483647.0, "L * F * p must stay below 2^31");
+    RCCHK(check_mbw_args(weights, weights_per_matrix, F, p, mode, sig_tol, max_outer));
+    HIPCHK(hipSetDevice(c->device));
+    DROP_PRE(c);
+    const size_t pp = (size_t)p * p, nLF = (size_t)L * F, nW = weights ? (weights_per_matrix ? (size_t)F : 1) * pp : 0;
+    DevBuf dLam, dStack, dCoef, dRes, dHeld, dT, dVar, dW;
+    IntBuf dInfo;
+    HIPCHK(dLam.alloc(L));
+    HIPCHK(dStack.alloc(nLF * pp));
+    if (refit) HIPCHK(dCoef.alloc(nLF * pp));
+    HIPCHK(dRes.alloc(nLF * p));
+    HIPCHK(dHeld.alloc(nLF * p));
+    HIPCHK(dT.alloc((size_t)F * pp));
+    HIPCHK(dVar.alloc((size_t)F * p));
+    if (weights) HIPCHK(dW.alloc(nW));
+    HIPCHK(dInfo.alloc(nLF * p * 3));
+    hipStream_t st = c->stream;
+    RCCHK(heldout_fold_covariances(c, X_host, N, F, m, idx_test, flags, dT.p, dVar.p));
+    HIPCHK(hipMemcpyAsync(dLam.p, lam, L * sizeof(double), hipMemcpyHostToDevice, st));
+    if (weights) HIPCHK(hipMemcpyAsync(dW.p, weights, nW * sizeof(double), hipMemcpyHostToDevice, st));
+    // slot (fold f, lambda l) is l * F + f, as in ggl_neighborhood_stability; its matrices are S[f], T[f]
+    HIPCHK(launch_mb_path_w(st, c->S, F, p, dW.p, weights_per_matrix ? pp : 0, dLam.p, L, mode, tol, max_sweeps, sig_tol, max_outer,
+                            dStack.p, refit ? nullptr : dRes.p, dInfo.p, 1, (size_t)F));
+    if (!refit) {
+        launch_mb_heldout(st, dT.p, dStack.p, p, nLF, 1, F, dHeld.p);       // the lasso's own beta, still in rows
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(info_out, dInfo.p, nLF * p * 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    launch_mb_symmetrize(st, dStack.p, nLF, p, rule);
+    HIPCHK(hipGetLastError());
+    if (refit) RCCHK(run_refit(st, c->S, dT.p, dStack.p, t, p, nLF, 1, F, dCoef.p, dRes.p, dHeld.p, dInfo.p, info_out));
+    HIPCHK(hipMemcpyAsync(resvar_out, dRes.p, nLF * p * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(heldout_out, dHeld.p, nLF * p * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (stack_out) HIPCHK(hipMemcpyAsync(stack_out, dStack.p, nLF * pp * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return GGL_OK;
+}

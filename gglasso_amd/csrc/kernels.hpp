@@ -589,6 +589,15 @@ void launch_mb_path(hipStream_t st, const double* S, int M, int p, const double*
 // 'or' matrix -- of beta^(j)_i and beta^(i)_j the one of smaller / larger magnitude to (i,j) and (j,i), the former on a tie
 void launch_mb_symmetrize(hipStream_t st, double* C, size_t nmat, int p, int rule);
 
+// launch_mb_path with per-entry penalty weights and the scaled lasso (neighborhood_weighted.hip).  Wt: node j of
+// matrix m reads its weights from ROW j of the (p,p) table at Wt + m * wstride (wstride 0: one table for all; p * p: one per
+// matrix); null: all 1.  mode 0 plain, 1 scaled (sig_tol, max_outer: the alternation on sigma).  info: slots of (p,3) =
+// sweeps, status (as above; 3: scaled mode, tau^2 <= 1e-10 S_jj), outer iterations (0 in plain mode).  Returns what setting
+// the kernel's LDS limit or the launch returned.
+hipError_t launch_mb_path_w(hipStream_t st, const double* S, int M, int p, const double* Wt, size_t wstride, const double* lam,
+                            int L, int mode, double tol, int max_sweeps, double sig_tol, int max_outer, double* coef,
+                            double* resvar, int* info, size_t strideM, size_t strideL);
+
 // Refit of neighbourhood selection on its graph (mb_refit.hip).  W: nslot slots of (p,p); the unit (slot s, node j)
 // takes its neighbours from ROW j of slot s (|.| >= t, a NaN is none) and its data from matrix (s / sdiv) % smod of S and,
 // where heldout is not null, of T.  coef: nslot slots of (p,p), ZEROED by the caller; ROW j receives beta^(j) (as

@@ -701,9 +701,26 @@ def _host_edge_counts(Theta, t):
     return (up + up.transpose(0, 2, 1)).astype(np.int32), num.astype(np.int64)
 
 
+def _mbw_kwargs(method, weights, scaled, X):
+    """The keyword arguments ``weights`` / ``scaled`` add to every path call of a search ({} without them), and their
+    refusals."""
+    if weights is None and not scaled:
+        return {}
+    if method != 'mb':
+        raise ValueError("weights= and scaled= belong to method='mb' (utils.neighborhood_selection): the node-wise lasso's "
+                         "penalty weights and the scaled lasso.  The graphical lasso's per-entry penalties are lambda1_mask")
+    kw = {'scaled': True} if scaled else {}
+    if weights is not None:
+        p = np.shape(X)[0]
+        Wt = np.asarray(weights, dtype=np.float64)
+        assert Wt.shape == (p, p), f"weights must be one ({p},{p}) table (row j: node j's weights) for every fit, got {Wt.shape}"
+        kw['weights'] = Wt
+    return kw
+
+
 def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.05, seed=0, indices=None, t=1e-8, center=True,
                  scale=False, tol=1e-7, rtol=1e-7, max_iter=1000, store_all=False, lambdas_per_batch=None, correlation=None,
-                 missing=None, min_pairs=2, project=False, method='glasso', rule='and', refit=False):
+                 missing=None, min_pairs=2, project=False, method='glasso', rule='and', refit=False, weights=None, scaled=False):
     """StARS for the Single Graphical Lasso from observations ``X`` (p,N), variables in rows.  Returns ``(sol, stats)``.
 
     * Subsamples: ``stars_subsamples(N, n_subsamples, subsample_size, seed)``, or ``indices`` (B,b) given by the caller
@@ -759,13 +776,17 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
     is what huge does.  ``refit=True`` (``method='mb'`` only): ``sol`` gains ``coef_refit`` and ``resvar_refit``, the
     least-squares refit of every node on its neighbours in ``sol['adjacency']`` (``utils.neighborhood_refit``), and
     ``precision``, ``utils.neighborhood_precision`` of the two; with the default the keys and bits of ``sol`` stay.  With
-    ``method='glasso'`` nothing of this applies."""
+    ``method='glasso'`` nothing of this applies.  ``weights`` ((p,p): row j holds node j's penalty weights) and ``scaled`` (the
+    scaled lasso) are those of ``utils.neighborhood_selection`` (``method='mb'`` only; the graphical lasso's per-entry
+    penalties are ``lambda1_mask``): they apply to every subsample fit and to the final fit, on the device and on the host
+    route; statuses 2 and 3 put a lambda into ``FAILED``.  Without them the calls and the bits are what they were."""
     import warnings
     from . import solver as _solver, utils
     from .batch import _sgl_batch_impl
     assert method in ('glasso', 'mb'), "method must be 'glasso' or 'mb'"
     mb = method == 'mb'
     assert not mb or rule in ('and', 'or'), "rule must be 'and' or 'or'"
+    mbw = _mbw_kwargs(method, weights, scaled, X)
     assert mb or not refit, "refit=True needs method='mb': the graphical lasso has no node-wise regressions to refit"
     assert correlation in (None, 'kendall', 'mixed'), "correlation must be None (Pearson), 'kendall' or 'mixed'"
     assert missing in (None, 'pairwise'), "missing must be None (complete data) or 'pairwise'"
@@ -841,20 +862,20 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
                 eng = _solver.ENGINE(ph, ph, ph, np.broadcast_to(np.zeros((p, p)), (B, p, p)))
                 try:
                     before(eng)
-                    out = eng.neighborhood_stability(lam[sl], rule, tol=tol, t=t, counts=store_all, stack=store_all)
+                    out = eng.neighborhood_stability(lam[sl], rule, tol=tol, t=t, counts=store_all, stack=store_all, **mbw)
                 finally:
                     eng.close()
                 NUM[sl], status = out['num'], out['status']
                 if store_all:
                     COUNTS[sl], THETA[sl] = out['counts'], out['stack']
             else:
-                W, inf = utils.host_neighborhood_selection(S_host, lam[sl], rule, tol=tol, return_info=True)
+                W, inf = utils.host_neighborhood_selection(S_host, lam[sl], rule, tol=tol, return_info=True, **mbw)
                 Th = np.ascontiguousarray(np.swapaxes(W, 0, 1))              # (B,nl,p,p) -> (nl,B,p,p)
                 cnt, NUM[sl] = _host_edge_counts(Th, t)
                 status = np.swapaxes(inf['STATUS'], 0, 1)
                 if store_all:
                     COUNTS[sl], THETA[sl] = cnt, Th
-            failed[sl] = (status == 2).any(axis=(1, 2))
+            failed[sl] = (status >= 2).any(axis=(1, 2))
             capped += int((status == 1).sum())
             continue
         if on_device:
@@ -909,7 +930,7 @@ def stars_search(X, lambda_range, n_subsamples=20, subsample_size=None, beta=0.0
                'lambda1': lam[ix]}
     elif mb:
         path = utils.neighborhood_selection if on_device else utils.host_neighborhood_selection
-        W, inf = path(S_full, lam[:ix + 1], rule, tol=tol, return_info=True)
+        W, inf = path(S_full, lam[:ix + 1], rule, tol=tol, return_info=True, **mbw)
         with np.errstate(invalid='ignore'):
             sol = {'adjacency': (np.abs(W[ix]) >= t) & (W[ix] != 0), 'coef': inf['COEF'][ix],
                    'resvar': inf['RESVAR'][ix], 'lambda1': lam[ix]}
@@ -991,7 +1012,8 @@ def _host_heldout_scores(Theta, S_test):
 
 def cv_search(X, lambda_range, n_folds=5, seed=0, folds=None, rule='min', center=True, scale=False, tol=1e-7, rtol=1e-7,
               max_iter=1000, store_all=False, lambdas_per_batch=None, correlation=None, missing=None, project=False,
-              latent=False, lambda1_mask=None, method='glasso', graph_rule='and', refit=True, score='pseudo', t=1e-8):
+              latent=False, lambda1_mask=None, method='glasso', graph_rule='and', refit=True, score='pseudo', t=1e-8,
+              weights=None, scaled=False):
     """K-fold cross-validation of lambda1 for the Single Graphical Lasso from observations ``X`` (p,N), variables in rows.
     Returns ``(sol, stats)``.
 
@@ -1030,12 +1052,17 @@ def cv_search(X, lambda_range, n_folds=5, seed=0, folds=None, rule='min', center
     the path as in ``stars_search``, and with ``refit`` also ``coef_refit``, ``resvar_refit``; ``precision`` is
     ``utils.neighborhood_precision`` of the refit (without ``refit``: of the lasso's own pair).  On the device one ctx of F
     instances holds the train matrices and ``HipEngine.neighborhood_cv`` does the rest; the matrices never exist on the host.
-    ``rtol``, ``max_iter`` are not used.  With ``method='glasso'`` nothing of this applies."""
+    ``rtol``, ``max_iter`` are not used.  With ``method='glasso'`` nothing of this applies.  ``weights`` ((p,p): row j holds
+    node j's penalty weights) and ``scaled`` (the scaled lasso) are those of ``utils.neighborhood_selection``, for
+    ``method='mb'`` only (the graphical lasso's per-entry penalties are ``lambda1_mask``): they apply to every fold's path and
+    to the final fit, on the device (``ggl_neighborhood_cv_w``) and on the host route; with ``scaled`` and without ``refit``
+    ``tau_j^2`` is the scaled lasso's ``sigma_j^2``.  Without them the calls and the bits are what they were."""
     import warnings
     from . import solver as _solver, utils
     from .batch import _late_failures, _sgl_batch_impl
     if method not in ('glasso', 'mb'):
         raise ValueError(f"method = {method!r}: 'glasso' or 'mb'")
+    mbw = _mbw_kwargs(method, weights, scaled, X)
     if method == 'mb':
         if graph_rule not in ('and', 'or'):
             raise ValueError(f"graph_rule = {graph_rule!r}: 'and' or 'or'")
@@ -1081,7 +1108,8 @@ def cv_search(X, lambda_range, n_folds=5, seed=0, folds=None, rule='min', center
         X = np.ascontiguousarray(X / np.sqrt(var)[:, None])
     per = L if lambdas_per_batch is None else max(1, int(lambdas_per_batch))
     if method == 'mb':
-        return _cv_search_mb(X, lam, train, test, rule, graph_rule, bool(refit), score, float(t), center, var, tol, store_all, per)
+        return _cv_search_mb(X, lam, train, test, rule, graph_rule, bool(refit), score, float(t), center, var, tol, store_all, per,
+                             mbw)
     on_device = hasattr(_solver.ENGINE, "set_data_subsets") and hasattr(_solver.ENGINE, "heldout_scores")
     eye = np.eye(p)
     OUT = np.zeros((L, F, 4))
@@ -1145,7 +1173,7 @@ def cv_search(X, lambda_range, n_folds=5, seed=0, folds=None, rule='min', center
     return sol, stats
 
 
-def _cv_search_mb(X, lam, train, test, rule, graph_rule, refit, score, t, center, var, tol, store_all, per):
+def _cv_search_mb(X, lam, train, test, rule, graph_rule, refit, score, t, center, var, tol, store_all, per, mbw={}):
     """``cv_search(method='mb')`` behind its argument checks: X scaled already, the grid descending."""
     import warnings
     from . import solver as _solver, utils
@@ -1166,14 +1194,15 @@ def _cv_search_mb(X, lam, train, test, rule, graph_rule, refit, score, t, center
             eng = _solver.ENGINE(ph, ph, ph, np.broadcast_to(np.zeros((p, p)), (F, p, p)))
             try:
                 eng.set_data_subsets(X, train, center=center)
-                out = eng.neighborhood_cv(X, test, lam[sl], graph_rule, tol=tol, t=t, refit=refit, center=center, stack=store_all)
+                out = eng.neighborhood_cv(X, test, lam[sl], graph_rule, tol=tol, t=t, refit=refit, center=center, stack=store_all,
+                                          **mbw)
             finally:
                 eng.close()
             TAU[sl], R[sl], STATUS[sl] = out['resvar'], out['heldout'], out['status']
             if store_all:
                 THETA[sl] = out['stack']
             continue
-        W, inf = utils.host_neighborhood_selection(S_train, lam[sl], graph_rule, tol=tol, return_info=True)     # (F,nl,..)
+        W, inf = utils.host_neighborhood_selection(S_train, lam[sl], graph_rule, tol=tol, return_info=True, **mbw)     # (F,nl,..)
         if refit:
             rf = utils.host_neighborhood_refit(S_train, W, t, S_test)
             tau, r, st = rf['RESVAR'], rf['HELDOUT'], rf['STATUS']
@@ -1190,7 +1219,7 @@ def _cv_search_mb(X, lam, train, test, rule, graph_rule, refit, score, t, center
         TAU[sl], R[sl], STATUS[sl] = (np.swapaxes(a, 0, 1) for a in (tau, r, st))
         if store_all:
             THETA[sl] = np.swapaxes(W, 0, 1)
-    bad = (STATUS != 0) if refit else (STATUS == 2)
+    bad = (STATUS != 0) if refit else (STATUS >= 2)
     SC = utils.mb_cv_scores(TAU, R, bad, score)
     capped = 0 if refit else int((STATUS == 1).sum())
     if capped:
@@ -1206,7 +1235,7 @@ def _cv_search_mb(X, lam, train, test, rule, graph_rule, refit, score, t, center
     else:
         S_full = _host_subset_covariances(X, np.arange(N)[None], center, False)[0]
     path = utils.neighborhood_selection if on_device else utils.host_neighborhood_selection
-    W, inf = path(S_full, lam[:ix + 1], graph_rule, tol=tol, return_info=True)
+    W, inf = path(S_full, lam[:ix + 1], graph_rule, tol=tol, return_info=True, **mbw)
     with np.errstate(invalid='ignore'):
         sol = {'adjacency': (np.abs(W[ix]) >= t) & (W[ix] != 0), 'coef': inf['COEF'][ix], 'resvar': inf['RESVAR'][ix],
                'lambda1': lam[ix]}

@@ -476,7 +476,7 @@ class glasso_problem:
         self._keep(sol)
         self.modelselect_stats = dict(stats)
 
-    def neighborhood_selection(self, lambda_range, select='stars', rule='and', refit=True, **kw):
+    def neighborhood_selection(self, lambda_range=None, select='stars', rule='and', refit=True, weights=None, **kw):
         """Meinshausen-Buhlmann neighbourhood selection for a Single Graphical Lasso problem built by ``from_data``: the
         penalty is chosen along ``lambda_range`` by StARS (``select='stars'``, ``model_selection.stars_search(method='mb')``) or
         by cross-validated prediction error (``select='cv'``, ``model_selection.cv_search(method='mb')``); ``rule`` (``'and'`` /
@@ -488,10 +488,21 @@ class glasso_problem:
         ``modelselect_stats`` the search's tables and ``neighborhood_`` the search's ``sol``.  The precision matrix is not
         positive definite by construction (``utils.neighborhood_precision``).  ``solve``, ``model_selection`` and the other
         methods are untouched.  With ``do_scaling`` the method works on correlations and the precision matrix goes back to the
-        covariances' scale, as in ``solve``.  ``select='cv'`` refuses what ``cross_validation`` refuses."""
+        covariances' scale, as in ``solve``.  ``select='cv'`` refuses what ``cross_validation`` refuses.
+
+        ``weights`` ((p,p): row j holds node j's penalty weights, ``utils.adaptive_weights``) goes to the search and its final
+        fit.  ``select='scaled'``: no grid and no search -- the scaled lasso (``utils.scaled_lasso_precision``) on the
+        problem's matrix at ONE penalty, ``lambda0=`` in ``kw`` or the universal ``sqrt(2 log(p) / N)``, with the weights
+        ``'sd'`` unless given.  ``solution.precision_`` is its precision matrix (``rule='and'``: of the two regressions' entries
+        the smaller, ``'or'``: their average), ``adjacency_`` its off-diagonal pattern, ``modelselect_stats`` holds ``LAMBDA0``,
+        ``SIGMA`` (the noise levels), ``STATUS``, ``SWEEPS`` and ``OUTER``; ``refit`` is not used.  ``kw``: ``tol``,
+        ``sig_tol``, ``max_outer``, ``device``.  The same refusals."""
         from . import utils as _utils
-        assert select in ('stars', 'cv'), f"select = {select!r}: 'stars' or 'cv'"
+        assert select in ('stars', 'cv', 'scaled'), f"select = {select!r}: 'stars', 'cv' or 'scaled'"
         assert rule in ('and', 'or'), f"rule = {rule!r}: 'and' or 'or'"
+        assert select == 'scaled' or lambda_range is not None, f"select = {select!r} searches along lambda_range: give one"
+        if weights is not None and select != 'scaled':
+            kw = dict(kw, weights=weights)
         assert getattr(self, '_observations', None) is not None, \
             "Neighbourhood selection resamples the observations: build the problem with glasso_problem.from_data(X)."
         assert not self.multiple, "Neighbourhood selection is implemented for Single Graphical Lasso problems only."
@@ -499,6 +510,20 @@ class glasso_problem:
                                 "node has no low-rank component."
         assert self.reg_params.get('lambda1_mask') is None, "Neighbourhood selection is not implemented with a lambda1_mask."
         X = self._observations[0]
+        if select == 'scaled':
+            assert lambda_range is None, "select='scaled' searches nothing: the penalty is lambda0= (default: sqrt(2 log(p) / N))"
+            host = not hasattr(_solver.ENGINE, "neighborhood_stability")
+            Theta, info = _utils.scaled_lasso_precision(self.S, n=self.N, weights='sd' if weights is None else weights,
+                                                        rule={'and': 'min', 'or': 'average'}[rule], host=host, **kw)
+            self.set_reg_params({'lambda1': info['LAMBDA0']})
+            self._keep({'Theta': Theta})
+            with np.errstate(invalid='ignore'):
+                self.solution.adjacency_ = ((Theta != 0) & ~np.eye(self.p, dtype=bool)).astype(int)
+            self.neighborhood_ = {'coef': info['COEF'], 'resvar': info['RESVAR'], 'lambda1': info['LAMBDA0'],
+                                  'adjacency': self.solution.adjacency_.astype(bool), 'precision': Theta}
+            self.modelselect_stats = {'select': 'scaled', 'LAMBDA0': info['LAMBDA0'], 'SIGMA': info['SIGMA'],
+                                      'STATUS': info['STATUS'], 'SWEEPS': info['SWEEPS'], 'OUTER': info['OUTER']}
+            return
         if select == 'stars':
             how = dict(correlation=self._correlation) if getattr(self, '_correlation', None) in ('kendall', 'mixed') else \
                 dict(center=self._center, scale=bool(self.do_scaling))

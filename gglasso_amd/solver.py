@@ -229,21 +229,40 @@ class HipEngine:
                                           num.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
         return (num, tab) if counts else num
 
-    def neighborhood_stability(self, lambda_range, rule='and', tol=1e-7, max_sweeps=10000, t=1e-8, counts=False, stack=False):
+    def neighborhood_stability(self, lambda_range, rule='and', tol=1e-7, max_sweeps=10000, t=1e-8, counts=False, stack=False,
+                               weights=None, scaled=False, sig_tol=1e-7, max_outer=100):
         """Meinshausen-Buhlmann neighbourhood selection on the K matrices the ctx's S holds -- the B = K subsample matrices
         a ``set_*_subsets`` call wrote -- along the descending grid ``lambda_range`` (``ggl_neighborhood_stability``, see
         ``utils.neighborhood_selection``), and the edge stability of the result: the symmetrised (L,K,p,p) stack stays on the
         device and is reduced as in ``edge_stability``.  Returns a dict: ``num`` (L,) int64, ``sweeps`` and ``status``
-        (L,K,p), with ``counts`` the (L,p,p) int32 tables, with ``stack`` the stack itself."""
+        (L,K,p), with ``counts`` the (L,p,p) int32 tables, with ``stack`` the stack itself.  ``weights`` ((p,p) shared or
+        (K,p,p)), ``scaled``, ``sig_tol``, ``max_outer`` as in ``utils.neighborhood_selection``: with ``weights`` or ``scaled``
+        the call goes to ``ggl_neighborhood_stability_w`` and the dict gains ``outer`` (L,K,p); without, it is the call it
+        was."""
         import ctypes
-        from .utils import _MB_RULES
+        from .utils import _MB_RULES, _mbw_args
         lam = as_c(np.asarray(lambda_range, dtype=np.float64).reshape(-1))
         assert rule in ('and', 'or'), f"rule = {rule!r}: 'and' or 'or'"
         L = lam.size
         num = np.zeros(L, dtype=np.int64)
-        info = np.empty((L, self.K, self.p, 2), dtype=np.int32)
         tab = np.empty((L, self.p, self.p), dtype=np.int32) if counts else None
         W = np.empty((L, self.K, self.p, self.p)) if stack else None
+        if weights is not None or scaled:
+            Wt, per_matrix = _mbw_args(weights, scaled, sig_tol, max_outer, self.K, self.p)
+            info = np.empty((L, self.K, self.p, 3), dtype=np.int32)
+            check(self.lib.ggl_neighborhood_stability_w(self.h, L, ptr(lam), _MB_RULES[rule], float(tol), int(max_sweeps), float(t),
+                                                        ptr(Wt), int(per_matrix), int(bool(scaled)), float(sig_tol), int(max_outer),
+                                                        num.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)),
+                                                        None if tab is None else tab.ctypes.data_as(_lib._ip), ptr(W),
+                                                        info.ctypes.data_as(_lib._ip)))
+            out = {'num': num, 'sweeps': info[..., 0].astype(np.int64), 'status': info[..., 1].astype(np.int64),
+                   'outer': info[..., 2].astype(np.int64)}
+            if counts:
+                out['counts'] = tab
+            if stack:
+                out['stack'] = W
+            return out
+        info = np.empty((L, self.K, self.p, 2), dtype=np.int32)
         check(self.lib.ggl_neighborhood_stability(self.h, L, ptr(lam), _MB_RULES[rule], float(tol), int(max_sweeps), float(t),
                                                   num.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)),
                                                   None if tab is None else tab.ctypes.data_as(_lib._ip), ptr(W),
@@ -256,15 +275,17 @@ class HipEngine:
         return out
 
     def neighborhood_cv(self, X, test_idx, lambda_range, rule='and', tol=1e-7, max_sweeps=10000, t=1e-8, refit=True,
-                        center=True, stack=False):
+                        center=True, stack=False, weights=None, scaled=False, sig_tol=1e-7, max_outer=100):
         """One cross-validation step of neighbourhood selection on the K = F train matrices the ctx's S holds (a
         ``set_*_subsets`` call with the train indices wrote them), ``ggl_neighborhood_cv``: the path along the descending grid,
         symmetrised by ``rule``; the F test covariances of ``X[:, test_idx[f]]`` built on the device as ``heldout_scores``
         builds them; then with ``refit`` every node regressed on its neighbours by least squares on the train matrix
         (``utils.neighborhood_refit``) and scored on the test matrix, without it the lasso's own coefficients scored there.
         Returns a dict of (L,K,p) arrays: ``resvar`` (tau^2), ``heldout`` (r), ``status``, and ``degree`` (with ``refit``) or
-        ``sweeps`` (without); with ``stack`` the symmetrised (L,K,p,p) stack."""
-        from .utils import _MB_RULES, _subset_indices
+        ``sweeps`` (without); with ``stack`` the symmetrised (L,K,p,p) stack.  ``weights`` ((p,p) shared or (K,p,p)),
+        ``scaled``, ``sig_tol``, ``max_outer`` as in ``utils.neighborhood_selection``: with ``weights`` or ``scaled`` the call
+        goes to ``ggl_neighborhood_cv_w`` (without ``refit`` the dict gains ``outer``); without, it is the call it was."""
+        from .utils import _MB_RULES, _mbw_args, _subset_indices
         X = as_c(X)
         assert X.ndim == 2 and X.shape[0] == self.p, f"data must be a ({self.p}, N) array"
         idx = _subset_indices(test_idx)
@@ -272,8 +293,25 @@ class HipEngine:
         assert rule in ('and', 'or'), f"rule = {rule!r}: 'and' or 'or'"
         L = lam.size
         resvar, heldout = np.empty((L, self.K, self.p)), np.empty((L, self.K, self.p))
-        info = np.empty((L, self.K, self.p, 2), dtype=np.int32)
         W = np.empty((L, self.K, self.p, self.p)) if stack else None
+        if weights is not None or scaled:
+            Wt, per_matrix = _mbw_args(weights, scaled, sig_tol, max_outer, self.K, self.p)
+            buf = np.empty(L * self.K * self.p * 3, dtype=np.int32)     # the refit's info: two ints per node, in front
+            check(self.lib.ggl_neighborhood_cv_w(self.h, ptr(X), X.shape[1], idx.shape[0], idx.shape[1],
+                                                 idx.ctypes.data_as(_lib._ip), _lib.COV_CENTER if center else 0, L, ptr(lam),
+                                                 _MB_RULES[rule], float(tol), int(max_sweeps), float(t), 1 if refit else 0,
+                                                 ptr(Wt), int(per_matrix), int(bool(scaled)), float(sig_tol), int(max_outer),
+                                                 ptr(resvar), ptr(heldout), buf.ctypes.data_as(_lib._ip), ptr(W)))
+            ni = 2 if refit else 3
+            info = buf[:L * self.K * self.p * ni].reshape(L, self.K, self.p, ni)
+            out = {'resvar': resvar, 'heldout': heldout, 'status': info[..., 1].astype(np.int64),
+                   ('degree' if refit else 'sweeps'): info[..., 0].astype(np.int64)}
+            if not refit:
+                out['outer'] = info[..., 2].astype(np.int64)
+            if stack:
+                out['stack'] = W
+            return out
+        info = np.empty((L, self.K, self.p, 2), dtype=np.int32)
         check(self.lib.ggl_neighborhood_cv(self.h, ptr(X), X.shape[1], idx.shape[0], idx.shape[1], idx.ctypes.data_as(_lib._ip),
                                            _lib.COV_CENTER if center else 0, L, ptr(lam), _MB_RULES[rule], float(tol),
                                            int(max_sweeps), float(t), 1 if refit else 0, ptr(resvar), ptr(heldout),

@@ -1192,15 +1192,59 @@ def neighborhood_graph(coef, rule='and'):
     return up + np.swapaxes(up, -1, -2)
 
 
-def _mb_result(W, raw, resvar, info, lam, single, return_info):
+def _mb_result(W, raw, resvar, info, lam, single, return_info, scaled=False):
     pick = (lambda a: a[0]) if single else (lambda a: a)
     if not return_info:
         return pick(W)
-    return pick(W), {'LAMBDA': lam, 'COEF': pick(raw), 'RESVAR': pick(resvar), 'SWEEPS': pick(info[..., 0].astype(np.int64)),
-                     'STATUS': pick(info[..., 1].astype(np.int64))}
+    out = {'LAMBDA': lam, 'COEF': pick(raw), 'RESVAR': pick(resvar), 'SWEEPS': pick(info[..., 0].astype(np.int64)),
+           'STATUS': pick(info[..., 1].astype(np.int64))}
+    if info.shape[-1] == 3:                                             # the weighted / scaled route
+        out['OUTER'] = pick(info[..., 2].astype(np.int64))
+        if scaled:
+            with np.errstate(invalid='ignore'):
+                out['SIGMA'] = np.sqrt(out['RESVAR'])
+    return pick(W), out
 
 
-def neighborhood_selection(S, lambda_range, rule='and', tol=1e-7, max_sweeps=10000, device=0, return_info=False):
+def _mbw_args(weights, scaled, sig_tol, max_outer, M, p):
+    """(Wt C-contiguous (p,p) or (M,p,p) or None, per_matrix) of the arguments of the weighted / scaled route; its refusals."""
+    assert np.isfinite(sig_tol) and sig_tol >= 0, f"sig_tol = {sig_tol}: it must be non-negative and finite"
+    assert int(max_outer) >= 1, f"max_outer = {max_outer}: at least one outer iteration is needed"
+    if weights is None:
+        return None, False
+    Wt = np.asarray(weights, dtype=np.float64)
+    assert Wt.shape in ((p, p), (M, p, p)), \
+        f"weights must have shape ({p},{p}), one table for every matrix, or ({M},{p},{p}), one per matrix; got {Wt.shape}"
+    bad = np.argwhere(~(Wt >= 0))
+    if bad.size:
+        ix = tuple(int(v) for v in bad[0])
+        raise ValueError(f"weights{list(ix)} = {Wt[ix]}: a penalty weight must lie in [0, +inf] (row j holds node j's weights)")
+    return as_c(Wt), Wt.ndim == 3
+
+
+def adaptive_weights(coef, gamma=1.0, eps=0.0):
+    """The weights of the adaptive lasso's second stage (Zou 2006): ``w = 1 / (|coef| + eps)^gamma`` from first-stage raw
+    coefficients ``coef`` ([M,]p,p: column j holds ``beta^(j)``, the ``COEF`` of ``neighborhood_selection`` at one lambda),
+    laid out as the ``weights`` argument wants them: ``Wt[..., j, k]`` is node j's weight of variable k.  A zero coefficient
+    with ``eps = 0`` gives ``+inf``: the coordinate is excluded and the second stage keeps the first stage's support."""
+    C = np.asarray(coef, dtype=np.float64)
+    assert C.ndim in (2, 3) and C.shape[-1] == C.shape[-2], f"coef must be (p,p) or (M,p,p), got {C.shape}"
+    assert gamma > 0 and np.isfinite(gamma) and eps >= 0 and np.isfinite(eps), "gamma must be positive, eps non-negative, both finite"
+    assert np.all(np.isfinite(C)), "adaptive_weights: coef holds a non-finite value (a node that was not solved)"
+    with np.errstate(divide='ignore'):
+        w = 1.0 / (np.abs(np.swapaxes(C, -1, -2)) + eps) ** gamma
+    return np.ascontiguousarray(w)
+
+
+def scaled_lasso_lambda(p, n):
+    """The universal penalty of the scaled lasso, ``sqrt(2 log(p) / n)`` (Sun & Zhang 2012): one value for every node,
+    whatever its noise level.  ``p = 1`` has no regression to penalise; any positive number serves, 1.0 is returned."""
+    assert int(p) >= 1 and int(n) >= 1, f"scaled_lasso_lambda needs p >= 1 and n >= 1, got p = {p}, n = {n}"
+    return float(np.sqrt(2.0 * np.log(int(p)) / int(n))) if int(p) > 1 else 1.0
+
+
+def neighborhood_selection(S, lambda_range, rule='and', tol=1e-7, max_sweeps=10000, device=0, return_info=False, weights=None,
+                           scaled=False, sig_tol=1e-7, max_outer=100):
     """Meinshausen-Buhlmann neighbourhood selection on the device (``ggl_neighborhood_path``).  S: (p,p) or (M,p,p),
     symmetric with a positive diagonal, p <= 2048; the grid is used in descending order, every lambda warm-started from the
     one before.  Returns the (L,p,p) or (M,L,p,p) stack of symmetrised coefficient matrices (``neighborhood_graph``;
@@ -1215,11 +1259,40 @@ def neighborhood_selection(S, lambda_range, rule='and', tol=1e-7, max_sweeps=100
     residual variances ``S_jj - 2 s_j' beta + beta' S beta``), ``SWEEPS`` and ``STATUS`` ([M,]L,p: 0 converged, 1 a cap was
     reached, 2 a non-finite value -- that node's coefficients are NaN from that lambda on).  (The raw columns are a second
     call of the library; the bits of a call do not change.)  The same bits on every call, matrix m's independent of the
-    others, a lambda's independent of those behind it."""
+    others, a lambda's independent of those behind it.
+
+    ``weights`` ((p,p) shared or (M,p,p), entries in [0, +inf]): node j's penalty of variable k is ``lambda *
+    weights[j,k]`` (glmnet's ``penalty.factor``; ``adaptive_weights``); 0 leaves a coordinate unpenalised, ``+inf`` excludes
+    it.  ``scaled``: the scaled / square-root lasso (Sun & Zhang 2012; Belloni et al. 2011), ``min sqrt(tau^2(beta)) + lambda
+    sum_k w_k |beta_k|``, by alternation: the lasso at ``lambda sigma w_k``, ``sigma = sqrt(tau^2)`` of its result, until
+    sigma moves by at most ``sig_tol`` relative, at most ``max_outer`` times; ``RESVAR`` is then ``sigma_j^2`` and
+    ``scaled_lasso_lambda`` the one penalty that serves every node.  With either, ``ggl_neighborhood_path_w`` is called
+    (csrc/neighborhood_weighted.hip) and the info gains ``OUTER`` (outer iterations, 0 without ``scaled``) and,
+    with ``scaled``, ``SIGMA``; status 1 also means ``max_outer`` was reached and status 3 that ``tau^2 <= 1e-10 S_jj``, a
+    degenerate square-root problem (a duplicated variable, a perfect fit): NaN from there on, as for status 2.  Without
+    both, the call and its bits are what they were."""
     Sm, lam, single = _mb_args(S, lambda_range, rule, tol, max_sweeps)
     M, p, L = Sm.shape[0], Sm.shape[1], lam.size
+    weighted = weights is not None or bool(scaled)
+    if weighted:
+        Wt, per_matrix = _mbw_args(weights, scaled, sig_tol, max_outer, M, p)
     _lib.require_gpu()
     lib = _lib.load()
+
+    def call_w(r, with_resvar):
+        coef, info = np.empty((M, L, p, p)), np.empty((M, L, p, 3), dtype=np.int32)
+        resvar = np.empty((M, L, p)) if with_resvar else None
+        check(lib.ggl_neighborhood_path_w(int(device), M, p, ptr(Sm), L, ptr(lam), _MB_RULES[r], float(tol), int(max_sweeps),
+                                          ptr(Wt), int(per_matrix), int(bool(scaled)), float(sig_tol), int(max_outer),
+                                          ptr(coef), ptr(resvar), info.ctypes.data_as(_lib._ip)))
+        return coef, resvar, info
+
+    if weighted:
+        if not return_info:
+            return _mb_result(call_w(rule, False)[0], None, None, None, lam, single, False)
+        raw, resvar, info = call_w('raw', True)
+        W = raw if rule == 'raw' else call_w(rule, False)[0]
+        return _mb_result(W, raw, resvar, info, lam, single, True, bool(scaled))
 
     def call(r, with_resvar):
         coef, info = np.empty((M, L, p, p)), np.empty((M, L, p, 2), dtype=np.int32)
@@ -1313,14 +1386,138 @@ def _host_mb_node(S, j, lam, tol, max_sweeps, max_rounds=100):
     return out_b, out_r, out_s, out_st
 
 
-def host_neighborhood_selection(S, lambda_range, rule='and', tol=1e-7, max_sweeps=10000, return_info=False):
+def _host_mb_node_w(S, j, lam, w, scaled, tol, max_sweeps, sig_tol, max_outer, max_rounds=100):
+    """The path of node j with the weights w (p,): (beta (L,p), resvar (L,), sweeps, status, outer (L,)) -- ``k_mb_path_w``'s
+    unit of work, step by step: ``_host_mb_node`` with the threshold ``ls * w[k]``, ``ls = lambda`` or ``lambda * sigma``, and
+    around it the alternation on sigma."""
+    p, L = S.shape[0], lam.size
+    beta, g = np.zeros(p), S[j].copy()
+    member = np.zeros(p, dtype=bool)
+    act = np.zeros(0, dtype=np.int64)
+    out_b, out_r = np.zeros((L, p)), np.zeros(L)
+    out_s, out_st, out_o = np.zeros(L, dtype=np.int64), np.zeros(L, dtype=np.int64), np.zeros(L, dtype=np.int64)
+    sjj = S[j, j]
+    tau, dead, dead_status = sjj, False, 2
+
+    def sweep(ls):
+        dmax = 0.0
+        for k in act:
+            skk, bk = S[k, k], beta[k]
+            z = g[k] + skk * bk
+            b = np.sign(z) * max(abs(z) - ls * w[k], 0.0) / skk
+            d = b - bk
+            if d != 0.0:
+                g[:] -= d * S[k]
+                beta[k] = b
+            c = abs(d) * skk
+            dmax = c if c > dmax else dmax
+        return dmax
+
+    def screen(ls):
+        viol = ~member & (np.abs(g) > ls * w)
+        viol[j] = False
+        member[viol] = True
+        return int(viol.sum())
+
+    def bad():
+        return not (np.all(np.isfinite(g)) and np.all(np.isfinite(beta[act])))
+
+    def tau2():
+        return sjj - float(np.sum(beta[act] * (S[j, act] + g[act])))
+
+    for l in range(L):
+        lamv, sweeps, status, outer = lam[l], 0, 1, 0
+        if dead:
+            status = dead_status
+        elif bad():
+            status = 2
+        else:
+            sig = np.sqrt(tau) if scaled else 1.0
+            for it in range(max_outer if scaled else 1):
+                ls = lamv * sig if scaled else lamv
+                st, d1 = 1, 0.0
+                for rnd in range(max_rounds):
+                    nviol = screen(ls)
+                    act = np.flatnonzero(member)
+                    if nviol == 0 and (not (d1 > tol) if rnd > 0 else act.size == 0):
+                        st = 0
+                        break
+                    conv = False
+                    while sweeps < max_sweeps:
+                        dm = sweep(ls)
+                        sweeps += 1
+                        if not (dm > tol):
+                            conv = True
+                            break
+                    if not conv:
+                        break
+                    g[:] = S[j]
+                    for k in act:
+                        if beta[k] != 0.0:
+                            g[:] -= beta[k] * S[k]
+                    if sweeps >= max_sweeps:
+                        break
+                    d1 = sweep(ls)
+                    sweeps += 1
+                    if bad():
+                        st = 2
+                        break
+                if st == 1 and bad():
+                    st = 2
+                outer += 1
+                if not scaled:
+                    status = st
+                    break
+                if st == 2:
+                    status = 2
+                    break
+                tau = tau2()
+                if not (tau > 1e-10 * sjj):
+                    status = 3
+                    break
+                if st == 1:
+                    break
+                sn = np.sqrt(tau)
+                done = abs(sn - sig) <= sig_tol * sn
+                sig = sn
+                if done:
+                    status = 0
+                    break
+        if status >= 2:
+            dead, dead_status = True, status
+        if dead:
+            out_b[l], out_r[l] = np.nan, np.nan
+            out_b[l, j] = 0.0
+        else:
+            out_b[l] = beta
+            out_r[l] = tau if scaled else tau2()
+        out_s[l], out_st[l], out_o[l] = sweeps, status, outer if scaled else 0
+    return out_b, out_r, out_s, out_st, out_o
+
+
+def host_neighborhood_selection(S, lambda_range, rule='and', tol=1e-7, max_sweeps=10000, return_info=False, weights=None,
+                                scaled=False, sig_tol=1e-7, max_outer=100):
     """numpy twin of ``neighborhood_selection``: the same algorithm in the same order (screen, sweeps over the ascending
     active set, the gradient recomputed in ascending order, one further sweep, one further screen; the same caps and the same
     statuses), in float64 without fused multiply-adds, so its last bits differ from the device's.  For engines without the
-    device route and for tests without a GPU."""
+    device route and for tests without a GPU.  ``weights``, ``scaled``, ``sig_tol``, ``max_outer`` as there: the twin of
+    ``k_mb_path_w``, the same alternation in the same order."""
     Sm, lam, single = _mb_args(S, lambda_range, rule, tol, max_sweeps)
     M, p, L = Sm.shape[0], Sm.shape[1], lam.size
     raw, resvar = np.zeros((M, L, p, p)), np.zeros((M, L, p))
+    if weights is not None or scaled:
+        Wt, per_matrix = _mbw_args(weights, scaled, sig_tol, max_outer, M, p)
+        ones = np.ones(p)
+        info = np.zeros((M, L, p, 3), dtype=np.int32)
+        with np.errstate(all='ignore'):
+            for m in range(M):
+                for j in range(p):
+                    w = ones if Wt is None else (Wt[m, j] if per_matrix else Wt[j])
+                    b, r, s, st, o = _host_mb_node_w(Sm[m], j, lam, w, bool(scaled), float(tol), int(max_sweeps), float(sig_tol),
+                                                     int(max_outer))
+                    raw[m, :, :, j], resvar[m, :, j], info[m, :, j, 0], info[m, :, j, 1], info[m, :, j, 2] = b, r, s, st, o
+        W = raw if rule == 'raw' else neighborhood_graph(raw, rule)
+        return _mb_result(W, raw, resvar, info, lam, single, return_info, bool(scaled))
     info = np.zeros((M, L, p, 2), dtype=np.int32)
     with np.errstate(all='ignore'):
         for m in range(M):
@@ -1329,6 +1526,33 @@ def host_neighborhood_selection(S, lambda_range, rule='and', tol=1e-7, max_sweep
                 raw[m, :, :, j], resvar[m, :, j], info[m, :, j, 0], info[m, :, j, 1] = b, r, s, st
     W = raw if rule == 'raw' else neighborhood_graph(raw, rule)
     return _mb_result(W, raw, resvar, info, lam, single, return_info)
+
+
+def scaled_lasso_precision(S, n=None, lambda0=None, weights='sd', rule='min', device=0, host=False, tol=1e-7, sig_tol=1e-7,
+                           max_outer=100):
+    """The scaled-lasso precision matrix (Sun & Zhang 2013; TIGER, Liu & Wang 2017): one scaled path per node at ONE penalty,
+    no search.  ``lambda0`` defaults to the universal ``scaled_lasso_lambda(p, n)``, which needs the sample size ``n``.
+    ``weights='sd'``: ``w_jk = sqrt(S_kk)``, the penalty on the scale of the predictors, with which the estimator commutes with
+    rescaling the variables (on a correlation matrix the weights are 1); ``None``: none; or a (p,p) table.  Returns
+    ``(Theta, info)``: ``neighborhood_precision(COEF, RESVAR, rule)[0]`` of the path and the path's info with ``LAMBDA0``;
+    ``RESVAR`` holds ``sigma_j^2``.  ``host``: through the numpy twin."""
+    Sm = np.asarray(S, dtype=np.float64)
+    assert Sm.ndim == 2 and Sm.shape[0] == Sm.shape[1] and Sm.shape[0] >= 1, f"scaled_lasso_precision needs one (p,p) matrix, S has shape {Sm.shape}"
+    p = Sm.shape[0]
+    if lambda0 is None:
+        assert n is not None, "scaled_lasso_precision: the universal penalty sqrt(2 log(p) / n) needs the sample size n"
+        lambda0 = scaled_lasso_lambda(p, n)
+    assert np.isfinite(lambda0) and lambda0 > 0, f"lambda0 = {lambda0}: it must be positive and finite"
+    if isinstance(weights, str):
+        assert weights == 'sd', f"weights = {weights!r}: 'sd', None or a (p,p) table"
+        Wt = np.ascontiguousarray(np.broadcast_to(np.sqrt(np.diagonal(Sm))[None, :], (p, p)))
+    else:
+        Wt = weights
+    kw = dict(rule='raw', tol=tol, return_info=True, weights=Wt, scaled=True, sig_tol=sig_tol, max_outer=max_outer)
+    _, info = host_neighborhood_selection(Sm, [lambda0], **kw) if host else neighborhood_selection(Sm, [lambda0], device=device, **kw)
+    info = {k: (v if k == 'LAMBDA' else v[0]) for k, v in info.items()}
+    info['LAMBDA0'] = float(lambda0)
+    return neighborhood_precision(info['COEF'], info['RESVAR'], rule)[0], info
 
 
 # -----------------------------------------------------------------------------------------------------------------

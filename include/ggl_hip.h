@@ -32,7 +32,7 @@ extern "C" {
  * ggl_set_S_from_subsets_pairwise, ggl_covariance_weighted, ggl_set_S_from_weighted, ggl_mixed_correlation,
  * ggl_set_S_from_mixed, ggl_nearest_correlation, ggl_project_S, ggl_heldout_scores, ggl_debias, ggl_cholesky_predict,
  * ggl_weighted_predictive_scores, ggl_neighborhood_path, ggl_neighborhood_stability, ggl_neighborhood_refit,
- * ggl_neighborhood_cv, ggl_mb_refit_limits) leave every existing layout alone and the number where it is. */
+ * ggl_neighborhood_cv, ggl_mb_refit_limits, ggl_neighborhood_path_w, ggl_neighborhood_stability_w, ggl_neighborhood_cv_w) leave every existing layout alone and the number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -1055,6 +1055,45 @@ int ggl_neighborhood_refit(int device, int M, int p, const double *S_host, int G
 int ggl_neighborhood_cv(ggl_ctx *ctx, const double *X_host, int N, int F, int m, const int *idx_test, int flags, int L,
                         const double *lam, int rule, double tol, int max_sweeps, double t, int refit, double *resvar_out,
                         double *heldout_out, int *info_out, double *stack_out);
+
+/* ---- Neighbourhood selection with per-entry penalty weights and the scaled lasso (neighborhood_weighted.hip).
+ * Weights: the adaptive lasso (Zou 2006, JASA 101), glmnet's penalty.factor.  Scaled lasso: Sun & Zhang (2012, Biometrika 99;
+ * precision matrix: 2013, JMLR 14, R's scalreg), the square-root lasso of Belloni, Chernozhukov, Wang (2011, Biometrika 98),
+ * the estimator behind TIGER (Liu & Wang 2017, EJS 11; method = "tiger" of R's huge / flare).  Entry points that are only
+ * ADDED: GGL_VERSION stays where it is.
+ *
+ * Node j has the weights w_k = weights[j,k] in [0, +inf] (ROW j; the diagonal is not read) and, with g = s_j - S beta and
+ * tau^2(beta) = S_jj - 2 s_j' beta + beta' S beta:
+ *     GGL_MB_LASSO:   min 1/2 beta' S beta - s_j' beta + lambda sum_k w_k |beta_k|      thr_k = lambda w_k
+ *     GGL_MB_SCALED:  min sqrt(tau^2(beta)) + lambda sum_k w_k |beta_k|                  thr_k = lambda sigma w_k, sigma = tau
+ * w_k = 0: an unpenalised coordinate; w_k = +inf: an excluded one, its coefficient is exactly 0.  GGL_MB_LASSO is the
+ * procedure of ggl_neighborhood_path with thr_k in place of lambda; with unit weights it returns that entry's bits.
+ * GGL_MB_SCALED alternates, per (node, lambda): sigma_t = sqrt(tau^2) of the warm start (sqrt(S_jj) at the first lambda) ->
+ * that procedure at lambda sigma_t w_k -> sigma_new = sqrt(tau^2) -> finished if |sigma_new - sigma_t| <= sig_tol sigma_new,
+ * else again with sigma_new, at most max_outer times.  resvar is the final tau^2: in scaled mode sigma_j^2.
+ *
+ * Each entry is its sibling (ggl_neighborhood_path, _stability, _cv) plus
+ *   weights (p,p), with weights_per_matrix != 0 (M,p,p) / (K,p,p) / (F,p,p): host memory; NULL: all 1
+ *   mode, sig_tol, max_outer (the last two are checked in both modes and used in GGL_MB_SCALED)
+ * and its info holds THREE ints per (matrix, lambda, node): sweeps, status, outer iterations (0 with GGL_MB_LASSO).  Status
+ * 0 finished / 1 a cap was reached (max_sweeps, 100 screens, max_outer) / 2 a non-finite value / 3 GGL_MB_SCALED only:
+ * tau^2 <= 1e-10 S_jj or not positive, the square-root problem is degenerate (a duplicated variable, a perfect fit).  For 2
+ * and 3 the node is NaN (diagonal 0) at this lambda and every later one.  ggl_neighborhood_cv_w with refit != 0 returns the
+ * refit's info, two ints per node as its sibling does, in the leading part of info_out; info_out has room for three.
+ * GGL_E_ARG before any device work, nothing written: what the sibling refuses; a weight that is negative or NaN (matrix, row
+ * and column named; +inf is legal); an unknown mode; sig_tol negative or not finite; max_outer < 1. */
+#define GGL_MB_LASSO 0
+#define GGL_MB_SCALED 1
+int ggl_neighborhood_path_w(int device, int M, int p, const double *S_host, int L, const double *lam, int rule, double tol,
+                            int max_sweeps, const double *weights, int weights_per_matrix, int mode, double sig_tol,
+                            int max_outer, double *coef_out, double *resvar_out, int *info_out);
+int ggl_neighborhood_stability_w(ggl_ctx *ctx, int L, const double *lam, int rule, double tol, int max_sweeps, double t,
+                                 const double *weights, int weights_per_matrix, int mode, double sig_tol, int max_outer,
+                                 long long *num_out, int *counts_out, double *stack_out, int *info_out);
+int ggl_neighborhood_cv_w(ggl_ctx *ctx, const double *X_host, int N, int F, int m, const int *idx_test, int flags, int L,
+                          const double *lam, int rule, double tol, int max_sweeps, double t, int refit, const double *weights,
+                          int weights_per_matrix, int mode, double sig_tol, int max_outer, double *resvar_out,
+                          double *heldout_out, int *info_out, double *stack_out);
 
 #ifdef __cplusplus
 }
