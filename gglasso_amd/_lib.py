@@ -188,6 +188,11 @@ _SIGNATURES = {
                                _dp], _i),
     "ggl_neighborhood_refit": ([_i, _i, _i, _dp, _i, _dp, _d, _dp, _dp, _dp, _dp, _ip], _i),
     "ggl_neighborhood_cv": ([_vp, _dp, _i, _i, _i, _ip, _i, _i, _dp, _i, _d, _i, _d, _i, _dp, _dp, _ip, _dp], _i),
+    "ggl_mb_joint_limits": ([_ip], None),
+    "ggl_mb_joint_chunk_budget": ([ctypes.c_longlong], None),
+    "ggl_dev_mb_joint_bench": ([_i, _i, _dp, _i, _i, _dp, _dp, _d, _i, _i, _dp], _i),
+    "ggl_neighborhood_joint_last": ([_i, _i, _i, _dp, _dp, _i, _i, _dp, _dp, _i, _d, _i, _i, _d, _dp, _dp, _ip, _dp, _dp, _ip], _i),
+    "ggl_neighborhood_joint_path": ([_i, _i, _i, _dp, _dp, _i, _i, _dp, _dp, _i, _d, _i, _i, _d, _dp, _dp, _ip, _dp, _dp, _ip], _i),
 }
 
 # libggl_hip_dev.so only (-DGGL_DEV)

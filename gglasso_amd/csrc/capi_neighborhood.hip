@@ -428,3 +428,204 @@ extern "C" int ggl_neighborhood_cv_w(ggl_ctx* c, const double* X_host, int N, in
     HIPCHK(hipStreamSynchronize(st));
     return GGL_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Joint neighbourhood selection of K instances under the GGL penalty (kernel: neighborhood_joint.hip): the group
+// lasso across the instances of Chiquet, Grandvalet, Ambroise (2011) with the penalty of Danaher, Wang, Witten (2014), the
+// sparse-group block update of Simon, Friedman, Hastie, Tibshirani (2013).  Everything behind the path -- the rule per
+// instance, the refit on the symmetrised stack -- is the code of the entries above.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr size_t MBJ_CHUNK_BYTES = (size_t)2 << 30;   // the coefficient stacks of a chunk of chains take at most this
+std::atomic<long long> mbj_chunk_bytes{0};            // ggl_mb_joint_chunk_budget: 0 = MBJ_CHUNK_BYTES
+
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
+
+// what ggl_neighborhood_joint_path and ggl_neighborhood_joint_last share; last_only: coef_out and refit_coef_out are (C,K,p,p)
+// and receive the LAST pair of every chain
+int joint_path_impl(int device, int K, int p, const double* S_host, const double* omega, int C, int L, const double* lam1,
+                    const double* lam2, int rule, double tol, int max_sweeps, int refit, double t, double* coef_out,
+                    double* resvar_out, int* info_out, double* refit_coef_out, double* refit_resvar_out, int* refit_info_out,
+                    bool last_only);
+}  // namespace
+
+extern "C" void ggl_mb_joint_limits(int out[2])
+{
+    if (!out) return;
+    out[0] = MBJ_MAX_K;
+    out[1] = MBJ_MAX_P;
+}
+
+extern "C" void ggl_mb_joint_chunk_budget(long long bytes) { mbj_chunk_bytes.store(bytes > 0 ? bytes : 0); }
+
+extern "C" int ggl_neighborhood_joint_path(int device, int K, int p, const double* S_host, const double* omega, int C, int L,
+                                           const double* lam1, const double* lam2, int rule, double tol, int max_sweeps, int refit,
+                                           double t, double* coef_out, double* resvar_out, int* info_out, double* refit_coef_out,
+                                           double* refit_resvar_out, int* refit_info_out)
+{
+    return joint_path_impl(device, K, p, S_host, omega, C, L, lam1, lam2, rule, tol, max_sweeps, refit, t, coef_out, resvar_out,
+                           info_out, refit_coef_out, refit_resvar_out, refit_info_out, false);
+}
+
+extern "C" int ggl_neighborhood_joint_last(int device, int K, int p, const double* S_host, const double* omega, int C, int L,
+                                           const double* lam1, const double* lam2, int rule, double tol, int max_sweeps, int refit,
+                                           double t, double* coef_out, double* resvar_out, int* info_out, double* refit_coef_out,
+                                           double* refit_resvar_out, int* refit_info_out)
+{
+    return joint_path_impl(device, K, p, S_host, omega, C, L, lam1, lam2, rule, tol, max_sweeps, refit, t, coef_out, resvar_out,
+                           info_out, refit_coef_out, refit_resvar_out, refit_info_out, true);
+}
+
+// The path kernel alone, timed by HIP events on the device for tools/bench_neighborhood_joint.py (the convention of
+// ggl_dev_chol_bench): all C chains in one launch, iters launches behind one warm-up, ms_out[iters].  S_host is not checked.
+extern "C" int ggl_dev_mb_joint_bench(int K, int p, const double* S_host, int C, int L, const double* lam1, const double* lam2,
+                                      double tol, int max_sweeps, int iters, double* ms_out)
+{
+    ARGCHK(C >= 1 && L >= 1 && iters >= 1 && S_host && lam1 && lam2 && ms_out, "C, L, iters >= 1 and no NULL buffer");
+    ARGCHK(mb_joint_supported(K, p), "K, p outside ggl_mb_joint_limits");
+    ARGCHK((double)C * L * K * p < 2147483647.0, "C * L * K * p must stay below 2^31");
+    const size_t pp = (size_t)p * p, nCL = (size_t)C * L;
+    DevBuf dS, dL1, dL2, dCoef, dG;
+    IntBuf dInfo;
+    HIPCHK(dS.alloc((size_t)K * pp));
+    HIPCHK(dL1.alloc(nCL));
+    HIPCHK(dL2.alloc(nCL));
+    HIPCHK(dCoef.alloc(nCL * K * pp));
+    HIPCHK(dInfo.alloc(nCL * p * 3));
+    HIPCHK(dG.alloc((size_t)C * p * mb_joint_workspace(K, p)));
+    UP(dS.p, S_host, (size_t)K * pp);
+    UP(dL1.p, lam1, nCL);
+    UP(dL2.p, lam2, nCL);
+    EventPair ev;
+    HIPCHK(hipEventCreate(&ev.a));
+    HIPCHK(hipEventCreate(&ev.b));
+    for (int it = -1; it < iters; ++it) {
+        HIPCHK(hipEventRecord(ev.a, nullptr));
+        launch_mb_joint_path(nullptr, dS.p, K, p, nullptr, dL1.p, dL2.p, C, L, tol, max_sweeps, dCoef.p, nullptr, dInfo.p, dG.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev.b, nullptr));
+        HIPCHK(hipEventSynchronize(ev.b));
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
+        if (it >= 0) ms_out[it] = ms;
+    }
+    return GGL_OK;
+}
+
+namespace {
+int joint_path_impl(int device, int K, int p, const double* S_host, const double* omega, int C, int L, const double* lam1,
+                    const double* lam2, int rule, double tol, int max_sweeps, int refit, double t, double* coef_out,
+                    double* resvar_out, int* info_out, double* refit_coef_out, double* refit_resvar_out, int* refit_info_out,
+                    bool last_only)
+{
+    if (K < 1 || p < 1 || C < 1 || L < 1)
+        return fail(GGL_E_ARG, "bad argument: K = %d, p = %d, C = %d, L = %d; each must be at least 1", K, p, C, L);
+    if (K > MBJ_MAX_K) return fail(GGL_E_ARG, "bad argument: K = %d, k_mb_joint_path serves K <= %d", K, MBJ_MAX_K);
+    if (p > MBJ_MAX_P) return fail(GGL_E_ARG, "bad argument: p = %d, k_mb_joint_path serves p <= %d", p, MBJ_MAX_P);
+    ARGCHK(S_host, "S must not be NULL");
+    ARGCHK(lam1 && lam2, "lam1 and lam2 must not be NULL");
+    ARGCHK(info_out, "info_out must not be NULL");
+    for (int c = 0; c < C; ++c)
+        for (int l = 0; l < L; ++l) {
+            const double a = lam1[(size_t)c * L + l], b = lam2[(size_t)c * L + l];
+            if (!(a >= 0.0) || !std::isfinite(a))
+                return fail(GGL_E_ARG, "bad argument: lam1 of (chain %d, index %d) = %g; a penalty must be non-negative and finite", c, l, a);
+            if (!(b >= 0.0) || !std::isfinite(b))
+                return fail(GGL_E_ARG, "bad argument: lam2 of (chain %d, index %d) = %g; a penalty must be non-negative and finite", c, l, b);
+            if (!(a + b > 0.0))
+                return fail(GGL_E_ARG, "bad argument: lam1 + lam2 of (chain %d, index %d) = %g; one of the two must be positive", c, l, a + b);
+        }
+    if (omega)
+        for (int k = 0; k < K; ++k)
+            if (!(omega[k] > 0.0) || !std::isfinite(omega[k]))
+                return fail(GGL_E_ARG, "bad argument: omega[%d] = %g; an instance weight must be positive and finite", k, omega[k]);
+    ARGCHK(tol >= 0.0 && std::isfinite(tol), "tol must be non-negative and finite");
+    ARGCHK(max_sweeps >= 1, "max_sweeps >= 1");
+    if (rule < GGL_MB_RAW || rule > GGL_MB_OR)
+        return fail(GGL_E_ARG, "bad argument: rule = %d (GGL_MB_RAW 0, GGL_MB_AND 1, GGL_MB_OR 2)", rule);
+    if (refit) {
+        if (rule == GGL_MB_RAW)
+            return fail(GGL_E_ARG, "bad argument: rule = GGL_MB_RAW with refit; the refit needs a graph (GGL_MB_AND 1, GGL_MB_OR 2)");
+        RCCHK(check_threshold(t));
+    }
+    const size_t pp = (size_t)p * p;
+    for (int k = 0; k < K; ++k) {
+        const double* a = S_host + (size_t)k * pp;
+        for (size_t e = 0; e < pp; ++e)
+            if (!std::isfinite(a[e]))
+                return fail(GGL_E_ARG, "bad argument: S of instance %d: the entry (%d, %d) is not finite", k, (int)(e / p), (int)(e % p));
+        for (int i = 0; i < p; ++i)
+            if (!(a[(size_t)i * p + i] > 0.0))
+                return fail(GGL_E_ARG, "bad argument: S of instance %d, variable %d: the diagonal entry is %g; it must be positive", k,
+                            i, a[(size_t)i * p + i]);
+        for (int i = 0; i < p; ++i)
+            for (int q = i + 1; q < p; ++q)
+                if (std::memcmp(&a[(size_t)i * p + q], &a[(size_t)q * p + i], sizeof(double)) != 0)
+                    return fail(GGL_E_ARG, "bad argument: S of instance %d is not bitwise symmetric: the entries (%d, %d) = %.17g and "
+                                "(%d, %d) = %.17g differ", k, i, q, a[(size_t)i * p + q], q, i, a[(size_t)q * p + i]);
+    }
+    // chunks of chains: a chain's bits do not depend on the chains beside it, so the outputs do not depend on the chunking
+    const size_t per_chain = ((size_t)L * K * pp * (refit ? 2 : 1) + (size_t)p * mb_joint_workspace(K, p)) * sizeof(double);
+    const long long forced = mbj_chunk_bytes.load();
+    const size_t budget = forced > 0 ? (size_t)forced : MBJ_CHUNK_BYTES;
+    int Cc = (int)std::min<size_t>((size_t)C, std::max<size_t>(1, budget / per_chain));
+    ARGCHK((double)L * K * p < 2147483647.0, "L * K * p must stay below 2^31");
+    while (Cc > 1 && (double)Cc * L * K * p >= 2147483647.0) --Cc;
+
+    HIPCHK(hipSetDevice(device));
+    const size_t nCL = (size_t)Cc * L, nslot = nCL * K;
+    DevBuf dS, dOm, dL1, dL2, dCoef, dRes, dRCoef, dRRes, dG;
+    IntBuf dInfo, dRInfo;
+    HIPCHK(dS.alloc((size_t)K * pp));
+    if (omega) HIPCHK(dOm.alloc(K));
+    HIPCHK(dL1.alloc((size_t)C * L));
+    HIPCHK(dL2.alloc((size_t)C * L));
+    HIPCHK(dCoef.alloc(nslot * pp));
+    HIPCHK(dG.alloc((size_t)Cc * p * mb_joint_workspace(K, p)));      // empty where the gradients fit the registers
+    if (resvar_out) HIPCHK(dRes.alloc(nslot * p));
+    HIPCHK(dInfo.alloc(nCL * p * 3));
+    std::vector<int> rinfo;
+    if (refit) {
+        HIPCHK(dRCoef.alloc(nslot * pp));
+        HIPCHK(dRRes.alloc(nslot * p));
+        HIPCHK(dRInfo.alloc(nslot * p * 2));
+        if (!refit_info_out) rinfo.resize(nslot * p * 2);
+    }
+    UP(dS.p, S_host, (size_t)K * pp);
+    if (omega) UP(dOm.p, omega, K);
+    UP(dL1.p, lam1, (size_t)C * L);
+    UP(dL2.p, lam2, (size_t)C * L);
+    // a (cc,L,K,p,p) device stack to the host: whole, or with last_only the last pair of every chain to (cc,K,p,p)
+    auto down_stack = [&](double* host, const double* dev, int c0, int cc) -> int {
+        if (!last_only) {
+            DOWN(host + (size_t)c0 * L * K * pp, dev, (size_t)cc * L * K * pp);
+            return GGL_OK;
+        }
+        for (int c = 0; c < cc; ++c)
+            DOWN(host + (size_t)(c0 + c) * K * pp, dev + ((size_t)c * L + (L - 1)) * K * pp, (size_t)K * pp);
+        return GGL_OK;
+    };
+    for (int c0 = 0; c0 < C; c0 += Cc) {
+        const int cc = std::min(Cc, C - c0);
+        const size_t nl = (size_t)cc * L, ns = nl * K, o = (size_t)c0 * L;
+        launch_mb_joint_path(nullptr, dS.p, K, p, omega ? dOm.p : nullptr, dL1.p + o, dL2.p + o, cc, L, tol, max_sweeps, dCoef.p,
+                             resvar_out ? dRes.p : nullptr, dInfo.p, dG.p);
+        HIPCHK(hipGetLastError());
+        launch_mb_symmetrize(nullptr, dCoef.p, ns, p, rule);
+        HIPCHK(hipGetLastError());
+        if (refit) {
+            int* ih = refit_info_out ? refit_info_out + o * K * p * 2 : rinfo.data();
+            RCCHK(run_refit(nullptr, dS.p, nullptr, dCoef.p, t, p, ns, 1, K, dRCoef.p, dRRes.p, nullptr, dRInfo.p, ih));
+            if (refit_coef_out) RCCHK(down_stack(refit_coef_out, dRCoef.p, c0, cc));
+            if (refit_resvar_out) DOWN(refit_resvar_out + o * K * p, dRRes.p, ns * p);
+        }
+        if (coef_out) RCCHK(down_stack(coef_out, dCoef.p, c0, cc));
+        if (resvar_out) DOWN(resvar_out + o * K * p, dRes.p, ns * p);
+        HIPCHK(hipMemcpy(info_out + o * p * 3, dInfo.p, nl * p * 3 * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    return GGL_OK;
+}
+}  // namespace

@@ -613,4 +613,19 @@ void launch_mb_refit_listed(hipStream_t st, const double* S, const double* T, co
 // heldout[s,j] = q(T; ROW j of slot s of C) over the row's non-zero entries, the sums of launch_mb_refit's q
 void launch_mb_heldout(hipStream_t st, const double* T, const double* C, int p, size_t nslot, int sdiv, int smod, double* heldout);
 
+// Joint neighbourhood selection of K instances under the GGL penalty (neighborhood_joint.hip).  S (K,p,p) bitwise
+// symmetric with positive diagonals, omega (K) positive or null (all 1), lam1 / lam2 (C,L) on the device: C chains of L penalty
+// pairs, each walked in order with warm starts.  coef: (C,L,K) slots of (p,p), ROW j = beta^(k) of node j (diagonal 0; it is
+// also the kernel's working storage, every row is written); resvar (C,L,K,p), may be null; info (C,L,p,3) = sweeps, status
+// 0 converged / 1 a cap was reached / 2 non-finite (all K rows of the node NaN from that pair on), largest Newton count of a
+// block.  Serves K <= MBJ_MAX_K and p <= MBJ_MAX_P.  The gradients of a workgroup's K regressions live in its registers
+// where they fit (K <= 64 up to p = 384, 32 up to 512, 16 beyond) and otherwise in the workspace gws, C * p *
+// mb_joint_workspace(K, p) doubles (0: none needed, gws may be null).  C * p < 2^31.
+static constexpr int MBJ_MAX_K = 64, MBJ_MAX_P = 1024;
+bool mb_joint_supported(int K, int p);
+size_t mb_joint_workspace(int K, int p);
+void launch_mb_joint_path(hipStream_t st, const double* S, int K, int p, const double* omega, const double* lam1,
+                          const double* lam2, int C, int L, double tol, int max_sweeps, double* coef, double* resvar, int* info,
+                          double* gws);
+
 }  // namespace ggl

@@ -1290,3 +1290,77 @@ def bandwidth_search(X, bandwidths, rule='min', times=None, kernel='gaussian', c
              'NOT_PD': [(int(b), int(ev[r])) for b, r in zip(*np.nonzero(STATUS >= 0))], 'N_EFF': N_EFF, 'EVAL': ev,
              'rule': rule}
     return float(h[ix]), stats
+
+
+# -----------------------------------------------------------------------------------------------------------------
+# Joint neighbourhood selection of K instances (utils.joint_neighborhood_selection): the (lambda1, lambda2) grid
+# in ONE device call with the refit, only tables downloaded, scored on the host by the extended BIC of every regression.
+# -----------------------------------------------------------------------------------------------------------------
+def joint_neighborhood_score(refit_resvar, degree, N, p, method='eBIC', gamma=0.1, bad=None):
+    """(...) scores from ``refit_resvar`` and ``degree`` (...,K,p): ``sum_k sum_j [ N_k log tau_jk^2 + deg_jk (log N_k + 2 gamma
+    log(p - 1)) ]`` -- the extended BIC of each regression (Chen & Chen 2008) summed over nodes and instances; ``'BIC'``:
+    ``gamma = 0``; ``'AIC'``: ``2 deg`` in place of ``deg log N_k``.  NaN where ``bad`` (...) is set or a ``tau^2`` is not positive."""
+    assert method in ('eBIC', 'BIC', 'AIC'), f"method = {method!r}: 'eBIC', 'BIC' or 'AIC'"
+    tau, deg = np.asarray(refit_resvar, dtype=np.float64), np.asarray(degree, dtype=np.float64)
+    K = tau.shape[-2]
+    Nk = np.broadcast_to(np.asarray(N, dtype=np.float64).reshape(-1), (K,))[:, None]
+    per_edge = 2.0 if method == 'AIC' else np.log(Nk)
+    if method == 'eBIC' and p > 1:
+        per_edge = per_edge + 2.0 * float(gamma) * np.log(p - 1.0)
+    with np.errstate(all='ignore'):
+        score = (Nk * np.log(tau) + deg * per_edge).sum(axis=(-1, -2))
+        score = np.where(np.all(tau > 0, axis=(-1, -2)), score, np.nan)
+    if bad is not None:
+        score = np.where(np.asarray(bad, dtype=bool), np.nan, score)
+    return score
+
+
+def joint_neighborhood_search(S, N, lambda1_range, lambda2_range, rule='and', method='eBIC', gamma=0.1, instance_weights=None,
+                              host=None, **kw):
+    """Pick ``(lambda1, lambda2)`` of ``utils.joint_neighborhood_selection`` on a grid: one device call with the refit (only
+    tables come back), then ``joint_neighborhood_score`` on the host from the refit's residual variances and degrees.  A grid
+    point with any node of non-zero path or refit status scores NaN and is never chosen.  ``N``: one number or (K,).  ``kw``:
+    ``tol``, ``max_sweeps``, ``t``, ``device``.  ``host``: through the numpy twin (default: when the engine has no
+    neighbourhood route).
+
+    Returns ``(sol, stats)``.  ``stats``: ``SCORE`` (L1,L2), ``IX`` (i1, i2), ``BEST`` ``{'lambda1', 'lambda2'}``, ``LAMBDA1``
+    (descending), ``LAMBDA2``, ``STATUS``, ``SWEEPS``, ``NEWTON`` (L1,L2,p), ``REFIT_STATUS``, ``DEGREE`` (L1,L2,K,p).  ``sol``:
+    ``coef`` (K,p,p) and ``resvar`` (K,p) of the refit at the chosen point, ``adjacency`` (K,p,p), ``common_adjacency`` (p,p:
+    the edges present in every instance), ``precision`` (K,p,p: ``utils.joint_neighborhood_precision``), ``W`` the symmetrised
+    lasso coefficients.  They come from one further call, the chosen ``lambda2``'s chain down to the chosen ``lambda1``, whose
+    bits are that point's part of the grid call; only the chosen point's two coefficient stacks are downloaded."""
+    from . import solver as _solver, utils
+    assert rule in ('and', 'or'), f"rule = {rule!r}: 'and' or 'or'"
+    assert method in ('eBIC', 'BIC', 'AIC'), f"method = {method!r}: 'eBIC', 'BIC' or 'AIC'"
+    assert 0 <= gamma <= 1, "gamma needs to be chosen as a parameter in [0,1]."
+    unknown = set(kw) - {'tol', 'max_sweeps', 't', 'device'}
+    assert not unknown, f"joint_neighborhood_search: unknown arguments {sorted(unknown)}"
+    tol, max_sweeps, t, device = kw.get('tol', 1e-7), kw.get('max_sweeps', 10000), kw.get('t', 1e-8), kw.get('device', 0)
+    if host is None:
+        host = not hasattr(_solver.ENGINE, "neighborhood_stability")
+    Sm, l1, l2, om = utils._mbj_args(S, lambda1_range, lambda2_range, rule, instance_weights, tol, max_sweeps, True, t)
+    K, p = Sm.shape[0], Sm.shape[1]
+    Nk = np.asarray(N, dtype=np.float64).reshape(-1)
+    assert Nk.size in (1, K) and np.all(Nk >= 1), f"N must be one number or one per instance ({K}), each at least 1"
+    out = utils._joint_run(Sm, l1, l2, om, rule, tol, max_sweeps, True, t, device, host, want_coef=False)
+    status, rstatus = out['INFO'][..., 1].astype(np.int64), out['REFIT_INFO'][..., 1].astype(np.int64)
+    degree = out['REFIT_INFO'][..., 0].astype(np.int64)
+    bad = np.any(status != 0, axis=-1) | np.any(rstatus != 0, axis=(-1, -2))
+    score = joint_neighborhood_score(out['REFIT_RESVAR'], degree, Nk, p, method, gamma, bad)
+    if np.all(np.isnan(score)):
+        raise ValueError("joint_neighborhood_search: no grid point finished with every node's status 0")
+    i1, i2 = (int(v) for v in np.unravel_index(int(np.nanargmin(score)), score.shape))
+    stats = {'SCORE': score, 'IX': (i1, i2), 'BEST': {'lambda1': float(l1[i1]), 'lambda2': float(l2[i2])}, 'LAMBDA1': l1,
+             'LAMBDA2': l2, 'STATUS': status, 'SWEEPS': out['INFO'][..., 0].astype(np.int64),
+             'NEWTON': out['INFO'][..., 2].astype(np.int64), 'REFIT_STATUS': rstatus, 'DEGREE': degree, 'method': method}
+    fin = utils._joint_run(Sm, l1[:i1 + 1], l2[i2:i2 + 1], om, rule, tol, max_sweeps, True, t, device, host, last_only=True)
+    W, coef, resvar = fin['W'][0], fin['REFIT_COEF'][0], fin['REFIT_RESVAR'][i1, 0]
+    with np.errstate(invalid='ignore'):
+        adj = (np.abs(W) >= t) & ~np.eye(p, dtype=bool)[None]
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', RuntimeWarning)                     # not positive definite by construction (utils)
+        Theta, lmin = utils.joint_neighborhood_precision(coef, resvar)
+    sol = {'coef': coef, 'resvar': resvar, 'W': W, 'adjacency': adj, 'common_adjacency': np.all(adj, axis=0), 'precision': Theta,
+           'lambda_min': lmin, 'lambda1': float(l1[i1]), 'lambda2': float(l2[i2])}
+    return sol, stats

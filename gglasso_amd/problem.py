@@ -550,6 +550,35 @@ class glasso_problem:
         self.neighborhood_ = dict(sol)
         self.modelselect_stats = dict(stats)
 
+    def joint_neighborhood_selection(self, lambda1_range, lambda2_range, rule='and', method='eBIC', gamma=0.1, **kw):
+        """Joint neighbourhood selection for a multiple, conforming problem with ``reg='GGL'``: the regression counterpart of
+        the Group Graphical Lasso (``utils.joint_neighborhood_selection``: every node's K regressions coupled by a group penalty
+        ``lambda2`` across the instances beside the lasso penalty ``lambda1``), the pair chosen on the grid by the extended BIC of
+        the refitted regressions (``model_selection.joint_neighborhood_search``; ``method``: 'eBIC', 'BIC', 'AIC').  It works on
+        ``self.S`` (the correlations under ``do_scaling``; the precision goes back as in ``solve``) with ``self.N``; ``kw``:
+        ``instance_weights``, ``tol``, ``max_sweeps``, ``t``, ``device``, ``host``.  ``solution.precision_`` is the (K,p,p)
+        regression-based precision of the refit (not positive definite by construction, ``utils.neighborhood_precision``),
+        ``solution.adjacency_`` the K selected graphs, ``reg_params`` gets ``lambda1`` and ``lambda2``, ``modelselect_stats``
+        the search's tables and ``neighborhood_`` the search's ``sol``.  ``neighborhood_selection``, ``solve`` and
+        ``model_selection`` are untouched."""
+        assert rule in ('and', 'or'), f"rule = {rule!r}: 'and' or 'or'"
+        assert self.multiple, "Joint neighbourhood selection couples the instances of a multiple problem; this is a single one " \
+                              "(see neighborhood_selection)."
+        assert self.conforming, "Joint neighbourhood selection is not implemented for instances of different dimension " \
+                                "(non-conforming problems)."
+        assert not self.latent, "Joint neighbourhood selection is not implemented for problems with latent variables: a lasso " \
+                                "per node has no low-rank component."
+        assert self.reg_params.get('lambda1_mask') is None, "Joint neighbourhood selection is not implemented with a lambda1_mask."
+        assert self.reg == 'GGL', "Joint neighbourhood selection is implemented for reg='GGL' only: the fused penalty of " \
+                                  "reg='FGL' has no such block update."
+        sol, stats = _ms.joint_neighborhood_search(self.S, self.N, lambda1_range, lambda2_range, rule=rule, method=method,
+                                                   gamma=gamma, **kw)
+        self.set_reg_params(stats['BEST'])
+        self._keep({'Theta': sol['precision']})
+        self.solution.adjacency_ = np.asarray(sol['adjacency']).astype(int)
+        self.neighborhood_ = dict(sol)
+        self.modelselect_stats = dict(stats)
+
     # -- inference ---------------------------------------------------------------------------------------------------------
     def edge_inference(self, alpha=0.05, method='bh', differential=None, host=False):
         """Edge-wise tests and confidence intervals for the solution at hand by the debiased graphical lasso (Jankova & van de

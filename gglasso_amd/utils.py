@@ -1771,3 +1771,276 @@ def mb_cv_scores(resvar, heldout, bad, score='pseudo'):
             else:
                 out[l, f] = math.fsum(np.log(tau[l, f]) + r[l, f] / tau[l, f])
     return out
+
+
+# -----------------------------------------------------------------------------------------------------------------
+# Joint neighbourhood selection of K instances that share structure: the regression counterpart of the GGL penalty
+# (Chiquet, Grandvalet, Ambroise 2011, R's simone; the penalty of Danaher, Wang, Witten 2014).  For node j
+#     min_B  sum_k omega_k [ 1/2 beta^(k)' S^(k) beta^(k) - s_j^(k)' beta^(k) ]
+#            + lambda1 sum_k sum_{i != j} |beta^(k)_i| + lambda2 sum_{i != j} ||(beta^(1)_i, ..., beta^(K)_i)||_2
+# by block coordinate descent (one block: the K coefficients of one variable; Simon, Friedman, Hastie, Tibshirani 2013).
+# On the device: csrc/neighborhood_joint.hip, one workgroup per (chain, node); DESIGN 30.
+# -----------------------------------------------------------------------------------------------------------------
+_MBJ_MAX_ROUNDS = 100
+_MBJ_NEWTON_CAP = 64
+
+
+def mb_joint_limits():
+    """(largest K, largest p) of the device route, as the library reports them (``ggl_mb_joint_limits``)."""
+    out = (ctypes.c_int * 2)()
+    _lib.load().ggl_mb_joint_limits(out)
+    return int(out[0]), int(out[1])
+
+
+def _mbj_args(S, lambda1, lambda2, rule, instance_weights, tol, max_sweeps, refit, t):
+    """(S (K,p,p) C-contiguous, lambda1 descending (L1,), lambda2 (L2,), omega (K,) or None) of what
+    ``joint_neighborhood_selection`` accepts; its refusals."""
+    Sm = np.asarray(S, dtype=np.float64)
+    assert Sm.ndim == 3 and Sm.shape[-1] == Sm.shape[-2] and Sm.shape[-1] >= 1 and Sm.shape[0] >= 1, \
+        f"joint_neighborhood_selection needs a (K,p,p) stack of square matrices, S has shape {Sm.shape}"
+    K, p = Sm.shape[0], Sm.shape[1]
+    l1 = np.sort(np.atleast_1d(np.asarray(lambda1, dtype=np.float64)).reshape(-1))[::-1].copy()
+    l2 = np.atleast_1d(np.asarray(lambda2, dtype=np.float64)).reshape(-1).copy()
+    assert l1.size >= 1 and l2.size >= 1, "lambda1 and lambda2 need at least one value each"
+    assert np.all(np.isfinite(l1)) and np.all(l1 >= 0), "every lambda1 must be non-negative and finite"
+    assert np.all(np.isfinite(l2)) and np.all(l2 >= 0), "every lambda2 must be non-negative and finite"
+    assert np.all(np.diff(l1) < 0), "the lambda1 of a grid must differ"
+    assert l1.min() + l2.min() > 0, "lambda1 + lambda2 must be positive at every grid point"
+    assert rule in _MB_RULES, f"rule = {rule!r}: 'and', 'or' or 'raw'"
+    assert not (refit and rule == 'raw'), "refit needs a graph: rule 'and' or 'or'"
+    assert tol >= 0 and np.isfinite(tol), f"tol = {tol}: it must be non-negative and finite"
+    assert int(max_sweeps) >= 1, f"max_sweeps = {max_sweeps}: at least one sweep is needed"
+    assert np.isfinite(t) and t >= 0, f"t = {t}: the edge threshold must be finite and not negative"
+    om = None
+    if instance_weights is not None:
+        om = np.ascontiguousarray(np.asarray(instance_weights, dtype=np.float64).reshape(-1))
+        assert om.shape == (K,), f"instance_weights must hold one weight per instance ({K}), has shape {om.shape}"
+        if not (np.all(np.isfinite(om)) and np.all(om > 0)):
+            k = int(np.flatnonzero(~(np.isfinite(om) & (om > 0)))[0])
+            raise ValueError(f"instance_weights[{k}] = {om[k]}: an instance weight must be positive and finite")
+    if not np.all(np.isfinite(Sm)):
+        k, i, q = np.argwhere(~np.isfinite(Sm))[0]
+        raise ValueError(f"joint_neighborhood_selection: S of instance {int(k)}: the entry ({int(i)}, {int(q)}) is not finite")
+    dg = np.diagonal(Sm, axis1=1, axis2=2)
+    if not np.all(dg > 0):
+        k, i = np.argwhere(~(dg > 0))[0]
+        raise ValueError(f"joint_neighborhood_selection: S of instance {int(k)}, variable {int(i)}: the diagonal entry is "
+                         f"{dg[k, i]}; it must be positive")
+    asym = np.argwhere(Sm != np.swapaxes(Sm, 1, 2))
+    if asym.size:
+        k, i, q = asym[0]
+        raise ValueError(f"joint_neighborhood_selection: S of instance {int(k)} is not bitwise symmetric: the entries "
+                         f"({int(i)}, {int(q)}) and ({int(q)}, {int(i)}) differ")
+    return as_c(Sm), l1, l2, om
+
+
+def _host_mbj_unit(S, om, dg, j, l1s, l2s, tol, max_sweeps):
+    """The chain of node j: (B (L,K,p), resvar (L,K), sweeps (L,), status (L,), newton (L,)) -- ``k_mb_joint_path``'s unit of
+    work, step by step."""
+    K, p, L = S.shape[0], S.shape[1], len(l1s)
+    B, g = np.zeros((K, p)), om[:, None] * S[:, j, :]
+    member = np.zeros(p, dtype=bool)
+    act = np.zeros(0, dtype=np.int64)
+    out_b, out_r = np.zeros((L, K, p)), np.zeros((L, K))
+    out_s, out_st, out_n = np.zeros(L, dtype=np.int64), np.zeros(L, dtype=np.int64), np.zeros(L, dtype=np.int64)
+    state = {'newton': 0, 'nfb': False}
+    dead = False
+
+    def sweep(l1, l2):
+        dmax = 0.0
+        for i in act:
+            a, bo = om * dg[:, i], B[:, i].copy()
+            z = g[:, i] + a * bo
+            u = np.sign(z) * np.maximum(np.abs(z) - l1, 0.0)
+            un = np.sqrt(np.sum(u * u))
+            b = np.zeros(K)
+            if un > l2:
+                if l2 == 0.0:
+                    b = u / a
+                else:
+                    nu, it = (un - l2) / np.max(a), 0
+                    while it < _MBJ_NEWTON_CAP:
+                        tt = 1.0 / (a * nu + l2)
+                        ut = u * tt
+                        f, fp = np.sum(ut * ut) - 1.0, -2.0 * np.sum(ut * ut * a * tt)
+                        nn = nu - f / fp
+                        if not (nn > nu):
+                            break
+                        nu, it = nn, it + 1
+                    state['newton'] = max(state['newton'], it)
+                    b = u * nu / (a * nu + l2)
+            if not np.all(np.isfinite(b)):
+                state['nfb'] = True
+            d = b - bo
+            nz = d != 0.0
+            if np.any(nz):
+                g[nz] -= (om[nz] * d[nz])[:, None] * S[nz, i, :]
+                B[nz, i] = b[nz]
+            cm = np.fmax.reduce(np.abs(d) * a)
+            dmax = cm if cm > dmax else dmax
+        return dmax
+
+    def screen(l1, l2):
+        sg = np.maximum(np.abs(g) - l1, 0.0)
+        viol = ~member & (np.sqrt(np.sum(sg * sg, axis=0)) > l2)
+        viol[j] = False
+        member[viol] = True
+        return int(viol.sum())
+
+    def bad():
+        return state['nfb'] or not np.all(np.isfinite(g))
+
+    for l in range(L):
+        l1, l2, sweeps, status = l1s[l], l2s[l], 0, 1
+        state['newton'] = 0
+        if dead or bad():
+            status = 2
+        else:
+            d1 = 0.0
+            for rnd in range(_MBJ_MAX_ROUNDS):
+                nviol = screen(l1, l2)
+                act = np.flatnonzero(member)
+                if nviol == 0 and (not (d1 > tol) if rnd > 0 else act.size == 0):
+                    status = 0
+                    break
+                conv = False
+                while sweeps < max_sweeps:
+                    dm = sweep(l1, l2)
+                    sweeps += 1
+                    if not (dm > tol):
+                        conv = True
+                        break
+                if not conv:
+                    break
+                g[:] = om[:, None] * S[:, j, :]
+                for i in act:
+                    nz = B[:, i] != 0.0
+                    if np.any(nz):
+                        g[nz] -= (om[nz] * B[nz, i])[:, None] * S[nz, i, :]
+                if sweeps >= max_sweeps:
+                    break
+                d1 = sweep(l1, l2)
+                sweeps += 1
+                if bad():
+                    status = 2
+                    break
+            if status == 1 and bad():
+                status = 2
+        dead = status == 2
+        if dead:
+            out_b[l], out_r[l] = np.nan, np.nan
+            out_b[l, :, j] = 0.0
+        else:
+            out_b[l] = B
+            out_r[l] = dg[:, j] - np.sum(B[:, act] * (S[:, j, act] + g[:, act] / om[:, None]), axis=1)
+        out_s[l], out_st[l], out_n[l] = sweeps, status, state['newton']
+    return out_b, out_r, out_s, out_st, out_n
+
+
+def _joint_run(Sm, l1, l2, om, rule, tol, max_sweeps, refit, t, device, host, want_coef=True, last_only=False):
+    """The grid ``l1`` (L1, descending) x ``l2`` (L2) as L2 chains of L1 pairs, on the device or through the twin.  Returns a
+    dict of arrays in grid layout (L1,L2,...): W (None without ``want_coef``), RESVAR, INFO (L1,L2,p,3) and, with ``refit``,
+    REFIT_COEF (None without ``want_coef``), REFIT_RESVAR, REFIT_INFO (L1,L2,K,p,2).  ``last_only``: W and REFIT_COEF are
+    (L2,K,p,p), the LAST pair of every chain (``ggl_neighborhood_joint_last``: nothing else is downloaded); the tables stay
+    whole."""
+    K, p, L, C = Sm.shape[0], Sm.shape[1], l1.size, l2.size
+    lam1 = np.ascontiguousarray(np.broadcast_to(l1[None, :], (C, L)))
+    lam2 = np.ascontiguousarray(np.broadcast_to(l2[:, None], (C, L)))
+    out = {'W': None, 'REFIT_COEF': None}
+    if host:
+        omv = np.ones(K) if om is None else om
+        dg = np.ascontiguousarray(np.diagonal(Sm, axis1=1, axis2=2))
+        raw, resvar = np.zeros((C, L, K, p, p)), np.zeros((C, L, K, p))
+        info = np.zeros((C, L, p, 3), dtype=np.int32)
+        with np.errstate(all='ignore'):
+            for c in range(C):
+                for j in range(p):
+                    b, r, s, st, nw = _host_mbj_unit(Sm, omv, dg, j, lam1[c], lam2[c], float(tol), int(max_sweeps))
+                    raw[c, :, :, :, j], resvar[c, :, :, j] = b, r
+                    info[c, :, j, 0], info[c, :, j, 1], info[c, :, j, 2] = s, st, nw
+        W = raw if rule == 'raw' else neighborhood_graph(raw, rule)
+        out.update(W=W, RESVAR=resvar, INFO=info)
+        if refit:
+            rf = host_neighborhood_refit(Sm, np.ascontiguousarray(np.moveaxis(W.reshape(C * L, K, p, p), 1, 0)), t=t)
+            out['REFIT_COEF'] = np.moveaxis(rf['COEF'], 0, 1).reshape(C, L, K, p, p)
+            out['REFIT_RESVAR'] = np.moveaxis(rf['RESVAR'], 0, 1).reshape(C, L, K, p)
+            out['REFIT_INFO'] = np.stack([np.moveaxis(rf['DEGREE'], 0, 1), np.moveaxis(rf['STATUS'], 0, 1)], axis=-1) \
+                .reshape(C, L, K, p, 2).astype(np.int32)
+    else:
+        _lib.require_gpu()
+        lib = _lib.load()
+        cshape = (C, K, p, p) if last_only else (C, L, K, p, p)
+        coef = np.empty(cshape) if want_coef else None
+        resvar, info = np.empty((C, L, K, p)), np.empty((C, L, p, 3), dtype=np.int32)
+        rcoef = np.empty(cshape) if (refit and want_coef) else None
+        rres = np.empty((C, L, K, p)) if refit else None
+        rinfo = np.empty((C, L, K, p, 2), dtype=np.int32) if refit else None
+        ip = lambda a: None if a is None else a.ctypes.data_as(_lib._ip)
+        entry = lib.ggl_neighborhood_joint_last if last_only else lib.ggl_neighborhood_joint_path
+        check(entry(int(device), K, p, ptr(Sm), ptr(om), C, L, ptr(lam1), ptr(lam2), _MB_RULES[rule], float(tol), int(max_sweeps),
+                    int(bool(refit)), float(t), ptr(coef), ptr(resvar), ip(info), ptr(rcoef), ptr(rres), ip(rinfo)))
+        out.update(W=coef, RESVAR=resvar, INFO=info)
+        if refit:
+            out.update(REFIT_COEF=rcoef, REFIT_RESVAR=rres, REFIT_INFO=rinfo)
+    sw = lambda a: None if a is None else np.ascontiguousarray(np.swapaxes(a, 0, 1))        # (C,L,...) -> (L1,L2,...)
+    res = {k: sw(v) for k, v in out.items()}
+    if last_only:
+        for k in ('W', 'REFIT_COEF'):
+            if out[k] is not None:
+                res[k] = np.ascontiguousarray(out[k][:, L - 1]) if host else out[k]
+    return res
+
+
+def _joint_result(out, l1, l2, refit, return_info):
+    if not return_info:
+        return out['W']
+    info = {'LAMBDA1': l1, 'LAMBDA2': l2, 'RESVAR': out['RESVAR'], 'SWEEPS': out['INFO'][..., 0].astype(np.int64),
+            'STATUS': out['INFO'][..., 1].astype(np.int64), 'NEWTON': out['INFO'][..., 2].astype(np.int64)}
+    if refit:
+        info.update(REFIT_COEF=out['REFIT_COEF'], REFIT_RESVAR=out['REFIT_RESVAR'],
+                    DEGREE=out['REFIT_INFO'][..., 0].astype(np.int64), REFIT_STATUS=out['REFIT_INFO'][..., 1].astype(np.int64))
+    return out['W'], info
+
+
+def joint_neighborhood_selection(S, lambda1, lambda2, rule='and', instance_weights=None, tol=1e-7, max_sweeps=10000, refit=False,
+                                 t=1e-8, device=0, return_info=False):
+    """Joint neighbourhood selection of K instances on the device (``ggl_neighborhood_joint_path``): every node's K
+    regressions are coupled by a group penalty across the instances (``lambda2``) beside the lasso penalty of each
+    (``lambda1``) -- ``reg='GGL'`` for neighbourhood selection.  S: (K,p,p), every ``S[k]`` bitwise symmetric with a positive
+    diagonal; ``instance_weights`` (K,) positive, default all 1.  Limits: ``mb_joint_limits()``, read from the library.
+
+    ``lambda1`` (L1) x ``lambda2`` (L2): one chain per ``lambda2``, walked along the descending ``lambda1`` with warm starts.
+    Returns W (L1,L2,K,p,p): per instance the symmetrised coefficients (``neighborhood_graph``; ``rule='raw'``: column j holds
+    ``beta^(k)`` of node j).  With ``lambda1 = 0`` the K supports coincide; with ``lambda2 = 0`` these are K separate lassos.
+
+    ``return_info``: also a dict with ``LAMBDA1`` (descending), ``LAMBDA2``, ``RESVAR`` (L1,L2,K,p: the unweighted residual
+    variances), ``SWEEPS``, ``STATUS`` (L1,L2,p: 0 converged, 1 a cap was reached, 2 a non-finite value -- all K columns of that
+    node are NaN from that ``lambda1`` on), ``NEWTON`` (the largest number of Newton steps a block's root took) and, with
+    ``refit`` (rule 'and' / 'or'): ``REFIT_COEF``, ``REFIT_RESVAR``, ``DEGREE``, ``REFIT_STATUS`` -- every instance refitted on its
+    graph (entries with ``|W| >= t``) as ``neighborhood_refit`` does, on the device.  The same bits on every call, a chain's
+    independent of the others, a point's independent of the ``lambda1`` below it."""
+    Sm, l1, l2, om = _mbj_args(S, lambda1, lambda2, rule, instance_weights, tol, max_sweeps, refit, t)
+    out = _joint_run(Sm, l1, l2, om, rule, tol, max_sweeps, bool(refit), t, device, False)
+    return _joint_result(out, l1, l2, bool(refit), return_info)
+
+
+def host_joint_neighborhood_selection(S, lambda1, lambda2, rule='and', instance_weights=None, tol=1e-7, max_sweeps=10000,
+                                      refit=False, t=1e-8, return_info=False):
+    """numpy twin of ``joint_neighborhood_selection``: the same procedure in the same order (screen of the groups, sweeps of
+    block updates over the ascending active list with the same Newton iteration, all gradients recomputed in ascending order,
+    one further sweep, one further screen; the same caps and statuses) in float64 with numpy's own summation orders, so its
+    last bits differ from the device's.  The refit goes through ``host_neighborhood_refit``.  For engines without the device
+    route and for tests without a GPU."""
+    Sm, l1, l2, om = _mbj_args(S, lambda1, lambda2, rule, instance_weights, tol, max_sweeps, refit, t)
+    out = _joint_run(Sm, l1, l2, om, rule, tol, max_sweeps, bool(refit), t, 0, True)
+    return _joint_result(out, l1, l2, bool(refit), return_info)
+
+
+def joint_neighborhood_precision(coef, resvar, rule='min'):
+    """``neighborhood_precision`` per instance: ``coef`` (K,p,p) with column j node j's coefficients in instance k, ``resvar``
+    (K,p).  Returns ``(Theta (K,p,p), lambda_min (K,))``."""
+    C, tau = np.asarray(coef, dtype=np.float64), np.asarray(resvar, dtype=np.float64)
+    assert C.ndim == 3 and C.shape[1] == C.shape[2] and tau.shape == C.shape[:2], \
+        f"coef (K,p,p) and resvar (K,p) do not fit: {C.shape}, {tau.shape}"
+    res = [neighborhood_precision(C[k], tau[k], rule) for k in range(C.shape[0])]
+    return np.stack([r[0] for r in res]), np.array([r[1] for r in res])

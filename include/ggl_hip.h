@@ -32,7 +32,8 @@ extern "C" {
  * ggl_set_S_from_subsets_pairwise, ggl_covariance_weighted, ggl_set_S_from_weighted, ggl_mixed_correlation,
  * ggl_set_S_from_mixed, ggl_nearest_correlation, ggl_project_S, ggl_heldout_scores, ggl_debias, ggl_cholesky_predict,
  * ggl_weighted_predictive_scores, ggl_neighborhood_path, ggl_neighborhood_stability, ggl_neighborhood_refit,
- * ggl_neighborhood_cv, ggl_mb_refit_limits, ggl_neighborhood_path_w, ggl_neighborhood_stability_w, ggl_neighborhood_cv_w) leave every existing layout alone and the number where it is. */
+ * ggl_neighborhood_cv, ggl_mb_refit_limits, ggl_neighborhood_path_w, ggl_neighborhood_stability_w, ggl_neighborhood_cv_w, ggl_neighborhood_joint_path,
+ * ggl_neighborhood_joint_last, ggl_mb_joint_limits, ggl_mb_joint_chunk_budget, ggl_dev_mb_joint_bench) leave every existing layout alone and the number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -1094,6 +1095,54 @@ int ggl_neighborhood_cv_w(ggl_ctx *ctx, const double *X_host, int N, int F, int 
                           const double *lam, int rule, double tol, int max_sweeps, double t, int refit, const double *weights,
                           int weights_per_matrix, int mode, double sig_tol, int max_outer, double *resvar_out,
                           double *heldout_out, int *info_out, double *stack_out);
+
+/* ---- Joint neighbourhood selection of K instances under the GGL penalty (neighborhood_joint.hip).  Entry points
+ * that are only ADDED: GGL_VERSION stays where it is.
+ *
+ * The regression counterpart of reg = 'GGL' (Chiquet, Grandvalet, Ambroise 2011; Danaher, Wang, Witten 2014): for node j
+ *     min_B  sum_k omega_k [ 1/2 beta^(k)' S^(k) beta^(k) - s_j^(k)' beta^(k) ]
+ *            + lam1 sum_k sum_{i != j} |beta^(k)_i| + lam2 sum_{i != j} ||(beta^(1)_i, ..., beta^(K)_i)||_2 ,   beta^(k)_j = 0,
+ * by block coordinate descent on an active set of groups (one block: the K coefficients of one variable; its solution is the
+ * root of a scalar equation, found by a monotone Newton iteration), with the screen / sweep / recompute / confirm procedure,
+ * the caps and the statuses of ggl_neighborhood_path.
+ *
+ * ggl_neighborhood_joint_path: S_host (K,p,p), every S[k] bitwise symmetric, finite, with a positive diagonal; omega (K)
+ * positive and finite, or NULL (all 1); lam1, lam2 (C,L): C chains of L penalty pairs, each chain walked in order with warm
+ * starts (no order is asked of the pairs); lam1, lam2 >= 0, finite, lam1 + lam2 > 0.  rule is applied per instance to every
+ * (c,l,k) matrix as in ggl_neighborhood_path.
+ *   coef_out (C,L,K,p,p) or NULL;  resvar_out (C,L,K,p) or NULL: S^(k)_jj - 2 s_j^(k)' beta^(k) + beta^(k)' S^(k) beta^(k), unweighted
+ *   info_out (C,L,p,3): sweeps, status (0 finished / 1 a cap was reached: max_sweeps, 100 screens / 2 a non-finite value: all K
+ *     columns of that node are NaN, diagonal 0, at this pair and every later one of the chain, nobody else is touched), the
+ *     largest number of Newton steps one block took
+ *   refit != 0 (rule GGL_MB_AND or GGL_MB_OR): every (c,l,k) matrix is refitted on its graph (|W| >= t) against S[k] by the
+ *     kernels of ggl_neighborhood_refit, on the device; refit_coef_out (C,L,K,p,p), refit_resvar_out (C,L,K,p),
+ *     refit_info_out (C,L,K,p,2: degree, status as there), each or NULL.
+ * The same bits on every call; a chain's do not depend on C or on the other chains, a pair's not on the pairs behind it.
+ * The device stack is processed in chunks of chains under a fixed memory budget; the outputs do not depend on the chunking
+ * (ggl_mb_joint_chunk_budget sets the budget in bytes for tests, 0 restores the default).
+ * ggl_neighborhood_joint_last: the same call, but coef_out and refit_coef_out are (C,K,p,p) and receive the LAST pair of every
+ * chain only (the tables stay whole): what a search wants of the chain that leads to its chosen point.
+ * ggl_mb_joint_limits: out[0] = largest K (64), out[1] = largest p (1024); every (K, p) inside is served.  The K gradients of a
+ * node live in the registers of one workgroup where they fit (K <= 64 up to p = 384, 32 up to 512, 16 up to 1024) and in a
+ * workspace in device memory beyond: the same procedure, slower.
+ * ggl_dev_mb_joint_bench: the path kernel alone on all C chains, HIP-event times of iters launches in ms_out (for tools).
+ * GGL_E_ARG before any device work, nothing written, the message naming the offender: K, p, C or L < 1 or beyond the limits; a
+ * NULL S_host, lam1, lam2 or info_out; a penalty that is negative or not finite, or a pair with lam1 + lam2 = 0 (chain, index);
+ * an omega that is not positive and finite; tol negative or not finite; max_sweeps < 1; an unknown rule; GGL_MB_RAW with
+ * refit; with refit, t negative or not finite; an entry of S_host that is not finite or a diagonal entry that is not positive
+ * (instance, index); an S_host[k] that is not bitwise symmetric (instance, pair). */
+void ggl_mb_joint_limits(int out[2]);
+void ggl_mb_joint_chunk_budget(long long bytes);
+int ggl_neighborhood_joint_last(int device, int K, int p, const double *S_host, const double *omega, int C, int L,
+                                const double *lam1, const double *lam2, int rule, double tol, int max_sweeps, int refit, double t,
+                                double *coef_out, double *resvar_out, int *info_out, double *refit_coef_out,
+                                double *refit_resvar_out, int *refit_info_out);
+int ggl_dev_mb_joint_bench(int K, int p, const double *S_host, int C, int L, const double *lam1, const double *lam2, double tol,
+                           int max_sweeps, int iters, double *ms_out);
+int ggl_neighborhood_joint_path(int device, int K, int p, const double *S_host, const double *omega, int C, int L,
+                                const double *lam1, const double *lam2, int rule, double tol, int max_sweeps, int refit, double t,
+                                double *coef_out, double *resvar_out, int *info_out, double *refit_coef_out,
+                                double *refit_resvar_out, int *refit_info_out);
 
 #ifdef __cplusplus
 }
