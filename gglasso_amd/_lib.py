@@ -193,6 +193,10 @@ _SIGNATURES = {
     "ggl_dev_mb_joint_bench": ([_i, _i, _dp, _i, _i, _dp, _dp, _d, _i, _i, _dp], _i),
     "ggl_neighborhood_joint_last": ([_i, _i, _i, _dp, _dp, _i, _i, _dp, _dp, _i, _d, _i, _i, _d, _dp, _dp, _ip, _dp, _dp, _ip], _i),
     "ggl_neighborhood_joint_path": ([_i, _i, _i, _dp, _dp, _i, _i, _dp, _dp, _i, _d, _i, _i, _d, _dp, _dp, _ip, _dp, _dp, _ip], _i),
+    "ggl_mb_fused_limits": ([_ip], None),
+    "ggl_dev_mb_fused_bench": ([_i, _i, _dp, _i, _i, _dp, _dp, _d, _i, _i, _dp], _i),
+    "ggl_neighborhood_fused_last": ([_i, _i, _i, _dp, _dp, _i, _i, _dp, _dp, _i, _d, _i, _i, _d, _dp, _dp, _ip, _dp, _dp, _ip], _i),
+    "ggl_neighborhood_fused_path": ([_i, _i, _i, _dp, _dp, _i, _i, _dp, _dp, _i, _d, _i, _i, _d, _dp, _dp, _ip, _dp, _dp, _ip], _i),
 }
 
 # libggl_hip_dev.so only (-DGGL_DEV)

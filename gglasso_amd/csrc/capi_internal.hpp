@@ -26,7 +26,7 @@
 //                       and the same on a ctx's S with the edge stability of the result (ggl_neighborhood_stability); the
 //                       least-squares refit on a graph (ggl_neighborhood_refit) and one cross-validation step of it on a
 //                       ctx (ggl_neighborhood_cv); the joint path of K instances under the GGL penalty
-//                       (ggl_neighborhood_joint_path)
+//                       (ggl_neighborhood_joint_path) and under the fused penalty (ggl_neighborhood_fused_path)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>

@@ -449,7 +449,7 @@ struct EventPair {
 int joint_path_impl(int device, int K, int p, const double* S_host, const double* omega, int C, int L, const double* lam1,
                     const double* lam2, int rule, double tol, int max_sweeps, int refit, double t, double* coef_out,
                     double* resvar_out, int* info_out, double* refit_coef_out, double* refit_resvar_out, int* refit_info_out,
-                    bool last_only);
+                    bool last_only, bool fused);
 }  // namespace
 
 extern "C" void ggl_mb_joint_limits(int out[2])
@@ -467,7 +467,7 @@ extern "C" int ggl_neighborhood_joint_path(int device, int K, int p, const doubl
                                            double* refit_resvar_out, int* refit_info_out)
 {
     return joint_path_impl(device, K, p, S_host, omega, C, L, lam1, lam2, rule, tol, max_sweeps, refit, t, coef_out, resvar_out,
-                           info_out, refit_coef_out, refit_resvar_out, refit_info_out, false);
+                           info_out, refit_coef_out, refit_resvar_out, refit_info_out, false, false);
 }
 
 extern "C" int ggl_neighborhood_joint_last(int device, int K, int p, const double* S_host, const double* omega, int C, int L,
@@ -476,16 +476,17 @@ extern "C" int ggl_neighborhood_joint_last(int device, int K, int p, const doubl
                                            double* refit_resvar_out, int* refit_info_out)
 {
     return joint_path_impl(device, K, p, S_host, omega, C, L, lam1, lam2, rule, tol, max_sweeps, refit, t, coef_out, resvar_out,
-                           info_out, refit_coef_out, refit_resvar_out, refit_info_out, true);
+                           info_out, refit_coef_out, refit_resvar_out, refit_info_out, true, false);
 }
 
 // The path kernel alone, timed by HIP events on the device for tools/bench_neighborhood_joint.py (the convention of
-// ggl_dev_chol_bench): all C chains in one launch, iters launches behind one warm-up, ms_out[iters].  S_host is not checked.
-extern "C" int ggl_dev_mb_joint_bench(int K, int p, const double* S_host, int C, int L, const double* lam1, const double* lam2,
-                                      double tol, int max_sweeps, int iters, double* ms_out)
+// ggl_dev_chol_bench) and, with fused, k_mb_fused_path for tools/bench_neighborhood_fused.py: all C chains in one launch,
+// iters launches behind one warm-up, ms_out[iters].  S_host is not checked.
+static int mb_joint_bench_impl(int K, int p, const double* S_host, int C, int L, const double* lam1, const double* lam2, double tol,
+                               int max_sweeps, int iters, double* ms_out, bool fused)
 {
     ARGCHK(C >= 1 && L >= 1 && iters >= 1 && S_host && lam1 && lam2 && ms_out, "C, L, iters >= 1 and no NULL buffer");
-    ARGCHK(mb_joint_supported(K, p), "K, p outside ggl_mb_joint_limits");
+    ARGCHK(fused ? mb_fused_supported(K, p) : mb_joint_supported(K, p), "K, p outside ggl_mb_joint_limits / ggl_mb_fused_limits");
     ARGCHK((double)C * L * K * p < 2147483647.0, "C * L * K * p must stay below 2^31");
     const size_t pp = (size_t)p * p, nCL = (size_t)C * L;
     DevBuf dS, dL1, dL2, dCoef, dG;
@@ -495,7 +496,7 @@ extern "C" int ggl_dev_mb_joint_bench(int K, int p, const double* S_host, int C,
     HIPCHK(dL2.alloc(nCL));
     HIPCHK(dCoef.alloc(nCL * K * pp));
     HIPCHK(dInfo.alloc(nCL * p * 3));
-    HIPCHK(dG.alloc((size_t)C * p * mb_joint_workspace(K, p)));
+    HIPCHK(dG.alloc((size_t)C * p * (fused ? mb_fused_workspace(K, p) : mb_joint_workspace(K, p))));
     UP(dS.p, S_host, (size_t)K * pp);
     UP(dL1.p, lam1, nCL);
     UP(dL2.p, lam2, nCL);
@@ -504,7 +505,8 @@ extern "C" int ggl_dev_mb_joint_bench(int K, int p, const double* S_host, int C,
     HIPCHK(hipEventCreate(&ev.b));
     for (int it = -1; it < iters; ++it) {
         HIPCHK(hipEventRecord(ev.a, nullptr));
-        launch_mb_joint_path(nullptr, dS.p, K, p, nullptr, dL1.p, dL2.p, C, L, tol, max_sweeps, dCoef.p, nullptr, dInfo.p, dG.p);
+        (fused ? launch_mb_fused_path : launch_mb_joint_path)(nullptr, dS.p, K, p, nullptr, dL1.p, dL2.p, C, L, tol, max_sweeps,
+                                                              dCoef.p, nullptr, dInfo.p, dG.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev.b, nullptr));
         HIPCHK(hipEventSynchronize(ev.b));
@@ -515,16 +517,60 @@ extern "C" int ggl_dev_mb_joint_bench(int K, int p, const double* S_host, int C,
     return GGL_OK;
 }
 
+extern "C" int ggl_dev_mb_joint_bench(int K, int p, const double* S_host, int C, int L, const double* lam1, const double* lam2,
+                                      double tol, int max_sweeps, int iters, double* ms_out)
+{
+    return mb_joint_bench_impl(K, p, S_host, C, L, lam1, lam2, tol, max_sweeps, iters, ms_out, false);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Fused joint neighbourhood selection of K ordered instances (kernel: neighborhood_fused.hip): lam2 weighs the
+// differences between consecutive instances.  The host work is that of the joint route, refusals and chunking included;
+// lam2 > 0 with K = 1 is accepted and inert.
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" void ggl_mb_fused_limits(int out[2])
+{
+    if (!out) return;
+    out[0] = MBF_MAX_K;
+    out[1] = MBF_MAX_P;
+}
+
+extern "C" int ggl_neighborhood_fused_path(int device, int K, int p, const double* S_host, const double* omega, int C, int L,
+                                           const double* lam1, const double* lam2, int rule, double tol, int max_sweeps, int refit,
+                                           double t, double* coef_out, double* resvar_out, int* info_out, double* refit_coef_out,
+                                           double* refit_resvar_out, int* refit_info_out)
+{
+    return joint_path_impl(device, K, p, S_host, omega, C, L, lam1, lam2, rule, tol, max_sweeps, refit, t, coef_out, resvar_out,
+                           info_out, refit_coef_out, refit_resvar_out, refit_info_out, false, true);
+}
+
+extern "C" int ggl_neighborhood_fused_last(int device, int K, int p, const double* S_host, const double* omega, int C, int L,
+                                           const double* lam1, const double* lam2, int rule, double tol, int max_sweeps, int refit,
+                                           double t, double* coef_out, double* resvar_out, int* info_out, double* refit_coef_out,
+                                           double* refit_resvar_out, int* refit_info_out)
+{
+    return joint_path_impl(device, K, p, S_host, omega, C, L, lam1, lam2, rule, tol, max_sweeps, refit, t, coef_out, resvar_out,
+                           info_out, refit_coef_out, refit_resvar_out, refit_info_out, true, true);
+}
+
+extern "C" int ggl_dev_mb_fused_bench(int K, int p, const double* S_host, int C, int L, const double* lam1, const double* lam2,
+                                      double tol, int max_sweeps, int iters, double* ms_out)
+{
+    return mb_joint_bench_impl(K, p, S_host, C, L, lam1, lam2, tol, max_sweeps, iters, ms_out, true);
+}
+
 namespace {
 int joint_path_impl(int device, int K, int p, const double* S_host, const double* omega, int C, int L, const double* lam1,
                     const double* lam2, int rule, double tol, int max_sweeps, int refit, double t, double* coef_out,
                     double* resvar_out, int* info_out, double* refit_coef_out, double* refit_resvar_out, int* refit_info_out,
-                    bool last_only)
+                    bool last_only, bool fused)
 {
+    const char* kernel = fused ? "k_mb_fused_path" : "k_mb_joint_path";
+    const int maxK = fused ? MBF_MAX_K : MBJ_MAX_K, maxP = fused ? MBF_MAX_P : MBJ_MAX_P;
     if (K < 1 || p < 1 || C < 1 || L < 1)
         return fail(GGL_E_ARG, "bad argument: K = %d, p = %d, C = %d, L = %d; each must be at least 1", K, p, C, L);
-    if (K > MBJ_MAX_K) return fail(GGL_E_ARG, "bad argument: K = %d, k_mb_joint_path serves K <= %d", K, MBJ_MAX_K);
-    if (p > MBJ_MAX_P) return fail(GGL_E_ARG, "bad argument: p = %d, k_mb_joint_path serves p <= %d", p, MBJ_MAX_P);
+    if (K > maxK) return fail(GGL_E_ARG, "bad argument: K = %d, %s serves K <= %d", K, kernel, maxK);
+    if (p > maxP) return fail(GGL_E_ARG, "bad argument: p = %d, %s serves p <= %d", p, kernel, maxP);
     ARGCHK(S_host, "S must not be NULL");
     ARGCHK(lam1 && lam2, "lam1 and lam2 must not be NULL");
     ARGCHK(info_out, "info_out must not be NULL");
@@ -568,7 +614,8 @@ int joint_path_impl(int device, int K, int p, const double* S_host, const double
                                 "(%d, %d) = %.17g differ", k, i, q, a[(size_t)i * p + q], q, i, a[(size_t)q * p + i]);
     }
     // chunks of chains: a chain's bits do not depend on the chains beside it, so the outputs do not depend on the chunking
-    const size_t per_chain = ((size_t)L * K * pp * (refit ? 2 : 1) + (size_t)p * mb_joint_workspace(K, p)) * sizeof(double);
+    const size_t gws_per_unit = fused ? mb_fused_workspace(K, p) : mb_joint_workspace(K, p);
+    const size_t per_chain = ((size_t)L * K * pp * (refit ? 2 : 1) + (size_t)p * gws_per_unit) * sizeof(double);
     const long long forced = mbj_chunk_bytes.load();
     const size_t budget = forced > 0 ? (size_t)forced : MBJ_CHUNK_BYTES;
     int Cc = (int)std::min<size_t>((size_t)C, std::max<size_t>(1, budget / per_chain));
@@ -584,7 +631,7 @@ int joint_path_impl(int device, int K, int p, const double* S_host, const double
     HIPCHK(dL1.alloc((size_t)C * L));
     HIPCHK(dL2.alloc((size_t)C * L));
     HIPCHK(dCoef.alloc(nslot * pp));
-    HIPCHK(dG.alloc((size_t)Cc * p * mb_joint_workspace(K, p)));      // empty where the gradients fit the registers
+    HIPCHK(dG.alloc((size_t)Cc * p * gws_per_unit));                  // empty where the gradients fit the registers
     if (resvar_out) HIPCHK(dRes.alloc(nslot * p));
     HIPCHK(dInfo.alloc(nCL * p * 3));
     std::vector<int> rinfo;
@@ -611,8 +658,9 @@ int joint_path_impl(int device, int K, int p, const double* S_host, const double
     for (int c0 = 0; c0 < C; c0 += Cc) {
         const int cc = std::min(Cc, C - c0);
         const size_t nl = (size_t)cc * L, ns = nl * K, o = (size_t)c0 * L;
-        launch_mb_joint_path(nullptr, dS.p, K, p, omega ? dOm.p : nullptr, dL1.p + o, dL2.p + o, cc, L, tol, max_sweeps, dCoef.p,
-                             resvar_out ? dRes.p : nullptr, dInfo.p, dG.p);
+        (fused ? launch_mb_fused_path : launch_mb_joint_path)(nullptr, dS.p, K, p, omega ? dOm.p : nullptr, dL1.p + o, dL2.p + o, cc,
+                                                              L, tol, max_sweeps, dCoef.p, resvar_out ? dRes.p : nullptr,
+                                                              dInfo.p, dG.p);
         HIPCHK(hipGetLastError());
         launch_mb_symmetrize(nullptr, dCoef.p, ns, p, rule);
         HIPCHK(hipGetLastError());

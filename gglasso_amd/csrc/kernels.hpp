@@ -628,4 +628,14 @@ void launch_mb_joint_path(hipStream_t st, const double* S, int K, int p, const d
                           const double* lam2, int C, int L, double tol, int max_sweeps, double* coef, double* resvar, int* info,
                           double* gws);
 
+// Fused joint neighbourhood selection of K ORDERED instances (neighborhood_fused.hip): the arguments, the layouts
+// and the statuses of launch_mb_joint_path, lam2 weighing sum_k |beta^(k+1)_i - beta^(k)_i| instead of the group norm.  Info
+// column 2 is 0.  Serves K <= MBF_MAX_K and p <= MBF_MAX_P; gws: C * p * mb_fused_workspace(K, p) doubles.  C * p < 2^31.
+static constexpr int MBF_MAX_K = 64, MBF_MAX_P = 1024;
+bool mb_fused_supported(int K, int p);
+size_t mb_fused_workspace(int K, int p);
+void launch_mb_fused_path(hipStream_t st, const double* S, int K, int p, const double* omega, const double* lam1,
+                          const double* lam2, int C, int L, double tol, int max_sweeps, double* coef, double* resvar, int* info,
+                          double* gws);
+
 }  // namespace ggl

@@ -1329,31 +1329,38 @@ def joint_neighborhood_search(S, N, lambda1_range, lambda2_range, rule='and', me
     the edges present in every instance), ``precision`` (K,p,p: ``utils.joint_neighborhood_precision``), ``W`` the symmetrised
     lasso coefficients.  They come from one further call, the chosen ``lambda2``'s chain down to the chosen ``lambda1``, whose
     bits are that point's part of the grid call; only the chosen point's two coefficient stacks are downloaded."""
+    return _joint_search('group', S, N, lambda1_range, lambda2_range, rule, method, gamma, instance_weights, host, kw)
+
+
+def _joint_search(coupling, S, N, lambda1_range, lambda2_range, rule, method, gamma, instance_weights, host, kw):
+    """``joint_neighborhood_search`` (``coupling='group'``) and ``fused_neighborhood_search`` (``'fused'``)."""
     from . import solver as _solver, utils
+    who = 'fused_neighborhood_search' if coupling == 'fused' else 'joint_neighborhood_search'
     assert rule in ('and', 'or'), f"rule = {rule!r}: 'and' or 'or'"
     assert method in ('eBIC', 'BIC', 'AIC'), f"method = {method!r}: 'eBIC', 'BIC' or 'AIC'"
     assert 0 <= gamma <= 1, "gamma needs to be chosen as a parameter in [0,1]."
     unknown = set(kw) - {'tol', 'max_sweeps', 't', 'device'}
-    assert not unknown, f"joint_neighborhood_search: unknown arguments {sorted(unknown)}"
+    assert not unknown, f"{who}: unknown arguments {sorted(unknown)}"
     tol, max_sweeps, t, device = kw.get('tol', 1e-7), kw.get('max_sweeps', 10000), kw.get('t', 1e-8), kw.get('device', 0)
     if host is None:
         host = not hasattr(_solver.ENGINE, "neighborhood_stability")
-    Sm, l1, l2, om = utils._mbj_args(S, lambda1_range, lambda2_range, rule, instance_weights, tol, max_sweeps, True, t)
+    Sm, l1, l2, om = utils._mbj_args(S, lambda1_range, lambda2_range, rule, instance_weights, tol, max_sweeps, True, t, coupling)
     K, p = Sm.shape[0], Sm.shape[1]
     Nk = np.asarray(N, dtype=np.float64).reshape(-1)
     assert Nk.size in (1, K) and np.all(Nk >= 1), f"N must be one number or one per instance ({K}), each at least 1"
-    out = utils._joint_run(Sm, l1, l2, om, rule, tol, max_sweeps, True, t, device, host, want_coef=False)
+    out = utils._joint_run(Sm, l1, l2, om, rule, tol, max_sweeps, True, t, device, host, want_coef=False, coupling=coupling)
     status, rstatus = out['INFO'][..., 1].astype(np.int64), out['REFIT_INFO'][..., 1].astype(np.int64)
     degree = out['REFIT_INFO'][..., 0].astype(np.int64)
     bad = np.any(status != 0, axis=-1) | np.any(rstatus != 0, axis=(-1, -2))
     score = joint_neighborhood_score(out['REFIT_RESVAR'], degree, Nk, p, method, gamma, bad)
     if np.all(np.isnan(score)):
-        raise ValueError("joint_neighborhood_search: no grid point finished with every node's status 0")
+        raise ValueError(f"{who}: no grid point finished with every node's status 0")
     i1, i2 = (int(v) for v in np.unravel_index(int(np.nanargmin(score)), score.shape))
     stats = {'SCORE': score, 'IX': (i1, i2), 'BEST': {'lambda1': float(l1[i1]), 'lambda2': float(l2[i2])}, 'LAMBDA1': l1,
              'LAMBDA2': l2, 'STATUS': status, 'SWEEPS': out['INFO'][..., 0].astype(np.int64),
              'NEWTON': out['INFO'][..., 2].astype(np.int64), 'REFIT_STATUS': rstatus, 'DEGREE': degree, 'method': method}
-    fin = utils._joint_run(Sm, l1[:i1 + 1], l2[i2:i2 + 1], om, rule, tol, max_sweeps, True, t, device, host, last_only=True)
+    fin = utils._joint_run(Sm, l1[:i1 + 1], l2[i2:i2 + 1], om, rule, tol, max_sweeps, True, t, device, host, last_only=True,
+                           coupling=coupling)
     W, coef, resvar = fin['W'][0], fin['REFIT_COEF'][0], fin['REFIT_RESVAR'][i1, 0]
     with np.errstate(invalid='ignore'):
         adj = (np.abs(W) >= t) & ~np.eye(p, dtype=bool)[None]
@@ -1363,4 +1370,17 @@ def joint_neighborhood_search(S, N, lambda1_range, lambda2_range, rule='and', me
         Theta, lmin = utils.joint_neighborhood_precision(coef, resvar)
     sol = {'coef': coef, 'resvar': resvar, 'W': W, 'adjacency': adj, 'common_adjacency': np.all(adj, axis=0), 'precision': Theta,
            'lambda_min': lmin, 'lambda1': float(l1[i1]), 'lambda2': float(l2[i2])}
+    if coupling == 'fused':
+        sol['changed_edges'] = np.sum(np.triu(adj[1:] != adj[:-1], 1), axis=(1, 2)).astype(np.int64)
     return sol, stats
+
+
+def fused_neighborhood_search(S, N, lambda1_range, lambda2_range, rule='and', method='eBIC', gamma=0.1, instance_weights=None,
+                              host=None, **kw):
+    """Pick ``(lambda1, lambda2)`` of ``utils.fused_neighborhood_selection`` (K ordered instances, ``lambda2`` on the
+    differences between consecutive ones) on a grid, by the table of ``joint_neighborhood_search``: the eBIC / BIC / AIC of the
+    regressions REFITTED on the selected graphs.  The refit is per instance and unfused, so ``lambda2`` acts on the score through
+    the supports it produces only, never through shrinkage of the differences.  Arguments, ``stats`` and ``sol`` as there
+    (``NEWTON`` is all 0); ``sol`` additionally carries ``changed_edges`` (K-1,): the number of edges that differ between the
+    graphs of instance k and k + 1."""
+    return _joint_search('fused', S, N, lambda1_range, lambda2_range, rule, method, gamma, instance_weights, host, kw)

@@ -570,14 +570,41 @@ class glasso_problem:
                                 "per node has no low-rank component."
         assert self.reg_params.get('lambda1_mask') is None, "Joint neighbourhood selection is not implemented with a lambda1_mask."
         assert self.reg == 'GGL', "Joint neighbourhood selection is implemented for reg='GGL' only: the fused penalty of " \
-                                  "reg='FGL' has no such block update."
+                                  "reg='FGL' has no such block update (see fused_neighborhood_selection)."
         sol, stats = _ms.joint_neighborhood_search(self.S, self.N, lambda1_range, lambda2_range, rule=rule, method=method,
                                                    gamma=gamma, **kw)
+        self._store_neighborhood_search(sol, stats)
+
+    def _store_neighborhood_search(self, sol, stats):
         self.set_reg_params(stats['BEST'])
         self._keep({'Theta': sol['precision']})
         self.solution.adjacency_ = np.asarray(sol['adjacency']).astype(int)
         self.neighborhood_ = dict(sol)
         self.modelselect_stats = dict(stats)
+
+    def fused_neighborhood_selection(self, lambda1_range, lambda2_range, rule='and', method='eBIC', gamma=0.1, **kw):
+        """Fused joint neighbourhood selection for a multiple, conforming problem with ``reg='FGL'``: the regression
+        counterpart of the Fused Graphical Lasso (``utils.fused_neighborhood_selection``: every node's K regressions coupled
+        along the instances' order by ``lambda2 sum_k |beta^(k+1) - beta^(k)|`` beside the lasso penalty ``lambda1``), the pair
+        chosen by ``model_selection.fused_neighborhood_search``.  Arguments, ``kw`` and what is stored as for
+        ``joint_neighborhood_selection``; ``neighborhood_['changed_edges']`` counts the edges that differ between consecutive
+        graphs.  For a time series::
+
+            glasso_problem.from_time_series(X, at, h).fused_neighborhood_selection(l1, l2)
+        """
+        assert rule in ('and', 'or'), f"rule = {rule!r}: 'and' or 'or'"
+        assert self.multiple, "Fused neighbourhood selection couples the instances of a multiple problem; this is a single one " \
+                              "(see neighborhood_selection)."
+        assert self.conforming, "Fused neighbourhood selection is not implemented for instances of different dimension " \
+                                "(non-conforming problems)."
+        assert not self.latent, "Fused neighbourhood selection is not implemented for problems with latent variables: a lasso " \
+                                "per node has no low-rank component."
+        assert self.reg_params.get('lambda1_mask') is None, "Fused neighbourhood selection is not implemented with a lambda1_mask."
+        assert self.reg == 'FGL', f"Fused neighbourhood selection is implemented for reg='FGL' only, this problem has " \
+                                  f"reg={self.reg!r}" + (" (see joint_neighborhood_selection)." if self.reg == 'GGL' else ".")
+        sol, stats = _ms.fused_neighborhood_search(self.S, self.N, lambda1_range, lambda2_range, rule=rule, method=method,
+                                                   gamma=gamma, **kw)
+        self._store_neighborhood_search(sol, stats)
 
     # -- inference ---------------------------------------------------------------------------------------------------------
     def edge_inference(self, alpha=0.05, method='bh', differential=None, host=False):

@@ -1783,6 +1783,7 @@ def mb_cv_scores(resvar, heldout, bad, score='pseudo'):
 # -----------------------------------------------------------------------------------------------------------------
 _MBJ_MAX_ROUNDS = 100
 _MBJ_NEWTON_CAP = 64
+_MBJ_COUPLINGS = {'group': 'joint_neighborhood_selection', 'fused': 'fused_neighborhood_selection'}     # coupling -> front end
 
 
 def mb_joint_limits():
@@ -1792,12 +1793,15 @@ def mb_joint_limits():
     return int(out[0]), int(out[1])
 
 
-def _mbj_args(S, lambda1, lambda2, rule, instance_weights, tol, max_sweeps, refit, t):
+def _mbj_args(S, lambda1, lambda2, rule, instance_weights, tol, max_sweeps, refit, t, coupling='group'):
     """(S (K,p,p) C-contiguous, lambda1 descending (L1,), lambda2 (L2,), omega (K,) or None) of what
-    ``joint_neighborhood_selection`` accepts; its refusals."""
+    ``joint_neighborhood_selection`` (``coupling='group'``) and ``fused_neighborhood_selection`` (``'fused'``) accept; their
+    refusals, which name the caller."""
+    assert coupling in _MBJ_COUPLINGS, f"coupling = {coupling!r}: 'group' or 'fused'"
+    who = _MBJ_COUPLINGS[coupling]
     Sm = np.asarray(S, dtype=np.float64)
     assert Sm.ndim == 3 and Sm.shape[-1] == Sm.shape[-2] and Sm.shape[-1] >= 1 and Sm.shape[0] >= 1, \
-        f"joint_neighborhood_selection needs a (K,p,p) stack of square matrices, S has shape {Sm.shape}"
+        f"{who} needs a (K,p,p) stack of square matrices, S has shape {Sm.shape}"
     K, p = Sm.shape[0], Sm.shape[1]
     l1 = np.sort(np.atleast_1d(np.asarray(lambda1, dtype=np.float64)).reshape(-1))[::-1].copy()
     l2 = np.atleast_1d(np.asarray(lambda2, dtype=np.float64)).reshape(-1).copy()
@@ -1820,23 +1824,80 @@ def _mbj_args(S, lambda1, lambda2, rule, instance_weights, tol, max_sweeps, refi
             raise ValueError(f"instance_weights[{k}] = {om[k]}: an instance weight must be positive and finite")
     if not np.all(np.isfinite(Sm)):
         k, i, q = np.argwhere(~np.isfinite(Sm))[0]
-        raise ValueError(f"joint_neighborhood_selection: S of instance {int(k)}: the entry ({int(i)}, {int(q)}) is not finite")
+        raise ValueError(f"{who}: S of instance {int(k)}: the entry ({int(i)}, {int(q)}) is not finite")
     dg = np.diagonal(Sm, axis1=1, axis2=2)
     if not np.all(dg > 0):
         k, i = np.argwhere(~(dg > 0))[0]
-        raise ValueError(f"joint_neighborhood_selection: S of instance {int(k)}, variable {int(i)}: the diagonal entry is "
+        raise ValueError(f"{who}: S of instance {int(k)}, variable {int(i)}: the diagonal entry is "
                          f"{dg[k, i]}; it must be positive")
     asym = np.argwhere(Sm != np.swapaxes(Sm, 1, 2))
     if asym.size:
         k, i, q = asym[0]
-        raise ValueError(f"joint_neighborhood_selection: S of instance {int(k)} is not bitwise symmetric: the entries "
+        raise ValueError(f"{who}: S of instance {int(k)} is not bitwise symmetric: the entries "
                          f"({int(i)}, {int(q)}) and ({int(q)}, {int(i)}) differ")
     return as_c(Sm), l1, l2, om
 
 
-def _host_mbj_unit(S, om, dg, j, l1s, l2s, tol, max_sweeps):
-    """The chain of node j: (B (L,K,p), resvar (L,K), sweeps (L,), status (L,), newton (L,)) -- ``k_mb_joint_path``'s unit of
-    work, step by step."""
+def _condat_tv(y, lam):
+    """Condat's direct 1-D total-variation prox of ``y`` (N >= 2) at ``lam`` in float64: ``mbf_condat``'s decisions and
+    arithmetic in its order (``condat_inplace`` of the Theta-step), the trip cap N (N + 1) / 2 and NaN behind it included."""
+    N, x = len(y), y.copy()
+    k = k0 = kplus = kminus = 0
+    vmin, vmax, umin, umax = y[0] - lam, y[0] + lam, lam, -lam
+    for _ in range(N * (N + 1) // 2):
+        if k == N - 1:
+            if umin < 0.0:
+                x[k0:kminus + 1] = vmin
+                kminus += 1
+                k = k0 = kminus
+                umin, vmin = lam, y[k]
+                umax = vmin + lam - vmax
+                if k == N - 1:
+                    x[k] = vmin + umin
+                    return x
+            elif umax > 0.0:
+                x[k0:kplus + 1] = vmax
+                kplus += 1
+                k = k0 = kplus
+                umax, vmax = -lam, y[k]
+                umin = vmax - lam - vmin
+                if k == N - 1:
+                    x[k] = vmin + umin
+                    return x
+            else:
+                x[k0:] = vmin + umin / float(k - k0 + 1)
+                return x
+        else:
+            yn = y[k + 1]
+            if yn + umin - vmin < -lam:
+                x[k0:kminus + 1] = vmin
+                kminus += 1
+                k = kplus = k0 = kminus
+                vmin = y[k]
+                vmax, umin, umax = vmin + 2 * lam, lam, -lam
+            elif yn + umax - vmax > lam:
+                x[k0:kplus + 1] = vmax
+                kplus += 1
+                k = kminus = k0 = kplus
+                vmax = y[k]
+                vmin, umin, umax = vmax - 2 * lam, lam, -lam
+            else:
+                k += 1
+                umin, umax = umin + yn - vmin, umax + yn - vmax
+                if umin >= lam:
+                    vmin += (umin - lam) / float(k - k0 + 1)
+                    umin, kminus = lam, k
+                if umax <= -lam:
+                    vmax += (umax + lam) / float(k - k0 + 1)
+                    umax, kplus = -lam, k
+    return np.full(N, np.nan)
+
+
+def _host_mbj_unit(S, om, dg, j, l1s, l2s, tol, max_sweeps, coupling='group'):
+    """The chain of node j: (B (L,K,p), resvar (L,K), sweeps (L,), status (L,), newton (L,)) -- the unit of work of
+    ``k_mb_joint_path`` (``coupling='group'``) or ``k_mb_fused_path`` (``'fused'``: the majorised fused-lasso block update and
+    the dual feasibility screen), step by step."""
+    fused = coupling == 'fused'
     K, p, L = S.shape[0], S.shape[1], len(l1s)
     B, g = np.zeros((K, p)), om[:, None] * S[:, j, :]
     member = np.zeros(p, dtype=bool)
@@ -1850,25 +1911,34 @@ def _host_mbj_unit(S, om, dg, j, l1s, l2s, tol, max_sweeps):
         dmax = 0.0
         for i in act:
             a, bo = om * dg[:, i], B[:, i].copy()
-            z = g[:, i] + a * bo
-            u = np.sign(z) * np.maximum(np.abs(z) - l1, 0.0)
-            un = np.sqrt(np.sum(u * u))
             b = np.zeros(K)
-            if un > l2:
-                if l2 == 0.0:
-                    b = u / a
-                else:
-                    nu, it = (un - l2) / np.max(a), 0
-                    while it < _MBJ_NEWTON_CAP:
-                        tt = 1.0 / (a * nu + l2)
-                        ut = u * tt
-                        f, fp = np.sum(ut * ut) - 1.0, -2.0 * np.sum(ut * ut * a * tt)
-                        nn = nu - f / fp
-                        if not (nn > nu):
-                            break
-                        nu, it = nn, it + 1
-                    state['newton'] = max(state['newton'], it)
-                    b = u * nu / (a * nu + l2)
+            if fused:
+                a = np.max(a)                                               # one curvature for the block
+                v = bo + g[:, i] / a
+                x = v if (l2 == 0.0 or K == 1) else _condat_tv(v, l2 / a)
+                if not np.all(np.isfinite(x)):
+                    state['nfb'] = True
+                x = np.where(np.isnan(x), 0.0, x)                           # (the device's soft turns a NaN into 0)
+                b = np.sign(x) * np.maximum(np.abs(x) - l1 / a, 0.0)
+            else:
+                z = g[:, i] + a * bo
+                u = np.sign(z) * np.maximum(np.abs(z) - l1, 0.0)
+                un = np.sqrt(np.sum(u * u))
+                if un > l2:
+                    if l2 == 0.0:
+                        b = u / a
+                    else:
+                        nu, it = (un - l2) / np.max(a), 0
+                        while it < _MBJ_NEWTON_CAP:
+                            tt = 1.0 / (a * nu + l2)
+                            ut = u * tt
+                            f, fp = np.sum(ut * ut) - 1.0, -2.0 * np.sum(ut * ut * a * tt)
+                            nn = nu - f / fp
+                            if not (nn > nu):
+                                break
+                            nu, it = nn, it + 1
+                        state['newton'] = max(state['newton'], it)
+                        b = u * nu / (a * nu + l2)
             if not np.all(np.isfinite(b)):
                 state['nfb'] = True
             d = b - bo
@@ -1881,8 +1951,18 @@ def _host_mbj_unit(S, om, dg, j, l1s, l2s, tol, max_sweeps):
         return dmax
 
     def screen(l1, l2):
-        sg = np.maximum(np.abs(g) - l1, 0.0)
-        viol = ~member & (np.sqrt(np.sum(sg * sg, axis=0)) > l2)
+        if fused:
+            # 0 solves the fused-lasso prox of g_i exactly if the dual is feasible: the interval of admissible t_k, walked along k
+            lo, hi, ok = np.zeros(p), np.zeros(p), np.ones(p, dtype=bool)
+            for k in range(K - 1):
+                lo, hi = lo + g[k] - l1, hi + g[k] + l1
+                lo, hi = np.where(lo < -l2, -l2, lo), np.where(hi > l2, l2, hi)
+                ok &= lo <= hi
+            out = ~(ok & (lo + g[K - 1] - l1 <= 0.0) & (hi + g[K - 1] + l1 >= 0.0))
+        else:
+            sg = np.maximum(np.abs(g) - l1, 0.0)
+            out = np.sqrt(np.sum(sg * sg, axis=0)) > l2
+        viol = ~member & out
         viol[j] = False
         member[viol] = True
         return int(viol.sum())
@@ -1937,12 +2017,12 @@ def _host_mbj_unit(S, om, dg, j, l1s, l2s, tol, max_sweeps):
     return out_b, out_r, out_s, out_st, out_n
 
 
-def _joint_run(Sm, l1, l2, om, rule, tol, max_sweeps, refit, t, device, host, want_coef=True, last_only=False):
+def _joint_run(Sm, l1, l2, om, rule, tol, max_sweeps, refit, t, device, host, want_coef=True, last_only=False, coupling='group'):
     """The grid ``l1`` (L1, descending) x ``l2`` (L2) as L2 chains of L1 pairs, on the device or through the twin.  Returns a
     dict of arrays in grid layout (L1,L2,...): W (None without ``want_coef``), RESVAR, INFO (L1,L2,p,3) and, with ``refit``,
     REFIT_COEF (None without ``want_coef``), REFIT_RESVAR, REFIT_INFO (L1,L2,K,p,2).  ``last_only``: W and REFIT_COEF are
     (L2,K,p,p), the LAST pair of every chain (``ggl_neighborhood_joint_last``: nothing else is downloaded); the tables stay
-    whole."""
+    whole.  ``coupling``: 'group' (``k_mb_joint_path``) or 'fused' (``k_mb_fused_path``, through the ``_fused_`` entries)."""
     K, p, L, C = Sm.shape[0], Sm.shape[1], l1.size, l2.size
     lam1 = np.ascontiguousarray(np.broadcast_to(l1[None, :], (C, L)))
     lam2 = np.ascontiguousarray(np.broadcast_to(l2[:, None], (C, L)))
@@ -1955,7 +2035,7 @@ def _joint_run(Sm, l1, l2, om, rule, tol, max_sweeps, refit, t, device, host, wa
         with np.errstate(all='ignore'):
             for c in range(C):
                 for j in range(p):
-                    b, r, s, st, nw = _host_mbj_unit(Sm, omv, dg, j, lam1[c], lam2[c], float(tol), int(max_sweeps))
+                    b, r, s, st, nw = _host_mbj_unit(Sm, omv, dg, j, lam1[c], lam2[c], float(tol), int(max_sweeps), coupling)
                     raw[c, :, :, :, j], resvar[c, :, :, j] = b, r
                     info[c, :, j, 0], info[c, :, j, 1], info[c, :, j, 2] = s, st, nw
         W = raw if rule == 'raw' else neighborhood_graph(raw, rule)
@@ -1976,7 +2056,7 @@ def _joint_run(Sm, l1, l2, om, rule, tol, max_sweeps, refit, t, device, host, wa
         rres = np.empty((C, L, K, p)) if refit else None
         rinfo = np.empty((C, L, K, p, 2), dtype=np.int32) if refit else None
         ip = lambda a: None if a is None else a.ctypes.data_as(_lib._ip)
-        entry = lib.ggl_neighborhood_joint_last if last_only else lib.ggl_neighborhood_joint_path
+        entry = getattr(lib, f"ggl_neighborhood_{'fused' if coupling == 'fused' else 'joint'}_{'last' if last_only else 'path'}")
         check(entry(int(device), K, p, ptr(Sm), ptr(om), C, L, ptr(lam1), ptr(lam2), _MB_RULES[rule], float(tol), int(max_sweeps),
                     int(bool(refit)), float(t), ptr(coef), ptr(resvar), ip(info), ptr(rcoef), ptr(rres), ip(rinfo)))
         out.update(W=coef, RESVAR=resvar, INFO=info)
@@ -2033,6 +2113,43 @@ def host_joint_neighborhood_selection(S, lambda1, lambda2, rule='and', instance_
     route and for tests without a GPU."""
     Sm, l1, l2, om = _mbj_args(S, lambda1, lambda2, rule, instance_weights, tol, max_sweeps, refit, t)
     out = _joint_run(Sm, l1, l2, om, rule, tol, max_sweeps, bool(refit), t, 0, True)
+    return _joint_result(out, l1, l2, bool(refit), return_info)
+
+
+def mb_fused_limits():
+    """(largest K, largest p) of the fused device route, as the library reports them (``ggl_mb_fused_limits``)."""
+    out = (ctypes.c_int * 2)()
+    _lib.load().ggl_mb_fused_limits(out)
+    return int(out[0]), int(out[1])
+
+
+def fused_neighborhood_selection(S, lambda1, lambda2, rule='and', instance_weights=None, tol=1e-7, max_sweeps=10000, refit=False,
+                                 t=1e-8, device=0, return_info=False):
+    """Fused joint neighbourhood selection of K ORDERED instances on the device (``ggl_neighborhood_fused_path``): every
+    node's K regressions are coupled by the total variation of each coefficient along the instances' given order
+    (``lambda2 sum_k |beta^(k+1)_i - beta^(k)_i|``) beside the lasso penalty of each (``lambda1``) -- ``reg='FGL'`` for
+    neighbourhood selection, time-varying neighbourhood selection (Kolar, Song, Ahmed, Xing 2010).  The arguments and the
+    results of ``joint_neighborhood_selection``; ``NEWTON`` is all 0.  Limits: ``mb_fused_limits()``, read from the library.
+
+    With ``lambda2 = 0`` these are K separate lassos; with ``lambda2`` large enough the K coefficient vectors of a node
+    coincide and are the lasso on ``sum_k omega_k S^(k)`` at ``K lambda1``; with K = 1 ``lambda2`` is inert.  A block (the K
+    coefficients of one variable) is updated by the fused-lasso prox under the one curvature ``max_k omega_k S^(k)_ii``: exact
+    block minimisation where these are equal (correlation stacks, equal weights), a majorise-minimise step with the same fixed
+    points otherwise, which takes more sweeps.  The same bits on every call, a chain's independent of the others, a point's
+    independent of the ``lambda1`` below it."""
+    Sm, l1, l2, om = _mbj_args(S, lambda1, lambda2, rule, instance_weights, tol, max_sweeps, refit, t, 'fused')
+    out = _joint_run(Sm, l1, l2, om, rule, tol, max_sweeps, bool(refit), t, device, False, coupling='fused')
+    return _joint_result(out, l1, l2, bool(refit), return_info)
+
+
+def host_fused_neighborhood_selection(S, lambda1, lambda2, rule='and', instance_weights=None, tol=1e-7, max_sweeps=10000,
+                                      refit=False, t=1e-8, return_info=False):
+    """numpy twin of ``fused_neighborhood_selection``: the same procedure in the same order (the dual feasibility screen,
+    sweeps of majorised block updates over the ascending active list with the same Condat scan, all gradients recomputed in
+    ascending order, one further sweep, one further screen; the same caps and statuses) in float64 with numpy's own summation
+    orders, so its last bits differ from the device's.  The refit goes through ``host_neighborhood_refit``."""
+    Sm, l1, l2, om = _mbj_args(S, lambda1, lambda2, rule, instance_weights, tol, max_sweeps, refit, t, 'fused')
+    out = _joint_run(Sm, l1, l2, om, rule, tol, max_sweeps, bool(refit), t, 0, True, coupling='fused')
     return _joint_result(out, l1, l2, bool(refit), return_info)
 
 

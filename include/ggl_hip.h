@@ -33,7 +33,8 @@ extern "C" {
  * ggl_set_S_from_mixed, ggl_nearest_correlation, ggl_project_S, ggl_heldout_scores, ggl_debias, ggl_cholesky_predict,
  * ggl_weighted_predictive_scores, ggl_neighborhood_path, ggl_neighborhood_stability, ggl_neighborhood_refit,
  * ggl_neighborhood_cv, ggl_mb_refit_limits, ggl_neighborhood_path_w, ggl_neighborhood_stability_w, ggl_neighborhood_cv_w, ggl_neighborhood_joint_path,
- * ggl_neighborhood_joint_last, ggl_mb_joint_limits, ggl_mb_joint_chunk_budget, ggl_dev_mb_joint_bench) leave every existing layout alone and the number where it is. */
+ * ggl_neighborhood_joint_last, ggl_mb_joint_limits, ggl_mb_joint_chunk_budget, ggl_dev_mb_joint_bench,
+ * ggl_neighborhood_fused_path, ggl_neighborhood_fused_last, ggl_mb_fused_limits, ggl_dev_mb_fused_bench) leave every existing layout alone and the number where it is. */
 #define GGL_VERSION 300
 
 /* error codes */
@@ -1140,6 +1141,35 @@ int ggl_neighborhood_joint_last(int device, int K, int p, const double *S_host, 
 int ggl_dev_mb_joint_bench(int K, int p, const double *S_host, int C, int L, const double *lam1, const double *lam2, double tol,
                            int max_sweeps, int iters, double *ms_out);
 int ggl_neighborhood_joint_path(int device, int K, int p, const double *S_host, const double *omega, int C, int L,
+                                const double *lam1, const double *lam2, int rule, double tol, int max_sweeps, int refit, double t,
+                                double *coef_out, double *resvar_out, int *info_out, double *refit_coef_out,
+                                double *refit_resvar_out, int *refit_info_out);
+
+/* ---- Fused joint neighbourhood selection of K ORDERED instances (neighborhood_fused.hip).  Entry points that are
+ * only ADDED: GGL_VERSION stays where it is.
+ *
+ * The regression counterpart of reg = 'FGL' (time-varying neighbourhood selection: Kolar, Song, Ahmed, Xing 2010; the penalty
+ * of Danaher, Wang, Witten 2014): for node j, in the instances' given order,
+ *     min_B  sum_k omega_k [ 1/2 beta^(k)' S^(k) beta^(k) - s_j^(k)' beta^(k) ]
+ *            + lam1 sum_k sum_{i != j} |beta^(k)_i| + lam2 sum_{i != j} sum_{k < K} |beta^(k+1)_i - beta^(k)_i| ,   beta^(k)_j = 0,
+ * by block coordinate descent (one block: the K coefficients of one variable, updated by the fused-lasso prox under the one
+ * curvature max_k omega_k S^(k)_ii -- exact where these are equal, a majorise-minimise step with the same fixed points
+ * otherwise; the total-variation prox is Condat's direct scan).
+ *
+ * ggl_neighborhood_fused_path, ggl_neighborhood_fused_last: the arguments, the outputs, the statuses, the chunking (and its
+ * budget, ggl_mb_joint_chunk_budget) and the GGL_E_ARG refusals of ggl_neighborhood_joint_path / _last; the third info column
+ * is 0.  lam2 > 0 with K = 1 is accepted and inert.
+ * ggl_mb_fused_limits: out[0] = largest K (64), out[1] = largest p (1024); every (K, p) inside is served (gradients in
+ * registers for K <= 64 up to p = 384, 32 up to 512, 8 up to 1024; in a device workspace beyond).
+ * ggl_dev_mb_fused_bench: as ggl_dev_mb_joint_bench, for k_mb_fused_path. */
+void ggl_mb_fused_limits(int out[2]);
+int ggl_neighborhood_fused_last(int device, int K, int p, const double *S_host, const double *omega, int C, int L,
+                                const double *lam1, const double *lam2, int rule, double tol, int max_sweeps, int refit, double t,
+                                double *coef_out, double *resvar_out, int *info_out, double *refit_coef_out,
+                                double *refit_resvar_out, int *refit_info_out);
+int ggl_dev_mb_fused_bench(int K, int p, const double *S_host, int C, int L, const double *lam1, const double *lam2, double tol,
+                           int max_sweeps, int iters, double *ms_out);
+int ggl_neighborhood_fused_path(int device, int K, int p, const double *S_host, const double *omega, int C, int L,
                                 const double *lam1, const double *lam2, int rule, double tol, int max_sweeps, int refit, double t,
                                 double *coef_out, double *resvar_out, int *info_out, double *refit_coef_out,
                                 double *refit_resvar_out, int *refit_info_out);
