@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libggl_hip.so")
-SOURCES = ["elementwise.hip", "theta_pair.hip", "theta_fsgl.hip", "ext_group.hip", "eig_jacobi.hip", "recon_gemm.hip", "gemm_sym.hip", "covariance.hip", "covariance_missing.hip", "covariance_weighted.hip", "stars.hip", "kendall.hip", "bridge.hip", "nearcorr.hip", "debias.hip", "cholesky.hip", "neighborhood.hip", "neighborhood_weighted.hip", "neighborhood_joint.hip", "neighborhood_fused.hip", "mb_refit.hip", "gemm_i8.hip", "deflate.hip", "omega_lds.hip", "newton_schulz.hip", "ggl_comm.hip", "probes_dev.hip",
+SOURCES = ["elementwise.hip", "theta_pair.hip", "theta_fsgl.hip", "ext_group.hip", "eig_jacobi.hip", "recon_gemm.hip", "gemm_sym.hip", "covariance.hip", "covariance_missing.hip", "covariance_weighted.hip", "stars.hip", "kendall.hip", "bridge.hip", "nearcorr.hip", "debias.hip", "cholesky.hip", "neighborhood.hip", "neighborhood_joint.hip", "neighborhood_fused.hip", "mb_refit.hip", "gemm_i8.hip", "deflate.hip", "omega_lds.hip", "newton_schulz.hip", "ggl_comm.hip", "probes_dev.hip",
            # the C ABI, by subject (csrc/capi_internal.hpp has the map)
            "capi_ctx.hip", "capi_omega.hip", "capi_lstep.hip", "capi_batch.hip", "capi_snapshots.hip", "capi_checks.hip",
            "capi_stats.hip", "capi_comm.hip", "capi_ext.hip", "capi_ops.hip", "capi_data.hip", "capi_nearcorr.hip",

@@ -2,7 +2,8 @@
 // stateless operator, host buffers in and out; ggl_neighborhood_stability runs the same path on the B matrices a ctx holds
 // (the StARS route: ggl_set_S_from_subsets and its siblings wrote them), keeps the symmetrised (L,B,p,p) stack on the device
 // and reduces it with the kernel behind ggl_edge_stability.  ggl_neighborhood_refit and ggl_neighborhood_cv (below) refit a
-// graph by least squares and score the regressions on held-out data (kernels: mb_refit.hip).
+// graph by least squares and score the regressions on held-out data (kernels: mb_refit.hip).  Each of path,
+// stability and cv has ONE host function (mb_*_host); the plain entry and its _w sibling both forward into it.
 #include "capi_internal.hpp"
 
 namespace {
@@ -31,86 +32,163 @@ struct IntBuf {
     ~IntBuf() { if (p) (void)hipFree(p); }
     hipError_t alloc(size_t n) { return hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(int)); }
 };
-}  // namespace
 
-extern "C" int ggl_neighborhood_path(int device, int M, int p, const double* S_host, int L, const double* lam, int rule,
-                                     double tol, int max_sweeps, double* coef_out, double* resvar_out, int* info_out)
+// the (p,p) matrices first .. n - 1 of S on the host: every entry finite, every diagonal entry positive; what: "matrix" /
+// "instance"
+int check_S_host(const double* S, int n, int p, const char* what, int first = 0)
+{
+    const size_t pp = (size_t)p * p;
+    for (int m = first; m < n; ++m) {
+        const double* a = S + (size_t)m * pp;
+        for (size_t e = 0; e < pp; ++e)
+            if (!std::isfinite(a[e]))
+                return fail(GGL_E_ARG, "bad argument: S of %s %d: the entry (%d, %d) is not finite", what, m, (int)(e / p), (int)(e % p));
+        for (int i = 0; i < p; ++i)
+            if (!(a[(size_t)i * p + i] > 0.0))
+                return fail(GGL_E_ARG, "bad argument: S of %s %d, variable %d: the diagonal entry is %g; it must be positive", what, m,
+                            i, a[(size_t)i * p + i]);
+    }
+    return GGL_OK;
+}
+
+int check_threshold(double t)
+{
+    if (!(t >= 0.0) || !(t <= 1.79769313486231570815e308))
+        return fail(GGL_E_ARG, "bad argument: the edge threshold t = %g must be finite and not negative", t);
+    return GGL_OK;
+}
+
+// Penalty weights and the scaled lasso: the adaptive lasso of Zou (2006, JASA 101), the scaled lasso of Sun &
+// Zhang (2012, Biometrika 99; 2013, JMLR 14) / the square-root lasso of Belloni, Chernozhukov, Wang (2011, Biometrika 98), the
+// estimator behind TIGER (Liu & Wang 2017, EJS 11).  A _w entry is its sibling plus (weights, weights_per_matrix, mode,
+// sig_tol, max_outer) and a third int of info per node; the sibling is the same host path with (no weights, GGL_MB_LASSO).
+int check_mbw_args(const double* weights, int weights_per_matrix, int M, int p, int mode, double sig_tol, int max_outer)
+{
+    if (mode != GGL_MB_LASSO && mode != GGL_MB_SCALED)
+        return fail(GGL_E_ARG, "bad argument: mode = %d (GGL_MB_LASSO 0, GGL_MB_SCALED 1)", mode);
+    if (!(sig_tol >= 0.0) || !std::isfinite(sig_tol))
+        return fail(GGL_E_ARG, "bad argument: sig_tol = %g must be non-negative and finite", sig_tol);
+    if (max_outer < 1) return fail(GGL_E_ARG, "bad argument: max_outer = %d; max_outer >= 1", max_outer);
+    if (weights) {
+        const size_t pp = (size_t)p * p;
+        const int nW = weights_per_matrix ? M : 1;
+        for (int m = 0; m < nW; ++m)
+            for (size_t e = 0; e < pp; ++e) {
+                const double v = weights[(size_t)m * pp + e];
+                if (!(v >= 0.0))                                            // +inf is legal: the coordinate is excluded
+                    return fail(GGL_E_ARG, "bad argument: weights of matrix %d: the entry (%d, %d) is %g; a penalty weight must "
+                                "lie in [0, +inf]", m, (int)(e / p), (int)(e % p), v);
+            }
+    }
+    return GGL_OK;
+}
+
+int mb_path_host(int device, int M, int p, const double* S_host, int L, const double* lam, int rule, double tol, int max_sweeps,
+                 const double* weights, int weights_per_matrix, int mode, double sig_tol, int max_outer, int ninfo,
+                 double* coef_out, double* resvar_out, int* info_out)
 {
     ARGCHK(M >= 1, "M >= 1");
     RCCHK(check_mb_args(L, lam, rule, GGL_MB_RAW, tol, max_sweeps, p));
     ARGCHK(S_host && coef_out && info_out, "S, coef_out and info_out must not be NULL");
     ARGCHK((double)M * p < 2147483647.0, "M * p must stay below 2^31");
-    const size_t pp = (size_t)p * p;
-    for (int m = 0; m < M; ++m) {
-        const double* a = S_host + (size_t)m * pp;
-        for (size_t e = 0; e < pp; ++e)
-            if (!std::isfinite(a[e]))
-                return fail(GGL_E_ARG, "bad argument: S of matrix %d: the entry (%d, %d) is not finite", m, (int)(e / p), (int)(e % p));
-        for (int i = 0; i < p; ++i)
-            if (!(a[(size_t)i * p + i] > 0.0))
-                return fail(GGL_E_ARG, "bad argument: S of matrix %d, variable %d: the diagonal entry is %g; it must be positive", m,
-                            i, a[(size_t)i * p + i]);
-    }
+    RCCHK(check_mbw_args(weights, weights_per_matrix, M, p, mode, sig_tol, max_outer));
+    RCCHK(check_S_host(S_host, M, p, "matrix"));
     HIPCHK(hipSetDevice(device));
-    const size_t nML = (size_t)M * L;
-    DevBuf dS, dLam, dCoef, dRes;
+    const size_t pp = (size_t)p * p, nML = (size_t)M * L, nW = weights ? (weights_per_matrix ? (size_t)M : 1) * pp : 0;
+    DevBuf dS, dLam, dCoef, dRes, dW;
     IntBuf dInfo;
     HIPCHK(dS.alloc((size_t)M * pp));
     HIPCHK(dLam.alloc(L));
     HIPCHK(dCoef.alloc(nML * pp));
     if (resvar_out) HIPCHK(dRes.alloc(nML * p));
-    HIPCHK(dInfo.alloc(nML * p * 2));
+    if (weights) HIPCHK(dW.alloc(nW));                                  // a plain call has no table
+    HIPCHK(dInfo.alloc(nML * p * ninfo));
     UP(dS.p, S_host, (size_t)M * pp);
     UP(dLam.p, lam, L);
-    launch_mb_path(nullptr, dS.p, M, p, dLam.p, L, tol, max_sweeps, dCoef.p, dRes.p, dInfo.p, (size_t)L, 1);
-    HIPCHK(hipGetLastError());
+    if (weights) UP(dW.p, weights, nW);
+    HIPCHK(launch_mb_path(nullptr, dS.p, M, p, dW.p, weights_per_matrix ? pp : 0, dLam.p, L, mode, tol, max_sweeps, sig_tol,
+                          max_outer, dCoef.p, dRes.p, dInfo.p, ninfo, (size_t)L, 1));
     launch_mb_symmetrize(nullptr, dCoef.p, nML, p, rule);
     HIPCHK(hipGetLastError());
     DOWN(coef_out, dCoef.p, nML * pp);
     if (resvar_out) DOWN(resvar_out, dRes.p, nML * p);
-    HIPCHK(hipMemcpy(info_out, dInfo.p, nML * p * 2 * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(info_out, dInfo.p, nML * p * ninfo * sizeof(int), hipMemcpyDeviceToHost));
     return GGL_OK;
 }
 
-extern "C" int ggl_neighborhood_stability(ggl_ctx* c, int L, const double* lam, int rule, double tol, int max_sweeps, double t,
-                                          long long* num_out, int* counts_out, double* stack_out, int* info_out)
+int mb_stability_host(ggl_ctx* c, int L, const double* lam, int rule, double tol, int max_sweeps, double t,
+                      const double* weights, int weights_per_matrix, int mode, double sig_tol, int max_outer, int ninfo,
+                      long long* num_out, int* counts_out, double* stack_out, int* info_out)
 {
     ARGCHK(c && num_out && info_out, "ctx, num_out and info_out must not be NULL");
     ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) holds no stack of one dimension");
     RCCHK(check_mb_args(L, lam, rule, GGL_MB_AND, tol, max_sweeps, c->p));
-    if (!(t >= 0.0) || !(t <= 1.79769313486231570815e308))
-        return fail(GGL_E_ARG, "bad argument: the edge threshold t = %g must be finite and not negative", t);
+    RCCHK(check_threshold(t));
     const int B = c->K, p = c->p;
     ARGCHK(L <= 65535, "more than 65535 lambdas in one call");
     ARGCHK((double)B * p < 2147483647.0, "K * p must stay below 2^31");
     ARGCHK((double)p * (double)p * (double)B * (double)B < 7e19, "p * B too large for exact 64-bit sums");
+    RCCHK(check_mbw_args(weights, weights_per_matrix, B, p, mode, sig_tol, max_outer));
     HIPCHK(hipSetDevice(c->device));
     DROP_PRE(c);
-    const size_t pp = (size_t)p * p, nLB = (size_t)L * B;
-    DevBuf dLam, dStack, dNum;
+    const size_t pp = (size_t)p * p, nLB = (size_t)L * B, nW = weights ? (weights_per_matrix ? (size_t)B : 1) * pp : 0;
+    DevBuf dLam, dStack, dNum, dW;
     IntBuf dInfo, dCnt;
     HIPCHK(dLam.alloc(L));
     HIPCHK(dStack.alloc(nLB * pp));
     HIPCHK(dNum.alloc(L));
-    HIPCHK(dInfo.alloc(nLB * p * 2));
+    if (weights) HIPCHK(dW.alloc(nW));                                  // a plain call has no table
+    HIPCHK(dInfo.alloc(nLB * p * ninfo));
     if (counts_out) HIPCHK(dCnt.alloc((size_t)L * pp));
     hipStream_t st = c->stream;
     unsigned long long* num = reinterpret_cast<unsigned long long*>(dNum.p);
     HIPCHK(hipMemcpyAsync(dLam.p, lam, L * sizeof(double), hipMemcpyHostToDevice, st));
+    if (weights) HIPCHK(hipMemcpyAsync(dW.p, weights, nW * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(num, 0, L * sizeof(unsigned long long), st));
     // slot (subsample r, lambda l) of the stack is l * B + r: the layout k_edge_stability reads
-    launch_mb_path(st, c->S, B, p, dLam.p, L, tol, max_sweeps, dStack.p, nullptr, dInfo.p, 1, (size_t)B);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_mb_path(st, c->S, B, p, dW.p, weights_per_matrix ? pp : 0, dLam.p, L, mode, tol, max_sweeps, sig_tol, max_outer,
+                          dStack.p, nullptr, dInfo.p, ninfo, 1, (size_t)B));
     launch_mb_symmetrize(st, dStack.p, nLB, p, rule);
     HIPCHK(hipGetLastError());
     launch_edge_stability(st, dStack.p, L, B, p, t, dCnt.p, num);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(num_out, num, L * sizeof(long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(info_out, dInfo.p, nLB * p * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(info_out, dInfo.p, nLB * p * ninfo * sizeof(int), hipMemcpyDeviceToHost, st));
     if (counts_out) HIPCHK(hipMemcpyAsync(counts_out, dCnt.p, (size_t)L * pp * sizeof(int), hipMemcpyDeviceToHost, st));
     if (stack_out) HIPCHK(hipMemcpyAsync(stack_out, dStack.p, nLB * pp * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return GGL_OK;
+}
+}  // namespace
+
+extern "C" int ggl_neighborhood_path(int device, int M, int p, const double* S_host, int L, const double* lam, int rule,
+                                     double tol, int max_sweeps, double* coef_out, double* resvar_out, int* info_out)
+{
+    return mb_path_host(device, M, p, S_host, L, lam, rule, tol, max_sweeps, nullptr, 0, GGL_MB_LASSO, 0.0, 1, 2, coef_out,
+                        resvar_out, info_out);
+}
+
+extern "C" int ggl_neighborhood_path_w(int device, int M, int p, const double* S_host, int L, const double* lam, int rule,
+                                       double tol, int max_sweeps, const double* weights, int weights_per_matrix, int mode,
+                                       double sig_tol, int max_outer, double* coef_out, double* resvar_out, int* info_out)
+{
+    return mb_path_host(device, M, p, S_host, L, lam, rule, tol, max_sweeps, weights, weights_per_matrix, mode, sig_tol, max_outer, 3,
+                        coef_out, resvar_out, info_out);
+}
+
+extern "C" int ggl_neighborhood_stability(ggl_ctx* c, int L, const double* lam, int rule, double tol, int max_sweeps, double t,
+                                          long long* num_out, int* counts_out, double* stack_out, int* info_out)
+{
+    return mb_stability_host(c, L, lam, rule, tol, max_sweeps, t, nullptr, 0, GGL_MB_LASSO, 0.0, 1, 2, num_out, counts_out,
+                             stack_out, info_out);
+}
+
+extern "C" int ggl_neighborhood_stability_w(ggl_ctx* c, int L, const double* lam, int rule, double tol, int max_sweeps, double t,
+                                            const double* weights, int weights_per_matrix, int mode, double sig_tol,
+                                            int max_outer, long long* num_out, int* counts_out, double* stack_out, int* info_out)
+{
+    return mb_stability_host(c, L, lam, rule, tol, max_sweeps, t, weights, weights_per_matrix, mode, sig_tol, max_outer, 3, num_out,
+                             counts_out, stack_out, info_out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -146,13 +224,6 @@ int run_refit(hipStream_t st, const double* dS, const double* dT, const double* 
     HIPCHK(hipStreamSynchronize(st));
     return GGL_OK;
 }
-
-int check_threshold(double t)
-{
-    if (!(t >= 0.0) || !(t <= 1.79769313486231570815e308))
-        return fail(GGL_E_ARG, "bad argument: the edge threshold t = %g must be finite and not negative", t);
-    return GGL_OK;
-}
 }  // namespace
 
 extern "C" void ggl_mb_refit_limits(int out[2])
@@ -176,19 +247,9 @@ extern "C" int ggl_neighborhood_refit(int device, int M, int p, const double* S_
     ARGCHK(!heldout_out || T_host, "heldout_out needs the second stack T");
     RCCHK(check_threshold(t));
     ARGCHK((double)M * G * p < 2147483647.0, "M * G * p must stay below 2^31");
-    const size_t pp = (size_t)p * p;
-    for (int m = 0; m < M; ++m) {
-        const double* a = S_host + (size_t)m * pp;
-        for (size_t e = 0; e < pp; ++e)
-            if (!std::isfinite(a[e]))
-                return fail(GGL_E_ARG, "bad argument: S of matrix %d: the entry (%d, %d) is not finite", m, (int)(e / p), (int)(e % p));
-        for (int i = 0; i < p; ++i)
-            if (!(a[(size_t)i * p + i] > 0.0))
-                return fail(GGL_E_ARG, "bad argument: S of matrix %d, variable %d: the diagonal entry is %g; it must be positive", m,
-                            i, a[(size_t)i * p + i]);
-    }
+    RCCHK(check_S_host(S_host, M, p, "matrix"));
     HIPCHK(hipSetDevice(device));
-    const size_t nslot = (size_t)M * G;
+    const size_t pp = (size_t)p * p, nslot = (size_t)M * G;
     const bool held = heldout_out != nullptr;
     DevBuf dS, dT, dW, dCoef, dRes, dHeld;
     IntBuf dInfo;
@@ -211,175 +272,10 @@ extern "C" int ggl_neighborhood_refit(int device, int M, int p, const double* S_
     return GGL_OK;
 }
 
-extern "C" int ggl_neighborhood_cv(ggl_ctx* c, const double* X_host, int N, int F, int m, const int* idx_test, int flags, int L,
-                                   const double* lam, int rule, double tol, int max_sweeps, double t, int refit,
-                                   double* resvar_out, double* heldout_out, int* info_out, double* stack_out)
-{
-    ARGCHK(c && resvar_out && heldout_out && info_out, "ctx, resvar_out, heldout_out and info_out must not be NULL");
-    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) holds no stack of one dimension");
-    RCCHK(check_mb_args(L, lam, rule, GGL_MB_AND, tol, max_sweeps, c->p));
-    RCCHK(check_threshold(t));
-    RCCHK(heldout_fold_check(c, X_host, N, F, m, idx_test, flags));
-    if (c->K != F)
-        return fail(GGL_E_ARG, "bad argument: the ctx holds K = %d matrices, the cross-validation has F = %d folds; instance f must "
-                    "be the train matrix of fold f", c->K, F);
-    const int p = c->p;
-    ARGCHK(L <= 65535, "more than 65535 lambdas in one call");
-    ARGCHK((double)L * F * p < 2147483647.0, "L * F * p must stay below 2^31");
-    HIPCHK(hipSetDevice(c->device));
-    DROP_PRE(c);
-    const size_t pp = (size_t)p * p, nLF = (size_t)L * F;
-    DevBuf dLam, dStack, dCoef, dRes, dHeld, dT, dVar;
-    IntBuf dInfo;
-    HIPCHK(dLam.alloc(L));
-    HIPCHK(dStack.alloc(nLF * pp));
-    if (refit) HIPCHK(dCoef.alloc(nLF * pp));
-    HIPCHK(dRes.alloc(nLF * p));
-    HIPCHK(dHeld.alloc(nLF * p));
-    HIPCHK(dT.alloc((size_t)F * pp));
-    HIPCHK(dVar.alloc((size_t)F * p));
-    HIPCHK(dInfo.alloc(nLF * p * 2));
-    hipStream_t st = c->stream;
-    RCCHK(heldout_fold_covariances(c, X_host, N, F, m, idx_test, flags, dT.p, dVar.p));
-    HIPCHK(hipMemcpyAsync(dLam.p, lam, L * sizeof(double), hipMemcpyHostToDevice, st));
-    // slot (fold f, lambda l) is l * F + f, as in ggl_neighborhood_stability; its matrices are S[f], T[f]
-    launch_mb_path(st, c->S, F, p, dLam.p, L, tol, max_sweeps, dStack.p, refit ? nullptr : dRes.p, dInfo.p, 1, (size_t)F);
-    HIPCHK(hipGetLastError());
-    if (!refit) {
-        launch_mb_heldout(st, dT.p, dStack.p, p, nLF, 1, F, dHeld.p);       // the lasso's own beta, still in rows
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(info_out, dInfo.p, nLF * p * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    }
-    launch_mb_symmetrize(st, dStack.p, nLF, p, rule);
-    HIPCHK(hipGetLastError());
-    if (refit) RCCHK(run_refit(st, c->S, dT.p, dStack.p, t, p, nLF, 1, F, dCoef.p, dRes.p, dHeld.p, dInfo.p, info_out));
-    HIPCHK(hipMemcpyAsync(resvar_out, dRes.p, nLF * p * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(heldout_out, dHeld.p, nLF * p * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (stack_out) HIPCHK(hipMemcpyAsync(stack_out, dStack.p, nLF * pp * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return GGL_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Penalty weights and the scaled lasso (kernel: neighborhood_weighted.hip): the adaptive lasso of Zou (2006, JASA
-// 101), the scaled lasso of Sun & Zhang (2012, Biometrika 99; 2013, JMLR 14) / the square-root lasso of Belloni, Chernozhukov,
-// Wang (2011, Biometrika 98), the estimator behind TIGER (Liu & Wang 2017, EJS 11).  Each entry is its sibling above plus
-// (weights, weights_per_matrix, mode, sig_tol, max_outer); everything behind the path is the sibling's code.
-// ---------------------------------------------------------------------------------------------------------------------
 namespace {
-int check_mbw_args(const double* weights, int weights_per_matrix, int M, int p, int mode, double sig_tol, int max_outer)
-{
-    if (mode != GGL_MB_LASSO && mode != GGL_MB_SCALED)
-        return fail(GGL_E_ARG, "bad argument: mode = %d (GGL_MB_LASSO 0, GGL_MB_SCALED 1)", mode);
-    if (!(sig_tol >= 0.0) || !std::isfinite(sig_tol))
-        return fail(GGL_E_ARG, "bad argument: sig_tol = %g must be non-negative and finite", sig_tol);
-    if (max_outer < 1) return fail(GGL_E_ARG, "bad argument: max_outer = %d; max_outer >= 1", max_outer);
-    if (weights) {
-        const size_t pp = (size_t)p * p;
-        const int nW = weights_per_matrix ? M : 1;
-        for (int m = 0; m < nW; ++m)
-            for (size_t e = 0; e < pp; ++e) {
-                const double v = weights[(size_t)m * pp + e];
-                if (!(v >= 0.0))                                            // +inf is legal: the coordinate is excluded
-                    return fail(GGL_E_ARG, "bad argument: weights of matrix %d: the entry (%d, %d) is %g; a penalty weight must "
-                                "lie in [0, +inf]", m, (int)(e / p), (int)(e % p), v);
-            }
-    }
-    return GGL_OK;
-}
-}  // namespace
-
-extern "C" int ggl_neighborhood_path_w(int device, int M, int p, const double* S_host, int L, const double* lam, int rule,
-                                       double tol, int max_sweeps, const double* weights, int weights_per_matrix, int mode,
-                                       double sig_tol, int max_outer, double* coef_out, double* resvar_out, int* info_out)
-{
-    ARGCHK(M >= 1, "M >= 1");
-    RCCHK(check_mb_args(L, lam, rule, GGL_MB_RAW, tol, max_sweeps, p));
-    ARGCHK(S_host && coef_out && info_out, "S, coef_out and info_out must not be NULL");
-    ARGCHK((double)M * p < 2147483647.0, "M * p must stay below 2^31");
-    RCCHK(check_mbw_args(weights, weights_per_matrix, M, p, mode, sig_tol, max_outer));
-    const size_t pp = (size_t)p * p;
-    for (int m = 0; m < M; ++m) {
-        const double* a = S_host + (size_t)m * pp;
-        for (size_t e = 0; e < pp; ++e)
-            if (!std::isfinite(a[e]))
-                return fail(GGL_E_ARG, "bad argument: S of matrix %d: the entry (%d, %d) is not finite", m, (int)(e / p), (int)(e % p));
-        for (int i = 0; i < p; ++i)
-            if (!(a[(size_t)i * p + i] > 0.0))
-                return fail(GGL_E_ARG, "bad argument: S of matrix %d, variable %d: the diagonal entry is %g; it must be positive", m,
-                            i, a[(size_t)i * p + i]);
-    }
-    HIPCHK(hipSetDevice(device));
-    const size_t nML = (size_t)M * L, nW = weights ? (weights_per_matrix ? (size_t)M : 1) * pp : 0;
-    DevBuf dS, dLam, dCoef, dRes, dW;
-    IntBuf dInfo;
-    HIPCHK(dS.alloc((size_t)M * pp));
-    HIPCHK(dLam.alloc(L));
-    HIPCHK(dCoef.alloc(nML * pp));
-    if (resvar_out) HIPCHK(dRes.alloc(nML * p));
-    if (weights) HIPCHK(dW.alloc(nW));
-    HIPCHK(dInfo.alloc(nML * p * 3));
-    UP(dS.p, S_host, (size_t)M * pp);
-    UP(dLam.p, lam, L);
-    if (weights) UP(dW.p, weights, nW);
-    HIPCHK(launch_mb_path_w(nullptr, dS.p, M, p, dW.p, weights_per_matrix ? pp : 0, dLam.p, L, mode, tol, max_sweeps, sig_tol,
-                            max_outer, dCoef.p, dRes.p, dInfo.p, (size_t)L, 1));
-    launch_mb_symmetrize(nullptr, dCoef.p, nML, p, rule);
-    HIPCHK(hipGetLastError());
-    DOWN(coef_out, dCoef.p, nML * pp);
-    if (resvar_out) DOWN(resvar_out, dRes.p, nML * p);
-    HIPCHK(hipMemcpy(info_out, dInfo.p, nML * p * 3 * sizeof(int), hipMemcpyDeviceToHost));
-    return GGL_OK;
-}
-
-extern "C" int ggl_neighborhood_stability_w(ggl_ctx* c, int L, const double* lam, int rule, double tol, int max_sweeps, double t,
-                                            const double* weights, int weights_per_matrix, int mode, double sig_tol,
-                                            int max_outer, long long* num_out, int* counts_out, double* stack_out, int* info_out)
-{
-    ARGCHK(c && num_out && info_out, "ctx, num_out and info_out must not be NULL");
-    ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) holds no stack of one dimension");
-    RCCHK(check_mb_args(L, lam, rule, GGL_MB_AND, tol, max_sweeps, c->p));
-    RCCHK(check_threshold(t));
-    const int B = c->K, p = c->p;
-    ARGCHK(L <= 65535, "more than 65535 lambdas in one call");
-    ARGCHK((double)B * p < 2147483647.0, "K * p must stay below 2^31");
-    ARGCHK((double)p * (double)p * (double)B * (double)B < 7e19, "p * B too large for exact 64-bit sums");
-    RCCHK(check_mbw_args(weights, weights_per_matrix, B, p, mode, sig_tol, max_outer));
-    HIPCHK(hipSetDevice(c->device));
-    DROP_PRE(c);
-    const size_t pp = (size_t)p * p, nLB = (size_t)L * B, nW = weights ? (weights_per_matrix ? (size_t)B : 1) * pp : 0;
-    DevBuf dLam, dStack, dNum, dW;
-    IntBuf dInfo, dCnt;
-    HIPCHK(dLam.alloc(L));
-    HIPCHK(dStack.alloc(nLB * pp));
-    HIPCHK(dNum.alloc(L));
-    if (weights) HIPCHK(dW.alloc(nW));
-    HIPCHK(dInfo.alloc(nLB * p * 3));
-    if (counts_out) HIPCHK(dCnt.alloc((size_t)L * pp));
-    hipStream_t st = c->stream;
-    unsigned long long* num = reinterpret_cast<unsigned long long*>(dNum.p);
-    HIPCHK(hipMemcpyAsync(dLam.p, lam, L * sizeof(double), hipMemcpyHostToDevice, st));
-    if (weights) HIPCHK(hipMemcpyAsync(dW.p, weights, nW * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(num, 0, L * sizeof(unsigned long long), st));
-    // slot (subsample r, lambda l) of the stack is l * B + r: the layout k_edge_stability reads
-    HIPCHK(launch_mb_path_w(st, c->S, B, p, dW.p, weights_per_matrix ? pp : 0, dLam.p, L, mode, tol, max_sweeps, sig_tol, max_outer,
-                            dStack.p, nullptr, dInfo.p, 1, (size_t)B));
-    launch_mb_symmetrize(st, dStack.p, nLB, p, rule);
-    HIPCHK(hipGetLastError());
-    launch_edge_stability(st, dStack.p, L, B, p, t, dCnt.p, num);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(num_out, num, L * sizeof(long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(info_out, dInfo.p, nLB * p * 3 * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (counts_out) HIPCHK(hipMemcpyAsync(counts_out, dCnt.p, (size_t)L * pp * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (stack_out) HIPCHK(hipMemcpyAsync(stack_out, dStack.p, nLB * pp * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return GGL_OK;
-}
-
-extern "C" int ggl_neighborhood_cv_w(ggl_ctx* c, const double* X_host, int N, int F, int m, const int* idx_test, int flags, int L,
-                                     const double* lam, int rule, double tol, int max_sweeps, double t, int refit,
-                                     const double* weights, int weights_per_matrix, int mode, double sig_tol, int max_outer,
-                                     double* resvar_out, double* heldout_out, int* info_out, double* stack_out)
+int mb_cv_host(ggl_ctx* c, const double* X_host, int N, int F, int m, const int* idx_test, int flags, int L, const double* lam,
+               int rule, double tol, int max_sweeps, double t, int refit, const double* weights, int weights_per_matrix, int mode,
+               double sig_tol, int max_outer, int ninfo, double* resvar_out, double* heldout_out, int* info_out, double* stack_out)
 {
     ARGCHK(c && resvar_out && heldout_out && info_out, "ctx, resvar_out, heldout_out and info_out must not be NULL");
     ARGCHK(!c->has_dims, "a ctx with instance dimensions (ggl_set_instance_dims) holds no stack of one dimension");
@@ -405,28 +301,47 @@ extern "C" int ggl_neighborhood_cv_w(ggl_ctx* c, const double* X_host, int N, in
     HIPCHK(dHeld.alloc(nLF * p));
     HIPCHK(dT.alloc((size_t)F * pp));
     HIPCHK(dVar.alloc((size_t)F * p));
-    if (weights) HIPCHK(dW.alloc(nW));
-    HIPCHK(dInfo.alloc(nLF * p * 3));
+    if (weights) HIPCHK(dW.alloc(nW));                                  // a plain call has no table
+    HIPCHK(dInfo.alloc(nLF * p * ninfo));
     hipStream_t st = c->stream;
     RCCHK(heldout_fold_covariances(c, X_host, N, F, m, idx_test, flags, dT.p, dVar.p));
     HIPCHK(hipMemcpyAsync(dLam.p, lam, L * sizeof(double), hipMemcpyHostToDevice, st));
     if (weights) HIPCHK(hipMemcpyAsync(dW.p, weights, nW * sizeof(double), hipMemcpyHostToDevice, st));
     // slot (fold f, lambda l) is l * F + f, as in ggl_neighborhood_stability; its matrices are S[f], T[f]
-    HIPCHK(launch_mb_path_w(st, c->S, F, p, dW.p, weights_per_matrix ? pp : 0, dLam.p, L, mode, tol, max_sweeps, sig_tol, max_outer,
-                            dStack.p, refit ? nullptr : dRes.p, dInfo.p, 1, (size_t)F));
+    HIPCHK(launch_mb_path(st, c->S, F, p, dW.p, weights_per_matrix ? pp : 0, dLam.p, L, mode, tol, max_sweeps, sig_tol, max_outer,
+                          dStack.p, refit ? nullptr : dRes.p, dInfo.p, ninfo, 1, (size_t)F));
     if (!refit) {
         launch_mb_heldout(st, dT.p, dStack.p, p, nLF, 1, F, dHeld.p);       // the lasso's own beta, still in rows
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(info_out, dInfo.p, nLF * p * 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(info_out, dInfo.p, nLF * p * ninfo * sizeof(int), hipMemcpyDeviceToHost, st));
     }
     launch_mb_symmetrize(st, dStack.p, nLF, p, rule);
     HIPCHK(hipGetLastError());
+    // (the refit's info is 2 ints per node whatever ninfo: dInfo is large enough for either)
     if (refit) RCCHK(run_refit(st, c->S, dT.p, dStack.p, t, p, nLF, 1, F, dCoef.p, dRes.p, dHeld.p, dInfo.p, info_out));
     HIPCHK(hipMemcpyAsync(resvar_out, dRes.p, nLF * p * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(heldout_out, dHeld.p, nLF * p * sizeof(double), hipMemcpyDeviceToHost, st));
     if (stack_out) HIPCHK(hipMemcpyAsync(stack_out, dStack.p, nLF * pp * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return GGL_OK;
+}
+}  // namespace
+
+extern "C" int ggl_neighborhood_cv(ggl_ctx* c, const double* X_host, int N, int F, int m, const int* idx_test, int flags, int L,
+                                   const double* lam, int rule, double tol, int max_sweeps, double t, int refit,
+                                   double* resvar_out, double* heldout_out, int* info_out, double* stack_out)
+{
+    return mb_cv_host(c, X_host, N, F, m, idx_test, flags, L, lam, rule, tol, max_sweeps, t, refit, nullptr, 0, GGL_MB_LASSO, 0.0, 1,
+                      2, resvar_out, heldout_out, info_out, stack_out);
+}
+
+extern "C" int ggl_neighborhood_cv_w(ggl_ctx* c, const double* X_host, int N, int F, int m, const int* idx_test, int flags, int L,
+                                     const double* lam, int rule, double tol, int max_sweeps, double t, int refit,
+                                     const double* weights, int weights_per_matrix, int mode, double sig_tol, int max_outer,
+                                     double* resvar_out, double* heldout_out, int* info_out, double* stack_out)
+{
+    return mb_cv_host(c, X_host, N, F, m, idx_test, flags, L, lam, rule, tol, max_sweeps, t, refit, weights, weights_per_matrix, mode,
+                      sig_tol, max_outer, 3, resvar_out, heldout_out, info_out, stack_out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -600,13 +515,7 @@ int joint_path_impl(int device, int K, int p, const double* S_host, const double
     const size_t pp = (size_t)p * p;
     for (int k = 0; k < K; ++k) {
         const double* a = S_host + (size_t)k * pp;
-        for (size_t e = 0; e < pp; ++e)
-            if (!std::isfinite(a[e]))
-                return fail(GGL_E_ARG, "bad argument: S of instance %d: the entry (%d, %d) is not finite", k, (int)(e / p), (int)(e % p));
-        for (int i = 0; i < p; ++i)
-            if (!(a[(size_t)i * p + i] > 0.0))
-                return fail(GGL_E_ARG, "bad argument: S of instance %d, variable %d: the diagonal entry is %g; it must be positive", k,
-                            i, a[(size_t)i * p + i]);
+        RCCHK(check_S_host(S_host, k + 1, p, "instance", k));               // instance k alone: its symmetry is tested next
         for (int i = 0; i < p; ++i)
             for (int q = i + 1; q < p; ++q)
                 if (std::memcmp(&a[(size_t)i * p + q], &a[(size_t)q * p + i], sizeof(double)) != 0)

@@ -29,6 +29,17 @@ __device__ __forceinline__ double wave_max(double v)
     return v;
 }
 
+// v of lane `lane`, a wave-uniform lane
+__device__ __forceinline__ double lane_read(double v, int lane)
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+    return __hiloint2double(hi, lo);
+}
+
+// true for +-inf and for a NaN
+__device__ __forceinline__ bool not_finite(double x) { return !(fabs(x) <= 1.79769313486231570815e308); }
+
 // Deterministic block reduction of NV running sums; result valid in thread 0.
 // scratch: NV * (blockDim/64) doubles of LDS.
 template <int NV>

@@ -578,25 +578,22 @@ void launch_chol_predict(hipStream_t st, double* S, double* d, double ridge, dou
 // d (K,p) = X[:, target[r]] - mean[r,:] for X (p,N); mean null: X[:, target[r]]
 void launch_predict_rhs(hipStream_t st, const double* X, const double* mean, const int* target, double* d, int K, int p, int N);
 
-// Meinshausen-Buhlmann neighbourhood selection (neighborhood.hip).  S (M,p,p) symmetric, lam (L) on the device,
-// positive and descending.  The result of (matrix m, lambda l) is slot m * strideM + l * strideL of coef (slots of (p,p):
-// ROW j = beta^(j), diagonal 0), resvar (slots of p, may be null) and info (slots of (p,2): sweeps, status 0 converged / 1 a
-// cap was reached / 2 non-finite, then the row is NaN from that lambda on).  1 <= p <= MB_MAX_P.
+// Meinshausen-Buhlmann neighbourhood selection with per-entry penalty weights and the scaled lasso (neighborhood.hip, DESIGN
+// 26, 29, 32).  S (M,p,p) symmetric, lam (L) on the device, positive and descending.  Wt: node j of matrix m reads its
+// weights from ROW j of the (p,p) table at Wt + m * wstride (wstride 0: one table for all; p * p: one per matrix); null:
+// all 1, and in plain mode the unweighted kernel.  mode 0 plain, 1 scaled (sig_tol, max_outer: the alternation on sigma).
+// The result of (matrix m, lambda l) is slot m * strideM + l * strideL of coef (slots of (p,p): ROW j = beta^(j), diagonal
+// 0), resvar (slots of p, may be null) and info (slots of (p,ninfo), ninfo 2 or 3: sweeps, status 0 converged / 1 a cap was
+// reached / 2 non-finite / 3 scaled mode, tau^2 <= 1e-10 S_jj -- 2 and 3: the row is NaN from that lambda on -- and with
+// ninfo 3 the outer iterations, 0 in plain mode).  1 <= p <= MB_MAX_P.  Returns what setting the kernel's LDS limit or the
+// launch returned.
 static constexpr int MB_MAX_P = 2048;
-void launch_mb_path(hipStream_t st, const double* S, int M, int p, const double* lam, int L, double tol, int max_sweeps,
-                    double* coef, double* resvar, int* info, size_t strideM, size_t strideL);
+hipError_t launch_mb_path(hipStream_t st, const double* S, int M, int p, const double* Wt, size_t wstride, const double* lam, int L,
+                          int mode, double tol, int max_sweeps, double sig_tol, int max_outer, double* coef, double* resvar,
+                          int* info, int ninfo, size_t strideM, size_t strideL);
 // nmat (p,p) matrices as launch_mb_path left them, in place: rule 0 the transpose (column j = beta^(j)), 1 / 2 the 'and' /
 // 'or' matrix -- of beta^(j)_i and beta^(i)_j the one of smaller / larger magnitude to (i,j) and (j,i), the former on a tie
 void launch_mb_symmetrize(hipStream_t st, double* C, size_t nmat, int p, int rule);
-
-// launch_mb_path with per-entry penalty weights and the scaled lasso (neighborhood_weighted.hip).  Wt: node j of
-// matrix m reads its weights from ROW j of the (p,p) table at Wt + m * wstride (wstride 0: one table for all; p * p: one per
-// matrix); null: all 1.  mode 0 plain, 1 scaled (sig_tol, max_outer: the alternation on sigma).  info: slots of (p,3) =
-// sweeps, status (as above; 3: scaled mode, tau^2 <= 1e-10 S_jj), outer iterations (0 in plain mode).  Returns what setting
-// the kernel's LDS limit or the launch returned.
-hipError_t launch_mb_path_w(hipStream_t st, const double* S, int M, int p, const double* Wt, size_t wstride, const double* lam,
-                            int L, int mode, double tol, int max_sweeps, double sig_tol, int max_outer, double* coef,
-                            double* resvar, int* info, size_t strideM, size_t strideL);
 
 // Refit of neighbourhood selection on its graph (mb_refit.hip).  W: nslot slots of (p,p); the unit (slot s, node j)
 // takes its neighbours from ROW j of slot s (|.| >= t, a NaN is none) and its data from matrix (s / sdiv) % smod of S and,

@@ -18,15 +18,6 @@ static constexpr int MBJ_MAX_ROUNDS = 100;
 static constexpr int MBJ_NEWTON_CAP = 64;
 static constexpr int MBJ_MAX_WAVES = 8;
 
-__device__ __forceinline__ double mbj_lane_read(double v, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ bool mbj_not_finite(double x) { return !(fabs(x) <= 1.79769313486231570815e308); }
-
 // Condat's direct 1-D total-variation prox of y_0 .. y_{N-1}, y_k held by lane k, 2 <= N <= 64: the arithmetic and the order
 // of condat_inplace (theta_pair.hip), one decision of the scan per trip as in condat_uniform.  Every lane runs the whole
 // scan: an element is read from its lane into a scalar (k is wave-uniform), a closed segment [a, b] is written by the lanes
@@ -43,7 +34,7 @@ __device__ __forceinline__ bool mbj_not_finite(double x) { return !(fabs(x) <= 1
 // extends to k = N - 1 and ends there.
 __device__ __forceinline__ double mbf_condat(const double y, const int N, const double lam, const int lane)
 {
-    auto at = [&](int k) -> double { return mbj_lane_read(y, k); };
+    auto at = [&](int k) -> double { return lane_read(y, k); };
     double x = y;
     auto fill = [&](int a, int b, double v) { x = (lane >= a && lane <= b) ? v : x; };
     int k = 0, k0 = 0, kplus = 0, kminus = 0;
@@ -144,10 +135,10 @@ __device__ __forceinline__ void mb_joint_body(const double* __restrict__ S, int 
     // (k_mb_path's pick: a choice among the slots themselves becomes an indexed load and puts the array into scratch)
     auto pick = [&](const double (&a)[NV], int i) -> double {
         const int iv = i >> 6, il = i & 63;
-        double x = mbj_lane_read(a[0], il);
+        double x = lane_read(a[0], il);
 #pragma unroll
         for (int v = 1; v < NV; ++v) {
-            const double t = mbj_lane_read(a[v], il);
+            const double t = lane_read(a[v], il);
             x = (iv == v) ? t : x;
         }
         return x;
@@ -178,7 +169,7 @@ __device__ __forceinline__ void mb_joint_body(const double* __restrict__ S, int 
         if constexpr (GMEM) {
             const int idx = (i & ~63) + lane;
             const double t = idx < p ? gws_row(k)[idx] : 0.0;
-            return mbj_lane_read(t, i & 63);
+            return lane_read(t, i & 63);
         } else {
             return pick(g[q], i);
         }
@@ -213,7 +204,7 @@ __device__ __forceinline__ void mb_joint_body(const double* __restrict__ S, int 
                 // lane k) and holds the same bits, as a scalar.  v_k = beta_k + g_k / a_i goes through the exchange; behind
                 // the barrier every wave runs the scan on the same K words.
                 const double ai =
-                    mbj_lane_read(wave_max(in ? oms[lane] * S[(size_t)lane * pp + (size_t)i * p + i] : 0.0), 0);
+                    lane_read(wave_max(in ? oms[lane] * S[(size_t)lane * pp + (size_t)i * p + i] : 0.0), 0);
 #pragma unroll QU
                 for (int q = 0; q < IPW; ++q) {
                     const int k = w + q * W;
@@ -230,7 +221,7 @@ __device__ __forceinline__ void mb_joint_body(const double* __restrict__ S, int 
                 a = ai;
                 bold = in ? xch[buf][2][lane] : 0.0;
                 const double x = (l2 == 0.0 || K == 1) ? v : mbf_condat(v, K, l2 / ai, lane);    // (K = 1: lambda2 is inert)
-                nfb = nfb || __ballot(in && mbj_not_finite(x)) != 0ull;        // (soft turns a NaN into 0: it is caught here)
+                nfb = nfb || __ballot(in && not_finite(x)) != 0ull;        // (soft turns a NaN into 0: it is caught here)
                 b = in ? soft(x, l1 / ai) : 0.0;
             } else {
 #pragma unroll QU
@@ -270,7 +261,7 @@ __device__ __forceinline__ void mb_joint_body(const double* __restrict__ S, int 
                     }
                 }
             }
-            nfb = nfb || __ballot(in && mbj_not_finite(b)) != 0ull;
+            nfb = nfb || __ballot(in && not_finite(b)) != 0ull;
             const double cm = wave_max(in ? fabs(b - bold) * a : 0.0);
             dmax = cm > dmax ? cm : dmax;
 #pragma unroll QU
@@ -278,7 +269,7 @@ __device__ __forceinline__ void mb_joint_body(const double* __restrict__ S, int 
                 const int k = w + q * W;
                 if (k < K) {
                     if (q > 0) load_row(k, i, row);
-                    const double bn = mbj_lane_read(b, k), d = bn - xch[buf][2][k];
+                    const double bn = lane_read(b, k), d = bn - xch[buf][2][k];
                     if (d != 0.0) {
                         const double wd = oms[k] * d;
                         double gq[NV];
@@ -388,7 +379,7 @@ __device__ __forceinline__ void mb_joint_body(const double* __restrict__ S, int 
 #pragma unroll QU
         for (int q = 0; q < IPW; ++q)
 #pragma unroll
-            for (int v = 0; v < NV; ++v) nf |= mbj_not_finite(gelem(q, w + q * W, v));    // (slots beyond p and instances not owned hold 0)
+            for (int v = 0; v < NV; ++v) nf |= not_finite(gelem(q, w + q * W, v));    // (slots beyond p and instances not owned hold 0)
         return __syncthreads_or(nf ? 1 : 0) != 0;
     };
 

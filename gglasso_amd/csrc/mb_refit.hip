@@ -38,8 +38,6 @@ namespace ggl {
 
 static constexpr int MBR_WAVE_DEG = 32;
 
-__device__ __forceinline__ bool mbr_not_finite(double x) { return !(fabs(x) <= 1.79769313486231570815e308); }
-
 template <int NT>
 __device__ __forceinline__ void mbr_sync()
 {
@@ -68,16 +66,16 @@ __device__ __forceinline__ double mbr_quad(const double* __restrict__ Mm, int p,
         double w = 0.0;
         for (int k = 0; k < d; ++k) {
             const double v = row[lst[k]];
-            nf |= mbr_not_finite(v);
+            nf |= not_finite(v);
             w = fma(v, beta[k], w);
         }
         const double mj = row[j];
-        nf |= mbr_not_finite(mj);
+        nf |= not_finite(mj);
         x[tid] = fma(-2.0, mj, w);
     }
     mbr_sync<NT>();
     double q = Mm[(size_t)j * p + j];
-    nf |= mbr_not_finite(q);
+    nf |= not_finite(q);
     for (int i = 0; i < d; ++i) q = fma(beta[i], x[i], q);
     mbr_sync<NT>();
     return q;
@@ -167,7 +165,7 @@ __global__ __launch_bounds__(NT * UPB) void k_mb_refit(const double* __restrict_
             const int i = i0 + gr;
             if (i < d && gc < d) {
                 const double v = Sm[(size_t)lst[i] * p + lst[gc]];
-                nf |= mbr_not_finite(v);
+                nf |= not_finite(v);
                 if (gc <= i) Lp[i * (i + 1) / 2 + gc] = v;
             }
         }
@@ -175,9 +173,9 @@ __global__ __launch_bounds__(NT * UPB) void k_mb_refit(const double* __restrict_
     double yi = 0.0;
     if (tid < d) {
         yi = Sm[(size_t)lst[tid] * p + j];
-        nf |= mbr_not_finite(yi);
+        nf |= not_finite(yi);
     }
-    nf |= mbr_not_finite(Sm[(size_t)j * p + j]);
+    nf |= not_finite(Sm[(size_t)j * p + j]);
     if (any_nf(nf)) {
         finish_bad(2);
         return;
@@ -195,7 +193,7 @@ __global__ __launch_bounds__(NT * UPB) void k_mb_refit(const double* __restrict_
         }
         mbr_sync<NT>();
         const double piv = bc[0];
-        if (!(piv > 0.0) || mbr_not_finite(piv)) {                          // the same value in every thread
+        if (!(piv > 0.0) || not_finite(piv)) {                          // the same value in every thread
             finish_bad(1);
             return;
         }

@@ -247,27 +247,18 @@ class HipEngine:
         num = np.zeros(L, dtype=np.int64)
         tab = np.empty((L, self.p, self.p), dtype=np.int32) if counts else None
         W = np.empty((L, self.K, self.p, self.p)) if stack else None
+        fn, extra, ni = self.lib.ggl_neighborhood_stability, (), 2
         if weights is not None or scaled:
             Wt, per_matrix = _mbw_args(weights, scaled, sig_tol, max_outer, self.K, self.p)
-            info = np.empty((L, self.K, self.p, 3), dtype=np.int32)
-            check(self.lib.ggl_neighborhood_stability_w(self.h, L, ptr(lam), _MB_RULES[rule], float(tol), int(max_sweeps), float(t),
-                                                        ptr(Wt), int(per_matrix), int(bool(scaled)), float(sig_tol), int(max_outer),
-                                                        num.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)),
-                                                        None if tab is None else tab.ctypes.data_as(_lib._ip), ptr(W),
-                                                        info.ctypes.data_as(_lib._ip)))
-            out = {'num': num, 'sweeps': info[..., 0].astype(np.int64), 'status': info[..., 1].astype(np.int64),
-                   'outer': info[..., 2].astype(np.int64)}
-            if counts:
-                out['counts'] = tab
-            if stack:
-                out['stack'] = W
-            return out
-        info = np.empty((L, self.K, self.p, 2), dtype=np.int32)
-        check(self.lib.ggl_neighborhood_stability(self.h, L, ptr(lam), _MB_RULES[rule], float(tol), int(max_sweeps), float(t),
-                                                  num.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)),
-                                                  None if tab is None else tab.ctypes.data_as(_lib._ip), ptr(W),
-                                                  info.ctypes.data_as(_lib._ip)))
+            fn, ni = self.lib.ggl_neighborhood_stability_w, 3
+            extra = (ptr(Wt), int(per_matrix), int(bool(scaled)), float(sig_tol), int(max_outer))
+        info = np.empty((L, self.K, self.p, ni), dtype=np.int32)
+        check(fn(self.h, L, ptr(lam), _MB_RULES[rule], float(tol), int(max_sweeps), float(t), *extra,
+                 num.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), None if tab is None else tab.ctypes.data_as(_lib._ip),
+                 ptr(W), info.ctypes.data_as(_lib._ip)))
         out = {'num': num, 'sweeps': info[..., 0].astype(np.int64), 'status': info[..., 1].astype(np.int64)}
+        if ni == 3:
+            out['outer'] = info[..., 2].astype(np.int64)
         if counts:
             out['counts'] = tab
         if stack:
@@ -294,30 +285,22 @@ class HipEngine:
         L = lam.size
         resvar, heldout = np.empty((L, self.K, self.p)), np.empty((L, self.K, self.p))
         W = np.empty((L, self.K, self.p, self.p)) if stack else None
+        fn, extra, ni = self.lib.ggl_neighborhood_cv, (), 2
         if weights is not None or scaled:
             Wt, per_matrix = _mbw_args(weights, scaled, sig_tol, max_outer, self.K, self.p)
-            buf = np.empty(L * self.K * self.p * 3, dtype=np.int32)     # the refit's info: two ints per node, in front
-            check(self.lib.ggl_neighborhood_cv_w(self.h, ptr(X), X.shape[1], idx.shape[0], idx.shape[1],
-                                                 idx.ctypes.data_as(_lib._ip), _lib.COV_CENTER if center else 0, L, ptr(lam),
-                                                 _MB_RULES[rule], float(tol), int(max_sweeps), float(t), 1 if refit else 0,
-                                                 ptr(Wt), int(per_matrix), int(bool(scaled)), float(sig_tol), int(max_outer),
-                                                 ptr(resvar), ptr(heldout), buf.ctypes.data_as(_lib._ip), ptr(W)))
-            ni = 2 if refit else 3
-            info = buf[:L * self.K * self.p * ni].reshape(L, self.K, self.p, ni)
-            out = {'resvar': resvar, 'heldout': heldout, 'status': info[..., 1].astype(np.int64),
-                   ('degree' if refit else 'sweeps'): info[..., 0].astype(np.int64)}
-            if not refit:
-                out['outer'] = info[..., 2].astype(np.int64)
-            if stack:
-                out['stack'] = W
-            return out
-        info = np.empty((L, self.K, self.p, 2), dtype=np.int32)
-        check(self.lib.ggl_neighborhood_cv(self.h, ptr(X), X.shape[1], idx.shape[0], idx.shape[1], idx.ctypes.data_as(_lib._ip),
-                                           _lib.COV_CENTER if center else 0, L, ptr(lam), _MB_RULES[rule], float(tol),
-                                           int(max_sweeps), float(t), 1 if refit else 0, ptr(resvar), ptr(heldout),
-                                           info.ctypes.data_as(_lib._ip), ptr(W)))
+            fn, ni = self.lib.ggl_neighborhood_cv_w, 3
+            extra = (ptr(Wt), int(per_matrix), int(bool(scaled)), float(sig_tol), int(max_outer))
+        buf = np.empty(L * self.K * self.p * ni, dtype=np.int32)
+        check(fn(self.h, ptr(X), X.shape[1], idx.shape[0], idx.shape[1], idx.ctypes.data_as(_lib._ip),
+                 _lib.COV_CENTER if center else 0, L, ptr(lam), _MB_RULES[rule], float(tol), int(max_sweeps), float(t),
+                 1 if refit else 0, *extra, ptr(resvar), ptr(heldout), buf.ctypes.data_as(_lib._ip), ptr(W)))
+        if refit:
+            ni = 2                                                      # the refit's info: two ints per node, in front
+        info = buf[:L * self.K * self.p * ni].reshape(L, self.K, self.p, ni)
         out = {'resvar': resvar, 'heldout': heldout, 'status': info[..., 1].astype(np.int64),
                ('degree' if refit else 'sweeps'): info[..., 0].astype(np.int64)}
+        if ni == 3:
+            out['outer'] = info[..., 2].astype(np.int64)
         if stack:
             out['stack'] = W
         return out

@@ -1267,129 +1267,40 @@ def neighborhood_selection(S, lambda_range, rule='and', tol=1e-7, max_sweeps=100
     sum_k w_k |beta_k|``, by alternation: the lasso at ``lambda sigma w_k``, ``sigma = sqrt(tau^2)`` of its result, until
     sigma moves by at most ``sig_tol`` relative, at most ``max_outer`` times; ``RESVAR`` is then ``sigma_j^2`` and
     ``scaled_lasso_lambda`` the one penalty that serves every node.  With either, ``ggl_neighborhood_path_w`` is called
-    (csrc/neighborhood_weighted.hip) and the info gains ``OUTER`` (outer iterations, 0 without ``scaled``) and,
+    (one kernel serves both) and the info gains ``OUTER`` (outer iterations, 0 without ``scaled``) and,
     with ``scaled``, ``SIGMA``; status 1 also means ``max_outer`` was reached and status 3 that ``tau^2 <= 1e-10 S_jj``, a
     degenerate square-root problem (a duplicated variable, a perfect fit): NaN from there on, as for status 2.  Without
     both, the call and its bits are what they were."""
     Sm, lam, single = _mb_args(S, lambda_range, rule, tol, max_sweeps)
     M, p, L = Sm.shape[0], Sm.shape[1], lam.size
     weighted = weights is not None or bool(scaled)
+    extra, ninfo = (), 2                                                # the five further arguments of the _w entry, ints of info
     if weighted:
         Wt, per_matrix = _mbw_args(weights, scaled, sig_tol, max_outer, M, p)
+        extra, ninfo = (ptr(Wt), int(per_matrix), int(bool(scaled)), float(sig_tol), int(max_outer)), 3
     _lib.require_gpu()
     lib = _lib.load()
-
-    def call_w(r, with_resvar):
-        coef, info = np.empty((M, L, p, p)), np.empty((M, L, p, 3), dtype=np.int32)
-        resvar = np.empty((M, L, p)) if with_resvar else None
-        check(lib.ggl_neighborhood_path_w(int(device), M, p, ptr(Sm), L, ptr(lam), _MB_RULES[r], float(tol), int(max_sweeps),
-                                          ptr(Wt), int(per_matrix), int(bool(scaled)), float(sig_tol), int(max_outer),
-                                          ptr(coef), ptr(resvar), info.ctypes.data_as(_lib._ip)))
-        return coef, resvar, info
-
-    if weighted:
-        if not return_info:
-            return _mb_result(call_w(rule, False)[0], None, None, None, lam, single, False)
-        raw, resvar, info = call_w('raw', True)
-        W = raw if rule == 'raw' else call_w(rule, False)[0]
-        return _mb_result(W, raw, resvar, info, lam, single, True, bool(scaled))
+    fn = lib.ggl_neighborhood_path_w if weighted else lib.ggl_neighborhood_path
 
     def call(r, with_resvar):
-        coef, info = np.empty((M, L, p, p)), np.empty((M, L, p, 2), dtype=np.int32)
+        coef, info = np.empty((M, L, p, p)), np.empty((M, L, p, ninfo), dtype=np.int32)
         resvar = np.empty((M, L, p)) if with_resvar else None
-        check(lib.ggl_neighborhood_path(int(device), M, p, ptr(Sm), L, ptr(lam), _MB_RULES[r], float(tol), int(max_sweeps),
-                                        ptr(coef), ptr(resvar), info.ctypes.data_as(_lib._ip)))
+        check(fn(int(device), M, p, ptr(Sm), L, ptr(lam), _MB_RULES[r], float(tol), int(max_sweeps), *extra, ptr(coef),
+                 ptr(resvar), info.ctypes.data_as(_lib._ip)))
         return coef, resvar, info
 
     if not return_info:
         return _mb_result(call(rule, False)[0], None, None, None, lam, single, False)
     raw, resvar, info = call('raw', True)
     W = raw if rule == 'raw' else call(rule, False)[0]
-    return _mb_result(W, raw, resvar, info, lam, single, True)
-
-
-def _host_mb_node(S, j, lam, tol, max_sweeps, max_rounds=100):
-    """The path of node j: (beta (L,p), resvar (L,), sweeps (L,), status (L,)) -- ``k_mb_path``'s unit of work, step by step."""
-    p, L = S.shape[0], lam.size
-    beta, g = np.zeros(p), S[j].copy()
-    member = np.zeros(p, dtype=bool)
-    act = np.zeros(0, dtype=np.int64)
-    out_b, out_r = np.zeros((L, p)), np.zeros(L)
-    out_s, out_st = np.zeros(L, dtype=np.int64), np.zeros(L, dtype=np.int64)
-    dead = False
-
-    def sweep(lamv):
-        dmax = 0.0
-        for k in act:
-            skk, bk = S[k, k], beta[k]
-            z = g[k] + skk * bk
-            b = np.sign(z) * max(abs(z) - lamv, 0.0) / skk
-            d = b - bk
-            if d != 0.0:
-                g[:] -= d * S[k]
-                beta[k] = b
-            c = abs(d) * skk
-            dmax = c if c > dmax else dmax
-        return dmax
-
-    def screen(lamv):
-        viol = ~member & (np.abs(g) > lamv)
-        viol[j] = False
-        member[viol] = True
-        return int(viol.sum())
-
-    def bad():
-        return not (np.all(np.isfinite(g)) and np.all(np.isfinite(beta[act])))
-
-    for l in range(L):
-        lamv, sweeps, status = lam[l], 0, 1
-        if dead or bad():
-            status = 2
-        else:
-            d1 = 0.0
-            for rnd in range(max_rounds):
-                nviol = screen(lamv)
-                act = np.flatnonzero(member)
-                if nviol == 0 and (not (d1 > tol) if rnd > 0 else act.size == 0):
-                    status = 0
-                    break
-                conv = False
-                while sweeps < max_sweeps:
-                    dm = sweep(lamv)
-                    sweeps += 1
-                    if not (dm > tol):
-                        conv = True
-                        break
-                if not conv:
-                    break
-                g[:] = S[j]
-                for k in act:
-                    if beta[k] != 0.0:
-                        g[:] -= beta[k] * S[k]
-                if sweeps >= max_sweeps:
-                    break
-                d1 = sweep(lamv)
-                sweeps += 1
-                if bad():
-                    status = 2
-                    break
-            if status == 1 and bad():
-                status = 2
-        dead = status == 2
-        if dead:
-            out_b[l], out_r[l] = np.nan, np.nan
-            out_b[l, j] = 0.0
-        else:
-            out_b[l] = beta
-            out_r[l] = S[j, j] - float(np.sum(beta[act] * (S[j, act] + g[act])))
-        out_s[l], out_st[l] = sweeps, status
-    return out_b, out_r, out_s, out_st
+    return _mb_result(W, raw, resvar, info, lam, single, True, bool(scaled))
 
 
 def _host_mb_node_w(S, j, lam, w, scaled, tol, max_sweeps, sig_tol, max_outer, max_rounds=100):
-    """The path of node j with the weights w (p,): (beta (L,p), resvar (L,), sweeps, status, outer (L,)) -- ``k_mb_path_w``'s
-    unit of work, step by step: ``_host_mb_node`` with the threshold ``ls * w[k]``, ``ls = lambda`` or ``lambda * sigma``, and
-    around it the alternation on sigma."""
+    """The path of node j with the weights w (p,): (beta (L,p), resvar (L,), sweeps, status, outer (L,)) -- ``k_mb_path``'s
+    unit of work, step by step: the threshold of coordinate k is ``ls * w[k]``, ``ls = lambda`` or ``lambda * sigma``, and
+    around the procedure runs the alternation on sigma.  ``w = 1`` and ``scaled = False`` is the unweighted lasso
+    (``lambda * 1.0`` is exact)."""
     p, L = S.shape[0], lam.size
     beta, g = np.zeros(p), S[j].copy()
     member = np.zeros(p, dtype=bool)
@@ -1500,32 +1411,24 @@ def host_neighborhood_selection(S, lambda_range, rule='and', tol=1e-7, max_sweep
     """numpy twin of ``neighborhood_selection``: the same algorithm in the same order (screen, sweeps over the ascending
     active set, the gradient recomputed in ascending order, one further sweep, one further screen; the same caps and the same
     statuses), in float64 without fused multiply-adds, so its last bits differ from the device's.  For engines without the
-    device route and for tests without a GPU.  ``weights``, ``scaled``, ``sig_tol``, ``max_outer`` as there: the twin of
-    ``k_mb_path_w``, the same alternation in the same order."""
+    device route and for tests without a GPU.  ``weights``, ``scaled``, ``sig_tol``, ``max_outer`` as there: the same
+    alternation in the same order; without them the one node function runs with unit weights and ``OUTER`` is dropped."""
     Sm, lam, single = _mb_args(S, lambda_range, rule, tol, max_sweeps)
     M, p, L = Sm.shape[0], Sm.shape[1], lam.size
     raw, resvar = np.zeros((M, L, p, p)), np.zeros((M, L, p))
-    if weights is not None or scaled:
-        Wt, per_matrix = _mbw_args(weights, scaled, sig_tol, max_outer, M, p)
-        ones = np.ones(p)
-        info = np.zeros((M, L, p, 3), dtype=np.int32)
-        with np.errstate(all='ignore'):
-            for m in range(M):
-                for j in range(p):
-                    w = ones if Wt is None else (Wt[m, j] if per_matrix else Wt[j])
-                    b, r, s, st, o = _host_mb_node_w(Sm[m], j, lam, w, bool(scaled), float(tol), int(max_sweeps), float(sig_tol),
-                                                     int(max_outer))
-                    raw[m, :, :, j], resvar[m, :, j], info[m, :, j, 0], info[m, :, j, 1], info[m, :, j, 2] = b, r, s, st, o
-        W = raw if rule == 'raw' else neighborhood_graph(raw, rule)
-        return _mb_result(W, raw, resvar, info, lam, single, return_info, bool(scaled))
-    info = np.zeros((M, L, p, 2), dtype=np.int32)
+    weighted = weights is not None or bool(scaled)
+    Wt, per_matrix = _mbw_args(weights, scaled, sig_tol, max_outer, M, p) if weighted else (None, False)
+    ones = np.ones(p)
+    info = np.zeros((M, L, p, 3), dtype=np.int32)
     with np.errstate(all='ignore'):
         for m in range(M):
             for j in range(p):
-                b, r, s, st = _host_mb_node(Sm[m], j, lam, float(tol), int(max_sweeps))
-                raw[m, :, :, j], resvar[m, :, j], info[m, :, j, 0], info[m, :, j, 1] = b, r, s, st
+                w = ones if Wt is None else (Wt[m, j] if per_matrix else Wt[j])
+                b, r, s, st, o = _host_mb_node_w(Sm[m], j, lam, w, bool(scaled), float(tol), int(max_sweeps), float(sig_tol),
+                                                 int(max_outer))
+                raw[m, :, :, j], resvar[m, :, j], info[m, :, j, 0], info[m, :, j, 1], info[m, :, j, 2] = b, r, s, st, o
     W = raw if rule == 'raw' else neighborhood_graph(raw, rule)
-    return _mb_result(W, raw, resvar, info, lam, single, return_info)
+    return _mb_result(W, raw, resvar, info if weighted else info[..., :2], lam, single, return_info, bool(scaled))
 
 
 def scaled_lasso_precision(S, n=None, lambda0=None, weights='sd', rule='min', device=0, host=False, tol=1e-7, sig_tol=1e-7,

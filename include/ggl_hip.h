@@ -1058,7 +1058,7 @@ int ggl_neighborhood_cv(ggl_ctx *ctx, const double *X_host, int N, int F, int m,
                         const double *lam, int rule, double tol, int max_sweeps, double t, int refit, double *resvar_out,
                         double *heldout_out, int *info_out, double *stack_out);
 
-/* ---- Neighbourhood selection with per-entry penalty weights and the scaled lasso (neighborhood_weighted.hip).
+/* ---- Neighbourhood selection with per-entry penalty weights and the scaled lasso (neighborhood.hip).
  * Weights: the adaptive lasso (Zou 2006, JASA 101), glmnet's penalty.factor.  Scaled lasso: Sun & Zhang (2012, Biometrika 99;
  * precision matrix: 2013, JMLR 14, R's scalreg), the square-root lasso of Belloni, Chernozhukov, Wang (2011, Biometrika 98),
  * the estimator behind TIGER (Liu & Wang 2017, EJS 11; method = "tiger" of R's huge / flare).  Entry points that are only

@@ -1,5 +1,5 @@
 """Inputs, comparison values and derived error bounds of neighbourhood selection with penalty weights and of the scaled lasso
-(csrc/neighborhood_weighted.hip, the ``weights`` / ``scaled`` arguments of utils.neighborhood_selection and of its twin),
+(the WEIGHTED / SCALED instantiations of csrc/neighborhood.hip, the ``weights`` / ``scaled`` arguments of utils.neighborhood_selection and of its twin),
 shared by test_cpu_mb_weighted.py and test_gpu_mb_weighted.py.  Inputs, ``gradient``, ``residual_bound``, ``resvar_reference``
 and ``and_or`` come from mb_ref.py, whose notation is used: u = 2^-53, g = s_j - S beta.
 

@@ -43,14 +43,14 @@ def test_twin_against_the_comparison_value(p, scaled):
 
 @pytest.mark.parametrize("p", (5, 17, 65))
 def test_unit_weights_keep_the_bits(p):
-    """``weights`` of ones without ``scaled`` is the arithmetic of the call without them; a shared table is the same table
-    given per matrix."""
+    """``weights`` of ones without ``scaled`` is the arithmetic of the call without them -- every key of the info but
+    ``OUTER`` bit for bit, and ``OUTER`` absent from the unweighted call; a shared table is the same table given per matrix."""
     from gglasso_amd import utils
     S = mb_ref.stack(p)[:2]
     W0, i0 = utils.host_neighborhood_selection(S, mb_ref.GRID, 'or', tol=TOL, return_info=True)
     W1, i1 = utils.host_neighborhood_selection(S, mb_ref.GRID, 'or', tol=TOL, return_info=True, weights=np.ones((p, p)))
     assert np.array_equal(W0, W1) and all(np.array_equal(i0[k], i1[k]) for k in i0)
-    assert sorted(set(i1) - set(i0)) == ['OUTER'] and not i1['OUTER'].any()
+    assert 'OUTER' not in i0 and sorted(set(i1) - set(i0)) == ['OUTER'] and not i1['OUTER'].any()
     Wt = mbw_ref.weights(p, 0)
     for scaled in (False, True):
         a = utils.host_neighborhood_selection(S, mb_ref.GRID, 'and', tol=TOL, return_info=True, weights=Wt, scaled=scaled)

@@ -1,7 +1,7 @@
-"""Neighbourhood selection with penalty weights and the scaled lasso on the device (csrc/neighborhood_weighted.hip behind
+"""Neighbourhood selection with penalty weights and the scaled lasso on the device (``k_mb_path`` of csrc/neighborhood.hip behind
 ``ggl_neighborhood_path_w``, ``ggl_neighborhood_stability_w`` and ``ggl_neighborhood_cv_w``): the checks of tests/mbw_ref.py
 against the longdouble comparison value at every size at which the kernel takes another path or a lane falls off an edge, the
-arithmetic it shares with ``k_mb_path``, the bits, the edges of the method, the refusals of the C ABI, and the searches and the
+arithmetic its instantiations share, the plain entries as forwards into the _w entries' host path, the bits, the edges of the method, the refusals of the C ABI, and the searches and the
 front end end to end."""
 import warnings
 
@@ -85,19 +85,22 @@ def _path_w_call(S, lam, rule=1, tol=TOL, max_sweeps=100, weights=None, per_matr
     return rc, _lib.last_error(), C, R, I
 
 
-@pytest.mark.parametrize("p", (17, 65, 257))
+@pytest.mark.parametrize("p", (17, 65, 257, 513, 1025))
 def test_same_arithmetic_as_the_existing_kernel(p):
-    """``ggl_neighborhood_path_w`` without weights, and with a table of ones, in plain mode: bit for bit the COEF, RESVAR,
-    SWEEPS, STATUS and the AND and OR stacks of ``ggl_neighborhood_path``."""
+    """``ggl_neighborhood_path_w`` without weights (the unweighted instantiation of ``k_mb_path``), and with a table of ones
+    (the weighted one), in plain mode: bit for bit the COEF, RESVAR, SWEEPS, STATUS and the AND and OR stacks of
+    ``ggl_neighborhood_path``, OUTER all zero.  p = 513 and 1025 are the smallest sizes of the instantiations with 16 and 32
+    values per lane (at 32, 2 waves per workgroup): one matrix there, and the two-lambda grid of ``test_device_wide_variants``."""
     from gglasso_amd import utils
-    S, lam = mb_ref.stack(p), np.array(mb_ref.GRID)
+    S, lam = (mb_ref.stack(p), np.array(mb_ref.GRID)) if p <= 257 else (mb_ref.case(p, 0)[None], np.array((0.2, 0.1)))
+    M, L = S.shape[0], lam.size
     want = {r: utils.neighborhood_selection(S, lam, r, tol=TOL, return_info=True) for r in ('and', 'or')}
     info0 = want['and'][1]
     for rule, code in (('raw', 0), ('and', 1), ('or', 2)):
         for Wt in (None, np.ones((p, p))):
             rc, msg, C, R, I = _path_w_call(S, lam, rule=code, max_sweeps=10000, weights=Wt)
             assert rc == 0, msg
-            C, R, I = C.reshape(3, 4, p, p), R.reshape(3, 4, p), I.reshape(3, 4, p, 3)
+            C, R, I = C.reshape(M, L, p, p), R.reshape(M, L, p), I.reshape(M, L, p, 3)
             assert np.array_equal(C, info0['COEF'] if rule == 'raw' else want[rule][0])
             assert np.array_equal(R, info0['RESVAR']) and np.array_equal(I[..., 0], info0['SWEEPS'])
             assert np.array_equal(I[..., 1], info0['STATUS']) and not I[..., 2].any()
@@ -326,6 +329,36 @@ def test_ctx_entries_have_the_stateless_bits():
         for kw in (dict(weights=-Wt), dict(scaled=True, sig_tol=-1.0), dict(scaled=True, max_outer=0), dict(weights=np.ones((2, p, p)))):
             with pytest.raises((AssertionError, ValueError)):
                 eng.neighborhood_stability(lam, 'and', **kw)
+    finally:
+        eng.close()
+
+
+def test_plain_ctx_entries_are_forwards():
+    """``HipEngine.neighborhood_stability`` and ``neighborhood_cv`` (with and without ``refit``) on a ctx of three matrices,
+    p = 65: without weights (``ggl_neighborhood_stability`` / ``_cv``) and with a table of ones in plain mode (their _w
+    siblings) every array both return is the same bit for bit, and the _w dicts' ``outer`` is all zero."""
+    from gglasso_amd import model_selection as ms, solver
+    p, B = 65, 3
+    X, lam, ones = mb_ref.stars_data(p=p, N=240), np.array(mb_ref.GRID), np.ones((p, p))
+    train, test = ms.cv_folds(X.shape[1], B, 4)
+    eye = np.broadcast_to(np.eye(p), (B, p, p))
+    eng = solver.HipEngine(eye, eye, eye, np.zeros((B, p, p)))
+
+    def same(a, b, more):
+        assert set(b) == set(a) | more and all(np.array_equal(a[k], b[k]) for k in a)
+        assert not b['status'].any() and a['stack'][-1].any() and all(not b[k].any() for k in more)
+
+    try:
+        eng.set_data_subsets(X, train)
+        kw = dict(rule='and', tol=TOL, counts=True, stack=True)
+        a, b = eng.neighborhood_stability(lam, **kw), eng.neighborhood_stability(lam, weights=ones, **kw)
+        assert {'num', 'counts', 'stack', 'sweeps', 'status'} <= set(a)
+        same(a, b, {'outer'})
+        for refit in (False, True):
+            kw = dict(rule='and', tol=TOL, refit=refit, stack=True)
+            a, b = eng.neighborhood_cv(X, test, lam, **kw), eng.neighborhood_cv(X, test, lam, weights=ones, **kw)
+            assert {'resvar', 'heldout', 'stack', 'status', 'degree' if refit else 'sweeps'} <= set(a)
+            same(a, b, set() if refit else {'outer'})
     finally:
         eng.close()
 

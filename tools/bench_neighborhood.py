@@ -80,10 +80,12 @@ def main():
         S0 = utils.sample_covariance_subsets(X, idx[:1], center=True, scale=True)
         S0 = (S0[0] if isinstance(S0, tuple) else S0)[0]
 
+        ones = np.ones(p)
+
         def twin():
             with np.errstate(all='ignore'):
                 for j in nodes:
-                    utils._host_mb_node(S0, j, lam, 1e-7, 10000)
+                    utils._host_mb_node_w(S0, j, lam, ones, False, 1e-7, 10000, 1e-7, 100)
 
         dev_ms, twin_ms = alternate_ms([search('mb'), twin], args.calls)
         scale = B * p / len(nodes)

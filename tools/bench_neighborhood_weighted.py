@@ -5,9 +5,10 @@
 One JSON line per part (whole-call times; the routes of a comparison alternate, --calls rounds after one warm-up round,
 reported as median, min and max):
 
-* kernel     ``HipEngine.neighborhood_stability`` on the B subsample matrices (``scale=True``) through ``k_mb_path`` against
-             the same call through ``k_mb_path_w`` with a table of ones in plain mode: the same arithmetic, so the gap is the
-             cost of the weight reads and of the larger LDS footprint.  Everything behind the path is shared.
+* kernel     ``HipEngine.neighborhood_stability`` on the B subsample matrices (``scale=True``) through the unweighted
+             instantiation of ``k_mb_path`` against the same call through the weighted one with a table of ones in plain
+             mode: the same arithmetic, so the gap is the cost of the weight reads, of the larger LDS footprint and of the
+             table's upload.  Everything else is shared.
 * scaled     the same call in scaled mode at the grid times ``1`` (on correlations sigma <= 1, so the thresholds are lower
              than the plain ones): time, sweeps and outer iterations per (subsample, lambda, node) unit, statuses.
 * precision  ONE ``utils.scaled_lasso_precision`` call on all N observations against the whole ``stars_search(method='mb')``
@@ -79,8 +80,8 @@ def main():
             eng.close()
         if "kernel" in parts:
             same = np.array_equal(got["plain"]["num"], got["unit"]["num"]) and np.array_equal(got["plain"]["sweeps"], got["unit"]["sweeps"])
-            print(json.dumps({**shape, "part": "kernel", "k_mb_path_call_ms": times[names.index("plain")],
-                              "k_mb_path_w_unit_weights_call_ms": times[names.index("unit")], "same_num_and_sweeps": bool(same),
+            print(json.dumps({**shape, "part": "kernel", "plain_call_ms": times[names.index("plain")],
+                              "unit_weights_call_ms": times[names.index("unit")], "same_num_and_sweeps": bool(same),
                               **unit_stats(got["plain"])}), flush=True)
         if "scaled" in parts:
             print(json.dumps({**shape, "part": "scaled", "plain_call_ms": times[names.index("plain")],
