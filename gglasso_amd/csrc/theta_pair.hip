@@ -45,15 +45,15 @@ int pval_blocks(int p)
 
 static inline int flat_blocks(int p) { return (int)(((size_t)p * p + 255) / 256); }
 
-// flat: 0 tile-pair kernels, 1 per-element kernel, 2 per-element kernel with the K-column split over the four waves of a
-// workgroup where that pays (K > FLAT4_MIN_K)
+// flat: 0 tile-pair kernels, 1 per-element kernel, 2 per-element kernel with the K-column split over the waves of a
+// workgroup (k_theta_ggl_cols) where that pays (K > FLAT4_MIN_K)
 static constexpr int FLAT4_MIN_K = 8;
 static constexpr int FLAT4_CHUNKS = 2;     // 64-element chunks per workgroup (halves the partial-sum rows of the reduction)
 static constexpr int GGL_FLAT1_MAX_K = 32;   // the one-thread-per-element kernel keeps the whole K-column in ONE lane's registers
 static inline bool use_flat4(int K, int flat) { return (flat == 2 && K > FLAT4_MIN_K) || (flat != 0 && K > GGL_FLAT1_MAX_K); }
 
 // Many instances of a SMALL matrix (one problem, K > 64, fewer than 256 workgroups of 128 elements): the workgroup takes 16
-// elements instead of 128 (k_theta_ggl_flat16), e.g. K = 256, p = 64: 256 workgroups instead of 32 on the chip's 256 CUs.
+// elements instead of 128 (k_theta_ggl_cols with SPLIT = 4), e.g. K = 256, p = 64: 256 workgroups instead of 32 on the chip's 256 CUs.
 static inline bool use_flat16(int K, int p, int flat, int G)
 {
     return G == 1 && use_flat4(K, flat) && K > 64 && ((size_t)p * p + 127) / 128 < 256;
@@ -186,6 +186,96 @@ __global__ __launch_bounds__(256) void k_group_partial_flat(double* __restrict__
     out[tri_index(i, j, p)] = ss;
 }
 
+// ---------------------------------------------------------------------------------------------
+// What every Theta kernel of this file does the same way (GGL: all of it; FGL: the first)
+// ---------------------------------------------------------------------------------------------
+// A batch of G independent problems of K instances each (model-selection grid, ggl_mgl_batch_step): blockIdx.y = g,
+// the stacks are (G*K,p,p), l1G / l2G hold the thresholds of instance g*K (null: the scalars l1 / l2, G = 1), the
+// partial sums are rows [g][blocks].  In place on the kernel's own arguments (Theta, X, C, Omega, OmegaPrev, L, l1, l2,
+// partials, l1G, l2G, K) with pp = p * p.  A macro: the statements reach the compiler as they stood in each kernel, and
+// every kernel that only gained this line has the machine code it had.
+#define GGL_THETA_BATCH_OFFSET()                                                                              \
+    do {                                                                                                      \
+        const size_t goff = (size_t)blockIdx.y * K * pp;                                                      \
+        Theta += goff; Omega += goff;                                                                         \
+        if (X) X += goff;                                                                                     \
+        if (C) C += goff;                                                                                     \
+        if (OmegaPrev) OmegaPrev += goff;                                                                     \
+        if (L) L += goff;                                                                                     \
+        if (l1G) { l1 = l1G[(size_t)blockIdx.y * K]; l2 = l2G[(size_t)blockIdx.y * K]; }                      \
+        if (partials) partials += (size_t)blockIdx.y * gridDim.x * GGL_NNORM;                                 \
+    } while (0)
+
+// theta = u (a - l2) / a of the soft-thresholded value (ggl_helper.py:38-43; amul = a - l2); the diagonal passes through
+__device__ __forceinline__ double theta_scale(const double v, const bool offd, const double l1, const double amul, const double a)
+{
+    return offd ? soft(v, l1) * amul / a : v;
+}
+
+// The write-out of one value th of instance k at offset o of the stacks, from the values om, x (and, FUSE_DUAL, op of
+// OmegaPrev) of the same place: Theta; FUSE_DUAL: the dual update X += Omega - Theta (admm_solver.py:208), with wn the W of
+// the NEXT Omega-step C = (Theta - X_new) - beta_k S (k_form_W_sym's arithmetic), and the value's terms of the five
+// stopping-test sums (admm_solver.py:316-331); else, where C is given, the L-step's C = (Theta - X) - Omega.
+// (k_theta_ggl_flat4v writes pairs of values and has this text once more, in its double2 form.)
+template <bool FUSE_DUAL>
+__device__ __forceinline__ void theta_write(const size_t o, const int k, const double th, const double om, const double x,
+                                            const double op, double* Theta, double* X, double* C, const WNext wn,
+                                            double (&acc)[GGL_NNORM])
+{
+    Theta[o] = th;
+    if (FUSE_DUAL) {
+        const double xn = x + (om - th);
+        X[o] = xn;
+        if (wn.S) C[o] = (th - xn) - wn.beta[k] * wn.S[o];
+        const double dp = om - op;
+        acc[0] += om * om;
+        acc[1] += th * th;
+        acc[2] += xn * xn;
+        acc[3] += (om - th) * (om - th);
+        acc[4] += dp * dp;
+    } else if (C) {
+        C[o] = (th - x) - om;
+    }
+}
+
+// NW partial sums as a fixed balanced tree (for NW = 4 the order it always had)
+template <int NW> __device__ __forceinline__ double tree_sum(const double (&v)[NW])
+{
+    if constexpr (NW == 4) return (v[0] + v[1]) + (v[2] + v[3]);
+    else {
+        double h0[NW / 2], h1[NW / 2];
+#pragma unroll
+        for (int i = 0; i < NW / 2; ++i) { h0[i] = v[i]; h1[i] = v[NW / 2 + i]; }
+        return tree_sum<NW / 2>(h0) + tree_sum<NW / 2>(h1);
+    }
+}
+
+// The five running sums of a workgroup of NW waves (thread tid) into row `row` of the partial sums: over the wave, then
+// over the waves through `scratch` (GGL_NNORM * NW doubles of LDS) as tree_sum
+template <int NW>
+__device__ __forceinline__ void theta_block_sums(double (&acc)[GGL_NNORM], double* scratch, const int tid, double* partials,
+                                                 const size_t row)
+{
+    const int lane = tid & 63, wid = tid >> 6;
+#pragma unroll
+    for (int v = 0; v < GGL_NNORM; ++v) acc[v] = wave_sum(acc[v]);
+    if (lane == 0) {
+#pragma unroll
+        for (int v = 0; v < GGL_NNORM; ++v) scratch[wid * GGL_NNORM + v] = acc[v];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double* o = partials + row * GGL_NNORM;
+#pragma unroll
+        for (int v = 0; v < GGL_NNORM; ++v) {
+            double sv[NW];
+#pragma unroll
+            for (int w = 0; w < NW; ++w) sv[w] = scratch[w * GGL_NNORM + v];
+            o[v] = tree_sum<NW>(sv);
+        }
+    }
+}
+
 template <bool FUSE_DUAL>
 __global__ __launch_bounds__(256) void k_theta_ggl(double* __restrict__ Theta, double* __restrict__ X,
                                                    double* __restrict__ C, const double* __restrict__ Omega,
@@ -253,63 +343,22 @@ __global__ __launch_bounds__(256) void k_theta_ggl(double* __restrict__ Theta, d
                 const double om = Omega[o];
                 const double l = L ? L[o] : 0.0;
                 const double x = X ? X[o] : 0.0;
-                const double v = (om + l) + x;
-                const double th = pr_ok[q] ? soft(v, l1) * amul[q] / adiv[q] : v;
-                Theta[o] = th;
+                const double th = theta_scale((om + l) + x, pr_ok[q], l1, amul[q], adiv[q]);
                 tile[buf][ty + PTY * q][tx] = th;
-                if (FUSE_DUAL) {
-                    const double xn = x + (om - th);
-                    X[o] = xn;
-                    const double dp = om - OmegaPrev[o];
-                    acc[0] += om * om;
-                    acc[1] += th * th;
-                    acc[2] += xn * xn;
-                    acc[3] += (om - th) * (om - th);
-                    acc[4] += dp * dp;
-                } else if (C) {
-                    C[o] = (th - x) - om;
-                }
+                const double op = FUSE_DUAL ? OmegaPrev[o] : 0.0;
+                theta_write<FUSE_DUAL>(o, k, th, om, x, op, Theta, X, C, WNext(), acc);
             }
         }
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < PQ; ++q) {
-            if (lo_ok[q]) {
-                const size_t o = base + lo_off[q];
-                const double th = tile[buf][tx][ty + PTY * q];
-                Theta[o] = th;
-                if (FUSE_DUAL) {
-                    const double om = lom[q];
-                    const double xn = lx[q] + (om - th);
-                    X[o] = xn;
-                    const double dp = om - lop[q];
-                    acc[0] += om * om;
-                    acc[1] += th * th;
-                    acc[2] += xn * xn;
-                    acc[3] += (om - th) * (om - th);
-                    acc[4] += dp * dp;
-                } else if (C) {
-                    C[o] = (th - lx[q]) - lom[q];
-                }
-            }
+            if (lo_ok[q])
+                theta_write<FUSE_DUAL>(base + lo_off[q], k, tile[buf][tx][ty + PTY * q], lom[q], lx[q], lop[q], Theta, X, C,
+                                       WNext(), acc);
         }
     }
-    if (FUSE_DUAL) {
-        const int lane = (ty * PT + tx) & 63, wid = (ty * PT + tx) >> 6;
-#pragma unroll
-        for (int v = 0; v < GGL_NNORM; ++v) acc[v] = wave_sum(acc[v]);
-        if (lane == 0) {
-#pragma unroll
-            for (int v = 0; v < GGL_NNORM; ++v) scratch[wid * GGL_NNORM + v] = acc[v];
-        }
-        __syncthreads();
-        if (tx == 0 && ty == 0) {
-            double* o = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * GGL_NNORM;
-#pragma unroll
-            for (int v = 0; v < GGL_NNORM; ++v)
-                o[v] = (scratch[v] + scratch[GGL_NNORM + v]) + (scratch[2 * GGL_NNORM + v] + scratch[3 * GGL_NNORM + v]);
-        }
-    }
+    if (FUSE_DUAL)
+        theta_block_sums<4>(acc, scratch, ty * PT + tx, partials, (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // sq: ggl_chunks(K,p) * p * p doubles.  Writes the per-chunk partial sums of squares.
@@ -510,9 +559,7 @@ __device__ __forceinline__ void condat_scan(double* y, const int s, const int N,
     else condat_uniform<5>(y, s, N, lam, f);
 }
 
-// A batch of G independent problems of K instances each (model-selection grid, ggl_mgl_batch_step): blockIdx.y = g,
-// the stacks are (G*K,p,p), l1G / l2G hold the thresholds of instance g*K (null: the scalars l1 / l2, G = 1), the
-// partial sums are rows [g][blocks].
+// blockIdx.y: the problem of a batch (GGL_THETA_BATCH_OFFSET).
 // ABL (GGL_DEV builds, timing ablations, 1-3 with wrong results): 1 no Condat scan, 2 no scan and no soft-threshold pass, 4 the
 // nested-loop scan,
 // 3 scan only (no global loads / stores)
@@ -528,16 +575,8 @@ __global__ __launch_bounds__(TD * TD) void k_theta_fgl(double* __restrict__ Thet
     extern __shared__ __attribute__((aligned(16))) double lds[];   // [K][TD*TD] then scratch
     constexpr int NT = TD * TD;
     if (spec_failed(skip)) return;
-    {
-        const size_t goff = (size_t)blockIdx.y * K * p * p;
-        Theta += goff; Omega += goff;
-        if (X) X += goff;
-        if (C) C += goff;
-        if (OmegaPrev) OmegaPrev += goff;
-        if (L) L += goff;
-        if (l1G) { l1 = l1G[(size_t)blockIdx.y * K]; l2 = l2G[(size_t)blockIdx.y * K]; }
-        if (partials) partials += (size_t)blockIdx.y * gridDim.x * GGL_NNORM;
-    }
+    const size_t pp = (size_t)p * p;
+    GGL_THETA_BATCH_OFFSET();
     const int T = (p + TD - 1) / TD;
     int I, J;
     decode_pair(blockIdx.x, T, I, J);
@@ -545,7 +584,6 @@ __global__ __launch_bounds__(TD * TD) void k_theta_fgl(double* __restrict__ Thet
     const int I0 = I * TD, J0 = J * TD;
     const int tx = threadIdx.x, ty = threadIdx.y;
     const int tid = ty * TD + tx;
-    const size_t pp = (size_t)p * p;
     double* ycol = lds + tid;
     double* scratch = lds + (size_t)K * NT;
 
@@ -676,17 +714,8 @@ __global__ __launch_bounds__(NT) void k_theta_fgl_flat(double* __restrict__ Thet
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];   // [K][NT] then scratch
     if (spec_failed(skip)) return;
-    {
-        const size_t goff = (size_t)blockIdx.y * K * p * p;
-        Theta += goff; Omega += goff;
-        if (X) X += goff;
-        if (C) C += goff;
-        if (OmegaPrev) OmegaPrev += goff;
-        if (L) L += goff;
-        if (l1G) { l1 = l1G[(size_t)blockIdx.y * K]; l2 = l2G[(size_t)blockIdx.y * K]; }
-        if (partials) partials += (size_t)blockIdx.y * gridDim.x * GGL_NNORM;
-    }
     const size_t pp = (size_t)p * p;
+    GGL_THETA_BATCH_OFFSET();
     const int tid = threadIdx.x;
     const size_t e = (size_t)blockIdx.x * NT + tid;
     const bool live = e < pp;
@@ -866,16 +895,7 @@ __global__ __launch_bounds__(256) void k_theta_ggl_flat(double* __restrict__ The
     if (spec_failed(skip)) return;
     if (gsq_rejected(gsq, p)) return;      // (K-sharded run: the all-reduced flag behind the packed sums)
     const size_t pp = (size_t)p * p;
-    {   // grid-point dimension of a batch of independent problems (see k_theta_fgl)
-        const size_t goff = (size_t)blockIdx.y * K * pp;
-        Theta += goff; Omega += goff;
-        if (X) X += goff;
-        if (C) C += goff;
-        if (OmegaPrev) OmegaPrev += goff;
-        if (L) L += goff;
-        if (l1G) { l1 = l1G[(size_t)blockIdx.y * K]; l2 = l2G[(size_t)blockIdx.y * K]; }
-        if (partials) partials += (size_t)blockIdx.y * gridDim.x * GGL_NNORM;
-    }
+    GGL_THETA_BATCH_OFFSET();
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     double acc[GGL_NNORM] = {0, 0, 0, 0, 0};
     if (e < pp) {
@@ -909,89 +929,49 @@ __global__ __launch_bounds__(256) void k_theta_ggl_flat(double* __restrict__ The
             if (k < K) {
                 const size_t o = (size_t)k * pp + e;
                 const double l = L ? L[o] : 0.0;
-                const double v = (om[k] + l) + x[k];
-                const double th = offd ? soft(v, l1) * amul / a : v;
-                Theta[o] = th;
-                if (FUSE_DUAL) {
-                    const double xn = x[k] + (om[k] - th);
-                    X[o] = xn;
-                    if (wn.S) C[o] = (th - xn) - wn.beta[k] * wn.S[o];      // W of the NEXT Omega-step (k_form_W_sym's arithmetic)
-                    const double dp = om[k] - OmegaPrev[o];
-                    acc[0] += om[k] * om[k];
-                    acc[1] += th * th;
-                    acc[2] += xn * xn;
-                    acc[3] += (om[k] - th) * (om[k] - th);
-                    acc[4] += dp * dp;
-                } else if (C) {
-                    C[o] = (th - x[k]) - om[k];
-                }
+                const double th = theta_scale((om[k] + l) + x[k], offd, l1, amul, a);
+                const double op = FUSE_DUAL ? OmegaPrev[o] : 0.0;
+                theta_write<FUSE_DUAL>(o, k, th, om[k], x[k], op, Theta, X, C, wn, acc);
             }
         }
     }
-    if (FUSE_DUAL) {
-        const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-        for (int v = 0; v < GGL_NNORM; ++v) acc[v] = wave_sum(acc[v]);
-        if (lane == 0) {
-#pragma unroll
-            for (int v = 0; v < GGL_NNORM; ++v) scratch[wid * GGL_NNORM + v] = acc[v];
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double* o = partials + (size_t)blockIdx.x * GGL_NNORM;
-#pragma unroll
-            for (int v = 0; v < GGL_NNORM; ++v)
-                o[v] = (scratch[v] + scratch[GGL_NNORM + v]) + (scratch[2 * GGL_NNORM + v] + scratch[3 * GGL_NNORM + v]);
-        }
-    }
+    if (FUSE_DUAL) theta_block_sums<4>(acc, scratch, threadIdx.x, partials, blockIdx.x);
 }
 
-// The same per-element Theta-step with the K-column of an element split over the four waves of a workgroup: wave w holds
-// the instances w*KQ .. (w+1)*KQ-1 of 64 consecutive elements (KQ values of Omega and X per lane instead of K: 8 waves
-// per SIMD instead of 3 at K = 32, and four times the workgroups, so the tail of the last round of workgroups is short),
-// the four partial sums of squares meet in LDS (fixed order).  Every access is still a full 512-byte wave row.
-// NW waves per workgroup (4, 8 or 16): K <= NW * KQ.  The partial sums of squares of the NW waves are added as a fixed
-// balanced tree (for NW = 4 the order it always had)
-template <int NW> __device__ __forceinline__ double tree_sum(const double (&v)[NW])
+// The same per-element Theta-step with the K-column of an element split over the lanes that hold it: NW waves (4, 8 or 16) of
+// SPLIT instance groups each, KQ instances per group, K <= NW * SPLIT * KQ.  A lane holds KQ values of Omega and X instead of K
+// (8 waves per SIMD instead of 3 at K = 32, and more workgroups, so the tail of the last round of workgroups is short).  The
+// partial sums of squares meet in a fixed order: SPLIT = 4 by two shuffles inside the wave, then one LDS round over the
+// waves, added as tree_sum.  Every access is a full row of the lanes that share an instance.
+//   SPLIT = 1: a wave row is 64 consecutive elements, FLAT4_CHUNKS rows per workgroup one after the other;
+//   SPLIT = 4: few elements, many instances (use_flat16): lanes 0-15 / 16-31 / 32-47 / 48-63 of wave w hold the instance groups
+//              4w .. 4w+3 of the same 16 consecutive elements (a 128-byte segment of every instance): p^2 / 16 workgroups
+//              of 16 waves where the others launch p^2 / 128.
+// One element per lane, 8-byte accesses; k_theta_ggl_flat4v below is the SPLIT = 1 layout with two.
+template <int KQ, int NW, int SPLIT, bool FUSE_DUAL>
+__global__ __launch_bounds__(NW * 64) void k_theta_ggl_cols(double* __restrict__ Theta, double* __restrict__ X,
+                                                        double* __restrict__ C, const double* __restrict__ Omega,
+                                                        const double* __restrict__ OmegaPrev,
+                                                        const double* __restrict__ L, double l1, double l2,
+                                                        double* __restrict__ partials, int K, int p,
+                                                        const int* __restrict__ skip, const double* __restrict__ l1G,
+                                                        const double* __restrict__ l2G, const double* __restrict__ gsq, WNext wn)
 {
-    if constexpr (NW == 4) return (v[0] + v[1]) + (v[2] + v[3]);
-    else {
-        double h0[NW / 2], h1[NW / 2];
-#pragma unroll
-        for (int i = 0; i < NW / 2; ++i) { h0[i] = v[i]; h1[i] = v[NW / 2 + i]; }
-        return tree_sum<NW / 2>(h0) + tree_sum<NW / 2>(h1);
-    }
-}
-
-template <int KQ, bool FUSE_DUAL, int NW = 4>
-__global__ __launch_bounds__(NW * 64) void k_theta_ggl_flat4(double* __restrict__ Theta, double* __restrict__ X,
-                                                         double* __restrict__ C, const double* __restrict__ Omega,
-                                                         const double* __restrict__ OmegaPrev,
-                                                         const double* __restrict__ L, double l1, double l2,
-                                                         double* __restrict__ partials, int K, int p,
-                                                         const int* __restrict__ skip, const double* __restrict__ l1G,
-                                                         const double* __restrict__ l2G, const double* __restrict__ gsq, WNext wn)
-{
-    __shared__ double ssh[NW][64];
+    static_assert(SPLIT == 1 || SPLIT == 4, "instance groups per wave");
+    constexpr int ROW = 64 / SPLIT;                               // elements of a wave row
+    constexpr int CHUNKS = SPLIT == 1 ? FLAT4_CHUNKS : 1;         // rows per workgroup
+    __shared__ double ssh[NW][ROW];
     __shared__ double scratch[GGL_NNORM * NW];
     if (spec_failed(skip)) return;
     if (gsq_rejected(gsq, p)) return;      // (K-sharded run: the all-reduced flag behind the packed sums)
     const size_t pp = (size_t)p * p;
-    {   // grid-point dimension of a batch of independent problems (see k_theta_fgl)
-        const size_t goff = (size_t)blockIdx.y * K * pp;
-        Theta += goff; Omega += goff;
-        if (X) X += goff;
-        if (C) C += goff;
-        if (OmegaPrev) OmegaPrev += goff;
-        if (L) L += goff;
-        if (l1G) { l1 = l1G[(size_t)blockIdx.y * K]; l2 = l2G[(size_t)blockIdx.y * K]; }
-        if (partials) partials += (size_t)blockIdx.y * gridDim.x * GGL_NNORM;
-    }
+    GGL_THETA_BATCH_OFFSET();
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int kb = wid * KQ;
+    const int el = lane % ROW, kb = (wid * SPLIT + lane / ROW) * KQ;
     double acc[GGL_NNORM] = {0, 0, 0, 0, 0};
-    for (int chunk = 0; chunk < FLAT4_CHUNKS; ++chunk) {
-        const size_t e = ((size_t)blockIdx.x * FLAT4_CHUNKS + chunk) * 64 + lane;
+#pragma unroll
+    for (int chunk = 0; chunk < CHUNKS; ++chunk) {
+        const size_t e = ((size_t)blockIdx.x * CHUNKS + chunk) * ROW + el;
         const bool live = e < pp;
         double om[KQ], x[KQ], u[KQ];
         double ss = 0.0;
@@ -1014,13 +994,17 @@ __global__ __launch_bounds__(NW * 64) void k_theta_ggl_flat4(double* __restrict_
                 }
             }
         }
+        if constexpr (SPLIT == 4) {
+            ss += __shfl_xor(ss, 16, 64);
+            ss += __shfl_xor(ss, 32, 64);
+        }
         if (chunk) __syncthreads();          // the previous chunk's sums have been read
-        ssh[wid][lane] = ss;
+        if (lane < ROW) ssh[wid][lane] = ss;
         __syncthreads();
         if (live) {
             double sv[NW];
 #pragma unroll
-            for (int w = 0; w < NW; ++w) sv[w] = ssh[w][lane];
+            for (int w = 0; w < NW; ++w) sv[w] = ssh[w][el];
             const int i = (int)(e / p), j = (int)(e - (size_t)i * p);
             const double tot = gsq ? gsq[tri_index(i, j, p)] : tree_sum<NW>(sv);
             const double a = fmax(sqrt(tot), l2);
@@ -1030,50 +1014,23 @@ __global__ __launch_bounds__(NW * 64) void k_theta_ggl_flat4(double* __restrict_
             for (int q = 0; q < KQ; ++q) {
                 if (kb + q < K) {
                     const size_t o = (size_t)(kb + q) * pp + e;
-                    const double v = u[q];
-                    const double th = offd ? soft(v, l1) * amul / a : v;
-                    Theta[o] = th;
-                    if (FUSE_DUAL) {
-                        const double xn = x[q] + (om[q] - th);
-                        X[o] = xn;
-                        if (wn.S) C[o] = (th - xn) - wn.beta[kb + q] * wn.S[o];
-                        const double dp = om[q] - OmegaPrev[o];
-                        acc[0] += om[q] * om[q];
-                        acc[1] += th * th;
-                        acc[2] += xn * xn;
-                        acc[3] += (om[q] - th) * (om[q] - th);
-                        acc[4] += dp * dp;
-                    } else if (C) {
-                        C[o] = (th - x[q]) - om[q];
-                    }
+                    const double op = FUSE_DUAL ? OmegaPrev[o] : 0.0;
+                    theta_write<FUSE_DUAL>(o, kb + q, theta_scale(u[q], offd, l1, amul, a), om[q], x[q], op, Theta, X, C, wn, acc);
                 }
             }
         }
     }
-    if (FUSE_DUAL) {
-#pragma unroll
-        for (int v = 0; v < GGL_NNORM; ++v) acc[v] = wave_sum(acc[v]);
-        if (lane == 0) {
-#pragma unroll
-            for (int v = 0; v < GGL_NNORM; ++v) scratch[wid * GGL_NNORM + v] = acc[v];
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double* o = partials + (size_t)blockIdx.x * GGL_NNORM;
-#pragma unroll
-            for (int v = 0; v < GGL_NNORM; ++v) {
-                double sv[NW];
-#pragma unroll
-                for (int w = 0; w < NW; ++w) sv[w] = scratch[w * GGL_NNORM + v];
-                o[v] = tree_sum<NW>(sv);
-            }
-        }
-    }
+    if (FUSE_DUAL) theta_block_sums<NW>(acc, scratch, threadIdx.x, partials, blockIdx.x);
 }
 
-// The same with 16-byte accesses: a lane holds TWO consecutive elements (p^2 even), a wave row is 1 KiB.  8-byte
+// The SPLIT = 1 layout with 16-byte accesses: a lane holds TWO consecutive elements (p^2 even), a wave row is 1 KiB.  8-byte
 // accesses run at 0.54-0.70x the 16-byte rate on this chip (MI355X_MICROARCH.md), and this kernel is nothing but accesses.
-// Same 128 elements per workgroup as the scalar form (one chunk of 2 x 64), so the partial-sum layout is unchanged.
+// Same 128 elements per workgroup as the one-element form (one chunk of 2 x 64), so the partial-sum layout is unchanged.
+// It is a kernel of its own, with the write-out of theta_write spelled in double2, because its five sums add the two
+// elements of a lane to each other first (.x * .x + .y * .y): which of the two products the compiler fuses into the addition
+// follows the shape of that text, and the sums' last bits follow the choice (a body generic in the
+// elements per lane changed them).  Its block sums are written out as well: through theta_block_sums the 16-wave
+// instantiation, which sits at its register limit, spills 4 bytes more.
 template <int KQ, bool FUSE_DUAL, int NW = 4>
 __global__ __launch_bounds__(NW * 64) void k_theta_ggl_flat4v(double* __restrict__ Theta, double* __restrict__ X,
                                                           double* __restrict__ C, const double* __restrict__ Omega,
@@ -1089,24 +1046,14 @@ __global__ __launch_bounds__(NW * 64) void k_theta_ggl_flat4v(double* __restrict
     if (spec_failed(skip)) return;
     if (gsq_rejected(gsq, p)) return;      // (K-sharded run: the all-reduced flag behind the packed sums)
     const size_t pp = (size_t)p * p;
-    {
-        const size_t goff = (size_t)blockIdx.y * K * pp;
-        Theta += goff; Omega += goff;
-        if (X) X += goff;
-        if (C) C += goff;
-        if (OmegaPrev) OmegaPrev += goff;
-        if (L) L += goff;
-        if (l1G) { l1 = l1G[(size_t)blockIdx.y * K]; l2 = l2G[(size_t)blockIdx.y * K]; }
-        if (partials) partials += (size_t)blockIdx.y * gridDim.x * GGL_NNORM;
-    }
+    GGL_THETA_BATCH_OFFSET();
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int kb = wid * KQ;
     double acc[GGL_NNORM] = {0, 0, 0, 0, 0};
     const size_t e = ((size_t)blockIdx.x * 64 + lane) * 2;
-    // p even: e + 1 < pp as well, in the same row, and every pair is 16-byte aligned.  Odd p (round 6; rounds 2-5 ran the
-    // one-element kernel there, 0.54-0.70x the access rate): the pairs of every other instance start on an 8-byte boundary
-    // (the hardware takes that), a pair may straddle two rows, and the last element of a matrix has no partner -- that one
-    // lane moves single elements and its second half counts as zero everywhere.
+    // p even: e + 1 < pp as well, in the same row, and every pair is 16-byte aligned.  Odd p: the pairs of every other
+    // instance start on an 8-byte boundary (the hardware takes that), a pair may straddle two rows, and the last element of a
+    // matrix has no partner -- that one lane moves single elements and its second half counts as zero everywhere.
     const bool live = e < pp, live1 = e + 1 < pp;
     double2 om[KQ], x[KQ], u[KQ];
     double2 ss = {0.0, 0.0};
@@ -1213,146 +1160,23 @@ __global__ __launch_bounds__(NW * 64) void k_theta_ggl_flat4v(double* __restrict
     }
 }
 
-// Few elements, many instances: a workgroup of 16 waves takes 16 consecutive elements (a 128-byte segment of every
-// instance) and ALL K <= 64 * KQ instances of them; lanes 0-15 / 16-31 / 32-47 / 48-63 of wave w hold the instance groups
-// 4w .. 4w+3 (KQ instances each).  The sums of squares meet by two shuffles inside the wave and one LDS round over the waves,
-// in a fixed order.  p^2 / 16 workgroups where the 128-element kernels above would launch p^2 / 128.
-template <int KQ, bool FUSE_DUAL>
-__global__ __launch_bounds__(1024) void k_theta_ggl_flat16(double* __restrict__ Theta, double* __restrict__ X,
-                                                           double* __restrict__ C, const double* __restrict__ Omega,
-                                                           const double* __restrict__ OmegaPrev,
-                                                           const double* __restrict__ L, double l1, double l2,
-                                                           double* __restrict__ partials, int K, int p,
-                                                           const int* __restrict__ skip, const double* __restrict__ gsq, WNext wn)
-{
-    constexpr int NW = 16;
-    __shared__ double ssh[NW][16];
-    __shared__ double scratch[GGL_NNORM * NW];
-    if (spec_failed(skip)) return;
-    if (gsq_rejected(gsq, p)) return;      // (K-sharded run: the all-reduced flag behind the packed sums)
-    const size_t pp = (size_t)p * p;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int el = lane & 15, kb = (wid * 4 + (lane >> 4)) * KQ;
-    const size_t e = (size_t)blockIdx.x * 16 + el;
-    const bool live = e < pp;
-    double acc[GGL_NNORM] = {0, 0, 0, 0, 0};
-    double om[KQ], x[KQ], u[KQ];
-    double ss = 0.0;
-    if (live) {
-#pragma unroll
-        for (int q = 0; q < KQ; ++q) {
-            if (kb + q < K) {
-                const size_t o = (size_t)(kb + q) * pp + e;
-                om[q] = Omega[o];
-                x[q] = X ? X[o] : 0.0;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < KQ; ++q) {
-            if (kb + q < K) {
-                const double l = L ? L[(size_t)(kb + q) * pp + e] : 0.0;
-                u[q] = (om[q] + l) + x[q];
-                const double sv = soft(u[q], l1);
-                ss += sv * sv;
-            }
-        }
-    }
-    ss += __shfl_xor(ss, 16, 64);
-    ss += __shfl_xor(ss, 32, 64);
-    if (lane < 16) ssh[wid][lane] = ss;
-    __syncthreads();
-    if (live) {
-        double sv[NW];
-#pragma unroll
-        for (int w = 0; w < NW; ++w) sv[w] = ssh[w][el];
-        const int i = (int)(e / p), j = (int)(e - (size_t)i * p);
-        const double tot = gsq ? gsq[tri_index(i, j, p)] : tree_sum<NW>(sv);
-        const double a = fmax(sqrt(tot), l2);
-        const double amul = a - l2;
-        const bool offd = (i != j);
-#pragma unroll
-        for (int q = 0; q < KQ; ++q) {
-            if (kb + q < K) {
-                const size_t o = (size_t)(kb + q) * pp + e;
-                const double v = u[q];
-                const double th = offd ? soft(v, l1) * amul / a : v;
-                Theta[o] = th;
-                if (FUSE_DUAL) {
-                    const double xn = x[q] + (om[q] - th);
-                    X[o] = xn;
-                    if (wn.S) C[o] = (th - xn) - wn.beta[kb + q] * wn.S[o];
-                    const double dp = om[q] - OmegaPrev[o];
-                    acc[0] += om[q] * om[q];
-                    acc[1] += th * th;
-                    acc[2] += xn * xn;
-                    acc[3] += (om[q] - th) * (om[q] - th);
-                    acc[4] += dp * dp;
-                } else if (C) {
-                    C[o] = (th - x[q]) - om[q];
-                }
-            }
-        }
-    }
-    if (FUSE_DUAL) {
-#pragma unroll
-        for (int v = 0; v < GGL_NNORM; ++v) acc[v] = wave_sum(acc[v]);
-        if (lane == 0) {
-#pragma unroll
-            for (int v = 0; v < GGL_NNORM; ++v) scratch[wid * GGL_NNORM + v] = acc[v];
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double* o = partials + (size_t)blockIdx.x * GGL_NNORM;
-#pragma unroll
-            for (int v = 0; v < GGL_NNORM; ++v) {
-                double sv[NW];
-#pragma unroll
-                for (int w = 0; w < NW; ++w) sv[w] = scratch[w * GGL_NNORM + v];
-                o[v] = tree_sum<NW>(sv);
-            }
-        }
-    }
-}
-
-template <int KQ>
-static void launch_flat16(hipStream_t st, double* Theta, double* X, double* C, const double* Omega, const double* OmegaPrev,
-                          const double* L, double l1, double l2, int fuse_dual, double* partials, int K, int p,
-                          const int* skip, const double* gsq, WNext wn = WNext())
-{
-    dim3 grid((unsigned)(((size_t)p * p + 15) / 16)), blk(1024);
-    if (fuse_dual)
-        hipLaunchKernelGGL((k_theta_ggl_flat16<KQ, true>), grid, blk, 0, st, Theta, X, C, Omega, OmegaPrev, L, l1, l2, partials, K, p, skip, gsq, wn);
-    else
-        hipLaunchKernelGGL((k_theta_ggl_flat16<KQ, false>), grid, blk, 0, st, Theta, X, C, Omega, OmegaPrev, L, l1, l2, partials, K, p, skip, gsq, wn);
-}
-
 static inline int flat4_blocks(int p) { return (int)(((size_t)p * p + 64 * FLAT4_CHUNKS - 1) / (64 * FLAT4_CHUNKS)); }
 
-template <int KQ, int NW = 4, bool VEC_OK = true>
-static void launch_flat4(hipStream_t st, double* Theta, double* X, double* C, const double* Omega,
-                         const double* OmegaPrev, const double* L, double l1, double l2, int fuse_dual, double* partials,
-                         int K, int p, const int* skip, int G = 1, const double* l1G = nullptr, const double* l2G = nullptr,
-                         const double* gsq = nullptr, WNext wn = WNext())
+// EPL: elements per lane (2: k_theta_ggl_flat4v, SPLIT = 1 only)
+template <int KQ, int NW, int EPL, int SPLIT>
+static void launch_cols(hipStream_t st, double* Theta, double* X, double* C, const double* Omega, const double* OmegaPrev,
+                        const double* L, double l1, double l2, int fuse_dual, double* partials, int K, int p, const int* skip,
+                        int G, const double* l1G, const double* l2G, const double* gsq, WNext wn)
 {
-    dim3 grid(flat4_blocks(p), G), blk(NW * 64);
-    if constexpr (VEC_OK) {
-        {                            // two consecutive elements per lane, 16-byte accesses (any p since round 6)
-            if (fuse_dual)
-                hipLaunchKernelGGL((k_theta_ggl_flat4v<KQ, true, NW>), grid, blk, 0, st, Theta, X, C, Omega, OmegaPrev, L, l1, l2, partials, K, p, skip, l1G, l2G, gsq, wn);
-            else
-                hipLaunchKernelGGL((k_theta_ggl_flat4v<KQ, false, NW>), grid, blk, 0, st, Theta, X, C, Omega, OmegaPrev, L, l1, l2, partials, K, p, skip, l1G, l2G, gsq, wn);
-            return;
-        }
-    }
-    if (fuse_dual)
-        hipLaunchKernelGGL((k_theta_ggl_flat4<KQ, true, NW>), grid, blk, 0, st, Theta, X, C, Omega, OmegaPrev, L, l1, l2, partials, K, p, skip, l1G, l2G, gsq, wn);
-    else
-        hipLaunchKernelGGL((k_theta_ggl_flat4<KQ, false, NW>), grid, blk, 0, st, Theta, X, C, Omega, OmegaPrev, L, l1, l2, partials, K, p, skip, l1G, l2G, gsq, wn);
+    static_assert(EPL == 1 || (EPL == 2 && SPLIT == 1), "layouts");
+    dim3 grid(SPLIT == 1 ? flat4_blocks(p) : (unsigned)(((size_t)p * p + 15) / 16), G), blk(NW * 64);
+    void (*kern)(double*, double*, double*, const double*, const double*, const double*, double, double, double*, int, int,
+                 const int*, const double*, const double*, const double*, WNext);
+    if constexpr (EPL == 2) kern = fuse_dual ? k_theta_ggl_flat4v<KQ, true, NW> : k_theta_ggl_flat4v<KQ, false, NW>;
+    else kern = fuse_dual ? k_theta_ggl_cols<KQ, NW, SPLIT, true> : k_theta_ggl_cols<KQ, NW, SPLIT, false>;
+    hipLaunchKernelGGL(kern, grid, blk, 0, st, Theta, X, C, Omega, OmegaPrev, L, l1, l2, partials, K, p, skip, l1G, l2G, gsq, wn);
 }
 
-// the K-column of an element over 4, 8 or 16 waves: K <= 16: 4 x 4, <= 32: 4 x 8, <= 64: 8 x 8, <= 128: 16 x 8 (16-byte
-// accesses throughout), <= 256: 16 x 16 with 8-byte accesses (two elements per lane would need 192 registers per lane, a
-// 16-wave workgroup has 128)
 // Which Theta kernel the last launch_theta_pair / launch_theta_batch of this process ran (ggl_last_dispatch; the parity tests
 // assert the dispatch of every BASELINE configuration): 0 GGL tile pairs; 100 + KMAX per-element, K-column in one thread;
 // 100 * KQ + NW per-element, K-column over NW waves of KQ values per lane (404, 408: four waves; 808 / 816 / 1616: K <= 64 /
@@ -1362,26 +1186,34 @@ static int g_theta_kernel = -1;
 int theta_last_kernel() { return g_theta_kernel; }
 void theta_note_kernel(int code) { g_theta_kernel = code; }     // (theta_fsgl.hip: 4000 / 5000 + tile edge)
 
-static void launch_flat4_any(hipStream_t st, double* Theta, double* X, double* C, const double* Omega,
-                             const double* OmegaPrev, const double* L, double l1, double l2, int fuse_dual,
-                             double* partials, int K, int p, const int* skip, int G, const double* l1G, const double* l2G,
-                             const double* gsq, WNext wn = WNext())
+// The split-column instantiations, launch_cols<KQ, NW, elements per lane, SPLIT>: the first row of its kind (few: use_flat16)
+// that holds K runs.  16-byte accesses up to K = 128; 16 x 16 instances with two elements per lane would need 192 registers
+// per lane, a 16-wave workgroup has 128.
+static const struct ColsRoute {
+    bool few;
+    int kmax, code;
+    decltype(&launch_cols<4, 4, 2, 1>) launch;
+} COLS_ROUTES[] = {
+    {false, 16, 404, launch_cols<4, 4, 2, 1>},          {false, 32, 408, launch_cols<8, 4, 2, 1>},
+    {false, 64, 808, launch_cols<8, 8, 2, 1>},          {false, 128, 816, launch_cols<8, 16, 2, 1>},
+    {false, GGL_FLAT_MAX_K, 1616, launch_cols<16, 16, 1, 1>},
+    {true, 128, 10216, launch_cols<2, 16, 1, 4>},       {true, GGL_FLAT_MAX_K, 10416, launch_cols<4, 16, 1, 4>},
+};
+
+static void launch_cols_any(hipStream_t st, double* Theta, double* X, double* C, const double* Omega,
+                            const double* OmegaPrev, const double* L, double l1, double l2, int fuse_dual,
+                            double* partials, int K, int p, const int* skip, int G, const double* l1G, const double* l2G,
+                            const double* gsq, WNext wn = WNext())
 {
-    if (use_flat16(K, p, 2, G)) {
-        g_theta_kernel = K <= 128 ? 10216 : 10416;
-        if (K <= 128) launch_flat16<2>(st, Theta, X, C, Omega, OmegaPrev, L, l1, l2, fuse_dual, partials, K, p, skip, gsq, wn);
-        else launch_flat16<4>(st, Theta, X, C, Omega, OmegaPrev, L, l1, l2, fuse_dual, partials, K, p, skip, gsq, wn);
+    const bool few = use_flat16(K, p, 2, G);
+    for (const ColsRoute& r : COLS_ROUTES) {
+        if (r.few != few || K > r.kmax) continue;
+        g_theta_kernel = r.code;
+        r.launch(st, Theta, X, C, Omega, OmegaPrev, L, l1, l2, fuse_dual, partials, K, p, skip, G, l1G, l2G, gsq, wn);
         return;
     }
-#define GGL_F4(...) launch_flat4<__VA_ARGS__>(st, Theta, X, C, Omega, OmegaPrev, L, l1, l2, fuse_dual, partials, K, p, skip, G, l1G, l2G, gsq, wn)
-    g_theta_kernel = K <= 16 ? 404 : K <= 32 ? 408 : K <= 64 ? 808 : K <= 128 ? 816 : 1616;
-    if (K <= 16) GGL_F4(4);
-    else if (K <= 32) GGL_F4(8);
-    else if (K <= 64) GGL_F4(8, 8);
-    else if (K <= 128) GGL_F4(8, 16);
-    else GGL_F4(16, 16, false);
-#undef GGL_F4
 }
+
 
 template <int KMAX>
 static void launch_flat(hipStream_t st, double* Theta, double* X, double* C, const double* Omega,
@@ -1409,7 +1241,7 @@ hipError_t launch_theta_pair(hipStream_t st, int reg, double* Theta, double* X, 
     // per-element kernels (exactly symmetric state): the group sums are the element's own K-column, or -- K-sharded run --
     // the all-reduced FULL matrix `groupsq` (launch_group_sums_full on every rank)
     if (reg == 1 && K <= GGL_FLAT_MAX_K && use_flat4(K, flat)) {
-        launch_flat4_any(st, Theta, X, C, Omega, OmegaPrev, L, l1, l2, fuse_dual, partials, K, p, skip, 1, nullptr, nullptr, groupsq, wn);
+        launch_cols_any(st, Theta, X, C, Omega, OmegaPrev, L, l1, l2, fuse_dual, partials, K, p, skip, 1, nullptr, nullptr, groupsq, wn);
         if (wn_done && wn.S) *wn_done = 1;
         return hipGetLastError();
     }
@@ -1469,7 +1301,7 @@ hipError_t launch_theta_batch(hipStream_t st, int reg, double* Theta, double* X,
     if (reg == 1) {
         if (K > GGL_FLAT_MAX_K) return hipErrorInvalidValue;
         if (use_flat4(K, 2)) {       // partial-sum rows: theta_partial_blocks(p, reg, K, 2) per problem
-            launch_flat4_any(st, Theta, X, C, Omega, OmegaPrev, L, 0.0, 0.0, fuse_dual, partials, K, p, skip, G, l1G, l2G, nullptr);
+            launch_cols_any(st, Theta, X, C, Omega, OmegaPrev, L, 0.0, 0.0, fuse_dual, partials, K, p, skip, G, l1G, l2G, nullptr);
             return hipGetLastError();
         }
         if (K <= 8) launch_flat<8>(st, Theta, X, C, Omega, OmegaPrev, L, 0.0, 0.0, fuse_dual, partials, K, p, skip, G, l1G, l2G);

@@ -140,7 +140,7 @@ def test_oracle_trajectory_mid_sizes(sol, reg, K, p, latent):
 
 
 @pytest.mark.parametrize("p,K", [(60, 4), (160, 4), (70, 12), (150, 20), (66, 32),
-                                 # K > 32: the K-column of an element over 8 / 16 waves (theta_pair.hip, launch_flat4_any):
+                                 # K > 32: the K-column of an element over 8 / 16 waves (theta_pair.hip, launch_cols_any):
                                  # 8 x 8 (K <= 64), 16 x 8 (<= 128), 16 x 16 with 8-byte accesses (<= 256); even and odd p
                                  (40, 40), (33, 64), (36, 100), (31, 128), (30, 200), (25, 256)])
 def test_asymmetric_dual_start_takes_the_mirroring_kernels(sol, p, K, monkeypatch):

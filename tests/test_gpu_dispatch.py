@@ -309,7 +309,7 @@ def test_c5_slab_dispatch_ggl_K32_p1000(stats):
 def test_c5_whole_ggl_K256_p1000(stats):
     """C5 WHOLE on one GPU (solver/admm_solver.py:172-246 at K = 256, p = 1000): 2 iterations, all of
     Omega / Theta / X against the oracle at 1e-9, on the Theta kernel that spreads the K-column over 16 waves of 16 values
-    (k_theta_ggl_flat4v<16,16>, the only one for 128 < K <= 256) and the double-buffered 64x64 DMA product kernel."""
+    (k_theta_ggl_cols<16,16,1>, the only one for 128 < K <= 256) and the double-buffered 64x64 DMA product kernel."""
     from gglasso_amd import solver
     S, Om0 = _problem("GGL", 256, 1000, 1240)
     kw = dict(max_iter=2, tol=1e-20, rtol=1e-20)
@@ -328,7 +328,7 @@ def test_c5_whole_ggl_K256_p1000(stats):
                                              (64, 64, False, 808), (256, 200, False, 1616)])
 def test_many_instances_of_a_small_matrix(stats, K, p, latent, code):
     """GGL with K > 64 and fewer than 256 workgroups of 128 elements (BASELINE's K = 256, p = 64 among them): the Theta-step
-    takes 16 elements per workgroup (k_theta_ggl_flat16: p^2 / 16 workgroups instead of p^2 / 128 on 256 CUs), the Omega-step
+    takes 16 elements per workgroup (k_theta_ggl_cols, SPLIT = 4: p^2 / 16 workgroups instead of p^2 / 128 on 256 CUs), the Omega-step
     the LDS-resident kernel.  Six iterations of all of Omega / Theta / X (/ L) against the oracle (admm_solver.py:172-246);
     the neighbouring shapes keep their 128-element kernels."""
     from gglasso_amd import solver

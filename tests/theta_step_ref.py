@@ -339,7 +339,10 @@ def _cases():
     # mgl_batch_step: G = 3 problems with their own (rho, lambda1, lambda2), odd p
     out += [C("mglb-ggl-Kp4", "mgl_batch", "GGL", 12, 13, 108, G=3), C("mglb-ggl-Kp12", "mgl_batch", "GGL", 36, 13, 404, G=3),
             C("mglb-ggl-Kp20", "mgl_batch", "GGL", 60, 13, 408, G=3), C("mglb-fgl-Kp5", "mgl_batch", "FGL", 15, 13, 3128, G=3),
-            C("mglb-ggl-latent-Kp12", "mgl_batch", "GGL", 36, 13, 404, G=3, latent=True)]
+            C("mglb-ggl-latent-Kp12", "mgl_batch", "GGL", 36, 13, 404, G=3, latent=True),
+            # the 16-wave kernels under blockIdx.y > 0 and l1G / l2G; (129, 7): 49 elements, the first 64-element chunk of the
+            # only workgroup partly live, its second chunk dead
+            C("mglb-ggl-Kp65", "mgl_batch", "GGL", 195, 13, 816, G=3), C("mglb-ggl-Kp129", "mgl_batch", "GGL", 387, 7, 1616, G=3)]
     # sgl_batch_step: K = 3 instances with their own (rho_k, lambda1_k)
     out += [C("sglb-p65", "sgl_batch", "SGL", 3, 65, None), C("sglb-p64-fused", "sgl_batch", "SGL", 3, 64, None, fused=True),
             C("sglb-p33-fused", "sgl_batch", "SGL", 3, 33, None, fused=True),
